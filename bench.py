@@ -23,9 +23,11 @@ Prints ONE JSON line on rank 0 (contract in the task statement): metric/value/un
                   against the 8 TB/s HBM peak.  The physics kernel keeps its state in LDS for 20 substeps, so the fraction is
                   tiny by design; the VALU view (counted flops of the oracle's instrumented build, profiles/flop_counts.json)
                   is reported next to it.
-  "cpu_baseline": the CPU oracle (oracle/liborc.so, a scalar f64 C restatement) timed on this host's cores on a bounded
-                  sample of the same workload.
-The default line (one GPU, config 2, f32) also carries short side runs on the same GPU, outside the timed region of `value`:
+  "cpu_baseline": (--full) the CPU oracle (oracle/liborc.so, a scalar f64 C restatement) timed on this host's cores on a bounded
+                  sample of the same workload; null in a plain run.
+A plain run does only what the headline needs: set up, warm up, time --steps steps, write --dump-outputs, print the line.
+`--full` adds the CPU baseline, MuJoCo where importable, and on the default line (one GPU, config 2, f32) short side runs on the same GPU,
+outside the timed region of `value`:
   "f64_value"         the same workload with AVSIM_F64_PHYSICS (the reference's arithmetic: MuJoCo computes in double)
   "value_episode300"  reset + one whole 300-step episode of config 2
   "config3_value", "config4_value"   the contact-rich configurations (whole 250-step grasp script; 100 steps of the random walk)
@@ -33,6 +35,8 @@ The default line (one GPU, config 2, f32) also carries short side runs on the sa
                                      image kernel's ms per launch (HIP events, avsim_render_kernel_time) and its fraction of the HBM write roof
 `roofline.bound` is "valu+latency" for the physics kernel: `frac` = its own floating-point work (profiles/kernel_flops.json) per launch time against
 the f32 vector peak; the HBM view of the contract (algorithmic bytes per launch / launch time against 8 TB/s) is kept as hbm_achieved / hbm_frac.
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step returned to its caller as DIR/<name>.npy (float64 / float32):
+agent_pos, reward, success, the gathered episode_return / episode_success and, with --render, a fixed seeded sample of the depth images.
 `scaling` is "weak" with --envs-per-gpu (default 4096 on every GPU) and "strong" with --envs-total; `n_ranks_seen` is
 torch.distributed's world size as the process group reports it.
 """
@@ -389,6 +393,31 @@ def side_run(args, torch, cfg_id, N, local, f64, warmup, steps, render=""):
     return info
 
 
+DUMP_MAX_ENVS = 131072                 # --dump-outputs: per-env rows beyond this are a fixed seeded sample (<= ~25 MB of rows)
+DUMP_DEPTH_SAMPLES = 1 << 22           # --dump-outputs with --render: a fixed seeded sample of this many depth pixels (16 MB)
+
+
+def last_step_outputs(w, all_ret, all_succ, dist):
+    """What the last timed step handed its caller, as host arrays: every rank's agent_pos / reward / success gathered in global env
+    order, the gathered episode returns / successes, and (rank 0's) depth pixels at seeded positions.  Called on every rank."""
+    torch = w.torch
+    outs = {"agent_pos": w.agent.to(torch.float64), "reward": w.reward.to(torch.float64), "success": w.success.to(torch.float32)}
+    if dist is not None:
+        from av_aloha_amd.dist import _all_gather
+        outs = {k: _all_gather(v.contiguous(), dist) for k, v in outs.items()}
+    outs["episode_return"] = all_ret.to(torch.float32)
+    outs["episode_success"] = all_succ.to(torch.float32)
+    n = outs["agent_pos"].shape[0]
+    if n > DUMP_MAX_ENVS:
+        rows = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_ENVS, replace=False)))
+        outs = {k: v[rows.to(v.device)] for k, v in outs.items()}
+    if w.depth is not None:
+        flat = w.depth.view(-1)
+        idx = np.sort(np.random.default_rng(1).integers(0, flat.numel(), min(DUMP_DEPTH_SAMPLES, flat.numel())))
+        outs["depth_sample"] = flat[torch.from_numpy(idx).to(flat.device)]
+    return {k: v.cpu().numpy() for k, v in outs.items()}
+
+
 def launch_ranks(n, share_gpu):
     """Re-run this command line as n ranks of one node through torch.distributed.run (rendezvous on 127.0.0.1, a free port), the
     form the driver itself uses for N > 1.  Fails loudly when the node has fewer GPUs than ranks (unless --share-gpu)."""
@@ -420,14 +449,19 @@ def main():
     ap.add_argument("--solver", choices=["pgs", "newton"], default="newton")
     ap.add_argument("--newton-iters", type=int, default=0, help="0 = the library default")
     ap.add_argument("--option", action="append", default=[], help="name=value passed to avsim_set_option (experiments)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the side runs (f64, whole episode, configs 3 and 4) that the default single-GPU config-2 line carries")
+    ap.add_argument("--full", action="store_true", help="also measure the CPU baseline, MuJoCo where importable and the side runs (f64, 1024 envs, one env, "
+                                                        "whole episode, configs 3, 4 and 5) of the default single-GPU config-2 line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the side runs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step returned as DIR/<name>.npy")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for --gpus > 1 (nccl = RCCL; gloo only for testing the multi-rank path on a one-GPU box together with --share-gpu)")
     ap.add_argument("--share-gpu", action="store_true", help="testing aid: every rank uses cuda:0")
     ap.add_argument("--dist-always", action="store_true", help="testing aid: initialise torch.distributed and run the collectives for a world of ONE rank too (RCCL init, barrier, all-reduce and all-gather on a one-GPU box)")
     ap.add_argument("--render", default="", help="HxW: render depth images of the 4 zed/wrist cameras every step (config 5 default 480x640)")
     ap.add_argument("--dump", default="", help="testing aid: rank 0 saves the gathered per-env returns / successes to this .npz")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks here (one process per GPU) and pass their
@@ -510,6 +544,7 @@ def main():
         all_agent = w.agent.sum(dim=1).contiguous()
         if dist is not None:
             all_agent = _all_gather(all_agent, dist)
+    outputs = last_step_outputs(w, all_ret, all_succ, dist) if args.dump_outputs else None
     k_ms, k_n = w.kernel_time()
     torch.cuda.synchronize()
     dg = w.diag.cpu().numpy()
@@ -533,6 +568,10 @@ def main():
     if rank == 0:
         if args.dump:
             np.savez(args.dump, ret=all_ret.cpu().numpy(), succ=all_succ.cpu().numpy(), agent_sum=all_agent.cpu().numpy())
+        if outputs is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, arr in outputs.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
         dtype = "f64" if args.f64 else "f32"
         ms_per_step = elapsed / args.steps * 1e3
         value = n_total * args.steps / elapsed
@@ -635,7 +674,7 @@ def main():
     if rank == 0:
         # Side runs next to the headline line (single GPU, default configuration): the same workload at the reference's precision,
         # one whole 300-step episode with its auto-reset, and the contact-rich configurations 3 and 4
-        if headline and world == 1 and not args.f64 and not args.no_extras:
+        if args.full and headline and world == 1 and not args.f64 and not args.no_extras:
             f = side_run(args, torch, 2, N, local, True, 5, 20)
             out["f64_value"] = f["value"]
             out["f64"] = {**f, "dtype": "f64", "note": "AVSIM_F64_PHYSICS: the arithmetic of the reference (MuJoCo mjtNum = double), same workload, same flags; "
@@ -661,11 +700,11 @@ def main():
             c5 = side_run(args, torch, 5, N, local, False, 2, 10, RENDER_DEFAULT)
             out["config5_value"] = c5["value"]
             out["config5"] = {**c5, "note": "config 2 + depth images of zed_cam_left/right + wrist_cam_left/right at 480x640 f32 every step (BASELINE configs[4]); 4.9 MB of depth per env-step: HBM-write bound by construction (SURVEY 8d)"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.config, n_total, home, 1 if args.solver == "newton" else 0)
-        elif world > 1:
+        elif world > 1 or not args.full:
             out["cpu_baseline"] = None
-        importable, mj = mujoco_row(args.config, home) if world == 1 else (None, None)
+        importable, mj = mujoco_row(args.config, home) if (args.full and world == 1) else (None, None)
         out["mujoco_importable"] = importable
         if mj is not None:
             out["mujoco_cpu"] = mj

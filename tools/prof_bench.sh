@@ -7,9 +7,9 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 o=gpurun_out/prof_$tag
 mkdir -p $o
-python bench.py --steps 100 --warmup 10 > $o/bench_config2.json 2> $o/bench2.err
-python bench.py --config 3 --steps 240 --warmup 5 > $o/bench_config3.json 2> $o/bench3.err
-python bench.py --config 4 --steps 100 --warmup 10 > $o/bench_config4.json 2> $o/bench4.err
+python bench.py --steps 100 --warmup 10 --full > $o/bench_config2.json 2> $o/bench2.err
+python bench.py --config 3 --steps 240 --warmup 5 --full > $o/bench_config3.json 2> $o/bench3.err
+python bench.py --config 4 --steps 100 --warmup 10 --full > $o/bench_config4.json 2> $o/bench4.err
 python bench.py --config 5 --steps 10 --warmup 2 --no-cpu-baseline --no-extras > $o/bench_config5.json 2> $o/bench5.err
 python bench.py --f64 --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $o/bench_config2_f64.json 2> $o/bench2f64.err
 rocprofv3 --kernel-trace --stats -d $o/trace2 -o t -f csv -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $o/trace2.log 2>&1
