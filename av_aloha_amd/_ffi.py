@@ -59,6 +59,13 @@ def lib():
         L.avsim_visual_info.argtypes = [vp, vp]
         L.avsim_visual_profile.argtypes = [vp, vp, i32]
         L.avsim_reward_from_pairs.argtypes = [vp, vp, i32, i32, vp, vp]
+        L.avsim_render_rgb_f32.argtypes = [vp, vp, i32, i32, i32, vp]
+        L.avsim_episode_setup.argtypes = [vp, vp, vp, C.c_uint64, i32, i32, C.c_int64]
+        L.avsim_sample_poses.argtypes = [vp, C.c_uint64, i32, vp, vp]
+        L.avsim_episode_reset.argtypes = [vp, vp, vp, vp]
+        L.avsim_episode_step.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.avsim_episode_log.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp]
+        L.avsim_episode_count.argtypes = [vp, vp]
         L.avsim_sync.argtypes = [vp]
         L.avsim_set_stream.argtypes = [vp, vp]
         L.avsim_event_record.argtypes = [vp, i32]

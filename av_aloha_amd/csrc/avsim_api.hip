@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/avsim.h"
+#include "avsim_episode.hip.h"
 #include "avsim_ik.hip.h"
 #include "avsim_model.h"
 #include "avsim_phys.hip.h"
@@ -82,8 +83,16 @@ struct avsim {
     void *d_qpos = nullptr, *d_qvel = nullptr, *d_ctrl = nullptr, *d_warm = nullptr;
     int* d_latch = nullptr;
     // device scratch for host-pointer I/O
-    void* d_io[8] = {};
-    size_t d_io_sz[8] = {};
+    void* d_io[16] = {};
+    size_t d_io_sz[16] = {};
+    // per-env episodes (avsim_episode_setup; avsim_episode.hip.h): parameters, per-env bookkeeping, records, outputs nobody asked for
+    bool ep_ready = false;
+    EpArgs ep{};
+    std::vector<void*> ep_allocs;
+    double* ep_ap = nullptr;
+    int *ep_rw = nullptr, *ep_el = nullptr;
+    uint8_t *ep_su = nullptr, *ep_te = nullptr, *ep_tr = nullptr;
+    int64_t* ep_id = nullptr;
     // kernel timing
     // kernel timing: pairs of HIP events recorded around every physics launch on the launch stream, read
     // back (and only then synchronised) by avsim_kernel_time
@@ -323,16 +332,7 @@ __global__ void k_reset(int N, int nq, int nv, int nu, int nobj, const unsigned 
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
     if (mask && !mask[i]) return;
-    for (int k = 0; k < nq; k++) qpos[(size_t)i * nq + k] = (real)qhome[k];
-    for (int o = 0; o < nobj; o++)
-        for (int k = 0; k < 7; k++) {
-            const double v = obj[((size_t)i * nobj + o) * 7 + k];
-            qpos[(size_t)i * nq + objadr[o] + k] = (real)v;
-            obj_keep[((size_t)i * nobj + o) * 7 + k] = v;      // where a diverged env of this episode is put back (check_divergence)
-        }
-    for (int k = 0; k < nv; k++) { qvel[(size_t)i * nv + k] = 0; warm[(size_t)i * nv + k] = 0; }
-    for (int k = 0; k < nu; k++) ctrl[(size_t)i * nu + k] = (real)chome[k];
-    latch[i] = 0;
+    reset_env<real>(i, nq, nv, nu, nobj, obj + (size_t)i * nobj * 7, qhome, chome, objadr, qpos, qvel, ctrl, warm, latch, obj_keep);      // (avsim_episode.hip.h)
 }
 
 template <typename A, typename B>
@@ -470,6 +470,7 @@ void avsim_destroy(avsim_t* h) {
         if (p) (void)hipFree(p);
     for (void* p : h->d_io)
         if (p) (void)hipFree(p);
+    for (void* p : h->ep_allocs) (void)hipFree(p);
     for (int k = 0; k < 2; k++) {
         if (h->pin[k]) (void)hipHostFree(h->pin[k]);
         if (h->pin_ev[k]) (void)hipEventDestroy(h->pin_ev[k]);
@@ -886,13 +887,14 @@ extern "C" {
 
 // E6 (env.py:180-188 get_obs pixels / :195-200 render) as depth images: forward pass of the physics kernel (nsub = 0) exports
 // the body poses, then the two render kernels run on the same stream.
-static int render_images(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, void* out, bool rgb) {
-    const char* who = rgb ? "avsim_render_rgb" : "avsim_render_depth";
+static int render_images(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, void* out, bool rgb, bool f32 = false) {
+    const char* who = f32 ? "avsim_render_rgb_f32" : rgb ? "avsim_render_rgb" : "avsim_render_depth";
     if (!h || !cam_ids || !out) { if (h) h->set_error("%s: bad arguments", who); return AVSIM_EINVAL; }
+    if (f32 && !(h->vis.loaded && !h->render_proxies)) { h->set_error("avsim_render_rgb_f32 draws the visual scene only (avsim_load_visual, render_proxies 0)"); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
     int rc;
     void* dout = nullptr;
-    const size_t bytes = (rgb ? 3 : sizeof(float)) * (size_t)h->N * ncam * height * width;
+    const size_t bytes = (f32 ? 3 * sizeof(float) : rgb ? 3 : sizeof(float)) * (size_t)h->N * ncam * height * width;
     if ((rc = h->out_begin(7, out, bytes, &dout))) return rc;
     if (h->xpose_ver != h->state_ver) {          // body poses of the current state (a forward pass of the physics kernel, no substep)
         h->phys.d_xpose = h->render.d_xpose;
@@ -903,7 +905,7 @@ static int render_images(avsim_t* h, const int32_t* cam_ids, int ncam, int heigh
     }
     if (rgb && h->vis.cam_major && !(h->vis.loaded && !h->render_proxies)) { h->set_error("option render_cam_major applies to the visual scene's images only (avsim_load_visual, render_proxies 0)"); return AVSIM_EINVAL; }
     if (rgb && h->vis.loaded && !h->render_proxies)
-        rc = h->vis.launch(h->stream, h->N, h->render.d_xpose, (const int*)cam_ids, ncam, h->render.m.ncam, height, width, dout, h->err, h->state_ver);
+        rc = h->vis.launch(h->stream, h->N, h->render.d_xpose, (const int*)cam_ids, ncam, h->render.m.ncam, height, width, dout, h->err, h->state_ver, f32);
     else
         rc = h->render.launch(h->stream, (const int*)cam_ids, ncam, height, width, dout, rgb, h->err);
     if (rc) return rc < -1 ? AVSIM_EHIP : AVSIM_EINVAL;
@@ -916,6 +918,10 @@ int avsim_render_depth(avsim_t* h, const int32_t* cam_ids, int ncam, int height,
 // E6 as colour images of the same proxies (env.py:180-188 "pixels" u8[H][W][3], :195-200 render)
 int avsim_render_rgb(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, uint8_t* out) {
     return render_images(h, cam_ids, ncam, height, width, out, true);
+}
+// the visual scene's colour images as a policy reads them (eval.py preprocess_observation): float32 planar CHW, (float)u8 / 255
+int avsim_render_rgb_f32(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, float* out) {
+    return render_images(h, cam_ids, ncam, height, width, out, true, true);
 }
 
 // The visual scene of avsim_render_rgb: the mesh library (models/visual_meshes.avv, compiler/vismesh.py) against the instances the
@@ -983,6 +989,193 @@ int avsim_reward_from_pairs(avsim_t* h, const int32_t* geom_pairs, int nsets, in
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     (void)hipFree(dp);
     if (e != hipSuccess) { h->set_error("avsim_reward_from_pairs: %s", hipGetErrorString(e)); return AVSIM_EHIP; }
+    return AVSIM_OK;
+}
+
+}  // extern "C"
+
+// ---- per-env episodes (avsim_episode.hip.h) ----------------------------------------------------------------------------------------
+static int ep_alloc(avsim_t* h, size_t bytes, void** p) {
+    if (hipMalloc(p, bytes ? bytes : 1) != hipSuccess) { *p = nullptr; h->set_error("avsim_episode_setup: hipMalloc(%zu) failed", bytes); return AVSIM_EHIP; }
+    h->ep_allocs.push_back(*p);
+    return 0;
+}
+// an output of the episode calls: the caller's pointer (staged in host-pointer mode), or the handle's own buffer when it is NULL
+static int ep_out(avsim_t* h, int slot, void* p, size_t bytes, void* own, void** dev) {
+    if (!p) { *dev = own; return 0; }
+    return h->out_begin(slot, p, bytes, dev);
+}
+
+template <typename real>
+static void ep_launch(avsim_t* h, int mode, const uint8_t* mask, double* ap, int* rw, uint8_t* su, uint8_t* te, uint8_t* tr, int64_t* id, int* el) {
+    EpArgs A = h->ep;
+    A.obs_off = h->f64 ? (const void*)(const double*)h->phys.md.obs_offset : (const void*)(const float*)h->phys.mf.obs_offset;
+    A.obs_scale = h->f64 ? (const void*)(const double*)h->phys.md.obs_scale : (const void*)(const float*)h->phys.mf.obs_scale;
+    A.obs_qposadr = h->f64 ? (const int*)h->phys.md.obs_qposadr : (const int*)h->phys.mf.obs_qposadr;
+    hipLaunchKernelGGL(k_episode<real>, dim3(1), dim3(EP_THREADS), 0, h->stream, A, mode, mask, (const int*)h->phys.d_diag, (real*)h->d_qpos, (real*)h->d_qvel,
+                       (real*)h->d_ctrl, (real*)h->d_warm, h->d_latch, ap, rw, su, te, tr, id, el);
+}
+
+extern "C" {
+
+int avsim_episode_setup(avsim_t* h, const double* box, const int32_t* share, uint64_t seed, int max_episode_steps, int terminate_on_success,
+                        int64_t log_capacity) {
+    if (!h || !box || !share || max_episode_steps < 1 || log_capacity < 0) { if (h) h->set_error("avsim_episode_setup: bad arguments"); return AVSIM_EINVAL; }
+    if (h->nobj > EP_MAXOBJ) { h->set_error("avsim_episode_setup: at most %d free objects", EP_MAXOBJ); return AVSIM_EINVAL; }
+    AVS_ON_DEVICE(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // (buffers of an earlier set-up may still be in use)
+    for (void* p : h->ep_allocs) (void)hipFree(p);
+    h->ep_allocs.clear();
+    h->ep_ready = false;
+    const size_t N = h->N, no = h->nobj, L = (size_t)log_capacity;
+    EpArgs& A = h->ep;
+    A = EpArgs{};
+    A.N = h->N; A.nq = h->nq; A.nv = h->nv; A.nu = h->nu; A.nj = h->nj; A.nobj = h->nobj;
+    A.max_steps = max_episode_steps; A.term_on_success = terminate_on_success != 0; A.seed = seed; A.log_cap = log_capacity;
+    A.qhome = h->phys.d_qpos_home; A.chome = h->phys.d_ctrl_home; A.objadr = h->phys.d_obj_qadr; A.obj_reset = h->phys.d_obj_reset;
+    void* p;
+    int rc;
+#define EPA(field, T, n) do { if ((rc = ep_alloc(h, sizeof(T) * (n), &p))) return rc; field = (T*)p; } while (0)
+    EPA(A.id, int64_t, N); EPA(A.elapsed, int, N); EPA(A.maxr, int, N); EPA(A.ret, double, N); EPA(A.succ, uint8_t, N); EPA(A.pending, uint8_t, N);
+    EPA(A.log_ret, double, L); EPA(A.log_obj, double, L * no * 7); EPA(A.log_len, int, L); EPA(A.log_maxr, int, L); EPA(A.log_succ, uint8_t, L);
+    EPA(A.count, int64_t, 2);
+    EPA(h->ep_ap, double, N * h->nj); EPA(h->ep_rw, int, N); EPA(h->ep_el, int, N); EPA(h->ep_su, uint8_t, N); EPA(h->ep_te, uint8_t, N);
+    EPA(h->ep_tr, uint8_t, N); EPA(h->ep_id, int64_t, N);
+#undef EPA
+    for (size_t o = 0; o < no; o++) {
+        for (int k = 0; k < 6; k++) A.box[6 * o + k] = box[6 * o + k];
+        A.share[o] = share[o];
+    }
+    // no episode yet: every env starts one at its first avsim_episode_step (or avsim_episode_reset); id -1 until then
+    HIPCHK(h, hipMemsetAsync(A.id, 0xff, sizeof(int64_t) * N, h->stream));
+    HIPCHK(h, hipMemsetAsync(A.pending, 1, N, h->stream));
+    for (auto q : {(void*)A.elapsed, (void*)A.maxr}) HIPCHK(h, hipMemsetAsync(q, 0, sizeof(int) * N, h->stream));
+    HIPCHK(h, hipMemsetAsync(A.ret, 0, sizeof(double) * N, h->stream));
+    HIPCHK(h, hipMemsetAsync(A.succ, 0, N, h->stream));
+    HIPCHK(h, hipMemsetAsync(A.count, 0, 2 * sizeof(int64_t), h->stream));
+    if (L) {
+        HIPCHK(h, hipMemsetAsync(A.log_len, 0, sizeof(int) * L, h->stream));
+        HIPCHK(h, hipMemsetAsync(A.log_maxr, 0, sizeof(int) * L, h->stream));
+        HIPCHK(h, hipMemsetAsync(A.log_succ, 0, L, h->stream));
+        HIPCHK(h, hipMemsetAsync(A.log_ret, 0, sizeof(double) * L, h->stream));
+        HIPCHK(h, hipMemsetAsync(A.log_obj, 0, sizeof(double) * L * no * 7, h->stream));
+    }
+    h->ep_ready = true;
+    return h->finish();
+}
+
+int avsim_sample_poses(avsim_t* h, uint64_t seed, int n, const int64_t* episode_id, double* obj_qpos) {
+    if (!h || n < 0 || (n && (!episode_id || !obj_qpos))) { if (h) h->set_error("avsim_sample_poses: bad arguments"); return AVSIM_EINVAL; }
+    if (!h->ep_ready) { h->set_error("avsim_sample_poses: call avsim_episode_setup first"); return AVSIM_EINVAL; }
+    if (n == 0) return AVSIM_OK;
+    AVS_ON_DEVICE(h);
+    int rc;
+    const void* did;
+    void* dout;
+    const size_t ob = sizeof(double) * (size_t)n * h->nobj * 7;
+    if ((rc = h->in(0, episode_id, sizeof(int64_t) * (size_t)n, &did))) return rc;
+    if ((rc = h->out_begin(1, obj_qpos, ob, &dout))) return rc;
+    hipLaunchKernelGGL(k_sample_poses, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->ep, seed, n, (const int64_t*)did, (double*)dout);
+    HIPCHK(h, hipGetLastError());
+    if ((rc = h->out_end(1, obj_qpos, ob))) return rc;
+    return h->finish();
+}
+
+int avsim_episode_reset(avsim_t* h, const uint8_t* mask, double* agent_pos, int64_t* episode_id) {
+    if (!h) return AVSIM_EINVAL;
+    if (!h->ep_ready) { h->set_error("avsim_episode_reset: call avsim_episode_setup first"); return AVSIM_EINVAL; }
+    AVS_ON_DEVICE(h);
+    h->state_ver++;
+    const size_t N = h->N;
+    int rc;
+    const void* dm = nullptr;
+    void *dap, *did;
+    if (mask && (rc = h->in(0, mask, N, &dm))) return rc;
+    if ((rc = ep_out(h, 4, agent_pos, sizeof(double) * N * h->nj, h->ep_ap, &dap))) return rc;
+    if ((rc = ep_out(h, 8, episode_id, sizeof(int64_t) * N, h->ep_id, &did))) return rc;
+    if (h->f64) ep_launch<double>(h, 0, (const uint8_t*)dm, (double*)dap, nullptr, nullptr, nullptr, nullptr, (int64_t*)did, nullptr);
+    else ep_launch<float>(h, 0, (const uint8_t*)dm, (double*)dap, nullptr, nullptr, nullptr, nullptr, (int64_t*)did, nullptr);
+    HIPCHK(h, hipGetLastError());
+    if ((rc = h->out_end(4, agent_pos, sizeof(double) * N * h->nj))) return rc;
+    if ((rc = h->out_end(8, episode_id, sizeof(int64_t) * N))) return rc;
+    return h->finish();
+}
+
+int avsim_episode_step(avsim_t* h, const float* action, int nsub, double* agent_pos, int32_t* reward, uint8_t* success, uint8_t* terminated,
+                       uint8_t* truncated, int64_t* episode_id, int32_t* elapsed) {
+    if (!h || !action || nsub < 0) { if (h) h->set_error("avsim_episode_step: bad arguments"); return AVSIM_EINVAL; }
+    if (!h->ep_ready) { h->set_error("avsim_episode_step: call avsim_episode_setup first"); return AVSIM_EINVAL; }
+    AVS_ON_DEVICE(h);
+    const size_t N = h->N;
+    int rc;
+    const void* da;
+    void *dap, *drw, *dsu, *dte, *dtr, *did, *del;
+    if ((rc = h->in(0, action, sizeof(float) * N * h->nj, &da))) return rc;
+    if ((rc = ep_out(h, 4, agent_pos, sizeof(double) * N * h->nj, h->ep_ap, &dap))) return rc;
+    if ((rc = ep_out(h, 5, reward, sizeof(int32_t) * N, h->ep_rw, &drw))) return rc;
+    if ((rc = ep_out(h, 6, success, N, h->ep_su, &dsu))) return rc;
+    if ((rc = ep_out(h, 8, terminated, N, h->ep_te, &dte))) return rc;
+    if ((rc = ep_out(h, 9, truncated, N, h->ep_tr, &dtr))) return rc;
+    if ((rc = ep_out(h, 10, episode_id, sizeof(int64_t) * N, h->ep_id, &did))) return rc;
+    if ((rc = ep_out(h, 11, elapsed, sizeof(int32_t) * N, h->ep_el, &del))) return rc;
+    // the physics launch of avsim_step on device buffers (it also steps the envs that start an episode below; k_episode overwrites them)
+    const bool io = h->io_device;
+    h->io_device = true;
+    rc = step_common(h, (const float*)da, nsub, (double*)dap, (int32_t*)drw, (uint8_t*)dsu);
+    h->io_device = io;
+    if (rc) return rc;
+    if (h->f64) ep_launch<double>(h, 1, nullptr, (double*)dap, (int*)drw, (uint8_t*)dsu, (uint8_t*)dte, (uint8_t*)dtr, (int64_t*)did, (int*)del);
+    else ep_launch<float>(h, 1, nullptr, (double*)dap, (int*)drw, (uint8_t*)dsu, (uint8_t*)dte, (uint8_t*)dtr, (int64_t*)did, (int*)del);
+    HIPCHK(h, hipGetLastError());
+    if ((rc = h->out_end(4, agent_pos, sizeof(double) * N * h->nj))) return rc;
+    if ((rc = h->out_end(5, reward, sizeof(int32_t) * N))) return rc;
+    if ((rc = h->out_end(6, success, N))) return rc;
+    if ((rc = h->out_end(8, terminated, N))) return rc;
+    if ((rc = h->out_end(9, truncated, N))) return rc;
+    if ((rc = h->out_end(10, episode_id, sizeof(int64_t) * N))) return rc;
+    if ((rc = h->out_end(11, elapsed, sizeof(int32_t) * N))) return rc;
+    return h->finish();
+}
+
+// Records and counters out: device pointers in device mode, or host pointers in either mode (a poll from the host); only a copy to host
+// memory synchronises the stream
+static bool ep_host_ptr(const void* p) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return true; }      // (memory HIP does not know: pageable host memory)
+    return a.type != hipMemoryTypeDevice;
+}
+static int ep_copy(avsim_t* h, void* dst, const void* src, size_t bytes, bool* to_host) {
+    if (!dst || !bytes) return 0;
+    const bool host = !h->io_device || ep_host_ptr(dst);
+    HIPCHK(h, hipMemcpyAsync(dst, src, bytes, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
+    *to_host = *to_host || host;
+    return 0;
+}
+
+int avsim_episode_log(avsim_t* h, int64_t n, double* ret, int32_t* length, int32_t* max_reward, uint8_t* success, double* obj_qpos0) {
+    if (!h || n < 0) { if (h) h->set_error("avsim_episode_log: bad arguments"); return AVSIM_EINVAL; }
+    if (!h->ep_ready || n > h->ep.log_cap) { h->set_error("avsim_episode_log: %lld records asked, %lld kept (avsim_episode_setup)", (long long)n, (long long)h->ep.log_cap); return AVSIM_EINVAL; }
+    AVS_ON_DEVICE(h);
+    const size_t m = (size_t)n;
+    int rc;
+    bool host = false;
+    if ((rc = ep_copy(h, ret, h->ep.log_ret, sizeof(double) * m, &host))) return rc;
+    if ((rc = ep_copy(h, length, h->ep.log_len, sizeof(int32_t) * m, &host))) return rc;
+    if ((rc = ep_copy(h, max_reward, h->ep.log_maxr, sizeof(int32_t) * m, &host))) return rc;
+    if ((rc = ep_copy(h, success, h->ep.log_succ, m, &host))) return rc;
+    if ((rc = ep_copy(h, obj_qpos0, h->ep.log_obj, sizeof(double) * m * h->nobj * 7, &host))) return rc;
+    if (host) HIPCHK(h, hipStreamSynchronize(h->stream));
+    return AVSIM_OK;
+}
+
+int avsim_episode_count(avsim_t* h, int64_t count[2]) {
+    if (!h || !count) return AVSIM_EINVAL;
+    if (!h->ep_ready) { h->set_error("avsim_episode_count: call avsim_episode_setup first"); return AVSIM_EINVAL; }
+    AVS_ON_DEVICE(h);
+    int rc;
+    bool host = false;
+    if ((rc = ep_copy(h, count, h->ep.count, 2 * sizeof(int64_t), &host))) return rc;
+    if (host) HIPCHK(h, hipStreamSynchronize(h->stream));
     return AVSIM_OK;
 }
 

@@ -291,10 +291,15 @@ __global__ void __launch_bounds__(VIS_SHADOW_THREADS) k_vis_shadow(VisScene S, c
 #else
 #define VIS_OCC_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))      // 128 VGPRs: sixteen wavefronts per CU
 #endif
-template <int SS, bool SH, bool SM>       // SS x SS samples per pixel; SH: shadows of the directional light (S.shmap); SM: smooth shading (a template flag: as a run-time one it
+// (unsigned)u8 / 255 for the planar float32 images: filled on the host (VisHost::load) with IEEE division -- this unit is compiled with
+// -fno-hip-fp32-correctly-rounded-divide-sqrt, so a '/' in the kernel would not round as torch's `/ 255` of the u8 image does
+__constant__ float vis_u8_unit[256];
+
+template <int SS, bool SH, bool SM, typename OT = unsigned char>       // SS x SS samples per pixel; SH: shadows of the directional light (S.shmap); SM: smooth shading (a template flag: as a run-time one it
                                          // cost the flat path 16 % -- registers of both paths live in the tile loop at the 128-VGPR cap)
+                                         // OT: unsigned char = interleaved u8 [H][W][3]; float = planar [3][H][W] in [0, 1] (avsim_render_rgb_f32)
 __global__ void __launch_bounds__(VIS_THREADS) VIS_OCC_ATTR k_vis_render(VisScene S, VisScratch X, const float* __restrict__ xpose, const int* __restrict__ cam_ids, int ncam_sel,
-                                                            int N, int H, int W, unsigned char* __restrict__ out, int cam_major) {
+                                                            int N, int H, int W, OT* __restrict__ out, int cam_major) {
     __shared__ float Rcb[VIS_MAXBODY * 12];
     __shared__ float cam[36];                // [31..33] Blinn's half vector of the directional light (viewer at infinity), camera frame; Rc (9), pc (3), light dir in the camera frame (3), world up in the camera frame (3), scale; [19..30] the light's frame
                                              // and shadow box (VisScene le1, le2, lw, sh_s0, sh_t0, sh_itex: read from here, not from SGPRs, by the few lanes that need them)
@@ -568,7 +573,7 @@ __global__ void __launch_bounds__(VIS_THREADS) VIS_OCC_ATTR k_vis_render(VisScen
         __syncthreads();
         const long long tc4 = __builtin_readcyclecounter();
         // 4. tiles: one wavefront each, lane = pixel
-        unsigned char* img = out + (size_t)(cam_major ? cs * N + env : view) * H * W * 3;      // [N][cam] or (option render_cam_major) [cam][N]
+        OT* img = out + (size_t)(cam_major ? cs * N + env : view) * H * W * 3;      // [N][cam] or (option render_cam_major) [cam][N]
         const unsigned* shenv = SH ? S.shmap + (size_t)env * S.shn * S.shn : nullptr;
         // (records and lists were written with vector stores: the barrier above made them visible in L2, this drops what the scalar cache
         // still holds of the slot's previous view)
@@ -719,8 +724,14 @@ __global__ void __launch_bounds__(VIS_THREADS) VIS_OCC_ATTR k_vis_render(VisScen
                     for (int q = 0; q < NS; q++) { accr += (float)(c[q] & 255u); accg += (float)((c[q] >> 8) & 255u); accb += (float)((c[q] >> 16) & 255u); }
                     col = (unsigned)(accr * (1.0f / NS) + 0.5f) | ((unsigned)(accg * (1.0f / NS) + 0.5f) << 8) | ((unsigned)(accb * (1.0f / NS) + 0.5f) << 16);
                 }
-                unsigned char* d = img + (unsigned)((iy * W + ix) * 3);
-                d[0] = (unsigned char)(col & 255u); d[1] = (unsigned char)((col >> 8) & 255u); d[2] = (unsigned char)((col >> 16) & 255u);
+                if constexpr (sizeof(OT) == 1) {
+                    unsigned char* d = img + (unsigned)((iy * W + ix) * 3);
+                    d[0] = (unsigned char)(col & 255u); d[1] = (unsigned char)((col >> 8) & 255u); d[2] = (unsigned char)((col >> 16) & 255u);
+                } else {
+                    const unsigned pl = (unsigned)(H * W);
+                    float* d = img + (unsigned)(iy * W + ix);
+                    d[0] = vis_u8_unit[col & 255u]; d[pl] = vis_u8_unit[(col >> 8) & 255u]; d[2 * pl] = vis_u8_unit[(col >> 16) & 255u];
+                }
             }
         }
         if (flag) atomicOr(&X.flags[8 * view], flag);
@@ -747,6 +758,7 @@ struct VisHost {
     int slots = 0, max_slots = 0, nviews_cap = 0, last_nviews = 0;     // scratch slots allocated / the most a launch uses (VIS_WG_PER_CU x CUs); flag rows allocated / written by the last launch
     bool attr_done = false;
     int* d_cam_ids = nullptr;
+    int cam_ids_last[16] = {}, ncam_last = -1;     // what d_cam_ids holds: a call with the same cameras copies nothing (no host-to-device copy per step)
     int samples = 1;                 // option "render_samples": 1, or 4 = 2 x 2 supersampling
     bool cam_major = false;          // option "render_cam_major": the images as [cam][N][H][W][3] (every camera's batch contiguous) instead of [N][cam][H][W][3]
     int shadow_size = VIS_SM;        // option "render_shadow_size": 512 | 1024 | 2048 texels per side (MuJoCo's own map is 8192 wide, scene.xml:12; 2.3 mm texels at 512)
@@ -777,6 +789,11 @@ struct VisHost {
     void load(const Blob& lib, int nbody, const float* d_cam_pos, const float* d_cam_mat, const float* d_cam_fovy, const int* d_cam_body, const float* d_light, float znear) {
         if (!have_inst) throw std::runtime_error("the model blob carries no visual instances (vis_inst_*): recompile it with av_aloha_amd.compiler.compile");
         if (loaded) return;
+        {
+            float unit[256];
+            for (int k = 0; k < 256; k++) unit[k] = (float)k / 255.0f;       // (host division: IEEE, the rounding of torch's u8.float() / 255)
+            if (hipMemcpyToSymbol(HIP_SYMBOL(vis_u8_unit), unit, sizeof unit) != hipSuccess) throw std::runtime_error("hipMemcpyToSymbol(vis_u8_unit) failed");
+        }
         auto vadr = lib.i("lib_vadr"), vnum = lib.i("lib_vnum"), tadr = lib.i("lib_tadr"), tnum = lib.i("lib_tnum"), ltri = lib.i("lib_tri"), ltex = lib.i("lib_tex");
         auto lvert = lib.f("lib_vert"), luv = lib.f("lib_uv");
         std::vector<double> ltn;
@@ -849,10 +866,12 @@ struct VisHost {
         for (void* p : allocs) (void)hipFree(p);
         allocs.clear();
         for (void* p : {(void*)X.vcam, (void*)X.rec, (void*)X.bbox, (void*)X.list, (void*)X.trec, (void*)X.grec, (void*)X.bigq, (void*)X.flags, (void*)d_cam_ids, (void*)d_shmap}) if (p) (void)hipFree(p);
-        X = VisScratch{}; d_cam_ids = nullptr; d_shmap = nullptr; shmap_envs = 0; shmap_ver = 0; loaded = false; slots = 0; max_slots = 0; nviews_cap = 0; last_nviews = 0;
+        X = VisScratch{}; d_cam_ids = nullptr; ncam_last = -1; d_shmap = nullptr; shmap_envs = 0; shmap_ver = 0; loaded = false; slots = 0; max_slots = 0; nviews_cap = 0; last_nviews = 0;
     }
     // overflow flags of the last launch, OR over the views (bit 0: triangle records, bit 1: tile lists); synchronises the stream
-    int launch(hipStream_t st, int N, const float* d_xpose, const int* cam_ids_host, int ncam_sel, int ncam_model, int H, int W, void* d_out, std::string& err, unsigned long long state_ver = 0) {
+    // f32: planar float32 [3][H][W] views in [0, 1], (float)u8 / 255 of the u8 image bit for bit (k_vis_render<..., float>)
+    int launch(hipStream_t st, int N, const float* d_xpose, const int* cam_ids_host, int ncam_sel, int ncam_model, int H, int W, void* d_out, std::string& err, unsigned long long state_ver = 0,
+               bool f32 = false) {
         if (!loaded) { err = "avsim_render_rgb: no visual scene loaded (avsim_load_visual)"; return -1; }
         if (ncam_sel < 1 || ncam_sel > 16 || H < 1 || W < 1) { err = "avsim_render_rgb: bad camera count or image size"; return -1; }
         const int ntile = ((W + VIS_TILE - 1) / VIS_TILE) * ((H + VIS_TILE - 1) / VIS_TILE);
@@ -893,12 +912,16 @@ struct VisHost {
             nviews_cap = nviews;
         }
         last_nviews = nviews;
-        if (hipMemsetAsync(X.flags, 0, (size_t)nviews * 8 * sizeof(int), st) != hipSuccess || hipMemcpyAsync(d_cam_ids, cam_ids_host, ncam_sel * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) { err = "visual render set-up copy failed"; return -3; }
+        const bool same_cams = ncam_last == ncam_sel && !std::memcmp(cam_ids_last, cam_ids_host, ncam_sel * sizeof(int));
+        if (hipMemsetAsync(X.flags, 0, (size_t)nviews * 8 * sizeof(int), st) != hipSuccess || (!same_cams && hipMemcpyAsync(d_cam_ids, cam_ids_host, ncam_sel * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess)) { ncam_last = -1; err = "visual render set-up copy failed"; return -3; }
+        std::memcpy(cam_ids_last, cam_ids_host, ncam_sel * sizeof(int));
+        ncam_last = ncam_sel;
         const int grid = nviews < slots ? nviews : slots;
         const size_t shmem = (size_t)(2 * ntile + 1) * sizeof(int);
         if (!attr_done) {
             bool ok = true;
-#define VIS_ATTR(SS_, SH_, SM_) ok = ok && hipFuncSetAttribute((const void*)k_vis_render<SS_, SH_, SM_>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024) == hipSuccess
+#define VIS_ATTR(SS_, SH_, SM_) ok = ok && hipFuncSetAttribute((const void*)k_vis_render<SS_, SH_, SM_>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024) == hipSuccess \
+                                    && hipFuncSetAttribute((const void*)k_vis_render<SS_, SH_, SM_, float>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024) == hipSuccess
             VIS_ATTR(1, false, false); VIS_ATTR(2, false, false); VIS_ATTR(1, true, false); VIS_ATTR(2, true, false);
             VIS_ATTR(1, false, true); VIS_ATTR(2, false, true); VIS_ATTR(1, true, true); VIS_ATTR(2, true, true);
 #undef VIS_ATTR
@@ -932,7 +955,9 @@ struct VisHost {
         }
         const bool sh = S.shmap != nullptr;
         const bool sm = S.smooth != 0 && S.tnorm != nullptr;
-#define VIS_LAUNCH(SS_, SH_) do { if (sm) hipLaunchKernelGGL((k_vis_render<SS_, SH_, true>), dim3(grid), dim3(VIS_THREADS), shmem, st, S, X, d_xpose, (const int*)d_cam_ids, ncam_sel, N, H, W, (unsigned char*)d_out, cam_major ? 1 : 0); \
+#define VIS_LAUNCH(SS_, SH_) do { if (f32) { if (sm) hipLaunchKernelGGL((k_vis_render<SS_, SH_, true, float>), dim3(grid), dim3(VIS_THREADS), shmem, st, S, X, d_xpose, (const int*)d_cam_ids, ncam_sel, N, H, W, (float*)d_out, cam_major ? 1 : 0); \
+                                            else hipLaunchKernelGGL((k_vis_render<SS_, SH_, false, float>), dim3(grid), dim3(VIS_THREADS), shmem, st, S, X, d_xpose, (const int*)d_cam_ids, ncam_sel, N, H, W, (float*)d_out, cam_major ? 1 : 0); break; } \
+                                  if (sm) hipLaunchKernelGGL((k_vis_render<SS_, SH_, true>), dim3(grid), dim3(VIS_THREADS), shmem, st, S, X, d_xpose, (const int*)d_cam_ids, ncam_sel, N, H, W, (unsigned char*)d_out, cam_major ? 1 : 0); \
                                   else hipLaunchKernelGGL((k_vis_render<SS_, SH_, false>), dim3(grid), dim3(VIS_THREADS), shmem, st, S, X, d_xpose, (const int*)d_cam_ids, ncam_sel, N, H, W, (unsigned char*)d_out, cam_major ? 1 : 0); } while (0)
         if (samples > 1) { if (sh) VIS_LAUNCH(2, true); else VIS_LAUNCH(2, false); }
         else { if (sh) VIS_LAUNCH(1, true); else VIS_LAUNCH(1, false); }

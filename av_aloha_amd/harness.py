@@ -6,6 +6,8 @@
 * `rollout` (eval.py:96-124): reset / select_action / step loop for `num_episodes` x `episode_len`, frames of zed_cam_left when
   the env returns pixels, plus the success / return bookkeeping the reference leaves out.  Works on one env (reference shapes)
   and on a batch (`num_envs > 1`).
+* `evaluate_vec`: the same evaluation on the device-resident vector env (vec_env.py): per-env episodes, NEXT_STEP autoreset, one
+  record per episode id, no host round trip per step.
 * `record_episode` / `save_episode` / `load_episode` (record_sim_episodes.py:83-128, :155-212): a scripted Cartesian action
   sequence replaces the VR headset; the episode holds T = len(actions) + 1 time steps with `/observations/qpos` (T, 21),
   `/observations/qvel` (T, 21), `/observations/all_qpos` (T, nq), `/action` (T, 21: the joint-space command with
@@ -77,6 +79,27 @@ def rollout(env, select_action, episode_len: int, num_episodes: int = 1, reset_p
                 frames.append(px["zed_cam_left"])
         results.append({"return": ret, "success": success if batched else bool(success[0]), "max_reward": env.max_reward, "frames": frames})
     return results
+
+
+def evaluate_vec(env, select_action, num_episodes: int, seed: int | None = None) -> list:
+    """Policy evaluation on a device-resident vector env (vec_env.make_vec): the episode ids restart at 0 and the env is stepped until
+    the episodes with ids [0, num_episodes) have all finished; envs go on to later ids by themselves (NEXT_STEP autoreset).
+    select_action(obs, info) -> float32 [N, nj] tensor on the env's device; info["episode_id"] changing marks an env's new episode.
+    The host reads the episode counter once per max_episode_steps calls.  Returns one dict per id: 'episode_id', 'return', 'length',
+    'max_reward', 'success', 'initial_object_poses'."""
+    env.start_log(num_episodes, seed=seed)
+    observation, info = env.reset()
+    calls = 0
+    while True:
+        observation, reward, terminated, truncated, info = env.step(select_action(observation, info))
+        calls += 1
+        if calls % env.max_episode_steps == 0 and env.episode_count()[1] >= num_episodes:
+            log = env.episode_log(num_episodes)
+            if (log["length"] > 0).all():
+                break
+    env.check_render_overflow()
+    return [{"episode_id": i, "return": float(log["return"][i]), "length": int(log["length"][i]), "max_reward": int(log["max_reward"][i]),
+             "success": bool(log["success"][i]), "initial_object_poses": log["initial_object_poses"][i]} for i in range(num_episodes)]
 
 
 def record_episode(env, actions23) -> dict:

@@ -1,0 +1,270 @@
+"""Device-resident vector env: the batch of env.py's facade with every observation, reward and flag kept in torch tensors on the GPU,
+per-env episodes and gymnasium's NEXT_STEP autoreset done by the library's kernels (avsim_episode_*, include/avsim.h).
+
+    env = make_vec("gym_guided_vision/InsertPeg-3Arms-v0", num_envs=256, max_episode_steps=300)
+    obs, info = env.reset(seed=0)
+    obs, reward, terminated, truncated, info = env.step(action)      # action: float32 [N, nj] on env.device
+
+* obs_format "lerobot" (eval.py:23-66 preprocess_observation, done by the rasteriser): `observation.images.<cam>` float32 [N, 3, H, W] in
+  [0, 1] (a contiguous view of the camera-major image batch) and `observation.state` float32 [N, nj]; "gym": GuidedVisionEnv's keys,
+  `pixels[cam]` uint8 [N, H, W, 3] and `agent_pos` float64 [N, nj].  depth_cameras adds `depth[cam]` float32 [N, H, W].
+* Every tensor returned is a preallocated buffer that the next reset / step overwrites: clone what must outlive the call.
+* NEXT_STEP: an env whose episode ended (terminated or truncated) in call t starts its next episode in call t + 1, whose action does
+  not reach it; that call reports reward 0, flags 0, elapsed 0, the new `info["episode_id"]` and the new episode's first observation.
+  A change of an env's episode id is the signal for per-env policy state.
+* Initial object poses come from Philox4x32-10 keyed by (seed, episode id) inside the library (OBJECT_BOXES below), not from the global
+  numpy RNG that env.py's sample_object_poses consumes like the reference: an episode's poses do not depend on the batch size.
+* torch's GPU must be initialised in the process before the first libavsim handle is created (torch ships its own HIP runtime
+  next to the one libavsim links; the one that comes up second finds no device): import torch and touch the GPU first.
+* No call synchronises the stream it runs on (torch's current stream, re-bound when it changes); check_render_overflow() reads the
+  rasteriser's overflow flags once, where a per-step check would synchronise.
+"""
+from __future__ import annotations
+
+import os
+import warnings
+
+import numpy as np
+
+from . import _ffi
+from .constants import CAMERAS, MODEL_DIR, SIM_PHYSICS_ENV_STEP_RATIO
+from .env import ENVS
+from .sim import load_blob
+
+# Initial positions of the free objects in qpos order: (lo xyz, hi xyz) of the reference's uniform draws (env.py:474-501, 513-543,
+# 604-637, 705-735, 792-818; the same ranges as env.sample_object_poses), and the earlier object whose draw an object shares.
+OBJECT_BOXES = {
+    "insert_peg": ([[0.1, -0.1, 0.01, 0.2, 0.1, 0.01], [-0.1, -0.1, 0.021, -0.2, 0.1, 0.021]], [-1, -1]),
+    "slot_insertion": ([[-0.05, 0.1, 0.0, 0.05, 0.15, 0.0], [-0.08, -0.1, 0.0, 0.08, 0.0, 0.0]], [-1, -1]),
+    "sew_needle": ([[-0.025, -0.025, 0.0, 0.025, 0.1, 0.0], [0.15, -0.025, 0.0, 0.2, 0.1, 0.0]], [-1, -1]),
+    "tube_transfer": ([[0.05, -0.05, 0.0, 0.1, 0.05, 0.0], [0.05, -0.05, 0.0, 0.1, 0.05, 0.0], [-0.1, -0.05, 0.0, -0.05, 0.05, 0.0]],
+                      [-1, 0, -1]),     # ball and tube1 share one draw
+    "hook_package": ([[-0.1, 0.3, 0.2, 0.1, 0.3, 0.3], [-0.1, 0.0, 0.0, 0.1, 0.15, 0.0]], [-1, -1]),
+}
+
+_TASK_OF_CLASS = {"InsertPegEnv": "insert_peg", "SlotInsertionEnv": "slot_insertion", "SewNeedleEnv": "sew_needle",
+                  "TubeTransferEnv": "tube_transfer", "HookPackageEnv": "hook_package"}
+
+
+def philox4x32_10(ctr, key):
+    """Random123's philox4x32-10 on uint32 arrays: ctr [..., 4], key [..., 2] -> [..., 4] (the library's avs::philox4x32_10)."""
+    c = [np.asarray(ctr, dtype=np.uint64)[..., j] for j in range(4)]
+    k0, k1 = (np.asarray(key, dtype=np.uint64)[..., j] for j in range(2))
+    m32 = np.uint64(0xFFFFFFFF)
+    for r in range(10):
+        if r:
+            k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & m32]
+    return np.stack(c, -1).astype(np.uint32)
+
+
+def sample_poses(task, seed, episode_ids):
+    """[n, nobj, 7] initial object poses of the given episode ids: the library's sampler (avsim_sample_poses) restated in numpy."""
+    box, share = (np.asarray(x) for x in OBJECT_BOXES[task])
+    ids = np.asarray(episode_ids, dtype=np.int64).astype(np.uint64)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    out = np.zeros((len(ids), len(share), 7))
+    out[:, :, 3] = 1.0
+    for o in range(len(share)):
+        if 0 <= share[o] < o:
+            out[:, o, :3] = out[:, share[o], :3]
+            continue
+        ctr = np.stack([ids & np.uint64(0xFFFFFFFF), ids >> np.uint64(32), np.full_like(ids, o), np.zeros_like(ids)], -1)
+        x = philox4x32_10(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))
+        u = (x[:, :3].astype(np.float64) + 0.5) * 2.0 ** -32
+        lo, hi = box[o, :3], box[o, 3:]
+        out[:, o, :3] = lo + (hi - lo) * u
+    return out
+
+
+class VecEnv:
+    """num_envs envs of one task on one GPU; see the module's docstring for the semantics."""
+
+    metadata = {"autoreset_mode": "NextStep", "render_modes": []}
+
+    def __init__(self, task, num_arms, num_envs, max_episode_steps, device=None, cameras=(), depth_cameras=(), obs_format="lerobot",
+                 seed=0, terminate_on_success=False, f64=False, options=None, observation_height=480, observation_width=640):
+        import torch
+        assert obs_format in ("lerobot", "gym"), obs_format
+        assert all(c in CAMERAS for c in list(cameras) + list(depth_cameras)), "Invalid camera names"
+        self.torch = torch
+        self.task, self.num_arms, self.num_envs = task, num_arms, int(num_envs)
+        self.max_episode_steps, self.terminate_on_success = int(max_episode_steps), bool(terminate_on_success)
+        self.cameras, self.depth_cameras, self.obs_format = list(cameras), list(depth_cameras), obs_format
+        self.observation_height, self.observation_width = int(observation_height), int(observation_width)
+        if not torch.cuda.is_available():
+            raise RuntimeError("vec_env: torch sees no GPU -- initialise torch's GPU before creating any other libavsim handle in this process")
+        d = torch.device("cuda", device) if isinstance(device, int) else torch.device(device if device is not None else "cuda")
+        self.device = torch.device("cuda", d.index if d.index is not None else torch.cuda.current_device())
+        blob, self.manifest = load_blob(task, num_arms)
+        flags = _ffi.AVSIM_IO_DEVICE | (_ffi.AVSIM_F64_PHYSICS if f64 else 0)
+        with torch.cuda.device(self.device):
+            self.h = _ffi.Handle(blob, self.num_envs, self.device.index, flags)
+        self.L, self.nj, self.nobj, self.max_reward = self.h.L, self.h.nj, self.h.nobj, self.h.max_reward
+        self.num_joints = self.nj
+        # the colour images as the gym facades draw them (env.py: shadows, 4 samples, smooth shading)
+        options = {"render_shadows": 1, "render_samples": 4, "render_smooth": 1, **(options or {})}
+        for k, v in options.items():
+            self.h.check(self.L.avsim_set_option(self.h.h, k.encode(), float(v)))
+        names = self.manifest["camera_names"]
+        self._cam_ids = np.array([names.index(c) for c in self.cameras], dtype=np.int32)
+        self._depth_ids = np.array([names.index(c) for c in self.depth_cameras], dtype=np.int32)
+        if self.cameras:
+            with open(os.path.join(MODEL_DIR, "visual_meshes.avv"), "rb") as f:
+                lib = f.read()
+            self.h.check(self.L.avsim_load_visual(self.h.h, lib, len(lib)))
+            self.h.check(self.L.avsim_set_option(self.h.h, b"render_proxies", 0.0))
+            self.h.check(self.L.avsim_set_option(self.h.h, b"render_cam_major", 1.0))     # every camera's batch contiguous
+        self._box = np.ascontiguousarray(OBJECT_BOXES[task][0], dtype=np.float64)
+        self._share = np.ascontiguousarray(OBJECT_BOXES[task][1], dtype=np.int32)
+        assert self._box.shape == (self.nobj, 6)
+        self.seed = int(seed)
+        self._log_capacity = 0
+        self._stream = None
+        # output buffers (overwritten by every call)
+        N, dev, H, W = self.num_envs, self.device, self.observation_height, self.observation_width
+        self._ap = torch.zeros((N, self.nj), dtype=torch.float64, device=dev)
+        self._state = torch.zeros((N, self.nj), dtype=torch.float32, device=dev)
+        self._reward = torch.zeros(N, dtype=torch.int32, device=dev)
+        self._success = torch.zeros(N, dtype=torch.uint8, device=dev)
+        self._term = torch.zeros(N, dtype=torch.uint8, device=dev)
+        self._trunc = torch.zeros(N, dtype=torch.uint8, device=dev)
+        self._id = torch.zeros(N, dtype=torch.int64, device=dev)
+        self._elapsed = torch.zeros(N, dtype=torch.int32, device=dev)
+        self._diag = torch.zeros((N, 4), dtype=torch.int32, device=dev)
+        nc = len(self.cameras)
+        if obs_format == "lerobot":
+            self._img = torch.zeros((nc, N, 3, H, W), dtype=torch.float32, device=dev) if nc else None
+        else:
+            self._img = torch.zeros((nc, N, H, W, 3), dtype=torch.uint8, device=dev) if nc else None
+        self._depth = torch.zeros((N, len(self.depth_cameras), H, W), dtype=torch.float32, device=dev) if self.depth_cameras else None
+        self._bind_stream()
+        self._setup(self.seed, 0)
+
+    # -- plumbing ----------------------------------------------------------------------------------
+    def _bind_stream(self):
+        s = self.torch.cuda.current_stream(self.device)
+        if self._stream is None or s.cuda_stream != self._stream.cuda_stream:
+            self.h.check(self.L.avsim_set_stream(self.h.h, s.cuda_stream))
+            self._stream = s
+
+    def _setup(self, seed, log_capacity):
+        self._bind_stream()
+        self.seed, self._log_capacity = int(seed), int(log_capacity)
+        self.h.check(self.L.avsim_episode_setup(self.h.h, self._box.ctypes.data, self._share.ctypes.data, self.seed & 0xFFFFFFFFFFFFFFFF,
+                                                self.max_episode_steps, int(self.terminate_on_success), self._log_capacity))
+
+    def _obs(self):
+        L, h = self.L, self.h.h
+        H, W = self.observation_height, self.observation_width
+        if self.cameras:
+            ids, nc = self._cam_ids.ctypes.data, len(self.cameras)
+            if self.obs_format == "lerobot":
+                self.h.check(L.avsim_render_rgb_f32(h, ids, nc, H, W, self._img.data_ptr()))
+            else:
+                self.h.check(L.avsim_render_rgb(h, ids, nc, H, W, self._img.data_ptr()))
+        if self.depth_cameras:
+            self.h.check(L.avsim_render_depth(h, self._depth_ids.ctypes.data, len(self.depth_cameras), H, W, self._depth.data_ptr()))
+        if self.obs_format == "lerobot":
+            self._state.copy_(self._ap)
+            obs = {f"observation.images.{c}": self._img[i] for i, c in enumerate(self.cameras)}
+            obs["observation.state"] = self._state
+        else:
+            obs = {"pixels": {c: self._img[i] for i, c in enumerate(self.cameras)}, "agent_pos": self._ap}
+        if self.depth_cameras:
+            obs["depth"] = {c: self._depth[:, i] for i, c in enumerate(self.depth_cameras)}
+        return obs
+
+    # -- gym API -------------------------------------------------------------------------------------
+    def reset(self, seed=None, options=None):
+        """seed: restart the episode ids at 0 under this seed (and drop the records); options={"reset_mask": bool [N]}: only those envs
+        start a new episode, the others keep theirs."""
+        self._bind_stream()
+        if seed is not None:
+            self._setup(seed, self._log_capacity)
+        mask = (options or {}).get("reset_mask")
+        if mask is not None:
+            mask = self.torch.as_tensor(mask, device=self.device).to(self.torch.uint8).contiguous()
+            assert mask.shape == (self.num_envs,)
+        self.h.check(self.L.avsim_episode_reset(self.h.h, _ffi.ptr(mask), self._ap.data_ptr(), self._id.data_ptr()))
+        for t in (self._elapsed, self._success, self._reward, self._term, self._trunc):      # (the envs that keep their episode keep their last step's)
+            t.masked_fill_(mask.bool(), 0) if mask is not None else t.zero_()
+        return self._obs(), {"episode_id": self._id, "elapsed_steps": self._elapsed, "is_success": self._success.view(self.torch.bool)}
+
+    def step(self, action):
+        torch = self.torch
+        self._bind_stream()
+        assert isinstance(action, torch.Tensor) and action.dtype == torch.float32 and action.device == self.device, \
+            "step(action): a float32 tensor on the env's device"
+        assert tuple(action.shape) == (self.num_envs, self.nj), f"action shape {tuple(action.shape)} != {(self.num_envs, self.nj)}"
+        a = action.contiguous()
+        self.h.check(self.L.avsim_episode_step(self.h.h, a.data_ptr(), SIM_PHYSICS_ENV_STEP_RATIO, self._ap.data_ptr(), self._reward.data_ptr(),
+                                               self._success.data_ptr(), self._term.data_ptr(), self._trunc.data_ptr(), self._id.data_ptr(),
+                                               self._elapsed.data_ptr()))
+        self.h.check(self.L.avsim_get_diag(self.h.h, self._diag.data_ptr()))
+        obs = self._obs()
+        diverged = ((self._diag[:, 3] & 1) != 0) & (self._elapsed > 0)       # (an env that starts an episode in this call has not diverged)
+        info = {"is_success": self._success.view(torch.bool), "episode_id": self._id, "elapsed_steps": self._elapsed, "diverged": diverged}
+        return obs, self._reward, self._term.view(torch.bool), self._trunc.view(torch.bool), info
+
+    # -- episode records -----------------------------------------------------------------------------
+    def start_log(self, log_capacity, seed=None):
+        """Restart the episode ids at 0 (under `seed`, default the current one) and keep the records of ids [0, log_capacity)."""
+        self._setup(self.seed if seed is None else seed, log_capacity)
+
+    def episode_count(self):
+        """(episodes started, episodes finished) since the last seed / start_log; synchronises."""
+        c = np.zeros(2, dtype=np.int64)
+        self.h.check(self.L.avsim_episode_count(self.h.h, c.ctypes.data))
+        return int(c[0]), int(c[1])
+
+    def episode_log(self, n):
+        """Records of episode ids [0, n) as numpy arrays (length 0: not finished); synchronises."""
+        ret, length = np.zeros(n), np.zeros(n, dtype=np.int32)
+        mr, su = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint8)
+        obj = np.zeros((n, self.nobj, 7))
+        self.h.check(self.L.avsim_episode_log(self.h.h, n, ret.ctypes.data, length.ctypes.data, mr.ctypes.data, su.ctypes.data, obj.ctypes.data))
+        return {"return": ret, "length": length, "max_reward": mr, "success": su.astype(bool), "initial_object_poses": obj}
+
+    def sample_poses(self, episode_ids, seed=None):
+        """The library's initial poses [n, nobj, 7] of the given episode ids (under `seed`, default the env's); synchronises."""
+        ids = np.ascontiguousarray(episode_ids, dtype=np.int64)
+        out = np.zeros((len(ids), self.nobj, 7))
+        if len(ids):
+            t_ids = self.torch.from_numpy(ids).to(self.device)
+            t_out = self.torch.zeros((len(ids), self.nobj, 7), dtype=self.torch.float64, device=self.device)
+            self._bind_stream()
+            self.h.check(self.L.avsim_sample_poses(self.h.h, (self.seed if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF, len(ids),
+                                                   t_ids.data_ptr(), t_out.data_ptr()))
+            out = t_out.cpu().numpy()
+        return out
+
+    def check_render_overflow(self):
+        """Overflow flags of the last colour render (bit 0 triangle records, bit 1 tile lists; 0 = complete images): warns when set.
+        Synchronises, so it is read once at the end of an evaluation rather than per step."""
+        if not self.cameras:
+            return 0
+        info = np.zeros(4, dtype=np.int32)
+        self.h.check(self.L.avsim_visual_info(self.h.h, info.ctypes.data))
+        if info[2]:
+            warnings.warn(f"vector env: a view ran out of triangle records / tile-list entries (flags {int(info[2])}): triangles were "
+                          "dropped from some images", RuntimeWarning, stacklevel=2)
+        return int(info[2])
+
+    def close(self):
+        if getattr(self, "h", None) is not None:
+            self.h.check(self.L.avsim_sync(self.h.h))
+            self.h.close()
+            self.h = None
+
+
+def make_vec(env_id, num_envs, max_episode_steps, device=None, cameras=None, depth_cameras=(), obs_format="lerobot", seed=0,
+             terminate_on_success=False, f64=False, options=None, observation_height=None, observation_width=None):
+    """A VecEnv of a registry id (env.ENVS); cameras default to the registry's, the image size to its 480 x 640."""
+    spec = ENVS[env_id]
+    return VecEnv(_TASK_OF_CLASS[spec["env"]], spec["num_arms"], num_envs, max_episode_steps, device=device,
+                  cameras=spec["cameras"] if cameras is None else cameras, depth_cameras=depth_cameras, obs_format=obs_format, seed=seed,
+                  terminate_on_success=terminate_on_success, f64=f64, options=options,
+                  observation_height=spec["observation_height"] if observation_height is None else observation_height,
+                  observation_width=spec["observation_width"] if observation_width is None else observation_width)

@@ -200,6 +200,46 @@ int avsim_visual_info(avsim_t* h, int32_t info[4]);
 int avsim_visual_profile(avsim_t* h, int32_t* out, int nviews);
 int avsim_camera_count(const avsim_t* h);
 
+/* avsim_render_rgb's visual-scene image as a policy reads it (eval.py:23-66 preprocess_observation: u8 HWC -> float32 CHW / 255):
+ * out = float32[N][ncam][3][height][width] ([ncam][N][3][height][width] under "render_cam_major"), every value (float)u8 / 255 of the
+ * u8 image of the same call, bit for bit.  Needs the visual scene (avsim_load_visual, render_proxies 0).  Pointer conventions as
+ * avsim_render_depth; in device mode nothing synchronises once a call with the same cameras has run. */
+int avsim_render_rgb_f32(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, float* out);
+
+/* Per-env episodes on the device (a vector env with gymnasium's NEXT_STEP autoreset; av_aloha_amd/vec_env.py).  Pointers follow the
+ * handle's I/O mode, except box / share of the set-up (host pointers).  In device mode no step, reset, sample or render call
+ * synchronises; avsim_episode_setup does (it reallocates the records: once per evaluation), and so do avsim_episode_log /
+ * avsim_episode_count given host pointers.
+ *
+ * avsim_episode_setup: box = double[nobj][6] (lo xyz, hi xyz of every free object's initial position, qpos order), share = int32[nobj]
+ * (-1, or the index of an earlier object whose position this one takes: TubeTransfer's tube1 and ball), seed; an episode ends after
+ * max_episode_steps steps (truncated) or, with terminate_on_success, at success (terminated); the records of episode ids
+ * [0, log_capacity) are kept.  Clears the id counter and the records; every env starts an episode at its next reset / step.
+ * Initial poses: Philox4x32-10 with key = seed and counter = (episode id, object index, 0); coordinate k of an object's block x gives
+ * u = (x_k + 0.5) 2^-32 and pos = lo + (hi - lo) u in double (each operation rounded); identity orientation.  They depend on
+ * (seed, episode id) only. */
+int avsim_episode_setup(avsim_t* h, const double* box, const int32_t* share, uint64_t seed, int max_episode_steps,
+                        int terminate_on_success, int64_t log_capacity);
+/* the sampler as a pure function: obj_qpos double[n][nobj][7] of episode_id int64[n] under `seed` (the set-up's boxes) */
+int avsim_sample_poses(avsim_t* h, uint64_t seed, int n, const int64_t* episode_id, double* obj_qpos);
+/* envs with mask[i] != 0 (uint8[N]; NULL = all) start an episode now: the next ids of the counter in env-index order, the state of
+ * avsim_reset at that episode's poses (no forward pass: a step starts from qpos, qvel, ctrl, warmstart and latch alone).  agent_pos
+ * double[N][nj] and episode_id int64[N] of every env (either may be NULL). */
+int avsim_episode_reset(avsim_t* h, const uint8_t* mask, double* agent_pos, int64_t* episode_id);
+/* avsim_step, then the episode bookkeeping.  An env whose episode ended in the previous call (NEXT_STEP) starts its next episode in
+ * this one: the action does not reach it, and it reports reward 0, success / terminated / truncated 0, elapsed 0, its new id and the
+ * new state's agent_pos (avsim_observe after avsim_reset of the same poses, bit for bit).  The others report the step with elapsed =
+ * steps of the episode so far; truncated = elapsed reached max_episode_steps or the state diverged (avsim_get_diag bit 0).  Outputs:
+ * agent_pos double[N][nj], reward int32[N], success / terminated / truncated uint8[N], episode_id int64[N], elapsed int32[N]; any may
+ * be NULL. */
+int avsim_episode_step(avsim_t* h, const float* action, int nsub, double* agent_pos, int32_t* reward, uint8_t* success,
+                       uint8_t* terminated, uint8_t* truncated, int64_t* episode_id, int32_t* elapsed);
+/* records of episode ids [0, n), n <= log_capacity: return double, length int32 (0 = not finished yet), max reward int32, success seen
+ * uint8, initial object poses double[nobj][7]; any may be NULL */
+int avsim_episode_log(avsim_t* h, int64_t n, double* ret, int32_t* length, int32_t* max_reward, uint8_t* success, double* obj_qpos0);
+/* count = {episodes started, episodes finished} since avsim_episode_setup */
+int avsim_episode_count(avsim_t* h, int64_t count[2]);
+
 /* get_reward of the handle's task (gym_guided_vision/gym_guided_vision/env.py:425-863, five subclasses) evaluated on
  * caller-supplied contact lists instead of the simulator's own contacts: geom_pairs = int32[nsets][cap][2], ids into the
  * model's collision geom table (manifest "geom_names"), a slot with a negative id is empty.  The kernel applies the same
