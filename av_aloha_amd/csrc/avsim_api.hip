@@ -15,6 +15,7 @@
 #include "../../include/avsim.h"
 #include "avsim_episode.hip.h"
 #include "avsim_ik.hip.h"
+#include "avsim_jpeg.hip.h"
 #include "avsim_model.h"
 #include "avsim_phys.hip.h"
 #include "avsim_render.hip.h"
@@ -75,6 +76,7 @@ struct avsim {
     PhysHost phys;  // device model image + launch configuration (avsim_phys.hip.h)
     RenderHost render;   // depth renderer (avsim_render.hip.h)
     VisHost vis;         // colour images of the visual meshes (avsim_vis.hip.h), once avsim_load_visual has run
+    JpegHost jpeg;       // JPEG streams of such images (avsim_jpeg.hip.h): tables per shape, the intervals' staging area
     // the state's version: bumped by everything that writes qpos (reset, the steps, set_state); the image calls skip their pose pass and the shadow
     // map when they already hold this version's (a facade that fetches its cameras one call at a time repeats neither)
     unsigned long long state_ver = 1, xpose_ver = 0;
@@ -466,6 +468,7 @@ void avsim_destroy(avsim_t* h) {
     h->phys.destroy();
     h->render.destroy();
     h->vis.destroy();
+    h->jpeg.destroy();
     for (void* p : {h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, (void*)h->d_latch})
         if (p) (void)hipFree(p);
     for (void* p : h->d_io)
@@ -922,6 +925,40 @@ int avsim_render_rgb(avsim_t* h, const int32_t* cam_ids, int ncam, int height, i
 // the visual scene's colour images as a policy reads them (eval.py preprocess_observation): float32 planar CHW, (float)u8 / 255
 int avsim_render_rgb_f32(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, float* out) {
     return render_images(h, cam_ids, ncam, height, width, out, true, true);
+}
+
+// JPEG streams of a batch of images (av_aloha_amd/jpeg.py is the specification; csrc/avsim_jpeg.hip.h)
+int64_t avsim_jpeg_bound(int height, int width) {
+    if (height < 1 || width < 1 || height > 65535 || width > 65535) return AVSIM_EINVAL;
+    return jpeg_bound(height, width);
+}
+int avsim_jpeg_encode(avsim_t* h, const void* img, int fmt, const int32_t* index, int nimg, int height, int width, int quality, uint8_t* out,
+                      int64_t stride, int32_t* out_len) {
+    if (!h) return AVSIM_EINVAL;
+    if (!img || !out || !out_len || nimg < 0 || stride < 0) { h->set_error("avsim_jpeg_encode: bad arguments"); return AVSIM_EINVAL; }
+    if (fmt != 0 && fmt != 1) { h->set_error("avsim_jpeg_encode: fmt is 0 (u8 HWC) or 1 (float32 CHW)"); return AVSIM_EINVAL; }
+    if (quality < 1 || quality > 100) { h->set_error("avsim_jpeg_encode: quality %d outside 1..100", quality); return AVSIM_EINVAL; }
+    if (height < 1 || width < 1 || height > 65535 || width > 65535) { h->set_error("avsim_jpeg_encode: image size %d x %d outside 1..65535", height, width); return AVSIM_EINVAL; }
+    if (nimg == 0) return AVSIM_OK;
+    AVS_ON_DEVICE(h);
+    int rc;
+    const void *dimg = nullptr, *dindex = nullptr;
+    void *dout = nullptr, *dlen = nullptr;
+    if (!h->io_device && index) {          // (a host caller's index says how many images `img` holds)
+        int top = 0;
+        for (int i = 0; i < nimg; i++) {
+            if (index[i] < 0) { h->set_error("avsim_jpeg_encode: negative index"); return AVSIM_EINVAL; }
+            top = index[i] > top ? index[i] : top;
+        }
+        if ((rc = h->in(8, img, (size_t)(top + 1) * height * width * (fmt ? 12 : 3), &dimg))) return rc;
+    } else if ((rc = h->in(8, img, (size_t)nimg * height * width * (fmt ? 12 : 3), &dimg))) return rc;
+    if (index && (rc = h->in(9, index, sizeof(int32_t) * (size_t)nimg, &dindex))) return rc;
+    if ((rc = h->out_begin(10, out, (size_t)nimg * stride, &dout))) return rc;
+    if ((rc = h->out_begin(11, out_len, sizeof(int32_t) * (size_t)nimg, &dlen))) return rc;
+    if ((rc = h->jpeg.launch(h->stream, dimg, fmt, (const int*)dindex, nimg, height, width, quality, (uint8_t*)dout, stride, (int*)dlen, h->err))) return AVSIM_EHIP;
+    if ((rc = h->out_end(10, out, (size_t)nimg * stride))) return rc;
+    if ((rc = h->out_end(11, out_len, sizeof(int32_t) * (size_t)nimg))) return rc;
+    return h->finish();
 }
 
 // The visual scene of avsim_render_rgb: the mesh library (models/visual_meshes.avv, compiler/vismesh.py) against the instances the

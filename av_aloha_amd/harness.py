@@ -7,7 +7,8 @@
   the env returns pixels, plus the success / return bookkeeping the reference leaves out.  Works on one env (reference shapes)
   and on a batch (`num_envs > 1`).
 * `evaluate_vec`: the same evaluation on the device-resident vector env (vec_env.py): per-env episodes, NEXT_STEP autoreset, one
-  record per episode id, no host round trip per step.
+  record per episode id, no host round trip per step; optionally the first episodes' videos (eval.py:118-128) as Motion-JPEG AVI files
+  whose frames are encoded on the device (jpeg.py, mjpeg.py).
 * `record_episode` / `save_episode` / `load_episode` (record_sim_episodes.py:83-128, :155-212): a scripted Cartesian action
   sequence replaces the VR headset; the episode holds T = len(actions) + 1 time steps with `/observations/qpos` (T, 21),
   `/observations/qvel` (T, 21), `/observations/all_qpos` (T, nq), `/action` (T, 21: the joint-space command with
@@ -56,12 +57,14 @@ def preprocess_observation(observations: dict) -> dict:
     return out
 
 
-def rollout(env, select_action, episode_len: int, num_episodes: int = 1, reset_policy=None):
+def rollout(env, select_action, episode_len: int, num_episodes: int = 1, reset_policy=None, video_path: str | None = None, video_quality: int = 90):
     """select_action(dict of tensors) -> array-like (batch, action_dim).  Returns per-episode dicts with 'return' (sum of the
-    rewards), 'success' (is_success seen at any step), 'max_reward' and the captured 'frames'."""
+    rewards), 'success' (is_success seen at any step), 'max_reward' and the captured 'frames'.  video_path: a format string taking the
+    episode number ("outputs/rollout_{}.avi", eval.py:123); the episode's zed_cam_left frames are then also encoded on the device
+    (BatchedSim.encode_jpeg) and written as a Motion-JPEG AVI at 50 frames per second (eval.py:128); of a batched env, env 0's frames."""
     results = []
     batched = getattr(env, "num_envs", 1) > 1
-    for _ in range(num_episodes):
+    for episode in range(num_episodes):
         if reset_policy is not None:
             reset_policy()
         observation, info = env.reset()
@@ -77,26 +80,126 @@ def rollout(env, select_action, episode_len: int, num_episodes: int = 1, reset_p
             px = observation.get("pixels") or {}
             if "zed_cam_left" in px:
                 frames.append(px["zed_cam_left"])
+        if video_path is not None and frames:
+            from .mjpeg import AviWriter
+            path = video_path.format(episode)
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            stack = np.stack([f[0] if batched else f for f in frames])
+            with AviWriter(path, stack.shape[2], stack.shape[1], fps=50) as w:
+                for stream in env.sim.encode_jpeg(stack, quality=video_quality):
+                    w.add(stream)
         results.append({"return": ret, "success": success if batched else bool(success[0]), "max_reward": env.max_reward, "frames": frames})
     return results
 
 
-def evaluate_vec(env, select_action, num_episodes: int, seed: int | None = None) -> list:
+class _VideoRecorder:
+    """The first `episodes` episodes of a vector env as Motion-JPEG files: every step's frames of envs [0, episodes) are encoded on the
+    device into a chunk of buffers next to their episode ids; a full chunk comes to the host in one copy and is split over the files."""
+
+    def __init__(self, env, video_dir, camera, episodes, quality, fps):
+        from .mjpeg import AviWriter
+        import torch
+        self.env, self.k, self.quality, self.camera = env, int(episodes), int(quality), camera
+        os.makedirs(video_dir, exist_ok=True)
+        H, W = env.observation_height, env.observation_width
+        self.writers = [AviWriter(os.path.join(video_dir, f"rollout_{i}.avi"), W, H, fps=fps) for i in range(self.k)]
+        self.open = [True] * self.k
+        stride = env.jpeg_stride(quality)
+        self.chunk = max(1, min(64, (256 << 20) // (stride * self.k)))
+        self.buf = torch.empty((self.chunk, self.k, stride), dtype=torch.uint8, device=env.device)
+        self.len = torch.zeros((self.chunk, self.k), dtype=torch.int32, device=env.device)
+        self.ids = torch.zeros((self.chunk, self.k), dtype=torch.int64, device=env.device)
+        self.fill = 0
+
+    @property
+    def active(self):
+        return any(self.open)
+
+    def add(self, info):
+        """After a step: its frames of envs [0, k)."""
+        c = self.fill
+        self.env.encode_jpeg(self.camera, envs=self.k, quality=self.quality, out=self.buf[c], out_len=self.len[c])
+        self.ids[c].copy_(info["episode_id"][:self.k])
+        self.fill += 1
+        if self.fill == self.chunk:
+            self.flush()
+
+    def flush(self):
+        n, self.fill = self.fill, 0
+        if n == 0:
+            return
+        ln, ids = self.len[:n].cpu().numpy(), self.ids[:n].cpu().numpy()          # (these copies wait for the stream)
+        stride = self.buf.shape[2]
+        keep = (ids == np.arange(self.k)[None]) & np.asarray(self.open)[None]
+        if (ln[keep] > stride).any():
+            raise RuntimeError(f"evaluate_vec: a frame's JPEG stream ({int(ln[keep].max())} B) is longer than the {stride} B reserved for it")
+        width = int(ln[keep].max()) if keep.any() else 0
+        data = self.buf[:n, :, :width].cpu().numpy()                                # only as many bytes per stream as the longest one has
+        for c in range(n):
+            for e in range(self.k):
+                if not self.open[e]:
+                    continue
+                if keep[c, e]:
+                    self.writers[e].add(data[c, e, :ln[c, e]].tobytes())
+                else:                                                               # env e went on to a later episode: its video is complete
+                    self.writers[e].close()
+                    self.open[e] = False
+
+    def close(self, ok=True):
+        try:
+            if ok:
+                self.flush()
+        finally:
+            for e, w in enumerate(self.writers):
+                if self.open[e]:
+                    w.close() if ok else w.abort()
+                    self.open[e] = False
+
+
+def evaluate_vec(env, select_action, num_episodes: int, seed: int | None = None, video_dir: str | None = None, video_camera: str | None = None,
+                 video_episodes: int = 0, video_quality: int = 90, video_fps: float = 50) -> list:
     """Policy evaluation on a device-resident vector env (vec_env.make_vec): the episode ids restart at 0 and the env is stepped until
     the episodes with ids [0, num_episodes) have all finished; envs go on to later ids by themselves (NEXT_STEP autoreset).
     select_action(obs, info) -> float32 [N, nj] tensor on the env's device; info["episode_id"] changing marks an env's new episode.
     The host reads the episode counter once per max_episode_steps calls.  Returns one dict per id: 'episode_id', 'return', 'length',
-    'max_reward', 'success', 'initial_object_poses'."""
+    'max_reward', 'success', 'initial_object_poses'.
+
+    Videos (eval.py:96-126 keeps zed_cam_left's frames and writes rollout_<i>.mp4): with video_dir and video_episodes = k > 0 the episodes
+    with ids 0 .. k-1 -- the first episodes of envs 0 .. k-1 -- are written to <video_dir>/rollout_<id>.avi (Motion-JPEG, mjpeg.py), one
+    frame per step call of the episode (the observation the call returned; the reset observation is not a frame), `length` frames in all.
+    video_camera defaults to zed_cam_left when the env renders it, else to its first camera.  The frames are encoded on the device
+    (VecEnv.encode_jpeg) into buffers that hold a chunk of calls and come to the host once per chunk -- that copy waits for the stream,
+    the steps in between do not; recording stops when those episodes are over.  The records are the same with and without video.
+    ValueError: video_episodes > env.num_envs, or a camera the env does not render."""
+    video = None
+    if video_dir is not None and video_episodes > 0:
+        if video_episodes > env.num_envs:
+            raise ValueError(f"evaluate_vec: video_episodes={video_episodes} > num_envs={env.num_envs} (the recorded episodes are the first episodes of envs 0 .. k-1)")
+        if video_camera is None:
+            video_camera = "zed_cam_left" if "zed_cam_left" in env.cameras else (env.cameras[0] if env.cameras else None)
+        if video_camera not in env.cameras:
+            raise ValueError(f"evaluate_vec: the env does not render {video_camera!r} (cameras: {list(env.cameras)})")
     env.start_log(num_episodes, seed=seed)
     observation, info = env.reset()
+    if video_dir is not None and video_episodes > 0:
+        video = _VideoRecorder(env, video_dir, video_camera, video_episodes, video_quality, video_fps)
     calls = 0
-    while True:
-        observation, reward, terminated, truncated, info = env.step(select_action(observation, info))
-        calls += 1
-        if calls % env.max_episode_steps == 0 and env.episode_count()[1] >= num_episodes:
-            log = env.episode_log(num_episodes)
-            if (log["length"] > 0).all():
-                break
+    try:
+        while True:
+            observation, reward, terminated, truncated, info = env.step(select_action(observation, info))
+            calls += 1
+            if video is not None and video.active:
+                video.add(info)
+            if calls % env.max_episode_steps == 0 and env.episode_count()[1] >= num_episodes:
+                log = env.episode_log(num_episodes)
+                if (log["length"] > 0).all():
+                    break
+    except BaseException:
+        if video is not None:
+            video.close(ok=False)
+        raise
+    if video is not None:
+        video.close()
     env.check_render_overflow()
     return [{"episode_id": i, "return": float(log["return"][i]), "length": int(log["length"][i]), "max_reward": int(log["max_reward"][i]),
              "success": bool(log["success"][i]), "initial_object_poses": log["initial_object_poses"][i]} for i in range(num_episodes)]

@@ -167,6 +167,34 @@ class BatchedSim:
                               f"at {height}x{width}: triangles were dropped from the image", RuntimeWarning, stacklevel=2)
         return out
 
+    def encode_jpeg(self, frames_u8, quality=90):
+        """JPEG streams (a list of bytes) of u8 frames [n, H, W, 3] -- or one [H, W, 3] --, encoded on the device (avsim_jpeg_encode): the
+        bytes of av_aloha_amd.jpeg.encode_reference.  The frames go to the device and only the streams come back."""
+        f = np.ascontiguousarray(frames_u8)
+        if f.ndim == 3:
+            f = f[None]
+        if f.dtype != np.uint8 or f.ndim != 4 or f.shape[3] != 3:
+            raise ValueError("encode_jpeg takes u8 frames [n, H, W, 3]")
+        n, H, W, _ = f.shape
+        L, out = self.h.L, []
+        bound = int(L.avsim_jpeg_bound(H, W))
+        if bound < 0:
+            raise ValueError(f"encode_jpeg: frame size {H} x {W}")
+        batch = max(1, min(n, (256 << 20) // (H * W * 3)))
+
+        def run(frames, stride):
+            buf = np.empty((len(frames), stride), dtype=np.uint8)
+            ln = np.empty(len(frames), dtype=np.int32)
+            self.h.check(L.avsim_jpeg_encode(self.h.h, frames.ctypes.data, 0, None, len(frames), H, W, int(quality), buf.ctypes.data, stride, ln.ctypes.data))
+            return buf, ln
+        for i0 in range(0, n, batch):
+            frames = f[i0:i0 + batch]
+            buf, ln = run(frames, min(bound, (H * W * 3 // 4 + 4095) // 4096 * 4096))
+            if int(ln.max()) > buf.shape[1]:          # some stream did not fit: its length says what it needs
+                buf, ln = run(frames, int(ln.max()))
+            out += [buf[i, :ln[i]].tobytes() for i in range(len(frames))]
+        return out
+
     def reward_from_pairs(self, geom_pairs, latch=None):
         """The task's get_reward (env.py:425-863) on explicit contact lists: geom_pairs int [nsets, cap, 2] (collision
         geom ids, negative = empty slot); latch int32 [nsets] is updated in place.  Returns int32 [nsets]."""

@@ -240,6 +240,46 @@ class VecEnv:
             out = t_out.cpu().numpy()
         return out
 
+    def jpeg_stride(self, quality=90):
+        """Bytes encode_jpeg reserves per stream by default: half the raw frame, never more than the worst case (avsim_jpeg_bound).  A
+        rendered 480 x 640 frame takes 31 KB at quality 90 and 95 KB at 100."""
+        H, W = self.observation_height, self.observation_width
+        return int(min(self.L.avsim_jpeg_bound(H, W), (H * W * 3 // 2 + 4095) // 4096 * 4096))
+
+    def encode_jpeg(self, camera, envs=None, quality=90, out=None, out_len=None):
+        """JPEG streams of `camera`'s CURRENT observation (the images the last reset / step returned), encoded on the device from the
+        observation buffer itself (lerobot format: the float32 planes, gym format: the u8 pixels; both give the same bytes).  envs: None =
+        all, an int n = the first n envs, or an int32 index tensor on the env's device (values outside [0, num_envs) are clamped).
+        -> (out uint8 [n, stride], out_len int32 [n]) on the device; stream i is out[i, :out_len[i]], and one with out_len[i] > stride did
+        not fit (pass a larger `out`; the default stride is jpeg_stride()).  out / out_len: buffers to write into.  Does not synchronise."""
+        torch = self.torch
+        self._bind_stream()
+        if camera not in self.cameras:
+            raise ValueError(f"encode_jpeg: the env does not render {camera!r} (cameras: {self.cameras})")
+        index = None
+        if envs is None:
+            n = self.num_envs
+        elif isinstance(envs, int):
+            n = envs
+            if not 0 <= n <= self.num_envs:
+                raise ValueError(f"encode_jpeg: envs={n} of {self.num_envs}")
+        else:
+            assert isinstance(envs, torch.Tensor) and envs.dtype == torch.int32 and envs.device == self.device and envs.ndim == 1, \
+                "encode_jpeg(envs=...): an int32 index tensor on the env's device"
+            index = envs.clamp(0, self.num_envs - 1).contiguous()
+            n = int(index.shape[0])
+        if out is None:
+            out = torch.empty((n, self.jpeg_stride(quality)), dtype=torch.uint8, device=self.device)
+        if out_len is None:
+            out_len = torch.empty(n, dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.uint8 and out.device == self.device and out.ndim == 2 and out.shape[0] == n and out.is_contiguous()
+        assert out_len.dtype == torch.int32 and out_len.device == self.device and tuple(out_len.shape) == (n,) and out_len.is_contiguous()
+        img = self._img[self.cameras.index(camera)]
+        self.h.check(self.L.avsim_jpeg_encode(self.h.h, img.data_ptr(), 1 if self.obs_format == "lerobot" else 0, _ffi.ptr(index), n,
+                                              self.observation_height, self.observation_width, int(quality), out.data_ptr(), int(out.shape[1]),
+                                              out_len.data_ptr()))
+        return out, out_len
+
     def check_render_overflow(self):
         """Overflow flags of the last colour render (bit 0 triangle records, bit 1 tile lists; 0 = complete images): warns when set.
         Synchronises, so it is read once at the end of an evaluation rather than per step."""

@@ -206,6 +206,22 @@ int avsim_camera_count(const avsim_t* h);
  * avsim_render_depth; in device mode nothing synchronises once a call with the same cameras has run. */
 int avsim_render_rgb_f32(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, float* out);
 
+/* Baseline JPEG streams of rendered frames, encoded on the device (csrc/avsim_jpeg.hip.h): SOF0, 8 bit, JFIF, Y Cb Cr 4:2:0, the Annex K
+ * Huffman tables in every frame, one restart interval per MCU row, integer arithmetic throughout -- byte for byte the stream of
+ * av_aloha_amd/jpeg.py encode_reference, which is its specification (colour matrix, DCT, quantiser rounding: DESIGN 8.y).
+ * avsim_jpeg_bound: worst-case stream length of one height x width image at any quality (header + every coefficient at its longest
+ * code, every byte stuffed); AVSIM_EINVAL for a size outside 1..65535.
+ * avsim_jpeg_encode: nimg images -> nimg streams.  fmt 0: u8 [nimg][H][W][3] (avsim_render_rgb's layout); fmt 1: float32 [nimg][3][H][W]
+ * in [0, 1] (avsim_render_rgb_f32's), turned back into u8 by (int)(v * 255 + 0.5f).  index (may be NULL, int32 [nimg]): encode images
+ * index[i] of the batch `img` points to instead of images 0..nimg-1 (a device caller vouches for the range: nothing reads it back).
+ * out: u8 [nimg][stride]; out_len: int32 [nimg] = the stream's length.  A stream longer than stride is not written past stride and is
+ * invalid; its length still says what it needed.  img, index, out and out_len follow the handle's I/O mode like every other bulk
+ * pointer; with AVSIM_IO_DEVICE nothing synchronises once a call of the same size and quality has run.  AVSIM_EINVAL: fmt, quality
+ * outside 1..100, height or width < 1 or > 65535. */
+int64_t avsim_jpeg_bound(int height, int width);
+int avsim_jpeg_encode(avsim_t* h, const void* img, int fmt, const int32_t* index, int nimg, int height, int width, int quality,
+                      uint8_t* out, int64_t stride, int32_t* out_len);
+
 /* Per-env episodes on the device (a vector env with gymnasium's NEXT_STEP autoreset; av_aloha_amd/vec_env.py).  Pointers follow the
  * handle's I/O mode, except box / share of the set-up (host pointers).  In device mode no step, reset, sample or render call
  * synchronises; avsim_episode_setup does (it reallocates the records: once per evaluation), and so do avsim_episode_log /
