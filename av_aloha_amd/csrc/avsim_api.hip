@@ -77,6 +77,8 @@ struct avsim {
     RenderHost render;   // depth renderer (avsim_render.hip.h)
     VisHost vis;         // colour images of the visual meshes (avsim_vis.hip.h), once avsim_load_visual has run
     JpegHost jpeg;       // JPEG streams of such images (avsim_jpeg.hip.h): tables per shape, the intervals' staging area
+    JpegDecHost jpegdec; // and those streams back into images: Huffman lookup tables, the coefficients' staging area
+    bool jpegdec_events = false;   // option "jpeg_decode_events": avsim_jpeg_decode records ev[12..15] around its three kernels
     // the state's version: bumped by everything that writes qpos (reset, the steps, set_state); the image calls skip their pose pass and the shadow
     // map when they already hold this version's (a facade that fetches its cameras one call at a time repeats neither)
     unsigned long long state_ver = 1, xpose_ver = 0;
@@ -469,6 +471,7 @@ void avsim_destroy(avsim_t* h) {
     h->render.destroy();
     h->vis.destroy();
     h->jpeg.destroy();
+    h->jpegdec.destroy();
     for (void* p : {h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, (void*)h->d_latch})
         if (p) (void)hipFree(p);
     for (void* p : h->d_io)
@@ -505,6 +508,8 @@ int avsim_set_option(avsim_t* h, const char* name, double value) {
     if (!std::strcmp(name, "render_shadow_size")) { if (value != 512 && value != 1024 && value != 2048) { h->set_error("render_shadow_size is 512, 1024 or 2048"); return AVSIM_EINVAL; } h->vis.shadow_size = (int)value; return AVSIM_OK; }
     if (!std::strcmp(name, "render_cam_major")) { h->vis.cam_major = value != 0; return AVSIM_OK; }
     if (!std::strcmp(name, "render_chunk")) { if (value < 1) { h->set_error("render_chunk is a number of envs >= 1"); return AVSIM_EINVAL; } h->render.env_chunk = (int)value; return AVSIM_OK; }
+    if (!std::strcmp(name, "jpeg_decode_events")) { h->jpegdec_events = value != 0; return AVSIM_OK; }
+    if (!std::strcmp(name, "jpeg_decode_budget")) { if (value < 1) { h->set_error("jpeg_decode_budget is a number of bytes >= 1"); return AVSIM_EINVAL; } h->jpegdec.coef_budget = (size_t)value; return AVSIM_OK; }
     if (!std::strcmp(name, "diffik_iters")) { h->ik.diff_iters = (int)value; return AVSIM_OK; }
     if (!std::strcmp(name, "gradik_iters")) { h->ik.grad_iters = (int)value; return AVSIM_OK; }
     try {
@@ -889,16 +894,9 @@ int avsim_get_diag(avsim_t* h, int32_t* diag) {
 extern "C" {
 
 // E6 (env.py:180-188 get_obs pixels / :195-200 render) as depth images: forward pass of the physics kernel (nsub = 0) exports
-// the body poses, then the two render kernels run on the same stream.
-static int render_images(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, void* out, bool rgb, bool f32 = false) {
-    const char* who = f32 ? "avsim_render_rgb_f32" : rgb ? "avsim_render_rgb" : "avsim_render_depth";
-    if (!h || !cam_ids || !out) { if (h) h->set_error("%s: bad arguments", who); return AVSIM_EINVAL; }
-    if (f32 && !(h->vis.loaded && !h->render_proxies)) { h->set_error("avsim_render_rgb_f32 draws the visual scene only (avsim_load_visual, render_proxies 0)"); return AVSIM_EINVAL; }
-    AVS_ON_DEVICE(h);
+// the body poses, then the two render kernels run on the same stream.  render_to: into device memory, with the handle's device current.
+static int render_to(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, void* dout, bool rgb, bool f32) {
     int rc;
-    void* dout = nullptr;
-    const size_t bytes = (f32 ? 3 * sizeof(float) : rgb ? 3 : sizeof(float)) * (size_t)h->N * ncam * height * width;
-    if ((rc = h->out_begin(7, out, bytes, &dout))) return rc;
     if (h->xpose_ver != h->state_ver) {          // body poses of the current state (a forward pass of the physics kernel, no substep)
         h->phys.d_xpose = h->render.d_xpose;
         rc = h->phys.launch(h->stream, h->N, 0, nullptr, h->nj, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, nullptr, nullptr, nullptr, h->err);
@@ -911,7 +909,18 @@ static int render_images(avsim_t* h, const int32_t* cam_ids, int ncam, int heigh
         rc = h->vis.launch(h->stream, h->N, h->render.d_xpose, (const int*)cam_ids, ncam, h->render.m.ncam, height, width, dout, h->err, h->state_ver, f32);
     else
         rc = h->render.launch(h->stream, (const int*)cam_ids, ncam, height, width, dout, rgb, h->err);
-    if (rc) return rc < -1 ? AVSIM_EHIP : AVSIM_EINVAL;
+    return rc ? (rc < -1 ? AVSIM_EHIP : AVSIM_EINVAL) : AVSIM_OK;
+}
+static int render_images(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, void* out, bool rgb, bool f32 = false) {
+    const char* who = f32 ? "avsim_render_rgb_f32" : rgb ? "avsim_render_rgb" : "avsim_render_depth";
+    if (!h || !cam_ids || !out) { if (h) h->set_error("%s: bad arguments", who); return AVSIM_EINVAL; }
+    if (f32 && !(h->vis.loaded && !h->render_proxies)) { h->set_error("avsim_render_rgb_f32 draws the visual scene only (avsim_load_visual, render_proxies 0)"); return AVSIM_EINVAL; }
+    AVS_ON_DEVICE(h);
+    int rc;
+    void* dout = nullptr;
+    const size_t bytes = (f32 ? 3 * sizeof(float) : rgb ? 3 : sizeof(float)) * (size_t)h->N * ncam * height * width;
+    if ((rc = h->out_begin(7, out, bytes, &dout))) return rc;
+    if ((rc = render_to(h, cam_ids, ncam, height, width, dout, rgb, f32))) return rc;
     if ((rc = h->out_end(7, out, bytes))) return rc;
     return h->finish();
 }
@@ -958,6 +967,76 @@ int avsim_jpeg_encode(avsim_t* h, const void* img, int fmt, const int32_t* index
     if ((rc = h->jpeg.launch(h->stream, dimg, fmt, (const int*)dindex, nimg, height, width, quality, (uint8_t*)dout, stride, (int*)dlen, h->err))) return AVSIM_EHIP;
     if ((rc = h->out_end(10, out, (size_t)nimg * stride))) return rc;
     if ((rc = h->out_end(11, out_len, sizeof(int32_t) * (size_t)nimg))) return rc;
+    return h->finish();
+}
+
+// avsim_render_rgb's visual-scene images as JPEG streams: rendered into a buffer of the library's and encoded from there, so that no pixel
+// leaves the device; a host caller gets the lengths and, of every stream, as many bytes as the longest one has.
+int avsim_render_jpeg(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, int tile, int quality, uint8_t* out, int64_t stride,
+                      int32_t* out_len) {
+    if (!h) return AVSIM_EINVAL;
+    if (!cam_ids || !out || !out_len || ncam < 1 || stride < 0) { h->set_error("avsim_render_jpeg: bad arguments"); return AVSIM_EINVAL; }
+    if (quality < 1 || quality > 100) { h->set_error("avsim_render_jpeg: quality %d outside 1..100", quality); return AVSIM_EINVAL; }
+    const int64_t iw = tile ? (int64_t)width * ncam : width;
+    if (height < 1 || width < 1 || height > 65535 || iw > 65535) { h->set_error("avsim_render_jpeg: image size %d x %lld outside 1..65535", height, (long long)iw); return AVSIM_EINVAL; }
+    if (!(h->vis.loaded && !h->render_proxies)) { h->set_error("avsim_render_jpeg draws the visual scene only (avsim_load_visual, render_proxies 0)"); return AVSIM_EINVAL; }
+    if (tile && h->vis.cam_major) { h->set_error("avsim_render_jpeg: tile puts the views of an env side by side (render_cam_major 0)"); return AVSIM_EINVAL; }
+    AVS_ON_DEVICE(h);
+    int rc;
+    const int nstream = tile ? h->N : h->N * ncam;
+    const size_t bytes = (size_t)3 * h->N * ncam * height * width;
+    void *dimg = nullptr, *dtile = nullptr, *dout = nullptr, *dlen = nullptr;
+    if ((rc = h->io_buf(7, bytes, &dimg))) return rc;
+    if ((rc = render_to(h, cam_ids, ncam, height, width, dimg, true, false))) return rc;
+    if (tile && ncam > 1) {
+        if ((rc = h->io_buf(13, bytes, &dtile))) return rc;
+        if (jpeg_tile(h->stream, dimg, dtile, h->N, ncam, height, width, h->err)) return AVSIM_EHIP;
+        dimg = dtile;
+    }
+    if ((rc = h->out_begin(10, out, (size_t)nstream * stride, &dout))) return rc;
+    if ((rc = h->out_begin(11, out_len, sizeof(int32_t) * (size_t)nstream, &dlen))) return rc;
+    if (h->jpeg.launch(h->stream, dimg, 0, nullptr, nstream, height, (int)iw, quality, (uint8_t*)dout, stride, (int*)dlen, h->err)) return AVSIM_EHIP;
+    if (h->io_device) return AVSIM_OK;
+    HIPCHK(h, hipMemcpyAsync(out_len, dlen, sizeof(int32_t) * (size_t)nstream, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    int64_t w = 0;
+    for (int i = 0; i < nstream; i++) w = out_len[i] > w ? out_len[i] : w;
+    w = w < stride ? w : stride;
+    if (w > 0) HIPCHK(h, hipMemcpy2DAsync(out, (size_t)stride, dout, (size_t)stride, (size_t)w, (size_t)nstream, hipMemcpyDeviceToHost, h->stream));
+    return h->finish();
+}
+
+// ... and back: the streams of avsim_jpeg_encode -> images (av_aloha_amd/jpeg.py decode_reference is the specification)
+int avsim_jpeg_decode(avsim_t* h, const uint8_t* in, int64_t stride, const int32_t* in_len, const int32_t* index, int nimg, int height, int width,
+                      int fmt, int upsample, void* out, int32_t* status) {
+    if (!h) return AVSIM_EINVAL;
+    if (!in || !in_len || !out || !status || nimg < 0 || stride < 1) { h->set_error("avsim_jpeg_decode: bad arguments"); return AVSIM_EINVAL; }
+    if (fmt != 0 && fmt != 1) { h->set_error("avsim_jpeg_decode: fmt is 0 (u8 HWC) or 1 (float32 CHW)"); return AVSIM_EINVAL; }
+    if (upsample != 0 && upsample != 1) { h->set_error("avsim_jpeg_decode: upsample is 0 (replicate) or 1 (triangle)"); return AVSIM_EINVAL; }
+    if (height < 1 || width < 1 || height > 65535 || width > 65535) { h->set_error("avsim_jpeg_decode: image size %d x %d outside 1..65535", height, width); return AVSIM_EINVAL; }
+    if (nimg == 0) return AVSIM_OK;
+    AVS_ON_DEVICE(h);
+    int rc;
+    size_t rows = (size_t)nimg;            // (a host caller's index says how many streams `in` holds)
+    if (!h->io_device && index) {
+        int top = 0;
+        for (int i = 0; i < nimg; i++) {
+            if (index[i] < 0) { h->set_error("avsim_jpeg_decode: negative index"); return AVSIM_EINVAL; }
+            top = index[i] > top ? index[i] : top;
+        }
+        rows = (size_t)top + 1;
+    }
+    const void *din = nullptr, *dlen = nullptr, *dindex = nullptr;
+    void *dout = nullptr, *dstatus = nullptr;
+    const size_t bytes = (size_t)nimg * height * width * (fmt ? 12 : 3);
+    if ((rc = h->in(8, in, rows * (size_t)stride, &din))) return rc;
+    if ((rc = h->in(12, in_len, sizeof(int32_t) * rows, &dlen))) return rc;
+    if (index && (rc = h->in(9, index, sizeof(int32_t) * (size_t)nimg, &dindex))) return rc;
+    if ((rc = h->out_begin(10, out, bytes, &dout))) return rc;
+    if ((rc = h->out_begin(11, status, sizeof(int32_t) * (size_t)nimg, &dstatus))) return rc;
+    if ((rc = h->jpegdec.launch(h->stream, (const uint8_t*)din, stride, (const int*)dlen, (const int*)dindex, nimg, height, width, fmt, upsample, dout, (int*)dstatus, h->err, h->jpegdec_events ? h->ev + 12 : nullptr))) return AVSIM_EHIP;
+    if ((rc = h->out_end(10, out, bytes))) return rc;
+    if ((rc = h->out_end(11, status, sizeof(int32_t) * (size_t)nimg))) return rc;
     return h->finish();
 }
 

@@ -1,4 +1,5 @@
-// avsim_jpeg.hip.h -- baseline JPEG encoding of rendered frames on the device (avsim_jpeg_encode).
+// avsim_jpeg.hip.h -- baseline JPEG encoding of rendered frames on the device (avsim_jpeg_encode) and decoding of those streams
+// (avsim_jpeg_decode; DESIGN 8.z: the section further down).
 //
 // The stream is the one av_aloha_amd/jpeg.py encode_reference writes, byte for byte: SOF0, 8 bit, JFIF, Y Cb Cr 4:2:0, the Annex K Huffman
 // tables, one restart interval per MCU row.  All arithmetic is integer.  Two kernels:
@@ -298,6 +299,376 @@ __global__ void __launch_bounds__(256) k_jpeg_pack(const JpegTables* __restrict_
     }
 }
 
+// The views of an env side by side (avsim_render_jpeg, tile 1: the Cartesian env's zed_cam = left | right): src [n][ntile][H][rw] -> dst
+// [n][H][ntile][rw] in units of U, rw = W * 3 / sizeof(U).  A bijection of [0, total): every index on either side is below total.
+template <typename U>
+__global__ void __launch_bounds__(256) k_jpeg_tile(const U* __restrict__ src, U* __restrict__ dst, int ntile, int H, int rw, size_t total) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const size_t x = i % rw, r = i / rw;            // r = (env * H + y) * ntile + view
+        const size_t c = r % ntile, ny = r / ntile, y = ny % H, n = ny / H;
+        dst[i] = src[((n * ntile + c) * H + y) * rw + x];
+    }
+}
+inline int jpeg_tile(hipStream_t stream, const void* src, void* dst, int n, int ntile, int H, int W, std::string& err) {
+    const size_t row = (size_t)W * 3;
+    const bool words = row % 4 == 0;                    // (both buffers come from hipMalloc: a view then starts on a dword)
+    const size_t total = (size_t)n * ntile * H * (words ? row / 4 : row);
+    const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 65536);
+    if (words) hipLaunchKernelGGL(k_jpeg_tile<uint32_t>, dim3(blocks), dim3(256), 0, stream, (const uint32_t*)src, (uint32_t*)dst, ntile, H, (int)(row / 4), total);
+    else hipLaunchKernelGGL(k_jpeg_tile<uint8_t>, dim3(blocks), dim3(256), 0, stream, (const uint8_t*)src, (uint8_t*)dst, ntile, H, (int)row, total);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { err = std::string("jpeg tile kernel: ") + hipGetErrorString(e); return -3; }
+    return 0;
+}
+
+// ---- decoding (avsim_jpeg_decode) ----------------------------------------------------------------------------------------------
+// The streams of the encoder above and nothing else, as av_aloha_amd/jpeg.py decode_reference reads them, byte for byte.  Three kernels:
+//   k_jpeg_index        per image: the header against the expected one for (H, W) outside the DQT payloads, the image's two quantiser tables,
+//                       a block-wide scan for the RST markers (stuffing leaves FF 00 as the only FF pair inside entropy data), the intervals'
+//                       byte ranges and the image's status.
+//   k_jpeg_entropy      one restart interval per lane: Huffman decoding through two-level tables in LDS (8 + 8 bits) from a 64-bit window
+//                       that drops the stuffed zeros on refill; the non-zero coefficients go to a zeroed int16 staging area
+//                       [image][MCU row][MCU][block][64] in natural order.  Every read is bounded by the interval's end, every coefficient
+//                       index by 63, the block count by the MCU row's: an error sets status bit 2 and ends that interval.
+//   k_jpeg_reconstruct  a workgroup per JPD_K MCUs of an MCU row, 8 lanes per block: dequantiser, the two IDCT passes through LDS, the planes
+//                       in LDS, then chroma upsampling and colour conversion per pixel.  The triangle filter needs one chroma row / column
+//                       of the neighbouring blocks: those blocks are transformed again here (no second staging area).
+constexpr int JPD_NSUB = 13;                 // second-level tables: the distinct 8-bit prefixes of the Annex K codes longer than 8 bits (1 + 5 + 1 + 6)
+constexpr int JPD_K = 10;                    // MCUs per workgroup of k_jpeg_reconstruct
+constexpr int JPD_BSTRIDE = 33;              // dwords between blocks in LDS (as JPG_BSTRIDE)
+constexpr int JPD_DQT0 = 25, JPD_DQT1 = 94;  // the quantiser payloads inside the header
+constexpr int JPD_SOF_SIZE = 163, JPD_DRI_MW = 613;
+
+struct JpegDecTables {
+    uint16_t l1[4][256];          // DC luma, AC luma, DC chroma, AC chroma by the next 8 bits: symbol << 5 | length, or table << 5 | 31; 0: no code
+    uint16_t l2[JPD_NSUB][256];   // by the 8 bits after those: symbol << 5 | length (9 .. 16)
+    uint8_t zz[64];               // zigzag position -> natural index
+    float unit[256];              // (float)k / 255, divided on the host (see vis_u8_unit)
+    uint8_t hdr[JPG_HDR + 3];     // the header of a 1 x 1 image: size and restart interval are patched in by the reader
+};
+constexpr int JPD_LDS_TABLE_WORDS = (4 * 256 + JPD_NSUB * 256) / 2 + 16;       // l1, l2, zz
+
+__global__ void __launch_bounds__(256) k_jpeg_index(const JpegDecTables* __restrict__ T, const uint8_t* __restrict__ in, long long stride, const int* __restrict__ in_len,
+                                                    const int* __restrict__ index, int img0, int H, int W, int mh, int* __restrict__ ivoff,
+                                                    uint8_t* __restrict__ qtab, int* __restrict__ status) {
+    __shared__ int s_wave[4];
+    __shared__ int s_bad;
+    const int iml = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, img = img0 + iml;
+    const size_t src = index ? (size_t)index[img] : (size_t)img;
+    const uint8_t* s = in + src * (size_t)stride;
+    const long long len = in_len[src];
+    int* off = ivoff + (size_t)iml * (mh + 1);          // off[r] + 2 .. off[r + 1]: the bytes of interval r
+    if (tid == 0) s_bad = 0;
+    __syncthreads();
+    if (len < JPG_HDR + 2 || len > stride) {            // (uniform)
+        if (tid == 0) status[img] = 2;
+        return;
+    }
+    const int mw = (W + 15) >> 4;
+    for (int i = tid; i < JPG_HDR; i += 256) {
+        const int b = s[i];
+        if (i >= JPD_DQT0 && i < JPD_DQT0 + 64) qtab[(size_t)iml * 128 + T->zz[i - JPD_DQT0]] = (uint8_t)b;
+        else if (i >= JPD_DQT1 && i < JPD_DQT1 + 64) qtab[(size_t)iml * 128 + 64 + T->zz[i - JPD_DQT1]] = (uint8_t)b;
+        else {
+            int e = T->hdr[i];
+            if (i == JPD_SOF_SIZE) e = H >> 8;
+            else if (i == JPD_SOF_SIZE + 1) e = H & 255;
+            else if (i == JPD_SOF_SIZE + 2) e = W >> 8;
+            else if (i == JPD_SOF_SIZE + 3) e = W & 255;
+            else if (i == JPD_DRI_MW) e = mw >> 8;
+            else if (i == JPD_DRI_MW + 1) e = mw & 255;
+            if (b != e) atomicOr(&s_bad, 1);
+        }
+    }
+    __syncthreads();
+    if (s_bad & 1) {
+        if (tid == 0) status[img] = 1;
+        return;
+    }
+    // the pairs (i, i + 1), JPG_HDR <= i < n: FF 00 is a stuffed byte, FF D0..D7 a restart marker, any other FF pair does not belong here
+    const long long n = len - 2;
+    int run = 0, bad = 0;
+    for (long long base = JPG_HDR; base < n; base += 1024) {
+        const long long p = base + 4 * tid;
+        int b[5];
+#pragma unroll
+        for (int j = 0; j < 5; j++) b[j] = p + j <= n ? s[p + j] : 0;
+        int c = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            if (p + j < n && b[j] == 0xFF) {
+                if ((b[j + 1] & 0xF8) == 0xD0) c++;
+                else if (b[j + 1] != 0) bad = 1;
+            }
+        int incl = c;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int o = __shfl_up(incl, d);
+            if (lane >= d) incl += o;
+        }
+        if (lane == 63) s_wave[wv] = incl;
+        __syncthreads();
+        int ord = run + incl - c;
+        for (int w = 0; w < wv; w++) ord += s_wave[w];
+        run += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            if (p + j < n && b[j] == 0xFF && (b[j + 1] & 0xF8) == 0xD0) {
+                if (ord < mh - 1) {
+                    off[ord + 1] = (int)(p + j);
+                    if ((b[j + 1] & 7) != (ord & 7)) bad = 1;
+                }
+                ord++;
+            }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        off[0] = JPG_HDR - 2;
+        off[mh] = (int)n;
+        if (s[n] != 0xFF || s[n + 1] != 0xD9) bad = 1;
+    }
+    if (run != mh - 1) bad = 1;
+    if (bad) atomicOr(&s_bad, 2);
+    __syncthreads();
+    if (tid == 0) status[img] = s_bad & 2;
+}
+
+__global__ void __launch_bounds__(64) k_jpeg_entropy(const JpegDecTables* __restrict__ T, const uint8_t* __restrict__ in, long long stride, const int* __restrict__ index,
+                                                     int img0, int nimg, int mw, int mh, const int* __restrict__ ivoff, int16_t* __restrict__ coef, int* status) {
+    __shared__ uint32_t s_tab[JPD_LDS_TABLE_WORDS];
+    const int lane = threadIdx.x;
+    for (int i = lane; i < JPD_LDS_TABLE_WORDS; i += 64) s_tab[i] = ((const uint32_t*)T)[i];
+    __syncthreads();
+    const uint16_t* l1 = (const uint16_t*)s_tab;
+    const uint16_t* l2 = l1 + 4 * 256;
+    const uint8_t* zz = (const uint8_t*)(l2 + JPD_NSUB * 256);
+    const long long iv = (long long)blockIdx.x * 64 + lane;
+    if (iv >= (long long)nimg * mh) return;
+    const int iml = (int)(iv / mh), row = (int)(iv - (long long)iml * mh), img = img0 + iml;
+    if (status[img] & 3) return;
+    const uint8_t* s = in + (index ? (size_t)index[img] : (size_t)img) * (size_t)stride;
+    long long pos = ivoff[(size_t)iml * (mh + 1) + row] + 2;
+    const long long end = ivoff[(size_t)iml * (mh + 1) + row + 1];
+    int16_t* c = coef + (size_t)iv * mw * 384;
+    unsigned long long acc = 0;             // the next nb bits of the interval, from bit 63 down
+    int nb = 0;
+    auto refill = [&]() {
+        while (nb <= 56 && pos < end) {
+            const unsigned v = s[pos++];
+            if (v == 0xFFu) pos++;          // (its stuffed zero: k_jpeg_index found no other pair in here)
+            acc |= (unsigned long long)v << (56 - nb);
+            nb += 8;
+        }
+    };
+    auto symbol = [&](int tab) -> int {     // -1: no such code, or the bytes ran out
+        refill();
+        const unsigned pk = (unsigned)(acc >> 48);
+        unsigned e = l1[tab * 256 + (pk >> 8)];
+        if ((e & 31u) == 31u) e = l2[(e >> 5) * 256 + (pk & 255u)];
+        const int len = (int)(e & 31u);
+        if (len == 0 || len > nb) return -1;
+        acc <<= len;
+        nb -= len;
+        return (int)(e >> 5);
+    };
+    auto amplitude = [&](int n, int& v) -> bool {      // 1 <= n <= 11; symbol() left 41 bits or all there are
+        if (n > nb) return false;
+        const int u = (int)(acc >> (64 - n));
+        acc <<= n;
+        nb -= n;
+        v = u < (1 << (n - 1)) ? u - (1 << n) + 1 : u;
+        return true;
+    };
+    int pred_y = 0, pred_cb = 0, pred_cr = 0;
+    bool ok = true;
+    for (int m = 0; m < mw && ok; m++) {
+        for (int j = 0; j < 6 && ok; j++, c += 64) {
+            const int comp = j < 4 ? 0 : 1;
+            int n = symbol(2 * comp), d = 0;
+            if (n < 0 || n > 11 || (n && !amplitude(n, d))) { ok = false; break; }
+            const int pred = d + (j < 4 ? pred_y : j == 4 ? pred_cb : pred_cr);
+            if (j < 4) pred_y = pred;
+            else if (j == 4) pred_cb = pred;
+            else pred_cr = pred;
+            if (pred) c[0] = (int16_t)(pred < -32768 ? -32768 : pred > 32767 ? 32767 : pred);
+            int k = 1;
+            while (k < 64) {
+                const int rs = symbol(2 * comp + 1);
+                if (rs < 0) { ok = false; break; }
+                if (rs == 0) break;
+                n = rs & 15;
+                k += rs >> 4;
+                if (n > 10 || k + (n == 0) > 63) { ok = false; break; }
+                if (n == 0) { k++; continue; }              // ZRL
+                int v;
+                if (!amplitude(n, v)) { ok = false; break; }
+                c[zz[k]] = (int16_t)v;
+                k++;
+            }
+        }
+    }
+    if (ok) {                               // fewer than 8 bits are left and all of them are 1
+        refill();
+        ok = pos >= end && nb < 8 && (nb == 0 || (acc >> (64 - nb)) == (1ull << nb) - 1ull);
+    }
+    if (!ok) atomicOr(&status[img], 4);
+}
+
+// FMT 0: u8 [.][H][W][3]; 1: float32 [.][3][H][W], (float)u8 / 255.  TRI: libjpeg's h2v2 triangle filter on the cropped chroma plane; else replication
+template <int FMT, bool TRI>
+__global__ void __launch_bounds__(256) k_jpeg_reconstruct(const JpegDecTables* __restrict__ T, const int16_t* __restrict__ coef, const uint8_t* __restrict__ qtab,
+                                                          const int* __restrict__ status, int img0, int H, int W, int mw, int mh, void* __restrict__ out) {
+    constexpr int YW = 16 * JPD_K;                          // the luma plane: 16 rows
+    constexpr int CW = TRI ? 8 * (JPD_K + 2) : 8 * JPD_K;   // a chroma plane: with the filter, the blocks around the tile too
+    constexpr int CR = TRI ? 24 : 8;
+    constexpr int NCJ = TRI ? 3 * (JPD_K + 2) : JPD_K;      // chroma blocks per component
+    constexpr int NJ = 4 * JPD_K + 2 * NCJ;
+    __shared__ uint32_t s_f[NJ * JPD_BSTRIDE];              // dequantised coefficients, int16 [k][l]
+    __shared__ uint32_t s_t[NJ * JPD_BSTRIDE];              // after the column pass, int16 [r][l]
+    __shared__ uint32_t s_pl[(16 * YW + 2 * CR * CW) / 4];  // Y, Cb, Cr samples, u8
+    __shared__ long long s_src[NJ];                         // a job's block in `coef`, -1: outside the image
+    __shared__ int s_dst[NJ], s_dw[NJ];                     // its place in s_pl: byte offset, row stride
+    __shared__ int16_t s_q[128];
+    __shared__ float s_unit[256];
+    const int tid = threadIdx.x, row = blockIdx.y, iml = blockIdx.z, m0 = blockIdx.x * JPD_K, img = img0 + iml;
+    if (status[img]) return;                                // (uniform)
+    if (tid < 128) s_q[tid] = qtab[(size_t)iml * 128 + tid];
+    if (FMT == 1) s_unit[tid] = T->unit[tid];
+    if (tid < NJ) {
+        int r = row, m, jb, dst, dw;
+        if (tid < 4 * JPD_K) {
+            m = tid >> 2; jb = tid & 3;
+            dst = (jb >> 1) * 8 * YW + m * 16 + (jb & 1) * 8; dw = YW;
+            m += m0;
+        } else {
+            const int t = tid - 4 * JPD_K, comp = t / NCJ, u = t - comp * NCJ;
+            const int dr = TRI ? u / (JPD_K + 2) : 0, mc = TRI ? u - dr * (JPD_K + 2) : u;
+            jb = 4 + comp;
+            dst = 16 * YW + comp * CR * CW + dr * 8 * CW + mc * 8; dw = CW;
+            r = TRI ? row + dr - 1 : row;
+            m = TRI ? m0 + mc - 1 : m0 + mc;
+        }
+        s_src[tid] = r >= 0 && r < mh && m >= 0 && m < mw ? (long long)(((((size_t)iml * mh + r) * mw + m) * 6 + jb) * 64) : -1;
+        s_dst[tid] = dst; s_dw[tid] = dw;
+    }
+    __syncthreads();
+    // 1. dequantiser: lane (block, k) takes the 8 coefficients F[k][.], clamps the products to [-2048, 2047]
+    for (int t = tid; t < NJ * 8; t += 256) {
+        const int b = t >> 3, k = t & 7;
+        if (s_src[b] < 0) continue;
+        const uint4 v = *(const uint4*)(coef + s_src[b] + k * 8);
+        const int16_t* q = s_q + (b < 4 * JPD_K ? 0 : 64) + k * 8;
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            int lo = (int)(int16_t)(w[i] & 0xffffu) * q[2 * i], hi = (int)(int16_t)(w[i] >> 16) * q[2 * i + 1];
+            lo = lo < -2048 ? -2048 : lo > 2047 ? 2047 : lo;
+            hi = hi < -2048 ? -2048 : hi > 2047 ? 2047 : hi;
+            s_f[b * JPD_BSTRIDE + k * 4 + i] = (uint32_t)(lo & 0xffff) | ((uint32_t)hi << 16);
+        }
+    }
+    __syncthreads();
+    // 2. columns: lane (block, l) -> t[r][l] = (sum_k M[k][r] F[k][l] + 1024) >> 11, |t| <= 32137
+    for (int t = tid; t < NJ * 8; t += 256) {
+        const int b = t >> 3, l = t & 7;
+        if (s_src[b] < 0) continue;
+        const int16_t* p = (const int16_t*)(s_f + b * JPD_BSTRIDE) + l;
+        int x[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) x[k] = p[k * 8];
+        int16_t* o = (int16_t*)(s_t + b * JPD_BSTRIDE) + l;
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            int s = 1024;
+#pragma unroll
+            for (int k = 0; k < 8; k++) s += JPG_DCT[k][r] * x[k];
+            o[r * 8] = (int16_t)(s >> 11);
+        }
+    }
+    __syncthreads();
+    // 3. rows: lane (block, r) -> p[r][c] = (sum_l M[l][c] t[r][l] + 16384) >> 15, + 128, a byte
+    for (int t = tid; t < NJ * 8; t += 256) {
+        const int b = t >> 3, r = t & 7;
+        if (s_src[b] < 0) continue;
+        int x[8];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t w = s_t[b * JPD_BSTRIDE + r * 4 + i];
+            x[2 * i] = (int)(int16_t)(w & 0xffffu);
+            x[2 * i + 1] = (int)(int16_t)(w >> 16);
+        }
+        uint32_t o[2] = {0, 0};
+#pragma unroll
+        for (int c = 0; c < 8; c++) {
+            int s = 16384;
+#pragma unroll
+            for (int l = 0; l < 8; l++) s += JPG_DCT[l][c] * x[l];
+            o[c >> 2] |= (uint32_t)jpg_clamp8((s >> 15) + 128) << (8 * (c & 3));
+        }
+        uint32_t* d = s_pl + ((s_dst[b] + r * s_dw[b]) >> 2);
+        d[0] = o[0]; d[1] = o[1];
+    }
+    __syncthreads();
+    // 4. pixels of the tile that lie inside the image
+    const uint8_t* pY = (const uint8_t*)s_pl;
+    const uint8_t* pC = pY + 16 * YW;
+    const int x0 = m0 * 16, y0 = row * 16, ch = (H + 1) >> 1, cw = (W + 1) >> 1;
+    const int cy0 = TRI ? row * 8 - 8 : row * 8, cx0 = TRI ? m0 * 8 - 8 : m0 * 8;
+    auto pixel = [&](int y, int x, int& R, int& G, int& B) {
+        const int Y = pY[(y - y0) * YW + (x - x0)];
+        int cb, cr;
+        const int cy = y >> 1, cx = x >> 1;
+        if (TRI) {
+            int ny = (y & 1) ? cy + 1 : cy - 1, nx = (x & 1) ? cx + 1 : cx - 1;
+            ny = ny < 0 ? 0 : ny > ch - 1 ? ch - 1 : ny;
+            nx = nx < 0 ? 0 : nx > cw - 1 ? cw - 1 : nx;
+            const int a = (cy - cy0) * CW - cx0, n = (ny - cy0) * CW - cx0, rnd = (x & 1) ? 7 : 8;
+            cb = (3 * (3 * pC[a + cx] + pC[n + cx]) + 3 * pC[a + nx] + pC[n + nx] + rnd) >> 4;
+            cr = (3 * (3 * pC[CR * CW + a + cx] + pC[CR * CW + n + cx]) + 3 * pC[CR * CW + a + nx] + pC[CR * CW + n + nx] + rnd) >> 4;
+        } else {
+            cb = pC[(cy - cy0) * CW + cx - cx0];
+            cr = pC[CR * CW + (cy - cy0) * CW + cx - cx0];
+        }
+        cb -= 128; cr -= 128;
+        R = jpg_clamp8(Y + ((91881 * cr + 32768) >> 16));
+        G = jpg_clamp8(Y - ((22554 * cb + 46802 * cr + 32768) >> 16));
+        B = jpg_clamp8(Y + ((116130 * cb + 32768) >> 16));
+    };
+    if (FMT == 1) {
+        float* o = (float*)out + (size_t)img * 3 * H * W;
+        const size_t plane = (size_t)H * W;
+        for (int p = tid; p < 16 * YW; p += 256) {
+            const int yl = p / YW, y = y0 + yl, x = x0 + p - yl * YW;
+            if (y >= H || x >= W) continue;
+            int R, G, B;
+            pixel(y, x, R, G, B);
+            float* d = o + (size_t)y * W + x;
+            d[0] = s_unit[R]; d[plane] = s_unit[G]; d[2 * plane] = s_unit[B];
+        }
+    } else {
+        uint8_t* o = (uint8_t*)out + (size_t)img * H * W * 3;
+        for (int p = tid; p < 16 * (YW / 4); p += 256) {          // four pixels, twelve bytes: three dwords where they are aligned
+            const int yl = p / (YW / 4), y = y0 + yl, x = x0 + 4 * (p - yl * (YW / 4));
+            if (y >= H || x >= W) continue;
+            uint8_t* d = o + ((size_t)y * W + x) * 3;
+            uint32_t w[3] = {0, 0, 0};
+            const int np = W - x < 4 ? W - x : 4;
+            for (int i = 0; i < np; i++) {
+                int R, G, B;
+                pixel(y, x + i, R, G, B);
+                const int v[3] = {R, G, B};
+#pragma unroll
+                for (int k = 0; k < 3; k++) w[(3 * i + k) >> 2] |= (uint32_t)v[k] << (8 * ((3 * i + k) & 3));
+            }
+            if (np == 4 && ((uintptr_t)d & 3) == 0) {
+                ((uint32_t*)d)[0] = w[0]; ((uint32_t*)d)[1] = w[1]; ((uint32_t*)d)[2] = w[2];
+            } else {
+                for (int i = 0; i < 3 * np; i++) d[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+            }
+        }
+    }
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------------------------
 // T.81 Annex K: quantiser tables K.1 / K.2 (natural order), Huffman tables K.3 - K.6 (codes per length, symbols in code order)
 static const uint8_t JPG_ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
@@ -444,6 +815,110 @@ struct JpegHost {
         }
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) { err = std::string("jpeg kernels: ") + hipGetErrorString(e); return -3; }
+        return 0;
+    }
+};
+
+inline int jpeg_build_dec_tables(JpegDecTables& t) {
+    std::memset(&t, 0, sizeof t);
+    const uint8_t* bits[4] = {JPG_DC_BITS[0], JPG_AC_BITS[0], JPG_DC_BITS[1], JPG_AC_BITS[1]};
+    const uint8_t* vals[4] = {JPG_DC_VALS, JPG_AC_VALS[0], JPG_DC_VALS, JPG_AC_VALS[1]};
+    int nsub = 0;
+    for (int tab = 0; tab < 4; tab++) {
+        uint32_t code = 0;
+        int k = 0;
+        for (int len = 1; len <= 16; len++) {
+            for (int i = 0; i < bits[tab][len - 1]; i++, code++) {
+                const uint16_t e = (uint16_t)((vals[tab][k++] << 5) | len);
+                if (len <= 8) {
+                    for (uint32_t x = code << (8 - len); x < (code + 1) << (8 - len); x++) t.l1[tab][x] = e;
+                } else {
+                    const uint32_t pre = code >> (len - 8), low = code & ((1u << (len - 8)) - 1u);
+                    if (!t.l1[tab][pre]) {
+                        if (nsub == JPD_NSUB) return -1;
+                        t.l1[tab][pre] = (uint16_t)((nsub++ << 5) | 31);
+                    }
+                    uint16_t* sub = t.l2[t.l1[tab][pre] >> 5];
+                    for (uint32_t x = low << (16 - len); x < (low + 1) << (16 - len); x++) sub[x] = e;
+                }
+            }
+            code <<= 1;
+        }
+    }
+    for (int i = 0; i < 64; i++) t.zz[i] = JPG_ZIGZAG[i];
+    for (int k = 0; k < 256; k++) t.unit[k] = (float)k / 255.0f;
+    JpegTables enc;
+    jpeg_build_tables(1, 1, 50, enc);
+    std::memcpy(t.hdr, enc.hdr, sizeof t.hdr);
+    return 0;
+}
+
+struct JpegDecHost {
+    JpegDecTables* d_tab = nullptr;
+    std::unique_ptr<JpegDecTables> host;         // the upload's source: never written again
+    int16_t* d_coef = nullptr;                   // [images of a launch][MCU row][MCU][6][64]: zeroed, then the entropy decoder's coefficients
+    size_t coef_sz = 0;
+    int* d_ivoff = nullptr;                      // [image][mh + 1]
+    size_t ivoff_n = 0;
+    uint8_t* d_qtab = nullptr;                   // [image][2][64], natural order
+    size_t qtab_n = 0;
+    size_t coef_budget = (size_t)512 << 20;      // a call whose staging would be larger goes through the kernels in groups of images
+
+    void destroy() {
+        for (void* p : {(void*)d_tab, (void*)d_coef, (void*)d_ivoff, (void*)d_qtab})
+            if (p) (void)hipFree(p);
+        d_tab = nullptr; d_coef = nullptr; d_ivoff = nullptr; d_qtab = nullptr;
+        coef_sz = ivoff_n = qtab_n = 0;
+        host.reset();
+    }
+    template <typename P>
+    static bool grow(P*& p, size_t& have, size_t want) {
+        if (have >= want) return true;
+        if (p) (void)hipFree(p);
+        p = nullptr; have = 0;
+        if (hipMalloc(&p, want * sizeof(P)) != hipSuccess) return false;
+        have = want;
+        return true;
+    }
+    // in, in_len, index, out, status: device pointers
+    int launch(hipStream_t stream, const uint8_t* in, long long stride, const int* in_len, const int* index, int nimg, int H, int W, int fmt, int upsample,
+               void* out, int* status, std::string& err, hipEvent_t* ev = nullptr) {          // ev: four events recorded around the three kernels (of the last group)
+        if (!d_tab) {
+            host = std::make_unique<JpegDecTables>();
+            if (jpeg_build_dec_tables(*host)) { err = "jpeg decode tables: more long-code prefixes than JPD_NSUB"; host.reset(); return -3; }
+            hipError_t rc = hipMalloc(&d_tab, sizeof(JpegDecTables));
+            if (rc == hipSuccess) rc = hipMemcpyAsync(d_tab, host.get(), sizeof(JpegDecTables), hipMemcpyHostToDevice, stream);
+            if (rc != hipSuccess) { if (d_tab) (void)hipFree(d_tab); d_tab = nullptr; err = std::string("jpeg decode tables: ") + hipGetErrorString(rc); return -3; }
+        }
+        const int mh = (H + 15) / 16, mw = (W + 15) / 16;
+        const size_t per_img = (size_t)mh * mw * 384;                 // coefficients
+        size_t group = coef_budget / (per_img * sizeof(int16_t));
+        group = group < 1 ? 1 : group > (size_t)nimg ? (size_t)nimg : group;
+        if (group > 65535) group = 65535;                             // (gridDim.z)
+        if (!grow(d_coef, coef_sz, group * per_img) || !grow(d_ivoff, ivoff_n, group * (mh + 1)) || !grow(d_qtab, qtab_n, group * 128)) {
+            err = "jpeg decode staging: hipMalloc failed";
+            return -3;
+        }
+        const int nchunk = (mw + JPD_K - 1) / JPD_K;
+        for (int i0 = 0; i0 < nimg; i0 += (int)group) {
+            const int n = nimg - i0 < (int)group ? nimg - i0 : (int)group;
+            if (hipMemsetAsync(d_coef, 0, (size_t)n * per_img * sizeof(int16_t), stream) != hipSuccess) { err = "jpeg decode staging: hipMemsetAsync failed"; return -3; }
+            if (ev) (void)hipEventRecord(ev[0], stream);
+            hipLaunchKernelGGL(k_jpeg_index, dim3(n), dim3(256), 0, stream, d_tab, in, stride, in_len, index, i0, H, W, mh, d_ivoff, d_qtab, status);
+            if (ev) (void)hipEventRecord(ev[1], stream);
+            hipLaunchKernelGGL(k_jpeg_entropy, dim3((unsigned)(((size_t)n * mh + 63) / 64)), dim3(64), 0, stream, d_tab, in, stride, index, i0, n, mw, mh, d_ivoff, d_coef, status);
+            if (ev) (void)hipEventRecord(ev[2], stream);
+            const dim3 grid(nchunk, mh, n);
+#define JPD_RECON(F, T) hipLaunchKernelGGL((k_jpeg_reconstruct<F, T>), grid, dim3(256), 0, stream, d_tab, d_coef, d_qtab, status, i0, H, W, mw, mh, out)
+            if (fmt == 0 && !upsample) JPD_RECON(0, false);
+            else if (fmt == 0) JPD_RECON(0, true);
+            else if (!upsample) JPD_RECON(1, false);
+            else JPD_RECON(1, true);
+#undef JPD_RECON
+            if (ev) (void)hipEventRecord(ev[3], stream);
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { err = std::string("jpeg decode kernels: ") + hipGetErrorString(e); return -3; }
         return 0;
     }
 };

@@ -227,7 +227,7 @@ def _image_bytes_per_step(cameras) -> int:
 
 def record_scripted(task_name: str, num_episodes: int, cameras=(), seed: int | None = None, device: int = 0, only_success: bool = False,
                     image_budget_bytes: int = 8 << 30, keep_diverged: bool = False, sink=None, stream_dir: str | None = None, max_batch: int = 256,
-                    **script_kw):
+                    jpeg_quality: int | None = None, **script_kw):
     """The counterpart of record_sim_episodes.py:68-212 with a scripted teleoperator in the headset's place (av_aloha_amd/scripted.py):
     `num_episodes` episodes of `task_name` ("sim_insert_peg", ...) are run SIDE BY SIDE on the device -- one env each, object poses from the
     task's own reset sampling (global numpy RNG, `seed` seeds it) -- through the Cartesian-action env (sim_env.py:277-312), and come back as
@@ -247,7 +247,13 @@ def record_scripted(task_name: str, num_episodes: int, cameras=(), seed: int | N
     (hdf5min.StreamWriter: a chunk per frame, as save_episode lays the image stacks out), the tables follow at the end, a dropped episode's file
     is removed, the kept ones are numbered consecutively from the files already there.  No image stays in memory, so the batches are not sized by
     the image budget but by `max_batch`: a step of 32 envs costs what a step of 3 costs (one wave each), which made the budgeted batches the
-    slow part of a recording with cameras.  The summaries then carry "path" instead of "data"."""
+    slow part of a recording with cameras.  The summaries then carry "path" instead of "data".
+    jpeg_quality: the images are kept as JPEG streams of that quality: every step's frames are rendered AND encoded on the device
+    (sim_env image_streams -> avsim_render_jpeg) and only the streams come to the host, as evaluate_vec's videos do.  The episodes have the
+    compressed layout of save_episode(jpeg_quality=...) -- in memory, handed to `sink`, or written to stream_dir (whole files through
+    save_episode: an episode's streams are a few tens of MB).  The streams of a whole batch stay in memory until it ends, so the batches are
+    sized by `max_batch` and by `image_budget_bytes` with an episode reckoned at 1/16 of its raw frames (rendered frames at quality 90
+    take about 1/26): 56 episodes of zed_cam plus one 480 x 640 camera under the default 8 GiB."""
     from . import scripted
     from .env import sample_object_poses
     from .sim_env import make_sim_env, _TASK_OF_SUBSTRING
@@ -263,10 +269,13 @@ def record_scripted(task_name: str, num_episodes: int, cameras=(), seed: int | N
     while start < n_all:
         # batch size from the image budget: T is only known once the script exists, so size it with the longest script (600 steps)
         per_ep = _image_bytes_per_step(cameras) * 601
-        n = min(n_all - start, max_batch) if (per_ep == 0 or stream_dir is not None) else max(1, min(n_all - start, int(image_budget_bytes // per_ep)))
+        if jpeg_quality is not None:            # a batch's streams stay in memory until it ends: reckoned at 1/16 of the raw frames
+            n = max(1, min(n_all - start, max_batch, int(image_budget_bytes // max(1, per_ep // 16))))
+        else:
+            n = min(n_all - start, max_batch) if (per_ep == 0 or stream_dir is not None) else max(1, min(n_all - start, int(image_budget_bytes // per_ep)))
         env = make_sim_env(task_name, cameras=cameras, num_envs=n, device=device)
         env.sim.reset(poses_all[start:start + n])
-        obs = env.get_obs()
+        obs = env.get_obs(images=jpeg_quality is None)
         home = {k: b(obs["poses"][k], n).copy() for k in ("left", "right", "middle")}
         script = scripted.make_script(scripted.SCRIPT_OF_TASK[task], home, b(obs["qpos"], n), **script_kw)
         T = script.steps() + 1
@@ -276,7 +285,11 @@ def record_scripted(task_name: str, num_episodes: int, cameras=(), seed: int | N
         # per-episode arrays, written step by step
         data = [{name: np.empty((T,) + b(f(obs), n).shape[1:], dtype=np.float32) for name, f in fields.items()} for _ in range(n)]
         writers = None
-        if stream_dir is not None:
+        streams = [{cam: [] for cam in cameras} for _ in range(n)] if jpeg_quality is not None else None
+        if streams is not None:
+            if stream_dir is not None:
+                os.makedirs(stream_dir, exist_ok=True)
+        elif stream_dir is not None:
             from . import hdf5min
             os.makedirs(stream_dir, exist_ok=True)
             writers = [hdf5min.StreamWriter(os.path.join(stream_dir, f".recording_{start + k}.part")) for k in range(n)]
@@ -292,6 +305,10 @@ def record_scripted(task_name: str, num_episodes: int, cameras=(), seed: int | N
                 v = b(f(o), n)
                 for k in range(n):
                     data[k][name][t] = v[k]
+            if streams is not None:             # rendered and encoded on the device: only the streams come to the host
+                for cam, ss in env.image_streams(jpeg_quality).items():
+                    for k in range(n):
+                        streams[k][cam].append(ss[k])
             for cam, img in o.get("images", {}).items():
                 img = b(img, n)
                 for k in range(n):
@@ -305,7 +322,7 @@ def record_scripted(task_name: str, num_episodes: int, cameras=(), seed: int | N
                 _, rw, _ = env.sim.step_cartesian(script.action(b(obs["qpos"], n)))
                 diverged |= (env.sim.diag()[:, 3] & 1).astype(bool)
                 rewards[t - 1] = rw
-                obs = env.get_obs()
+                obs = env.get_obs(images=jpeg_quality is None)
                 put(t, obs)
         except BaseException:
             for w in writers or []:
@@ -320,13 +337,20 @@ def record_scripted(task_name: str, num_episodes: int, cameras=(), seed: int | N
                 if writers is not None:
                     writers[k].abort()
                 continue
-            if writers is not None:
-                writers[k].finish(data[k], attrs={"sim": np.bool_(True)})
+            if streams is not None:
+                data[k].update(pack_streams(streams[k]))
+                streams[k] = None
+            if stream_dir is not None:
                 i = 0
                 while os.path.exists(os.path.join(stream_dir, f"episode_{i}.hdf5")):
                     i += 1
                 path = os.path.join(stream_dir, f"episode_{i}.hdf5")
-                os.replace(writers[k].path, path)
+                if writers is not None:
+                    writers[k].finish(data[k], attrs={"sim": np.bool_(True)})
+                    os.replace(writers[k].path, path)
+                else:
+                    save_episode(data[k], stream_dir, i, jpeg_quality=jpeg_quality)
+                    data[k] = None
                 episodes.append({"path": path, "success": bool(ok), "final_success": bool(rewards[-1, k] == max_reward), "max_reward_reached": reached,
                                  "rewards": rewards[:, k].copy(), "max_reward": int(max_reward), "diverged": bool(diverged[k]), "episode_index": start + k, "steps": T})
                 continue
@@ -346,7 +370,8 @@ def check_dataset_reward(gym_id: str, episodes: list, device: int = 0):
     into the episode's first recorded state (`set_qpos(all_qpos[0])`) and steps the recorded `/action` sequence OPEN LOOP through `step_action`
     -- on the gym assets' model, whose peg / needle contacts are stiffer than those of the data-collection assets the episode was recorded on
     (task_insert_peg.xml:7 "HACK: modified solref different from data collection") --, `get_reward()` after every step; an episode passes when
-    its largest reward is `max_reward`.  All episodes are replayed side by side in one batched env.  -> (passed bool [n], rewards int [T, n])"""
+    its largest reward is `max_reward`.  All episodes are replayed side by side in one batched env.  -> (passed bool [n], rewards int [T, n])
+    The images are never read, so an episode of a compressed file (save_episode(jpeg_quality=...)) is checked as it is."""
     from .env import make
     n = len(episodes)
     q0 = np.stack([np.asarray(e["/observations/all_qpos"][0], dtype=np.float64) for e in episodes])
@@ -363,11 +388,50 @@ def check_dataset_reward(gym_id: str, episodes: list, device: int = 0):
     return ok, rewards
 
 
-def save_episode(data: dict, dataset_dir: str, episode_idx: int, use_h5py: bool | None = None) -> str:
+def pack_streams(streams: dict) -> dict:
+    """{camera: [JPEG streams of the T frames]} -> the image part of a compressed episode, the layout of the ALOHA data sets:
+    `/observations/images/<cam>` u8 [T, max_len] (every stream zero-padded to the longest of the episode) and `/compress_len` int32
+    [ncam, T] (rows in sorted camera-name order)."""
+    cams = sorted(streams)
+    T = len(streams[cams[0]]) if cams else 0
+    assert all(len(streams[c]) == T for c in cams), "every camera has a stream per frame"
+    width = max((len(x) for c in cams for x in streams[c]), default=0)
+    out = {"/compress_len": np.array([[len(x) for x in streams[c]] for c in cams], dtype=np.int32).reshape(len(cams), T)}
+    for c in cams:
+        table = np.zeros((T, width), dtype=np.uint8)
+        for t, x in enumerate(streams[c]):
+            table[t, :len(x)] = np.frombuffer(x, np.uint8)
+        out[f"/observations/images/{c}"] = table
+    return out
+
+
+def compress_episode(data: dict, jpeg_quality: int, encoder=None) -> dict:
+    """An episode with u8 (T, H, W, 3) image stacks -> the same episode with the stacks as JPEG streams (pack_streams).  encoder: a
+    BatchedSim to encode on the device (encode_jpeg); None: av_aloha_amd.jpeg.encode_reference on the host, the same bytes, slowly."""
+    from . import jpeg
+    images = {k: v for k, v in data.items() if "/images/" in k}
+    out = {k: v for k, v in data.items() if k not in images}
+    enc = (lambda v: encoder.encode_jpeg(np.ascontiguousarray(v), jpeg_quality)) if encoder is not None else \
+        (lambda v: [jpeg.encode_reference(f, jpeg_quality) for f in np.asarray(v)])
+    out.update(pack_streams({k.rsplit("/", 1)[1]: enc(v) for k, v in images.items()}))
+    return out
+
+
+def save_episode(data: dict, dataset_dir: str, episode_idx: int, use_h5py: bool | None = None, jpeg_quality: int | None = None, encoder=None) -> str:
     """episode_<idx>.hdf5 with the reference's layout (record_sim_episodes.py:186-206): through h5py when it is importable
-    (use_h5py None / True), else through av_aloha_amd.hdf5min."""
+    (use_h5py None / True), else through av_aloha_amd.hdf5min.
+    jpeg_quality: the compressed layout the reference left commented out (record_sim_episodes.py:202-203) and the ALOHA data sets use:
+    `/observations/images/<cam>` u8 [T, max_len] JPEG streams of this project's encoder, zero-padded; `/compress_len` int32 [ncam, T],
+    rows in sorted camera-name order; attributes compress = True and jpeg_quality.  `data` holds either the raw u8 (T, H, W, 3) stacks,
+    which are encoded here (compress_episode; encoder: a BatchedSim to do it on the device), or streams that are packed already
+    (`/compress_len` present: record_scripted's).  load_episode(decode=...) gives the stacks back."""
     os.makedirs(dataset_dir, exist_ok=True)
     base = os.path.join(dataset_dir, f"episode_{episode_idx}")
+    attrs = {"sim": np.bool_(True)}
+    if jpeg_quality is not None:
+        if "/compress_len" not in data:
+            data = compress_episode(data, jpeg_quality, encoder)
+        attrs.update({"compress": np.bool_(True), "jpeg_quality": np.int32(jpeg_quality)})
     h5py = None
     if use_h5py is not False:
         try:
@@ -377,29 +441,58 @@ def save_episode(data: dict, dataset_dir: str, episode_idx: int, use_h5py: bool 
                 raise
     if h5py is None:
         from . import hdf5min
-        chunks = {k: (1, *v.shape[1:]) for k, v in data.items() if "/images/" in k}
-        hdf5min.write(base + ".hdf5", data, attrs={"sim": np.bool_(True)}, chunks=chunks)
+        chunks = {k: (1, *v.shape[1:]) for k, v in data.items() if "/images/" in k and jpeg_quality is None}
+        hdf5min.write(base + ".hdf5", data, attrs=attrs, chunks=chunks)
         return base + ".hdf5"
     with h5py.File(base + ".hdf5", "w", rdcc_nbytes=1024 ** 2 * 2) as root:
-        root.attrs["sim"] = True
+        for k, v in attrs.items():
+            root.attrs[k] = v
         for name, array in data.items():
-            chunks = (1, *array.shape[1:]) if "/images/" in name else None
+            chunks = (1, *array.shape[1:]) if "/images/" in name and jpeg_quality is None else None
             root.create_dataset(name, data=array, chunks=chunks)
     return base + ".hdf5"
 
 
-def load_episode(path: str) -> dict:
+def episode_streams(data: dict) -> dict:
+    """{camera: [T JPEG streams]} of a loaded compressed episode (`/compress_len` and the padded tables)."""
+    cams = sorted(k.rsplit("/", 1)[1] for k in data if "/images/" in k)
+    ln = np.asarray(data["/compress_len"])
+    assert ln.shape[0] == len(cams), "/compress_len has a row per camera"
+    return {c: [np.asarray(data[f"/observations/images/{c}"][t, :ln[i, t]]).tobytes() for t in range(ln.shape[1])] for i, c in enumerate(cams)}
+
+
+def load_episode(path: str, decode=None) -> dict:
+    """The data sets of an episode file.  decode None: what the file holds -- of a compressed file (save_episode(jpeg_quality=...)) the
+    padded stream tables and `/compress_len`.  decode "host": a compressed file's images as u8 (T, H, W, 3) stacks through
+    av_aloha_amd.jpeg.decode_reference (slow: a Python loop per coefficient); a BatchedSim: the same stacks through the device
+    (decode_jpeg).  `/compress_len` is dropped then; a raw file is returned as it is either way."""
     if path.endswith(".npz"):
         with np.load(path) as z:
-            return {k: z[k] for k in z.files if k != "sim"}
-    try:
-        import h5py
-    except ImportError:
-        from . import hdf5min
-        return hdf5min.read(path)[0]
-    out = {}
-    with h5py.File(path, "r") as root:
-        root.visititems(lambda n, o: out.__setitem__("/" + n, o[()]) if hasattr(o, "shape") else None)
+            out = {k: z[k] for k in z.files if k != "sim"}
+    else:
+        try:
+            import h5py
+        except ImportError:
+            h5py = None
+        if h5py is None:
+            from . import hdf5min
+            out = hdf5min.read(path)[0]
+        else:
+            out = {}
+            with h5py.File(path, "r") as root:
+                root.visititems(lambda n, o: out.__setitem__("/" + n, o[()]) if hasattr(o, "shape") else None)
+    if decode is None or "/compress_len" not in out:
+        return out
+    from . import jpeg
+    streams = episode_streams(out)
+    del out["/compress_len"]
+    for cam, ss in streams.items():
+        if isinstance(decode, str):
+            if decode != "host":
+                raise ValueError(f"load_episode: decode {decode!r} (None, 'host' or a BatchedSim)")
+            out[f"/observations/images/{cam}"] = np.stack([jpeg.decode_reference(x) for x in ss])
+        else:
+            out[f"/observations/images/{cam}"] = decode.decode_jpeg(ss)
     return out
 
 
@@ -424,7 +517,8 @@ def rerender_episode(data, env_id: str, save_path: str | None = None, device: in
     and `/observations/images/<cam>` u8 (T, H, W, 3) per camera; `all_qpos` is not carried over (the reference's data_dict does not have it).
     The frames are independent, so they are T envs of one batched handle, `frames_per_batch` at a time (one set_qpos + one render call each).
     save_path: also written there in the reference's layout (replay_sim_episode.py:11-44).  env: a batched gym env of `env_id` with
-    num_envs == frames_per_batch to reuse (rerender_dataset passes one)."""
+    num_envs == frames_per_batch to reuse (rerender_dataset passes one).  The episode's own images are never read -- the frames are drawn
+    anew --, so a compressed file (save_episode(jpeg_quality=...)) is rendered again as it is."""
     from .env import ENVS, make
     if isinstance(data, str):
         data = load_episode(data)

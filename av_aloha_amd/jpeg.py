@@ -181,3 +181,200 @@ def encode_reference(img, quality=90):
         out += data.replace(b"\xff", b"\xff\x00")
     out += b"\xff\xd9"
     return bytes(out)
+
+
+# ---- decoding (avsim_jpeg_decode, csrc/avsim_jpeg.hip.h: k_jpeg_index, k_jpeg_entropy, k_jpeg_reconstruct) ---------------------------------
+STATUS_HEADER, STATUS_STRUCTURE, STATUS_ENTROPY = 1, 2, 4
+_DQT_PAYLOADS = ((25, 89), (94, 158))           # the 2 x 64 quantiser bytes (zigzag order) inside header()
+_SOF_SIZE = 163                                 # height, width: two big-endian uint16
+
+
+class JpegError(ValueError):
+    """A stream decode_reference / parse does not read; `status` is the bit avsim_jpeg_decode reports for it."""
+
+    def __init__(self, status, msg):
+        super().__init__(msg)
+        self.status = status
+
+
+def stream_size(stream):
+    """(height, width) of a stream of this encoder: the cheap form of parse (the header is compared, the entropy data is not walked)."""
+    s = bytes(stream[:HEADER_BYTES])
+    if len(stream) < HEADER_BYTES + 2:
+        raise JpegError(STATUS_STRUCTURE, f"{len(stream)} bytes: shorter than the header and EOI")
+    H, W = int.from_bytes(s[_SOF_SIZE:_SOF_SIZE + 2], "big"), int.from_bytes(s[_SOF_SIZE + 2:_SOF_SIZE + 4], "big")
+    if H < 1 or W < 1:
+        raise JpegError(STATUS_HEADER, "not this encoder's header")
+    want = header(H, W, 50)
+    (a0, a1), (b0, b1) = _DQT_PAYLOADS
+    if s[:a0] != want[:a0] or s[a1:b0] != want[a1:b0] or s[b1:] != want[b1:]:
+        raise JpegError(STATUS_HEADER, "not this encoder's header")
+    return H, W
+
+
+def parse(stream):
+    """{"height", "width", "quant": [luma[64], chroma[64]] (natural order, read from the stream), "intervals": [(begin, end)] byte ranges of
+    the restart intervals}.  Raises JpegError (a ValueError) unless the stream has encode_reference's structure: header(H, W, q) byte for
+    byte apart from the DQT payloads, exactly ceil(H / 16) intervals separated by RST0..7 in order, EOI at the end."""
+    stream = bytes(stream)
+    H, W = stream_size(stream)
+    inv = np.argsort(ZIGZAG)
+    quant = [np.frombuffer(stream[a:b], np.uint8).astype(np.int64)[inv] for a, b in _DQT_PAYLOADS]
+    n, mh = len(stream), (H + 15) // 16
+    if stream[n - 2:] != b"\xff\xd9":
+        raise JpegError(STATUS_STRUCTURE, "no EOI at the end")
+    a = np.frombuffer(stream, np.uint8)
+    marks = HEADER_BYTES + np.nonzero((a[HEADER_BYTES:n - 2] == 0xFF) & (a[HEADER_BYTES + 1:n - 1] != 0))[0]      # stuffing leaves FF 00 only
+    code = a[marks + 1].astype(np.int64) - 0xD0
+    if len(marks) != mh - 1 or not np.array_equal(code, np.arange(mh - 1) & 7):
+        raise JpegError(STATUS_STRUCTURE, f"{len(marks)} markers in the entropy-coded data, not RST0..7 in order {mh - 1} times")
+    edges = [HEADER_BYTES - 2] + [int(m) for m in marks] + [n - 2]
+    return {"height": H, "width": W, "quant": quant, "intervals": [(edges[r] + 2, edges[r + 1]) for r in range(mh)]}
+
+
+def _decode_luts():
+    """Per table of HUFF_TABLES: uint32[65536], (symbol << 8 | length) of the code the next 16 bits start with, 0 where none does."""
+    out = []
+    for _, (bits, symbols) in HUFF_TABLES:
+        lut = np.zeros(65536, np.uint32)
+        for sym, (code, length) in huffman_codes(bits, symbols).items():
+            lut[code << (16 - length):(code + 1) << (16 - length)] = (sym << 8) | length
+        out.append(lut.tolist())
+    return out
+
+
+_LUTS = []
+
+
+def decode_interval(data, nblocks_mcu):
+    """The quantised coefficients int64 [nblocks_mcu, 6, 64] (natural order) of one restart interval's bytes (still stuffed)."""
+    if not _LUTS:
+        _LUTS.extend(_decode_luts())
+    dc_l, ac_l, dc_c, ac_c = _LUTS
+    raw = bytes(data).replace(b"\xff\x00", b"\xff")
+    total = 8 * len(raw)
+    big = int.from_bytes(raw, "big") if raw else 0
+    pos = 0                                      # bits consumed
+    zz = ZIGZAG.tolist()
+    out = np.zeros((nblocks_mcu, 6, 64), np.int64)
+    pred = [0, 0, 0]
+
+    def peek16():
+        left = total - pos
+        return (big >> (left - 16)) & 0xFFFF if left >= 16 else (big << (16 - left)) & 0xFFFF
+
+    def symbol(lut):
+        nonlocal pos
+        e = lut[peek16()]
+        if not e:
+            raise JpegError(STATUS_ENTROPY, "a code that is not in the table")
+        if pos + (e & 255) > total:
+            raise JpegError(STATUS_ENTROPY, "the interval's bytes run out")
+        pos += e & 255
+        return e >> 8
+
+    def amplitude(n):
+        nonlocal pos
+        if n == 0:
+            return 0
+        if pos + n > total:
+            raise JpegError(STATUS_ENTROPY, "the interval's bytes run out")
+        v = (big >> (total - pos - n)) & ((1 << n) - 1)
+        pos += n
+        return v if v >= 1 << (n - 1) else v - (1 << n) + 1
+
+    for m in range(nblocks_mcu):
+        for j in range(6):
+            comp = 0 if j < 4 else j - 3
+            n = symbol(dc_l if comp == 0 else dc_c)
+            if n > 11:
+                raise JpegError(STATUS_ENTROPY, "a DC size above 11")
+            pred[comp] += amplitude(n)
+            out[m, j, 0] = min(max(pred[comp], -32768), 32767)      # (the staging area is int16; no stream of the encoder comes near)
+            ac, k = (ac_l if comp == 0 else ac_c), 1
+            while k < 64:
+                rs = symbol(ac)
+                if rs == 0:
+                    break
+                run, n = rs >> 4, rs & 15
+                if n > 10:
+                    raise JpegError(STATUS_ENTROPY, "an AC size above 10")
+                k += run
+                if n == 0:                       # ZRL: sixteen zeros (the table has no other symbol of size 0)
+                    k += 1
+                    if k > 63:
+                        raise JpegError(STATUS_ENTROPY, "a coefficient index past 63")
+                    continue
+                if k > 63:
+                    raise JpegError(STATUS_ENTROPY, "a coefficient index past 63")
+                out[m, j, zz[k]] = amplitude(n)
+                k += 1
+    left = total - pos
+    if left >= 8 or (big & ((1 << left) - 1)) != (1 << left) - 1:
+        raise JpegError(STATUS_ENTROPY, "whole bytes left over or a pad bit that is not 1 at the interval's end")
+    return out
+
+
+def decode_coefficients(stream):
+    """parse + entropy decode: (info, Y [2 mh, 2 mw, 64], Cb [mh, mw, 64], Cr [mh, mw, 64]) quantised coefficients, natural order."""
+    info = parse(stream)
+    H, W = info["height"], info["width"]
+    mh, mw = (H + 15) // 16, (W + 15) // 16
+    cy, cb, cr = np.zeros((2 * mh, 2 * mw, 64), np.int64), np.zeros((mh, mw, 64), np.int64), np.zeros((mh, mw, 64), np.int64)
+    for r, (a, b) in enumerate(info["intervals"]):
+        c = decode_interval(stream[a:b], mw)
+        cy[2 * r:2 * r + 2] = c[:, :4].reshape(mw, 2, 2, 64).transpose(1, 0, 2, 3).reshape(2, 2 * mw, 64)
+        cb[r], cr[r] = c[:, 4], c[:, 5]
+    return info, cy, cb, cr
+
+
+def _idct(coef, q):
+    """coef [by, bx, 64] quantised, q[64] -> u8-valued samples [8 by, 8 bx] (int64): dequantise, clamp, columns, rows, + 128, clamp."""
+    F = np.clip(coef * q, -2048, 2047).reshape(coef.shape[:2] + (8, 8))                       # [.., k, l]
+    t = (np.einsum("kr,...kl->...rl", DCT_MATRIX, F) + 1024) >> 11                            # columns
+    p = (np.einsum("lc,...rl->...rc", DCT_MATRIX, t) + 16384) >> 15                           # rows
+    p = np.clip(p + 128, 0, 255)
+    return p.transpose(0, 2, 1, 3).reshape(coef.shape[0] * 8, coef.shape[1] * 8)
+
+
+def dequantised_peak(stream):
+    """max |coef * q| over the stream's coefficients: what the dequantiser's clamp to [-2048, 2047] would act on."""
+    info, cy, cb, cr = decode_coefficients(stream)
+    ql, qc = info["quant"]
+    return int(max(np.abs(cy * ql).max(), np.abs(cb * qc).max(), np.abs(cr * qc).max()))
+
+
+def _upsample_triangle(c, H, W):
+    """libjpeg's h2v2 "fancy" filter on the chroma plane cropped to ceil(H/2) x ceil(W/2), edge samples replicated -> [H, W]."""
+    ch, cw = (H + 1) // 2, (W + 1) // 2
+    c = c[:ch, :cw]
+    up, down = np.concatenate([c[:1], c[:-1]]), np.concatenate([c[1:], c[-1:]])
+    s = np.empty((2 * ch, cw), np.int64)
+    s[0::2], s[1::2] = 3 * c + up, 3 * c + down
+    left, right = np.concatenate([s[:, :1], s[:, :-1]], 1), np.concatenate([s[:, 1:], s[:, -1:]], 1)
+    o = np.empty((2 * ch, 2 * cw), np.int64)
+    o[:, 0::2], o[:, 1::2] = (3 * s + left + 8) >> 4, (3 * s + right + 7) >> 4
+    return o[:H, :W]
+
+
+def decode_reference(stream, upsample="replicate"):
+    """A stream of encode_reference (or of the device encoder) -> u8 [H, W, 3] RGB.  The specification of avsim_jpeg_decode: integer
+    arithmetic throughout, equal to the device's output byte for byte (tests/test_gpu_jpeg_decode.py).  upsample "replicate": a chroma
+    sample covers its 2 x 2 pixels (the inverse of the encoder's box filter); "triangle": libjpeg's default filter, what cv2 / Pillow show.
+    Raises JpegError for a stream that is not this encoder's (parse) or whose entropy-coded data is broken."""
+    if upsample not in ("replicate", "triangle"):
+        raise ValueError(f"upsample {upsample!r}: 'replicate' or 'triangle'")
+    info, cy, cb, cr = decode_coefficients(stream)
+    H, W = info["height"], info["width"]
+    ql, qc = info["quant"]
+    Y = _idct(cy, ql)[:H, :W]
+    Cb, Cr = _idct(cb, qc), _idct(cr, qc)
+    if upsample == "replicate":
+        Cb, Cr = (np.repeat(np.repeat(c, 2, 0), 2, 1)[:H, :W] for c in (Cb, Cr))
+    else:
+        Cb, Cr = _upsample_triangle(Cb, H, W), _upsample_triangle(Cr, H, W)
+    Cb, Cr = Cb - 128, Cr - 128
+    R = Y + ((91881 * Cr + 32768) >> 16)
+    G = Y - ((22554 * Cb + 46802 * Cr + 32768) >> 16)
+    B = Y + ((116130 * Cb + 32768) >> 16)
+    return np.clip(np.stack([R, G, B], -1), 0, 255).astype(np.uint8)

@@ -36,6 +36,7 @@ class BatchedSim:
         blob = file_blob if blob is None else blob        # (tests: the task's model with an edited constant, e.g. gravity)
         self.h = _ffi.Handle(blob, num_envs, device, _ffi.AVSIM_F64_PHYSICS if f64 else 0)
         self.N = num_envs
+        self._jpeg_stride = {}         # render_jpeg: the bytes reserved per stream of a shape, grown when a stream did not fit (a recorder calls per step)
         for k in ("nq", "nv", "nu", "nj", "nobj", "max_reward", "maxcon", "maxefc"):
             setattr(self, k, getattr(self.h, k))
         for k, v in (options or {}).items():
@@ -193,6 +194,66 @@ class BatchedSim:
             if int(ln.max()) > buf.shape[1]:          # some stream did not fit: its length says what it needs
                 buf, ln = run(frames, int(ln.max()))
             out += [buf[i, :ln[i]].tobytes() for i in range(len(frames))]
+        return out
+
+    def render_jpeg(self, cameras, height, width, quality=90, tile=False):
+        """render_rgb's visual-scene images as JPEG streams (avsim_render_jpeg): rendered and encoded on the device, only the streams come to
+        the host -- the bytes encode_jpeg gives for render_rgb's frames.  -> [N][len(cameras)] bytes; tile: the cameras' views of an env side
+        by side in one height x (len(cameras) * width) image, -> [N] bytes."""
+        if not getattr(self, "_visual", False):
+            self.load_visual()
+        self.set_option("render_proxies", 0)
+        self.set_option("render_cam_major", 0)
+        names = self.manifest["camera_names"]
+        ids = np.array([names.index(c) if isinstance(c, str) else int(c) for c in cameras], dtype=np.int32)
+        L = self.h.L
+        iw = width * len(ids) if tile else width
+        bound = int(L.avsim_jpeg_bound(height, iw))
+        if bound < 0:
+            raise ValueError(f"render_jpeg: image size {height} x {iw}")
+        n = self.N if tile else self.N * len(ids)
+        key = (height, iw, int(quality))
+        strides = self._jpeg_stride
+        stride = strides.get(key, min(bound, (height * iw * 3 // 8 + 4095) // 4096 * 4096))
+        while True:
+            buf, ln = np.empty((n, stride), dtype=np.uint8), np.empty(n, dtype=np.int32)
+            self.h.check(L.avsim_render_jpeg(self.h.h, ids.ctypes.data, len(ids), height, width, 1 if tile else 0, int(quality), buf.ctypes.data, stride, ln.ctypes.data))
+            if int(ln.max()) <= stride:
+                break
+            stride = strides[key] = min(bound, (int(ln.max()) * 5 // 4 + 4095) // 4096 * 4096)        # some stream did not fit: its length says what it needs
+        if self.visual_info()["overflow"]:
+            import warnings
+            warnings.warn(f"avsim_render_jpeg: a view ran out of triangle records or tile-list entries at {height}x{width}: triangles were dropped from the image", RuntimeWarning, stacklevel=2)
+        out = [buf[i, :ln[i]].tobytes() for i in range(n)]
+        return out if tile else [out[e * len(ids):(e + 1) * len(ids)] for e in range(self.N)]
+
+    def decode_jpeg(self, streams, upsample="replicate"):
+        """u8 frames [n, H, W, 3] of JPEG streams (a list of bytes, all of one size) that encode_jpeg / av_aloha_amd.jpeg.encode_reference
+        wrote, decoded on the device (avsim_jpeg_decode): the pixels of av_aloha_amd.jpeg.decode_reference.  Raises ValueError (a
+        jpeg.JpegError carrying the status) for a stream the decoder flags: it reads this encoder's streams and no others."""
+        from . import jpeg
+        if upsample not in ("replicate", "triangle"):
+            raise ValueError(f"upsample {upsample!r}: 'replicate' or 'triangle'")
+        streams = [bytes(s) for s in streams]
+        if not streams:
+            raise ValueError("decode_jpeg: no streams")
+        H, W = jpeg.stream_size(streams[0])
+        L = self.h.L
+        out = np.empty((len(streams), H, W, 3), dtype=np.uint8)
+        batch = max(1, (256 << 20) // (H * W * 3))
+        for i0 in range(0, len(streams), batch):
+            part = streams[i0:i0 + batch]
+            stride = max(len(s) for s in part)
+            buf, ln = np.zeros((len(part), stride), dtype=np.uint8), np.array([len(s) for s in part], dtype=np.int32)
+            for i, s in enumerate(part):
+                buf[i, :len(s)] = np.frombuffer(s, np.uint8)
+            status = np.zeros(len(part), dtype=np.int32)
+            self.h.check(L.avsim_jpeg_decode(self.h.h, buf.ctypes.data, stride, ln.ctypes.data, None, len(part), H, W, 0,
+                                             1 if upsample == "triangle" else 0, out[i0:i0 + batch].ctypes.data, status.ctypes.data))
+            if status.any():
+                i = int(np.nonzero(status)[0][0])
+                raise jpeg.JpegError(int(status[i]), f"decode_jpeg: stream {i0 + i} is not a {H} x {W} stream of this encoder (status {int(status[i])}: "
+                                                     "1 header, 2 marker structure or length, 4 entropy-coded data)")
         return out
 
     def reward_from_pairs(self, geom_pairs, latch=None):

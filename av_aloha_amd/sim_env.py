@@ -85,7 +85,8 @@ class GuidedVisionEnv:
         quat = mat2quat_xyzw(T[:, :3, :3])                       # mat2pose (:153-157) then xyzw_to_wxyz (:159-161)
         return np.concatenate([T[:, :3, 3], quat[:, [3, 0, 1, 2]]], axis=1)
 
-    def get_obs(self):
+    def get_obs(self, images=True):
+        """images False: the observation without its "images" (a recorder that keeps image_streams instead of frames)."""
         qpos, qvel, ctrl, _ = self.sim.get_state()
         pos = qpos[:, self._qadr].copy()
         vel = qvel[:, self._dadr].copy()
@@ -95,13 +96,15 @@ class GuidedVisionEnv:
             vel[:, k] = vel[:, k] / self._grip_span
             con[:, k] = (con[:, k] - self._grip_lo) / self._grip_span
         poses = {"left": self._fk_pose(0, ctrl[:, 0:6]), "right": self._fk_pose(1, ctrl[:, 7:13]), "middle": self._fk_pose(2, ctrl[:, 14:21])}
-        return {
+        obs = {
             "joints": {"position": self._sq(pos), "velocity": self._sq(vel)},
             "qpos": self._sq(qpos),
             "control": self._sq(con),
             "poses": {k: self._sq(v) for k, v in poses.items()},
-            "images": self._images(),
         }
+        if images:
+            obs["images"] = self._images()
+        return obs
 
     def _images(self):
         images = {}
@@ -112,6 +115,17 @@ class GuidedVisionEnv:
             else:
                 images[camera] = self._sq(self.sim.render_rgb([_CAMERA_IDS[camera]], 480, 640)[:, 0])       # (a view of the call's own array: one camera, contiguous)
         return images
+
+    def image_streams(self, quality=90):
+        """The images of get_obs as JPEG streams, {camera: [num_envs streams]}: rendered and encoded on the device (BatchedSim.render_jpeg),
+        zed_cam's two views put side by side there; the bytes of BatchedSim.encode_jpeg on the same images, without a pixel on the host."""
+        streams = {}
+        for camera in self._cameras:
+            if camera == "zed_cam":
+                streams["zed_cam"] = self.sim.render_jpeg(["zed_cam_left", "zed_cam_right"], 720, 720, quality, tile=True)
+            else:
+                streams[camera] = [s[0] for s in self.sim.render_jpeg([_CAMERA_IDS[camera]], 480, 640, quality)]
+        return streams
 
     # ---- gym-style surface (sim_env.py:220-312) ------------------------------------------------------
     def reset(self, seed=None):

@@ -280,6 +280,35 @@ class VecEnv:
                                               out_len.data_ptr()))
         return out, out_len
 
+    def decode_jpeg(self, buf, lengths, height=None, width=None, upsample="replicate", fmt=None, out=None, status=None):
+        """The inverse of encode_jpeg on the device (avsim_jpeg_decode): buf uint8 [n, stride] and lengths int32 [n] as encode_jpeg
+        returns them -> (images, status int32 [n]).  height / width default to the observation size, fmt to the env's observation format:
+        "lerobot" float32 [n, 3, H, W] in [0, 1], "gym" uint8 [n, H, W, 3].  The pixels are av_aloha_amd.jpeg.decode_reference's;
+        status[i] != 0 flags a stream that is not this encoder's (avsim.h), whose image is unspecified.  out / status: buffers to write
+        into.  Does not synchronise -- so it does not raise for a flagged stream either: read `status` when the host next waits."""
+        torch = self.torch
+        self._bind_stream()
+        if upsample not in ("replicate", "triangle"):
+            raise ValueError(f"upsample {upsample!r}: 'replicate' or 'triangle'")
+        fmt = self.obs_format if fmt is None else fmt
+        if fmt not in ("lerobot", "gym"):
+            raise ValueError(f"fmt {fmt!r}: 'lerobot' or 'gym'")
+        H = self.observation_height if height is None else int(height)
+        W = self.observation_width if width is None else int(width)
+        assert buf.dtype == torch.uint8 and buf.device == self.device and buf.ndim == 2 and buf.is_contiguous()
+        n = int(buf.shape[0])
+        assert lengths.dtype == torch.int32 and lengths.device == self.device and tuple(lengths.shape) == (n,) and lengths.is_contiguous()
+        shape, dtype = ((n, 3, H, W), torch.float32) if fmt == "lerobot" else ((n, H, W, 3), torch.uint8)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=self.device)
+        if status is None:
+            status = torch.empty(n, dtype=torch.int32, device=self.device)
+        assert out.dtype == dtype and out.device == self.device and tuple(out.shape) == shape and out.is_contiguous()
+        assert status.dtype == torch.int32 and status.device == self.device and tuple(status.shape) == (n,) and status.is_contiguous()
+        self.h.check(self.L.avsim_jpeg_decode(self.h.h, buf.data_ptr(), int(buf.shape[1]), lengths.data_ptr(), None, n, H, W,
+                                              1 if fmt == "lerobot" else 0, 1 if upsample == "triangle" else 0, out.data_ptr(), status.data_ptr()))
+        return out, status
+
     def check_render_overflow(self):
         """Overflow flags of the last colour render (bit 0 triangle records, bit 1 tile lists; 0 = complete images): warns when set.
         Synchronises, so it is read once at the end of an evaluation rather than per step."""

@@ -222,6 +222,33 @@ int64_t avsim_jpeg_bound(int height, int width);
 int avsim_jpeg_encode(avsim_t* h, const void* img, int fmt, const int32_t* index, int nimg, int height, int width, int quality,
                       uint8_t* out, int64_t stride, int32_t* out_len);
 
+/* avsim_render_rgb followed by avsim_jpeg_encode without the pixels leaving the device (a recorder keeps streams, not frames): the visual
+ * scene's u8 images of the cameras are rendered into a buffer of the library's and encoded from there.  tile 0: one stream per view of
+ * height x width, in avsim_render_rgb's order ([N][ncam], or [ncam][N] under "render_cam_major"); tile 1: the ncam views of an env side
+ * by side in ONE height x (ncam * width) image (the Cartesian env's zed_cam = left | right), one stream per env, "render_cam_major" 0.
+ * out, stride, out_len as avsim_jpeg_encode.  With host pointers only the lengths and, of every stream, its first min(stride, longest
+ * length) bytes come back (the rest of `out` is left as it was); with AVSIM_IO_DEVICE nothing synchronises once a call of the same size
+ * has run.  AVSIM_EINVAL: no visual scene, quality outside 1..100, an image size outside 1..65535, tile with "render_cam_major" 1. */
+int avsim_render_jpeg(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, int tile, int quality, uint8_t* out, int64_t stride,
+                      int32_t* out_len);
+
+/* The way back: streams of avsim_jpeg_encode (and of nothing else) -> images on the device, byte for byte the output of
+ * av_aloha_amd/jpeg.py decode_reference, its specification.  in: u8 [.][stride], in_len: int32 [.] = each stream's length;
+ * stream i of the call is row index[i] of both (index NULL: row i; a device caller vouches for the range).  fmt 0: out = u8
+ * [nimg][H][W][3]; fmt 1: float32 [nimg][3][H][W], every value (float)u8 / 255, the bits of avsim_render_rgb_f32.  upsample 0: a chroma
+ * sample covers its 2 x 2 pixels (the inverse of the encoder's box filter); 1: libjpeg's h2v2 triangle filter on the chroma plane
+ * cropped to ceil(H/2) x ceil(W/2) (what cv2 / Pillow show).  status: int32 [nimg], 0 = a valid image; bit 0: not this encoder's
+ * header for (height, width); bit 1: wrong marker structure or length (in_len below header + EOI or above stride, a marker other than
+ * RST0..7 in order ceil(H/16) - 1 times, no EOI at the end); bit 2: an entropy error (a code outside the tables, a coefficient index
+ * past 63, bytes that run out or are left over, a pad bit that is not 1).  The pixels of a flagged image are unspecified; nothing but
+ * its own slot of `out` is written, and no byte string makes the kernels read or write out of bounds.  Pointers follow the handle's
+ * I/O mode; with AVSIM_IO_DEVICE nothing synchronises once a call of the same size has run.  AVSIM_EINVAL: fmt, upsample, height or
+ * width < 1 or > 65535, stride < 1.  Options: "jpeg_decode_budget" -- bytes of coefficient staging (512 MB); a call that needs more goes
+ * through the kernels in groups of images.  "jpeg_decode_events" 1 -- the call records the handle's events 12, 13, 14, 15 before, between
+ * and after its three kernels (avsim_event_elapsed_ms(12, 13) = the index kernel, (13, 14) entropy, (14, 15) reconstruction). */
+int avsim_jpeg_decode(avsim_t* h, const uint8_t* in, int64_t stride, const int32_t* in_len, const int32_t* index, int nimg, int height, int width,
+                      int fmt, int upsample, void* out, int32_t* status);
+
 /* Per-env episodes on the device (a vector env with gymnasium's NEXT_STEP autoreset; av_aloha_amd/vec_env.py).  Pointers follow the
  * handle's I/O mode, except box / share of the set-up (host pointers).  In device mode no step, reset, sample or render call
  * synchronises; avsim_episode_setup does (it reallocates the records: once per evaluation), and so do avsim_episode_log /

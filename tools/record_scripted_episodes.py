@@ -3,7 +3,10 @@
 drives the sim with a VR headset and writes episode_<i>.hdf5, :155-212).  All episodes run side by side on the device.
 
     python tools/record_scripted_episodes.py --task_name sim_insert_peg --num_episodes 64 --dataset_dir data/sim_insert_peg \
-        [--cameras zed_cam,cam_left_wrist] [--seed 0] [--only_success] [--check]
+        [--cameras zed_cam,cam_left_wrist] [--seed 0] [--only_success] [--check] [--jpeg_quality 90]
+
+--jpeg_quality writes the images as JPEG streams encoded on the device (harness.save_episode's compressed layout: padded stream tables and
+/compress_len), some 26 times smaller at quality 90; harness.load_episode(decode=...) and av_aloha_amd.dataset.CompressedDataset read them.
 
 --check replays every saved episode on the task's gym env both ways the reference has: its recorded full states through set_qpos
 (replay_sim_episode.py:221-262) and its recorded actions open loop through step_action from the first state
@@ -31,11 +34,13 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--only_success", action="store_true")
     ap.add_argument("--check", action="store_true")
+    ap.add_argument("--jpeg_quality", type=int, default=None, help="1..100: store the images as JPEG streams of this quality (compressed layout); raw u8 stacks by default")
     args = ap.parse_args()
     cams = [c for c in args.cameras.split(",") if c]
     t0 = time.time()
     # the episodes are written while they are recorded (harness.record_scripted stream_dir: no image kept in memory, all episodes side by side)
-    eps = harness.record_scripted(args.task_name, args.num_episodes, cameras=cams, seed=args.seed, only_success=args.only_success, stream_dir=args.dataset_dir)
+    eps = harness.record_scripted(args.task_name, args.num_episodes, cameras=cams, seed=args.seed, only_success=args.only_success, stream_dir=args.dataset_dir,
+                                  jpeg_quality=args.jpeg_quality)
     paths = [e["path"] for e in eps]
     T = [eps[0]["steps"] if eps else 0]
     t1 = time.time()
