@@ -65,6 +65,10 @@ def lib():
         L.avsim_jpeg_encode.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, vp, C.c_int64, vp]
         L.avsim_render_jpeg.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, C.c_int64, vp]
         L.avsim_jpeg_decode.argtypes = [vp, vp, C.c_int64, vp, vp, i32, i32, i32, i32, i32, vp, vp]
+        L.avsim_compose.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32, i32, u32]
+        L.avsim_compose_label.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, C.c_char_p, vp, u32]
+        L.avsim_compose_font.argtypes = [vp]
+        L.avsim_compose_font.restype = None
         L.avsim_episode_setup.argtypes = [vp, vp, vp, C.c_uint64, i32, i32, C.c_int64]
         L.avsim_sample_poses.argtypes = [vp, C.c_uint64, i32, vp, vp]
         L.avsim_episode_reset.argtypes = [vp, vp, vp, vp]

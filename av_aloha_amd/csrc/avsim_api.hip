@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/avsim.h"
+#include "avsim_compose.hip.h"
 #include "avsim_episode.hip.h"
 #include "avsim_ik.hip.h"
 #include "avsim_jpeg.hip.h"
@@ -78,6 +79,7 @@ struct avsim {
     VisHost vis;         // colour images of the visual meshes (avsim_vis.hip.h), once avsim_load_visual has run
     JpegHost jpeg;       // JPEG streams of such images (avsim_jpeg.hip.h): tables per shape, the intervals' staging area
     JpegDecHost jpegdec; // and those streams back into images: Huffman lookup tables, the coefficients' staging area
+    ComposeHost compose; // views resampled into a canvas, labels (avsim_compose.hip.h): coefficient tables per size pair, the validated placements
     bool jpegdec_events = false;   // option "jpeg_decode_events": avsim_jpeg_decode records ev[12..15] around its three kernels
     // the state's version: bumped by everything that writes qpos (reset, the steps, set_state); the image calls skip their pose pass and the shadow
     // map when they already hold this version's (a facade that fetches its cameras one call at a time repeats neither)
@@ -472,6 +474,7 @@ void avsim_destroy(avsim_t* h) {
     h->vis.destroy();
     h->jpeg.destroy();
     h->jpegdec.destroy();
+    h->compose.destroy();
     for (void* p : {h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, (void*)h->d_latch})
         if (p) (void)hipFree(p);
     for (void* p : h->d_io)
@@ -1038,6 +1041,63 @@ int avsim_jpeg_decode(avsim_t* h, const uint8_t* in, int64_t stride, const int32
     if ((rc = h->out_end(10, out, bytes))) return rc;
     if ((rc = h->out_end(11, status, sizeof(int32_t) * (size_t)nimg))) return rc;
     return h->finish();
+}
+
+// Camera views resampled into rectangles of a canvas and labelled there (av_aloha_amd/compose.py is the specification; csrc/avsim_compose.hip.h)
+int avsim_compose(avsim_t* h, const void* src, int src_fmt, int nsrc, int src_h, int src_w, void* canvas, int canvas_fmt, int nout, int canvas_h, int canvas_w,
+                  const int32_t* places, int nplace, int clear, uint32_t clear_rgb) {
+    if (!h) return AVSIM_EINVAL;
+    if (!src || !canvas || nplace < 0 || (nplace > 0 && !places) || nsrc < 1 || nout < 1) { h->set_error("avsim_compose: bad arguments"); return AVSIM_EINVAL; }
+    if ((src_fmt != 0 && src_fmt != 1) || (canvas_fmt != 0 && canvas_fmt != 1)) { h->set_error("avsim_compose: a format is 0 (u8 HWC) or 1 (float32 CHW)"); return AVSIM_EINVAL; }
+    if (src_h < 1 || src_w < 1 || src_h > 65535 || src_w > 65535 || canvas_h < 1 || canvas_w < 1 || canvas_h > 65535 || canvas_w > 65535) {
+        h->set_error("avsim_compose: image sizes %d x %d, %d x %d outside 1..65535", src_h, src_w, canvas_h, canvas_w);
+        return AVSIM_EINVAL;
+    }
+    if (!h->io_device) {          // (the arguments are checked before a host caller's pixels move)
+        std::string why;
+        if (ComposeHost::validate(nsrc, src_h, src_w, nout, canvas_h, canvas_w, places, nplace, why)) { h->set_error("%s", why.c_str()); return AVSIM_EINVAL; }
+    }
+    AVS_ON_DEVICE(h);
+    int rc;
+    const void* dsrc = nullptr;
+    void* dcanvas = nullptr;
+    const size_t sbytes = (size_t)nsrc * src_h * src_w * (src_fmt ? 12 : 3), cbytes = (size_t)nout * canvas_h * canvas_w * (canvas_fmt ? 12 : 3);
+    if ((rc = h->in(8, src, sbytes, &dsrc))) return rc;
+    if ((rc = h->out_begin(10, canvas, cbytes, &dcanvas))) return rc;
+    if (!h->io_device && !clear) HIPCHK(h, hipMemcpyAsync(dcanvas, canvas, cbytes, hipMemcpyHostToDevice, h->stream));
+    if ((rc = h->compose.launch(h->stream, dsrc, src_fmt, nsrc, src_h, src_w, dcanvas, canvas_fmt, nout, canvas_h, canvas_w, places, nplace, clear, clear_rgb, h->err)))
+        return rc == -1 ? AVSIM_EINVAL : AVSIM_EHIP;
+    if ((rc = h->out_end(10, canvas, cbytes))) return rc;
+    return h->finish();
+}
+
+int avsim_compose_label(avsim_t* h, void* canvas, int canvas_fmt, int nout, int canvas_h, int canvas_w, const int32_t* where, int nlabel, const char* prefix,
+                        const int64_t* value, uint32_t rgb) {
+    if (!h) return AVSIM_EINVAL;
+    if (!canvas || nlabel < 0 || (nlabel > 0 && !where) || nout < 1) { h->set_error("avsim_compose_label: bad arguments"); return AVSIM_EINVAL; }
+    if (canvas_fmt != 0 && canvas_fmt != 1) { h->set_error("avsim_compose_label: canvas_fmt is 0 (u8 HWC) or 1 (float32 CHW)"); return AVSIM_EINVAL; }
+    if (canvas_h < 1 || canvas_w < 1 || canvas_h > 65535 || canvas_w > 65535) { h->set_error("avsim_compose_label: canvas size %d x %d outside 1..65535", canvas_h, canvas_w); return AVSIM_EINVAL; }
+    if (nlabel == 0) return AVSIM_OK;
+    AVS_ON_DEVICE(h);
+    int rc;
+    void* dcanvas = nullptr;
+    const void* dvalue = nullptr;
+    const size_t cbytes = (size_t)nout * canvas_h * canvas_w * (canvas_fmt ? 12 : 3);
+    if ((rc = h->out_begin(10, canvas, cbytes, &dcanvas))) return rc;
+    if (!h->io_device) HIPCHK(h, hipMemcpyAsync(dcanvas, canvas, cbytes, hipMemcpyHostToDevice, h->stream));
+    if (value && (rc = h->in(9, value, sizeof(int64_t) * (size_t)nlabel, &dvalue))) return rc;
+    if ((rc = h->compose.label(h->stream, dcanvas, canvas_fmt, nout, canvas_h, canvas_w, where, nlabel, prefix, (const long long*)dvalue, rgb, h->err)))
+        return rc == -1 ? AVSIM_EINVAL : AVSIM_EHIP;
+    if ((rc = h->out_end(10, canvas, cbytes))) return rc;
+    return h->finish();
+}
+
+void avsim_compose_font(uint8_t rows[128][7]) {
+    std::memset(rows, 0, 128 * 7);
+    for (int ch = 0; ch < 128; ch++) {
+        const int g = cmp_glyph(ch);
+        if (g >= 0) std::memcpy(rows[ch], CMP_FONT_HOST[g], 7);
+    }
 }
 
 // The visual scene of avsim_render_rgb: the mesh library (models/visual_meshes.avv, compiler/vismesh.py) against the instances the

@@ -156,8 +156,64 @@ class _VideoRecorder:
                     self.open[e] = False
 
 
+class _GridRecorder:
+    """One Motion-JPEG file of a vector env's batch: every step's frames of envs [0, k) are shrunk into the cells of a grid, labelled with the
+    envs' episode ids (read on the device) and encoded there, into a chunk of buffers that comes to the host in one copy."""
+
+    def __init__(self, env, path, camera, k, cols, cell, quality, fps):
+        from .compose import layout_grid
+        from .mjpeg import AviWriter
+        import torch
+        self.env, self.k, self.quality = env, int(k), int(quality)
+        self.src = env.camera_images(camera)
+        cell_h, cell_w = int(cell[0]), int(cell[1])
+        rows, CH, CW = layout_grid(self.k, cell_h, cell_w, cols)
+        self.places = np.array([(0, e, x0, y0, w, h) for e, (x0, y0, w, h) in enumerate(rows)], dtype=np.int32)
+        self.where = np.array([(0, x0 + 2, y0 + 2, max(1, cell_h // 60)) for x0, y0, _, _ in rows], dtype=np.int32)
+        self.canvas = torch.zeros((1, CH, CW, 3), dtype=torch.uint8, device=env.device)
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        self.writer = AviWriter(path, CW, CH, fps=fps)
+        stride = int(min(env.L.avsim_jpeg_bound(CH, CW), (CH * CW * 3 // 2 + 4095) // 4096 * 4096))
+        self.chunk = max(1, min(64, (256 << 20) // stride))
+        self.buf = torch.empty((self.chunk, 1, stride), dtype=torch.uint8, device=env.device)
+        self.len = torch.zeros((self.chunk, 1), dtype=torch.int32, device=env.device)
+        self.ids = torch.zeros(self.k, dtype=torch.int64, device=env.device)
+        self.fill = 0
+
+    def add(self, info):
+        """After a step: one frame."""
+        env, c = self.env, self.fill
+        env.compose(self.src, self.places, out=self.canvas, clear=0)
+        self.ids.copy_(info["episode_id"][:self.k])
+        env.compose_label(self.canvas, self.where, "", self.ids, 0xFFFFFF)
+        env.encode_images(self.canvas, self.quality, out=self.buf[c], out_len=self.len[c])
+        self.fill += 1
+        if self.fill == self.chunk:
+            self.flush()
+
+    def flush(self):
+        n, self.fill = self.fill, 0
+        if n == 0:
+            return
+        ln = self.len[:n, 0].cpu().numpy()                       # (this copy waits for the stream)
+        stride = self.buf.shape[2]
+        if (ln > stride).any():
+            raise RuntimeError(f"evaluate_vec: a grid frame's JPEG stream ({int(ln.max())} B) is longer than the {stride} B reserved for it")
+        data = self.buf[:n, 0, :int(ln.max())].cpu().numpy()
+        for c in range(n):
+            self.writer.add(data[c, :ln[c]].tobytes())
+
+    def close(self, ok=True):
+        try:
+            if ok:
+                self.flush()
+        finally:
+            self.writer.close() if ok else self.writer.abort()
+
+
 def evaluate_vec(env, select_action, num_episodes: int, seed: int | None = None, video_dir: str | None = None, video_camera: str | None = None,
-                 video_episodes: int = 0, video_quality: int = 90, video_fps: float = 50) -> list:
+                 video_episodes: int = 0, video_quality: int = 90, video_fps: float = 50, grid_video: str | None = None, grid_envs: int = 0,
+                 grid_cols: int | None = None, grid_cell=(120, 160), grid_quality: int = 90) -> list:
     """Policy evaluation on a device-resident vector env (vec_env.make_vec): the episode ids restart at 0 and the env is stepped until
     the episodes with ids [0, num_episodes) have all finished; envs go on to later ids by themselves (NEXT_STEP autoreset).
     select_action(obs, info) -> float32 [N, nj] tensor on the env's device; info["episode_id"] changing marks an env's new episode.
@@ -170,8 +226,21 @@ def evaluate_vec(env, select_action, num_episodes: int, seed: int | None = None,
     video_camera defaults to zed_cam_left when the env renders it, else to its first camera.  The frames are encoded on the device
     (VecEnv.encode_jpeg) into buffers that hold a chunk of calls and come to the host once per chunk -- that copy waits for the stream,
     the steps in between do not; recording stops when those episodes are over.  The records are the same with and without video.
-    ValueError: video_episodes > env.num_envs, or a camera the env does not render."""
-    video = None
+    ValueError: video_episodes > env.num_envs, or a camera the env does not render.
+
+    The batch at a glance: with grid_video (a path) and grid_envs = k > 0 ONE file is written whose every frame -- one per step call, until the
+    evaluation ends -- holds video_camera's observation of envs 0 .. k-1, shrunk to grid_cell = (height, width) and laid out row by row
+    (compose.layout_grid; grid_cols columns, default ceil(sqrt(k))), each cell labelled with its env's current episode id.  Composed
+    (VecEnv.compose / compose_label, the id read from the device tensor) and encoded on the device, a chunk of frames per copy to the host.
+    ValueError: grid_envs > env.num_envs, or a camera the env does not render."""
+    video = grid = None
+    if grid_video is not None and grid_envs > 0:
+        if grid_envs > env.num_envs:
+            raise ValueError(f"evaluate_vec: grid_envs={grid_envs} > num_envs={env.num_envs}")
+        if video_camera is None:
+            video_camera = "zed_cam_left" if "zed_cam_left" in env.cameras else (env.cameras[0] if env.cameras else None)
+        if video_camera not in env.cameras:
+            raise ValueError(f"evaluate_vec: the env does not render {video_camera!r} (cameras: {list(env.cameras)})")
     if video_dir is not None and video_episodes > 0:
         if video_episodes > env.num_envs:
             raise ValueError(f"evaluate_vec: video_episodes={video_episodes} > num_envs={env.num_envs} (the recorded episodes are the first episodes of envs 0 .. k-1)")
@@ -183,6 +252,8 @@ def evaluate_vec(env, select_action, num_episodes: int, seed: int | None = None,
     observation, info = env.reset()
     if video_dir is not None and video_episodes > 0:
         video = _VideoRecorder(env, video_dir, video_camera, video_episodes, video_quality, video_fps)
+    if grid_video is not None and grid_envs > 0:
+        grid = _GridRecorder(env, grid_video, video_camera, grid_envs, grid_cols, grid_cell, grid_quality, video_fps)
     calls = 0
     try:
         while True:
@@ -190,6 +261,8 @@ def evaluate_vec(env, select_action, num_episodes: int, seed: int | None = None,
             calls += 1
             if video is not None and video.active:
                 video.add(info)
+            if grid is not None:
+                grid.add(info)
             if calls % env.max_episode_steps == 0 and env.episode_count()[1] >= num_episodes:
                 log = env.episode_log(num_episodes)
                 if (log["length"] > 0).all():
@@ -197,9 +270,13 @@ def evaluate_vec(env, select_action, num_episodes: int, seed: int | None = None,
     except BaseException:
         if video is not None:
             video.close(ok=False)
+        if grid is not None:
+            grid.close(ok=False)
         raise
     if video is not None:
         video.close()
+    if grid is not None:
+        grid.close()
     env.check_render_overflow()
     return [{"episode_id": i, "return": float(log["return"][i]), "length": int(log["length"][i]), "max_reward": int(log["max_reward"][i]),
              "success": bool(log["success"][i]), "initial_object_poses": log["initial_object_poses"][i]} for i in range(num_episodes)]
@@ -494,6 +571,179 @@ def load_episode(path: str, decode=None) -> dict:
         else:
             out[f"/observations/images/{cam}"] = decode.decode_jpeg(ss)
     return out
+
+
+class _HostComposer:
+    """visualize_*'s steps through the specifications (compose.py, jpeg.py): for the CPU tests and for small files."""
+
+    def __init__(self):
+        self.bytes_to_device = self.bytes_from_device = 0
+
+    def images(self, frames=None, streams=None):
+        from . import jpeg
+        return np.ascontiguousarray(frames) if streams is None else np.stack([jpeg.decode_reference(x) for x in streams])
+
+    def compose(self, src, places, canvas, canvas_hw, n):
+        from .compose import compose_reference
+        canvas = np.zeros((n, canvas_hw[0], canvas_hw[1], 3), np.uint8) if canvas is None else canvas
+        return compose_reference(canvas, src, places)
+
+    def label(self, canvas, where, prefix, values):
+        from .compose import label_reference
+        return label_reference(canvas, where, prefix, values, 0xFFFFFF)
+
+    def encode(self, canvas, quality):
+        from . import jpeg
+        return [jpeg.encode_reference(f, quality) for f in canvas]
+
+    def close(self):
+        pass
+
+
+class _DeviceComposer:
+    """The same steps on the device (a camera-less VecEnv's handle: avsim_jpeg_decode, avsim_compose, avsim_compose_label, avsim_jpeg_encode):
+    streams or raw frames go in, streams come out, and no decoded or composed pixel leaves the device."""
+
+    def __init__(self, device):
+        from .vec_env import VecEnv
+        import torch
+        self.torch = torch
+        torch.zeros(1, device=torch.device("cuda", int(device)))        # torch's runtime first (vec_env.py)
+        self.env = VecEnv("insert_peg", 3, 1, 1, device=int(device))
+        self.bytes_to_device = self.bytes_from_device = 0
+        self._status = []          # of the decode calls since the last encode, read when that waits for the stream anyway
+
+    def _up(self, a):
+        self.bytes_to_device += a.nbytes
+        return self.torch.from_numpy(a).to(self.env.device)
+
+    def images(self, frames=None, streams=None):
+        from . import jpeg
+        if streams is None:
+            return self._up(np.ascontiguousarray(frames))
+        H, W = jpeg.stream_size(streams[0])
+        stride = max(len(x) for x in streams)
+        buf, ln = np.zeros((len(streams), stride), np.uint8), np.array([len(x) for x in streams], np.int32)
+        for i, x in enumerate(streams):
+            buf[i, :len(x)] = np.frombuffer(x, np.uint8)
+        out, status = self.env.decode_jpeg(self._up(buf), self._up(ln), height=H, width=W, fmt="gym")
+        self._status.append(status)
+        return out
+
+    def compose(self, src, places, canvas, canvas_hw, n):
+        return self.env.compose(src, places, out=canvas, canvas_hw=canvas_hw, nout=n, clear=0 if canvas is None else None)
+
+    def label(self, canvas, where, prefix, values):
+        v = None if values is None else self._up(np.ascontiguousarray(values, dtype=np.int64))
+        return self.env.compose_label(canvas, where, prefix, v, 0xFFFFFF)
+
+    def encode(self, canvas, quality):
+        out, ln = self.env.encode_images(canvas, quality)
+        n = ln.cpu().numpy()                                       # (waits for the stream)
+        if int(n.max()) > out.shape[1]:                            # some stream did not fit: its length says what it needs
+            out = self.torch.empty((len(n), int(n.max())), dtype=self.torch.uint8, device=self.env.device)
+            out, ln = self.env.encode_images(canvas, quality, out=out)
+            n = ln.cpu().numpy()
+        status, self._status = self._status, []
+        if any(bool(st.any().item()) for st in status):
+            raise ValueError("visualize: an episode's JPEG stream is not one of this project's encoder")
+        data = out[:, :int(n.max())].cpu().numpy()
+        self.bytes_from_device += data.nbytes + n.nbytes
+        return [data[i, :n[i]].tobytes() for i in range(len(n))]
+
+    def close(self):
+        self.env.close()
+
+
+def _visualize(episodes, video_path, cameras, stride, prefix, numbered, quality, fps, device, chunk_bytes):
+    """episodes: an iterable of (number, loaded episode dict).  -> a summary dict."""
+    import time
+    from . import jpeg
+    from .compose import layout_row
+    from .mjpeg import AviWriter
+    if int(stride) < 1:
+        raise ValueError(f"visualize: stride {stride}")
+    comp = _HostComposer() if device == "host" else _DeviceComposer(device)
+    writer, frames, t_start = None, 0, time.time()
+    try:
+        for number, data in episodes:
+            compressed = "/compress_len" in data
+            have = sorted(k.rsplit("/", 1)[1] for k in data if k.startswith("/observations/images/"))
+            cams = have if cameras is None else sorted(cameras)
+            if not cams or any(c not in have for c in cams):
+                raise ValueError(f"visualize: cameras {cams} of an episode that holds {have}")
+            streams = episode_streams(data) if compressed else None
+            sizes = [jpeg.stream_size(streams[c][0]) if compressed else tuple(data[f"/observations/images/{c}"].shape[1:3]) for c in cams]
+            rows, CH, CW = layout_row(sizes)
+            if writer is None:
+                os.makedirs(os.path.dirname(os.path.abspath(video_path)), exist_ok=True)
+                writer = AviWriter(video_path, CW, CH, fps=fps)
+            elif (writer.height, writer.width) != (CH, CW):
+                raise ValueError(f"visualize: episode {number} gives {CH} x {CW} frames, the video has {writer.height} x {writer.width}")
+            T = len(streams[cams[0]]) if compressed else data[f"/observations/images/{cams[0]}"].shape[0]
+            ts = list(range(0, T, int(stride)))
+            per_frame = sum(h * w * 3 for h, w in sizes) + 2 * CH * CW * 3
+            chunk = max(1, int(chunk_bytes) // per_frame)
+            for c0 in range(0, len(ts), chunk):
+                tt = ts[c0:c0 + chunk]
+                n, canvas = len(tt), None
+                for cam, (x0, y0, w, h) in zip(cams, rows):      # one call per camera onto the same canvas, cleared by the first
+                    src = comp.images(streams=[streams[cam][t] for t in tt]) if compressed else comp.images(frames=data[f"/observations/images/{cam}"][tt])
+                    canvas = comp.compose(src, [(i, i, x0, y0, w, h) for i in range(n)], canvas, (CH, CW), n)
+                if prefix is not None:
+                    canvas = comp.label(canvas, [(i, 10, 10, 3) for i in range(n)], prefix, [number] * n if numbered else None)
+                for x in comp.encode(canvas, quality):
+                    writer.add(x)
+                frames += n
+        if writer is None:
+            raise ValueError("visualize: no episodes")
+        writer.close()
+    except BaseException:
+        if writer is not None:
+            writer.abort()
+        raise
+    finally:
+        comp.close()
+    return {"video_path": video_path, "frames": frames, "seconds": time.time() - t_start, "bytes_to_device": comp.bytes_to_device,
+            "bytes_from_device": comp.bytes_from_device}
+
+
+def visualize_episode(path_or_data, video_path, cameras=None, stride=1, label=None, quality=90, fps=None, device=0, chunk_bytes=256 << 20):
+    """gym_guided_vision/scripts/visualize_episodes.py:47-98 `save_videos`: the cameras of one episode (a path, or a loaded dict; sorted by
+    name, or the given ones) side by side at the smallest camera's height (compose.layout_row: new_w = int(min_h * w / h)), every stride-th
+    frame, as ONE Motion-JPEG AVI (mjpeg.AviWriter; fps defaults to 50).  label: a text of at most 15 characters written at (10, 10).
+    A compressed file's streams are decoded on the device, a raw file's frames uploaded as u8, in chunks of about chunk_bytes of device
+    memory; each chunk is composed with one avsim_compose call per camera and encoded there, and only the streams come back.
+    device="host": the same steps through compose_reference and jpeg.encode_reference -- the same bytes, slowly (tests, small files).
+    The resampling is Pillow's antialiased bilinear, not cv2.resize's; the joint plots of the reference script are not made.
+    -> {"video_path", "frames", "seconds", "bytes_to_device", "bytes_from_device"}."""
+    data = load_episode(path_or_data) if isinstance(path_or_data, str) else path_or_data
+    return _visualize([(0, data)], video_path, cameras, stride, label, False, quality, 50 if fps is None else fps, device, chunk_bytes)
+
+
+def visualize_dataset(paths, video_path, stride=20, cameras=None, label="EPISODE ", quality=90, fps=None, device=0, chunk_bytes=256 << 20):
+    """gym_guided_vision/scripts/visualize_all_episodes.py:30-121: every stride-th frame of every episode file in ONE video, each frame
+    labelled `EPISODE <i>` at (10, 10) (label: the prefix; None: no label).  paths: the files (or a glob pattern); they are sorted by episode
+    number and must be numbered 0, 1, 2, ... without gaps (:53-61), else ValueError.  fps defaults to int(1 / SIM_DT / 10), the reference's.
+    The rest as visualize_episode."""
+    import glob
+    import re
+    from .constants import SIM_DT
+    paths = sorted(glob.glob(paths)) if isinstance(paths, str) else list(paths)
+    if not paths:
+        raise ValueError("visualize_dataset: no episode files")
+    number = {}
+    for p in paths:
+        m = re.fullmatch(r"episode_(\d+)\.hdf5", os.path.basename(p))
+        if m is None:
+            raise ValueError(f"visualize_dataset: {p} is not an episode_<i>.hdf5 file")
+        number[p] = int(m.group(1))
+    paths = sorted(paths, key=number.get)
+    for i, p in enumerate(paths):
+        if number[p] != i:
+            raise ValueError(f"visualize_dataset: episode_{i}.hdf5 is missing (the files must be numbered without gaps)")
+    return _visualize(((number[p], load_episode(p)) for p in paths), video_path, cameras, stride, label, True, quality,
+                      int(1 / SIM_DT / 10) if fps is None else fps, device, chunk_bytes)
 
 
 def replay_episode(env, data: dict):

@@ -256,6 +256,56 @@ class BatchedSim:
                                                      "1 header, 2 marker structure or length, 4 entropy-coded data)")
         return out
 
+    def _compose_check(self, rc):
+        if rc == -1:          # AVSIM_EINVAL: the library launched nothing
+            raise ValueError(self.h.L.avsim_last_error(self.h.h).decode())
+        self.h.check(rc)
+
+    def compose(self, src, places, out=None, canvas_hw=None, nout=None, clear=None):
+        """Images resampled into rectangles of a canvas on the device (avsim_compose): the pixels of av_aloha_amd.compose.compose_reference.
+        src: u8 [n, H, W, 3] or float32 [n, 3, H, W] in [0, 1]; places: int rows (out image, src image, x0, y0, w, h).  out: the canvas to
+        draw on -- u8 [nout, CH, CW, 3] or float32 [nout, 3, CH, CW], written in place and returned --, or None: a u8 canvas of
+        canvas_hw = (CH, CW) and nout images is made.  clear: 0xRRGGBB to fill the canvas with first (a new canvas is cleared to 0 when
+        nothing is said).  ValueError for what the library refuses (a rectangle outside the canvas, overlaps, a shrink of more than 16)."""
+        src = np.ascontiguousarray(src)
+        p = np.ascontiguousarray(places, dtype=np.int32).reshape(-1, 6)
+        if src.dtype == np.uint8 and src.ndim == 4 and src.shape[3] == 3:
+            sf, (n, H, W) = 0, src.shape[:3]
+        elif src.dtype == np.float32 and src.ndim == 4 and src.shape[1] == 3:
+            sf, (n, H, W) = 1, (src.shape[0],) + src.shape[2:]
+        else:
+            raise ValueError("compose takes u8 [n, H, W, 3] or float32 [n, 3, H, W] images")
+        if out is None:
+            if canvas_hw is None:
+                raise ValueError("compose: give a canvas (out=...) or its size (canvas_hw=...)")
+            nout = int(p[:, 0].max()) + 1 if nout is None and len(p) else int(nout or 1)
+            out = np.empty((nout, int(canvas_hw[0]), int(canvas_hw[1]), 3), dtype=np.uint8)
+            clear = 0 if clear is None else clear
+        df, (no, CH, CW) = self._canvas(out)
+        self._compose_check(self.h.L.avsim_compose(self.h.h, src.ctypes.data, sf, n, H, W, out.ctypes.data, df, no, CH, CW, p.ctypes.data, len(p),
+                                                  0 if clear is None else 1, int(clear or 0) & 0xFFFFFF))
+        return out
+
+    @staticmethod
+    def _canvas(out):
+        if not (isinstance(out, np.ndarray) and out.flags.c_contiguous and out.ndim == 4):
+            raise ValueError("compose: the canvas is a C-contiguous u8 [n, H, W, 3] or float32 [n, 3, H, W] array")
+        if out.dtype == np.uint8 and out.shape[3] == 3:
+            return 0, out.shape[:3]
+        if out.dtype == np.float32 and out.shape[1] == 3:
+            return 1, (out.shape[0],) + out.shape[2:]
+        raise ValueError("compose: the canvas is a C-contiguous u8 [n, H, W, 3] or float32 [n, 3, H, W] array")
+
+    def compose_label(self, canvas, where, prefix="", values=None, rgb=0xFFFFFF):
+        """prefix + str(values[i]) painted onto the canvas at where[i] = (out image, x, y, scale) in the colour rgb (avsim_compose_label):
+        the pixels of av_aloha_amd.compose.label_reference.  The canvas (compose's) is written in place and returned."""
+        df, (no, CH, CW) = self._canvas(canvas)
+        w = np.ascontiguousarray(where, dtype=np.int32).reshape(-1, 4)
+        v = None if values is None else np.ascontiguousarray(values, dtype=np.int64).reshape(len(w))
+        self._compose_check(self.h.L.avsim_compose_label(self.h.h, canvas.ctypes.data, df, no, CH, CW, w.ctypes.data, len(w), prefix.encode("ascii", "replace"),
+                                                        _ffi.ptr(v), int(rgb) & 0xFFFFFF))
+        return canvas
+
     def reward_from_pairs(self, geom_pairs, latch=None):
         """The task's get_reward (env.py:425-863) on explicit contact lists: geom_pairs int [nsets, cap, 2] (collision
         geom ids, negative = empty slot); latch int32 [nsets] is updated in place.  Returns int32 [nsets]."""

@@ -309,6 +309,81 @@ class VecEnv:
                                               1 if fmt == "lerobot" else 0, 1 if upsample == "triangle" else 0, out.data_ptr(), status.data_ptr()))
         return out, status
 
+    def camera_images(self, camera):
+        """The buffer that holds `camera`'s current observation of all envs: float32 [N, 3, H, W] (lerobot) or uint8 [N, H, W, 3] (gym)."""
+        if camera not in self.cameras:
+            raise ValueError(f"the env does not render {camera!r} (cameras: {self.cameras})")
+        return self._img[self.cameras.index(camera)]
+
+    def encode_images(self, images, quality=90, out=None, out_len=None):
+        """JPEG streams of any image batch on the env's device -- uint8 [n, H, W, 3] or float32 [n, 3, H, W], a compose() canvas for one --
+        through avsim_jpeg_encode: -> (out uint8 [n, stride], out_len int32 [n]) as encode_jpeg returns them.  Does not synchronise."""
+        torch = self.torch
+        self._bind_stream()
+        fmt, (n, H, W) = self._canvas_of(images)
+        if out is None:
+            out = torch.empty((n, int(min(self.L.avsim_jpeg_bound(H, W), (H * W * 3 // 2 + 4095) // 4096 * 4096))), dtype=torch.uint8, device=self.device)
+        if out_len is None:
+            out_len = torch.empty(n, dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.uint8 and out.device == self.device and out.ndim == 2 and out.shape[0] == n and out.is_contiguous()
+        assert out_len.dtype == torch.int32 and out_len.device == self.device and tuple(out_len.shape) == (n,) and out_len.is_contiguous()
+        self.h.check(self.L.avsim_jpeg_encode(self.h.h, images.data_ptr(), fmt, None, n, H, W, int(quality), out.data_ptr(), int(out.shape[1]), out_len.data_ptr()))
+        return out, out_len
+
+    def _canvas_of(self, t):
+        torch = self.torch
+        assert isinstance(t, torch.Tensor) and t.device == self.device and t.is_contiguous() and t.ndim == 4, "a contiguous 4-D tensor on the env's device"
+        if t.dtype == torch.uint8 and t.shape[3] == 3:
+            return 0, (int(t.shape[0]), int(t.shape[1]), int(t.shape[2]))
+        if t.dtype == torch.float32 and t.shape[1] == 3:
+            return 1, (int(t.shape[0]), int(t.shape[2]), int(t.shape[3]))
+        raise ValueError("compose: images are uint8 [n, H, W, 3] or float32 [n, 3, H, W]")
+
+    def _compose_check(self, rc):
+        if rc == -1:          # AVSIM_EINVAL: nothing was launched
+            raise ValueError(self.L.avsim_last_error(self.h.h).decode())
+        self.h.check(rc)
+
+    def compose(self, src, places, out=None, canvas_hw=None, nout=None, clear=None, fmt=None):
+        """Images resampled into rectangles of a canvas (avsim_compose; av_aloha_amd.compose.compose_reference's pixels).  src: a tensor on
+        the env's device, uint8 [n, H, W, 3] or float32 [n, 3, H, W] -- an observation of this env, a decode_jpeg result --; places: HOST int
+        rows (out image, src image, x0, y0, w, h), checked on the host (ValueError).  out: the canvas tensor (either format), written in
+        place; None: one of canvas_hw = (CH, CW) and nout images is allocated in format fmt ("gym" u8 HWC, the default, or "lerobot" float32
+        CHW) and cleared.  clear: 0xRRGGBB to fill the canvas with first.  Does not synchronise."""
+        torch = self.torch
+        self._bind_stream()
+        p = np.ascontiguousarray(places, dtype=np.int32).reshape(-1, 6)
+        sf, (n, H, W) = self._canvas_of(src)
+        if out is None:
+            if canvas_hw is None:
+                raise ValueError("compose: give a canvas (out=...) or its size (canvas_hw=...)")
+            if fmt not in (None, "gym", "lerobot"):
+                raise ValueError(f"fmt {fmt!r}: 'lerobot' or 'gym'")
+            nout = int(p[:, 0].max()) + 1 if nout is None and len(p) else int(nout or 1)
+            CH, CW = int(canvas_hw[0]), int(canvas_hw[1])
+            out = torch.empty((nout, 3, CH, CW), dtype=torch.float32, device=self.device) if fmt == "lerobot" else \
+                torch.empty((nout, CH, CW, 3), dtype=torch.uint8, device=self.device)
+            clear = 0 if clear is None else clear
+        df, (no, CH, CW) = self._canvas_of(out)
+        self._compose_check(self.L.avsim_compose(self.h.h, src.data_ptr(), sf, n, H, W, out.data_ptr(), df, no, CH, CW, p.ctypes.data, len(p),
+                                                0 if clear is None else 1, int(clear or 0) & 0xFFFFFF))
+        return out
+
+    def compose_label(self, canvas, where, prefix="", values=None, rgb=0xFFFFFF):
+        """prefix + the decimal digits of values[i] painted at where[i] = (out image, x, y, scale) (avsim_compose_label;
+        av_aloha_amd.compose.label_reference's pixels).  values: an int64 tensor [len(where)] on the env's device -- info["episode_id"], read by
+        the kernel --, or None: the prefix alone; where: HOST rows.  Writes the canvas in place; does not synchronise."""
+        torch = self.torch
+        self._bind_stream()
+        df, (no, CH, CW) = self._canvas_of(canvas)
+        w = np.ascontiguousarray(where, dtype=np.int32).reshape(-1, 4)
+        if values is not None:
+            assert isinstance(values, torch.Tensor) and values.dtype == torch.int64 and values.device == self.device and tuple(values.shape) == (len(w),) \
+                and values.is_contiguous(), "compose_label(values=...): a contiguous int64 tensor on the env's device, one value per label"
+        self._compose_check(self.L.avsim_compose_label(self.h.h, canvas.data_ptr(), df, no, CH, CW, w.ctypes.data, len(w), prefix.encode("ascii", "replace"),
+                                                      _ffi.ptr(values), int(rgb) & 0xFFFFFF))
+        return canvas
+
     def check_render_overflow(self):
         """Overflow flags of the last colour render (bit 0 triangle records, bit 1 tile lists; 0 = complete images): warns when set.
         Synchronises, so it is read once at the end of an evaluation rather than per step."""

@@ -249,6 +249,36 @@ int avsim_render_jpeg(avsim_t* h, const int32_t* cam_ids, int ncam, int height, 
 int avsim_jpeg_decode(avsim_t* h, const uint8_t* in, int64_t stride, const int32_t* in_len, const int32_t* index, int nimg, int height, int width,
                       int fmt, int upsample, void* out, int32_t* status);
 
+/* Camera views composed on the device (csrc/avsim_compose.hip.h): images are resampled and written into rectangles of a larger
+ * canvas, byte for byte the output of av_aloha_amd/compose.py compose_reference, its specification -- a separable triangle filter whose
+ * support grows with the shrink factor (antialiased when shrinking, plain bilinear when enlarging), the horizontal pass first, in Pillow's
+ * fixed-point scheme; integer arithmetic on the device, the coefficients computed on the host in double once per size pair.
+ * avsim_compose: src = nsrc images of src_h x src_w, fmt 0: u8 [nsrc][H][W][3], fmt 1: float32 [nsrc][3][H][W] in [0, 1], turned into u8 by
+ * (int)(v * 255 + 0.5f) as avsim_jpeg_encode does; canvas = nout images of canvas_h x canvas_w, fmt 0: u8 HWC, fmt 1: float32 CHW, every value
+ * written (float)u8 / 255, the bits of avsim_render_rgb_f32.  places: int32 [nplace][6] = (out image, src image, x0, y0, w, h): source image
+ * `src image` resampled to h x w goes to canvas[out image][y0 : y0 + h][x0 : x0 + w]; the rest of the canvas is left as it is, or, with
+ * clear != 0, filled with clear_rgb (0xRRGGBB) first.  One source batch per call: cameras of different sizes are successive calls onto the same
+ * canvas with clear set on the first only.  places is a HOST array in both I/O modes (as box / share of avsim_episode_setup) and is checked
+ * there; src and canvas follow the handle's I/O mode.  With host pointers and clear = 0 the canvas is copied in before the call and out after
+ * it; with AVSIM_IO_DEVICE nothing synchronises once a call with the same sizes and places has run.  AVSIM_EINVAL, with nothing launched
+ * and the canvas untouched: a format other than 0 / 1, an image size or a rectangle's w / h outside 1..65535, an image index out of range, a
+ * rectangle that does not lie inside the canvas, two rectangles of one output image that overlap (a parallel kernel gives overlaps no
+ * order), src_h > 16 h or src_w > 16 w (a shrink of more than 16 per axis; enlarging is unbounded).
+ * avsim_compose_label: the text prefix + decimal digits of value[i] painted onto the canvas in the solid colour rgb (0xRRGGBB), label i at
+ * where[i] = (out image, x, y, scale): 5 x 7 glyphs in 6 x 8 cells, every glyph pixel a scale x scale square, the first cell's top left
+ * corner at (x, y); the canvas is unchanged outside the glyph pixels, and pixels that fall outside the canvas are skipped (a label is clipped,
+ * not refused).  Glyphs: 0-9, A-Z, space and : . - = / ; any other character draws as a space.  prefix: a HOST string of at most 15
+ * characters (NULL = none); value: int64 [nlabel] following the I/O mode (it may live on the device: the digits are formatted there), NULL =
+ * the prefix alone; where: a HOST array.  With host pointers the canvas is copied in and out.  AVSIM_EINVAL: canvas_fmt, canvas size, an
+ * image index out of range, scale outside 1..64, |x| or |y| above 2^20, a longer prefix.
+ * avsim_compose_font: the glyph table, rows[ch][r] = row r (top first) of character ch, bit 4 = the left pixel, all zero for a character
+ * without a glyph; needs no handle and no device (av_aloha_amd/compose.py label_reference draws with this one copy of the font). */
+int avsim_compose(avsim_t* h, const void* src, int src_fmt, int nsrc, int src_h, int src_w, void* canvas, int canvas_fmt, int nout, int canvas_h,
+                  int canvas_w, const int32_t* places, int nplace, int clear, uint32_t clear_rgb);
+int avsim_compose_label(avsim_t* h, void* canvas, int canvas_fmt, int nout, int canvas_h, int canvas_w, const int32_t* where, int nlabel,
+                        const char* prefix, const int64_t* value, uint32_t rgb);
+void avsim_compose_font(uint8_t rows[128][7]);
+
 /* Per-env episodes on the device (a vector env with gymnasium's NEXT_STEP autoreset; av_aloha_amd/vec_env.py).  Pointers follow the
  * handle's I/O mode, except box / share of the set-up (host pointers).  In device mode no step, reset, sample or render call
  * synchronises; avsim_episode_setup does (it reallocates the records: once per evaluation), and so do avsim_episode_log /
