@@ -14,6 +14,7 @@
 
 #include "../../include/avsim.h"
 #include "avsim_compose.hip.h"
+#include "avsim_imgprep.hip.h"
 #include "avsim_episode.hip.h"
 #include "avsim_ik.hip.h"
 #include "avsim_jpeg.hip.h"
@@ -80,6 +81,7 @@ struct avsim {
     JpegHost jpeg;       // JPEG streams of such images (avsim_jpeg.hip.h): tables per shape, the intervals' staging area
     JpegDecHost jpegdec; // and those streams back into images: Huffman lookup tables, the coefficients' staging area
     ComposeHost compose; // views resampled into a canvas, labels (avsim_compose.hip.h): coefficient tables per size pair, the validated placements
+    ImgPrepHost imgprep; // image statistics, crops through tables (avsim_imgprep.hip.h): the pinned staging of a call's host arrays
     bool jpegdec_events = false;   // option "jpeg_decode_events": avsim_jpeg_decode records ev[12..15] around its three kernels
     // the state's version: bumped by everything that writes qpos (reset, the steps, set_state); the image calls skip their pose pass and the shadow
     // map when they already hold this version's (a facade that fetches its cameras one call at a time repeats neither)
@@ -475,6 +477,7 @@ void avsim_destroy(avsim_t* h) {
     h->jpeg.destroy();
     h->jpegdec.destroy();
     h->compose.destroy();
+    h->imgprep.destroy();
     for (void* p : {h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, (void*)h->d_latch})
         if (p) (void)hipFree(p);
     for (void* p : h->d_io)
@@ -1098,6 +1101,60 @@ void avsim_compose_font(uint8_t rows[128][7]) {
         const int g = cmp_glyph(ch);
         if (g >= 0) std::memcpy(rows[ch], CMP_FONT_HOST[g], 7);
     }
+}
+
+// Per-image sums for data-set statistics, and crops through look-up tables (av_aloha_amd/imgprep.py is the specification; csrc/avsim_imgprep.hip.h)
+int avsim_image_stats(avsim_t* h, const void* img, int fmt, const int32_t* index, int nimg, int height, int width, uint64_t* out) {
+    if (!h) return AVSIM_EINVAL;
+    if (!img || !out || nimg < 1) { h->set_error("avsim_image_stats: bad arguments"); return AVSIM_EINVAL; }
+    if (fmt != 0 && fmt != 1) { h->set_error("avsim_image_stats: fmt is 0 (u8 HWC) or 1 (float32 CHW)"); return AVSIM_EINVAL; }
+    if (height < 1 || width < 1 || height > 65535 || width > 65535) { h->set_error("avsim_image_stats: image size %d x %d outside 1..65535", height, width); return AVSIM_EINVAL; }
+    size_t rows = (size_t)nimg;            // (a host caller's index says how many images `img` holds)
+    if (!h->io_device && index) {
+        int top = 0;
+        for (int i = 0; i < nimg; i++) {
+            if (index[i] < 0) { h->set_error("avsim_image_stats: negative index"); return AVSIM_EINVAL; }
+            top = index[i] > top ? index[i] : top;
+        }
+        rows = (size_t)top + 1;
+    }
+    AVS_ON_DEVICE(h);
+    int rc;
+    const void *dimg = nullptr, *dindex = nullptr;
+    void* dout = nullptr;
+    const size_t obytes = sizeof(uint64_t) * 12 * (size_t)nimg;
+    if ((rc = h->in(8, img, rows * (size_t)height * width * (fmt ? 12 : 3), &dimg))) return rc;
+    if (index && (rc = h->in(9, index, sizeof(int32_t) * (size_t)nimg, &dindex))) return rc;
+    if ((rc = h->out_begin(10, out, obytes, &dout))) return rc;
+    if (ImgPrepHost::stats(h->stream, dimg, fmt, (const int*)dindex, nimg, height, width, (unsigned long long*)dout, h->err)) return AVSIM_EHIP;
+    if ((rc = h->out_end(10, out, obytes))) return rc;
+    return h->finish();
+}
+
+int avsim_image_prep(avsim_t* h, const void* img, int fmt, int nsrc, int height, int width, const float* lut, int nlut, const int32_t* lut_index,
+                     const int32_t* box, int nout, const int32_t* src_index, int out_h, int out_w, float* out) {
+    if (!h) return AVSIM_EINVAL;
+    if (!img || !lut || !box || !out || nsrc < 1 || nout < 1 || nlut < 1 || nlut > (1 << 20)) { h->set_error("avsim_image_prep: bad arguments"); return AVSIM_EINVAL; }
+    if (fmt != 0 && fmt != 1) { h->set_error("avsim_image_prep: fmt is 0 (u8 HWC) or 1 (float32 CHW)"); return AVSIM_EINVAL; }
+    if (height < 1 || width < 1 || height > 65535 || width > 65535 || out_h < 1 || out_w < 1 || out_h > 65535 || out_w > 65535) {
+        h->set_error("avsim_image_prep: image sizes %d x %d, %d x %d outside 1..65535", height, width, out_h, out_w);
+        return AVSIM_EINVAL;
+    }
+    {   // the host arrays are checked before anything moves or is launched
+        std::string why;
+        if (ImgPrepHost::validate(nsrc, height, width, nlut, lut_index, box, nout, src_index, out_h, out_w, why)) { h->set_error("%s", why.c_str()); return AVSIM_EINVAL; }
+    }
+    AVS_ON_DEVICE(h);
+    int rc;
+    const void *dimg = nullptr, *dlut = nullptr;
+    void* dout = nullptr;
+    const size_t obytes = sizeof(float) * 3 * (size_t)nout * out_h * out_w;
+    if ((rc = h->in(8, img, (size_t)nsrc * height * width * (fmt ? 12 : 3), &dimg))) return rc;
+    if ((rc = h->in(9, lut, sizeof(float) * 768 * (size_t)nlut, &dlut))) return rc;
+    if ((rc = h->out_begin(10, out, obytes, &dout))) return rc;
+    if (h->imgprep.launch(h->stream, dimg, fmt, height, width, (const float*)dlut, lut_index, box, nout, src_index, out_h, out_w, (float*)dout, h->err)) return AVSIM_EHIP;
+    if ((rc = h->out_end(10, out, obytes))) return rc;
+    return h->finish();
 }
 
 // The visual scene of avsim_render_rgb: the mesh library (models/visual_meshes.avv, compiler/vismesh.py) against the instances the

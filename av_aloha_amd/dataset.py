@@ -2,9 +2,11 @@
 batches are decoded on the device: the JPEG streams wait in pinned host memory, a batch's streams cross to the device -- some 26 times
 fewer bytes than the frames they hold -- and one avsim_jpeg_decode call per camera turns them into the float32 [B, 3, H, W]
 observations a policy reads in VecEnv, on torch's current stream."""
+import json
+
 import numpy as np
 
-from . import _ffi, jpeg
+from . import _ffi, imgprep, jpeg
 from .harness import load_episode
 
 
@@ -14,7 +16,8 @@ class CompressedDataset:
     `device`: "observation.images.<cam>" float32 [B, 3, H, W] in [0, 1] ((float)u8 / 255 of jpeg.decode_reference's pixels),
     "observation.state" float32 [B, 21 | 14], "action", "episode_index" and "frame_index" int64 [B]; ds.batches(batch_size, seed) walks a
     shuffled epoch.  batch() does not wait for the device.  check: a stream the decoder flags (not this encoder's) raises jpeg.JpegError -- from
-    the NEXT batch() call or from close(), when its status is read without holding the decode up; that batch's image is unspecified."""
+    the NEXT batch() call or from close(), when its status is read without holding the decode up; that batch's image is unspecified.
+    batch(indices, fmt="gym") hands the images out as the decoder's uint8 [B, H, W, 3] instead (what TrainingBatches and stats() read)."""
 
     def __init__(self, paths, cameras, device=None, upsample="replicate", check=True):
         import torch
@@ -51,6 +54,8 @@ class CompressedDataset:
         self.episode_index = torch.from_numpy(np.concatenate(ep_idx)).to(self.device)
         self.frame_index = torch.from_numpy(np.concatenate(fr_idx)).to(self.device)
         self.n = int(self.state.shape[0])
+        self.ep_len = np.array([len(x) for x in state], dtype=np.int64)      # the episodes' lengths and first global frames (imgprep.chunk_index)
+        self.ep_start = np.concatenate([[0], np.cumsum(self.ep_len)[:-1]]).astype(np.int64)
         # per camera: every stream back to back in one pinned buffer, with its offset and length
         self.buf, self.off, self.len, self.size, self.stride = {}, {}, {}, {}, {}
         for c, ss in streams.items():
@@ -70,38 +75,70 @@ class CompressedDataset:
     def __len__(self):
         return self.n
 
-    def batch(self, indices):
+    def batch(self, indices, fmt="lerobot"):
         torch = self.torch
+        if fmt not in ("lerobot", "gym"):
+            raise ValueError(f"fmt {fmt!r}: 'lerobot' (float32 [B, 3, H, W]) or 'gym' (uint8 [B, H, W, 3])")
         idx = np.asarray(indices, dtype=np.int64).reshape(-1)
         if len(idx) == 0 or idx.min() < 0 or idx.max() >= self.n:
             raise IndexError(f"batch indices outside [0, {self.n})")
-        B = len(idx)
         t_idx = torch.from_numpy(idx).to(self.device, non_blocking=True)
         out = {"observation.state": self.state[t_idx], "action": self.action[t_idx], "episode_index": self.episode_index[t_idx],
                "frame_index": self.frame_index[t_idx]}
         self.h.check(self.h.L.avsim_set_stream(self.h.h, torch.cuda.current_stream(self.device).cuda_stream))
         self._check_pending()
         for c in self.cameras:
-            ln = self.len[c][idx]
-            if (c, B) not in self._stage:            # pinned rows for a batch of B streams of the camera's longest length, reused by later batches
-                self._stage[c, B] = (torch.empty((B, self.stride[c]), dtype=torch.uint8).pin_memory(), torch.empty(B, dtype=torch.int32).pin_memory(),
-                                     torch.cuda.Event())
-            rows, lens, done = self._stage[c, B]
-            done.synchronize()                       # (the copy of the last batch that used these rows)
-            src, r = self.buf[c].numpy(), rows.numpy()
-            for i, (o, n) in enumerate(zip(self.off[c][idx], ln)):
-                r[i, :n] = src[o:o + n]
-            lens.numpy()[:] = ln
-            d_rows, d_len = rows.to(self.device, non_blocking=True), lens.to(self.device, non_blocking=True)
-            done.record()
+            out[f"observation.images.{c}"] = self._decode(c, idx, fmt)
+        return out
+
+    def _decode(self, c, idx, fmt):
+        """The frames idx of camera c, decoded on the handle's stream: float32 [B, 3, H, W] (fmt "lerobot") or uint8 [B, H, W, 3] ("gym")."""
+        torch = self.torch
+        B = len(idx)
+        ln = self.len[c][idx]
+        if (c, B) not in self._stage:            # pinned rows for a batch of B streams of the camera's longest length, reused by later batches
+            self._stage[c, B] = (torch.empty((B, self.stride[c]), dtype=torch.uint8).pin_memory(), torch.empty(B, dtype=torch.int32).pin_memory(),
+                                 torch.cuda.Event())
+        rows, lens, done = self._stage[c, B]
+        done.synchronize()                       # (the copy of the last batch that used these rows)
+        src, r = self.buf[c].numpy(), rows.numpy()
+        for i, (o, n) in enumerate(zip(self.off[c][idx], ln)):
+            r[i, :n] = src[o:o + n]
+        lens.numpy()[:] = ln
+        d_rows, d_len = rows.to(self.device, non_blocking=True), lens.to(self.device, non_blocking=True)
+        done.record()
+        H, W = self.size[c]
+        img = torch.empty((B, 3, H, W), dtype=torch.float32, device=self.device) if fmt == "lerobot" else \
+            torch.empty((B, H, W, 3), dtype=torch.uint8, device=self.device)
+        status = torch.empty(B, dtype=torch.int32, device=self.device)
+        self.h.check(self.h.L.avsim_jpeg_decode(self.h.h, d_rows.data_ptr(), self.stride[c], d_len.data_ptr(), None, B, H, W, 1 if fmt == "lerobot" else 0,
+                                                1 if self.upsample == "triangle" else 0, img.data_ptr(), status.data_ptr()))
+        if self.check:
+            self._pending.append((status, idx, c))
+        return img
+
+    def stats(self, batch_size=256):
+        """The data set's statistics, {key: {"mean", "std", "min", "max"}} as float32 arrays: of every camera ("observation.images.<cam>",
+        [3, 1, 1] in units of [0, 1]) over every pixel of every frame -- each frame decoded once as u8 and reduced on the device
+        (avsim_image_stats), the integer sums combined exactly (imgprep.combine_stats: no float accumulation, the same result for every
+        batch_size) --, and of "observation.state" and "action" per dimension, in float64.  std is the population std."""
+        torch = self.torch
+        self.h.check(self.h.L.avsim_set_stream(self.h.h, torch.cuda.current_stream(self.device).cuda_stream))
+        self._check_pending()
+        out = {}
+        for c in self.cameras:
             H, W = self.size[c]
-            img = torch.empty((B, 3, H, W), dtype=torch.float32, device=self.device)
-            status = torch.empty(B, dtype=torch.int32, device=self.device)
-            self.h.check(self.h.L.avsim_jpeg_decode(self.h.h, d_rows.data_ptr(), self.stride[c], d_len.data_ptr(), None, B, H, W, 1,
-                                                    1 if self.upsample == "triangle" else 0, img.data_ptr(), status.data_ptr()))
-            if self.check:
-                self._pending.append((status, idx, c))
-            out[f"observation.images.{c}"] = img
+            sums = torch.empty((self.n, 3, 4), dtype=torch.int64, device=self.device)
+            for i0 in range(0, self.n, int(batch_size)):
+                idx = np.arange(i0, min(self.n, i0 + int(batch_size)), dtype=np.int64)
+                img = self._decode(c, idx, "gym")
+                self.h.check(self.h.L.avsim_image_stats(self.h.h, img.data_ptr(), 0, None, len(idx), H, W, sums[i0:i0 + len(idx)].data_ptr()))
+            out[f"observation.images.{c}"] = imgprep.combine_stats(sums.cpu().numpy().view(np.uint64), H * W)
+            self._check_pending()
+        for key, t in (("observation.state", self.state), ("action", self.action)):
+            x = t.cpu().numpy().astype(np.float64)
+            out[key] = {"mean": x.mean(0).astype(np.float32), "std": x.std(0).astype(np.float32), "min": x.min(0).astype(np.float32),
+                        "max": x.max(0).astype(np.float32)}
         return out
 
     def _check_pending(self):
@@ -129,3 +166,121 @@ class CompressedDataset:
             finally:
                 self.h.close()
                 self.h = None
+
+
+def save_stats(stats, path):
+    """CompressedDataset.stats()'s result as JSON (every float32 written as the double that equals it: load_stats gives the same bits)."""
+    with open(path, "w") as f:
+        json.dump({k: {n: np.asarray(a, dtype=np.float32).astype(np.float64).tolist() for n, a in v.items()} for k, v in stats.items()}, f, indent=1)
+    return path
+
+
+def load_stats(path):
+    with open(path) as f:
+        return {k: {n: np.asarray(a, dtype=np.float32) for n, a in v.items()} for k, v in json.load(f).items()}
+
+
+def epoch_plan(n, batch_size, sizes, crop=None, crop_mode="random", seed=0, epoch=0, drop_last=True):
+    """The batches of one epoch and their crop boxes, on the host: [(frame indices int64 [B], {camera: int32 [B, 3] rows (x0, y0, 0)})].
+    rng = np.random.default_rng([seed, epoch]) draws the epoch's permutation first; then, per batch and per camera in the order of `sizes`
+    (a dict camera -> (H, W), in CompressedDataset.cameras' order), with crop = (h, w) and crop_mode "random": y0 and then x0 as
+    rng.integers(0, H - h + 1, B) / rng.integers(0, W - w + 1, B); "center": the centred box, nothing drawn.  crop None: the whole image."""
+    if crop_mode not in ("random", "center"):
+        raise ValueError(f"crop_mode {crop_mode!r}: 'random' or 'center'")
+    for c, (H, W) in sizes.items():
+        if crop is not None and not (1 <= crop[0] <= H and 1 <= crop[1] <= W):
+            raise ValueError(f"crop {tuple(crop)} does not fit camera {c!r} ({H} x {W})")
+    rng = np.random.default_rng([int(seed), int(epoch)])
+    order = rng.permutation(int(n))
+    plan = []
+    for i in range(0, int(n), int(batch_size)):
+        part = order[i:i + int(batch_size)].astype(np.int64)
+        if drop_last and len(part) < batch_size:
+            break
+        B, boxes = len(part), {}
+        for c, (H, W) in sizes.items():
+            h, w = (H, W) if crop is None else (int(crop[0]), int(crop[1]))
+            box = np.zeros((B, 3), dtype=np.int32)
+            if crop_mode == "random":
+                box[:, 1] = rng.integers(0, H - h + 1, B)
+                box[:, 0] = rng.integers(0, W - w + 1, B)
+            else:
+                box[:, 0], box[:, 1] = imgprep.center_box((H, W), (h, w))
+            boxes[c] = box
+        plan.append((part, boxes))
+    return plan
+
+
+class TrainingBatches:
+    """The batches a policy of the ACT / diffusion kind trains on, made on the device from a CompressedDataset.  Iterating walks one epoch
+    (the first iteration epoch 0, the next epoch 1, ...; epoch_plan says which frames and which crops) and yields dicts of tensors on the
+    data set's device:
+      "observation.images.<cam>"  float32 [B, 3, h, w]: the frame decoded as u8 and passed through avsim_image_prep -- cropped to
+                                  crop = (h, w) (None: the whole image) and every channel looked up in imgprep.normalise_lut(stats) (normalise
+                                  False: imgprep.identity_lut(), values in [0, 1]); the bits of imgprep.prep_reference
+      "observation.state"         float32 [B, D]: (x - mean) / std in float32
+      "action"                    float32 [B, chunk_size, A]: the actions of the frame and of the chunk_size - 1 that follow, clamped to the
+                                  episode's last (imgprep.chunk_index, LeRobot's delta_timestamps), normalised alike
+      "action_is_pad"             bool [B, chunk_size]: the clamped ones
+      "episode_index", "frame_index"  int64 [B]
+    stats: CompressedDataset.stats()'s (or load_stats'); a dimension whose std is 0 normalises to nan / inf, as the formula says.
+    Like batch(), an iteration step does not wait for the device."""
+
+    def __init__(self, ds, batch_size, chunk_size, stats, crop=None, crop_mode="random", normalise=True, seed=0, drop_last=True):
+        torch = ds.torch
+        self.ds, self.batch_size, self.chunk_size = ds, int(batch_size), int(chunk_size)
+        self.crop, self.crop_mode, self.normalise, self.seed, self.drop_last = crop, crop_mode, bool(normalise), int(seed), bool(drop_last)
+        if self.batch_size < 1 or self.chunk_size < 1:
+            raise ValueError("TrainingBatches: batch_size and chunk_size are at least 1")
+        self.sizes = {c: tuple(ds.size[c]) for c in ds.cameras}
+        epoch_plan(0, 1, self.sizes, crop, crop_mode)           # (the arguments' checks)
+        self.epoch = 0
+        self.lut, self.norm = {}, {}
+        for c in ds.cameras:
+            st = stats[f"observation.images.{c}"]
+            lut = imgprep.normalise_lut(st["mean"], st["std"]) if self.normalise else imgprep.identity_lut()
+            self.lut[c] = torch.from_numpy(np.ascontiguousarray(lut, dtype=np.float32).reshape(1, 3, 256)).to(ds.device)
+        for key in ("observation.state", "action"):
+            self.norm[key] = (torch.from_numpy(np.asarray(stats[key]["mean"], dtype=np.float32)).to(ds.device),
+                              torch.from_numpy(np.asarray(stats[key]["std"], dtype=np.float32)).to(ds.device))
+
+    def __len__(self):
+        return self.ds.n // self.batch_size if self.drop_last else -(-self.ds.n // self.batch_size)
+
+    def plan(self, epoch):
+        return epoch_plan(self.ds.n, self.batch_size, self.sizes, self.crop, self.crop_mode, self.seed, epoch, self.drop_last)
+
+    def __iter__(self):
+        epoch, self.epoch = self.epoch, self.epoch + 1
+        for part, boxes in self.plan(epoch):
+            yield self.make(part, boxes)
+
+    def _norm(self, key, x):
+        if not self.normalise:
+            return x
+        mean, std = self.norm[key]
+        return (x - mean) / std
+
+    def make(self, part, boxes):
+        """The batch of the frames `part` with the crop boxes {camera: int32 [B, 3]}."""
+        ds, torch = self.ds, self.ds.torch
+        raw = ds.batch(part, fmt="gym")
+        B = len(part)
+        out = {"observation.state": self._norm("observation.state", raw["observation.state"]), "episode_index": raw["episode_index"],
+               "frame_index": raw["frame_index"]}
+        index, pad = imgprep.chunk_index(ds.ep_start, ds.ep_len, part, self.chunk_size)
+        t_index = torch.from_numpy(index).to(ds.device, non_blocking=True)
+        out["action"] = self._norm("action", ds.action[t_index])
+        out["action_is_pad"] = torch.from_numpy(pad).to(ds.device, non_blocking=True)
+        for c in ds.cameras:
+            H, W = self.sizes[c]
+            h, w = (H, W) if self.crop is None else (int(self.crop[0]), int(self.crop[1]))
+            box = np.ascontiguousarray(boxes[c], dtype=np.int32).reshape(B, 3)
+            img = torch.empty((B, 3, h, w), dtype=torch.float32, device=ds.device)
+            rc = ds.h.L.avsim_image_prep(ds.h.h, raw[f"observation.images.{c}"].data_ptr(), 0, B, H, W, self.lut[c].data_ptr(), 1, None, box.ctypes.data,
+                                         B, None, h, w, img.data_ptr())
+            if rc == -1:          # AVSIM_EINVAL: nothing was launched
+                raise ValueError(ds.h.L.avsim_last_error(ds.h.h).decode())
+            ds.h.check(rc)
+            out[f"observation.images.{c}"] = img
+        return out

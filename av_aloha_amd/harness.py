@@ -282,6 +282,38 @@ def evaluate_vec(env, select_action, num_episodes: int, seed: int | None = None,
              "success": bool(log["success"][i]), "initial_object_poses": log["initial_object_poses"][i]} for i in range(num_episodes)]
 
 
+def make_preprocessor(venv, stats, crop=None):
+    """A function obs -> the policy's input for a VecEnv, with the numbers training used: dataset.TrainingBatches(crop_mode="center")'s.
+    stats: CompressedDataset.stats()'s (dataset.load_stats'); crop = (h, w): the centred box (None: the whole image).  The function reads
+    the env's own image buffers (VecEnv.camera_images, either observation format) through VecEnv.prep_images with
+    imgprep.normalise_lut(stats) -- the bits of imgprep.prep_reference -- and normalises the state as (x - mean) / std in float32; it returns
+    {"observation.images.<cam>": float32 [N, 3, h, w], "observation.state": float32 [N, D]} on the env's device and does not synchronise:
+    evaluate_vec(venv, lambda obs, info: policy(pre(obs)), ...)."""
+    import torch
+    from . import imgprep
+    H, W = venv.observation_height, venv.observation_width
+    h, w = (H, W) if crop is None else (int(crop[0]), int(crop[1]))
+    if not (1 <= h <= H and 1 <= w <= W):
+        raise ValueError(f"crop {(h, w)} does not fit the env's {H} x {W} images")
+    x0, y0 = imgprep.center_box((H, W), (h, w))
+    box = np.tile(np.array([[x0, y0, 0]], dtype=np.int32), (venv.num_envs, 1))
+    luts = {}
+    for c in venv.cameras:
+        st = stats[f"observation.images.{c}"]
+        luts[c] = torch.from_numpy(np.ascontiguousarray(imgprep.normalise_lut(st["mean"], st["std"]), dtype=np.float32).reshape(1, 3, 256)).to(venv.device)
+    mean = torch.from_numpy(np.asarray(stats["observation.state"]["mean"], dtype=np.float32)).to(venv.device)
+    std = torch.from_numpy(np.asarray(stats["observation.state"]["std"], dtype=np.float32)).to(venv.device)
+
+    def pre(obs):
+        state = obs["observation.state"] if "observation.state" in obs else obs["agent_pos"].to(torch.float32)
+        out = {"observation.state": (state - mean) / std}
+        for c in venv.cameras:
+            out[f"observation.images.{c}"] = venv.prep_images(venv.camera_images(c), luts[c], box, (h, w))
+        return out
+
+    return pre
+
+
 def record_episode(env, actions23) -> dict:
     """Steps a Cartesian-action env (av_aloha_amd.sim_env) through `actions23` [T-1, 23] and returns the episode arrays."""
     ts = env.get_obs()

@@ -306,6 +306,40 @@ class BatchedSim:
                                                         _ffi.ptr(v), int(rgb) & 0xFFFFFF))
         return canvas
 
+    def image_stats(self, img, index=None):
+        """uint64 [n, 3, 4]: (sum, sum of squares, min, max) of the u8 values per image and channel, reduced on the device
+        (avsim_image_stats): the integers of av_aloha_amd.imgprep.stats_reference.  img: u8 [n, H, W, 3] or float32 [n, 3, H, W]; index: the
+        images to reduce, in this order (None: all)."""
+        img = np.ascontiguousarray(img)
+        sf, (n, H, W) = self._canvas(img)
+        idx = None if index is None else np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+        if idx is not None and len(idx) and (idx.min() < 0 or idx.max() >= n):
+            raise ValueError(f"image_stats: index outside [0, {n})")
+        m = n if idx is None else len(idx)
+        out = np.empty((m, 3, 4), dtype=np.uint64)
+        self._compose_check(self.h.L.avsim_image_stats(self.h.h, img.ctypes.data, sf, _ffi.ptr(idx), m, H, W, out.ctypes.data))
+        return out
+
+    def prep_images(self, img, lut, box, out_hw, lut_index=None, src_index=None, out=None):
+        """float32 [nout, 3, oh, ow]: crops of img, mirrored where box says so, every channel through a table (avsim_image_prep): the bits of
+        av_aloha_amd.imgprep.prep_reference.  img: u8 [n, H, W, 3] or float32 [n, 3, H, W]; lut: float32 [nlut, 3, 256] (or [3, 256]); box:
+        int rows (x0, y0, flip), one per output; lut_index / src_index: the table / the source image of every output (None: table 0 /
+        image i).  ValueError for what the library refuses (a crop outside the source, an index out of range)."""
+        img = np.ascontiguousarray(img)
+        sf, (n, H, W) = self._canvas(img)
+        lut = np.ascontiguousarray(lut, dtype=np.float32).reshape(-1, 3, 256)
+        b = np.ascontiguousarray(box, dtype=np.int32).reshape(-1, 3)
+        li = None if lut_index is None else np.ascontiguousarray(lut_index, dtype=np.int32).reshape(len(b))
+        si = None if src_index is None else np.ascontiguousarray(src_index, dtype=np.int32).reshape(len(b))
+        oh, ow = int(out_hw[0]), int(out_hw[1])
+        if out is None:
+            out = np.empty((len(b), 3, max(oh, 0), max(ow, 0)), dtype=np.float32)
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (len(b), 3, oh, ow)):
+            raise ValueError("prep_images: out is a C-contiguous float32 [nout, 3, oh, ow] array")
+        self._compose_check(self.h.L.avsim_image_prep(self.h.h, img.ctypes.data, sf, n, H, W, lut.ctypes.data, len(lut), _ffi.ptr(li), b.ctypes.data,
+                                                      len(b), _ffi.ptr(si), oh, ow, out.ctypes.data))
+        return out
+
     def reward_from_pairs(self, geom_pairs, latch=None):
         """The task's get_reward (env.py:425-863) on explicit contact lists: geom_pairs int [nsets, cap, 2] (collision
         geom ids, negative = empty slot); latch int32 [nsets] is updated in place.  Returns int32 [nsets]."""

@@ -384,6 +384,47 @@ class VecEnv:
                                                       _ffi.ptr(values), int(rgb) & 0xFFFFFF))
         return canvas
 
+    def image_stats(self, img, index=None, out=None):
+        """(sum, sum of squares, min, max) of the u8 values per image and channel (avsim_image_stats; av_aloha_amd.imgprep.stats_reference's
+        integers): img a tensor on the env's device, uint8 [n, H, W, 3] or float32 [n, 3, H, W]; index: an int32 tensor there, the images to
+        reduce in this order (values outside [0, n) are clamped), None: all.  -> int64 [m, 3, 4] on the device (the values are below 2^63).
+        Does not synchronise."""
+        torch = self.torch
+        self._bind_stream()
+        sf, (n, H, W) = self._canvas_of(img)
+        if index is not None:
+            assert isinstance(index, torch.Tensor) and index.dtype == torch.int32 and index.device == self.device and index.ndim == 1, \
+                "image_stats(index=...): an int32 index tensor on the env's device"
+            index = index.clamp(0, n - 1).contiguous()
+        m = n if index is None else int(index.shape[0])
+        if out is None:
+            out = torch.empty((m, 3, 4), dtype=torch.int64, device=self.device)
+        assert out.dtype == torch.int64 and out.device == self.device and tuple(out.shape) == (m, 3, 4) and out.is_contiguous()
+        self._compose_check(self.L.avsim_image_stats(self.h.h, img.data_ptr(), sf, _ffi.ptr(index), m, H, W, out.data_ptr()))
+        return out
+
+    def prep_images(self, img, lut, box, out_hw, lut_index=None, src_index=None, out=None):
+        """Crops of img, mirrored where box says so, every channel through a table (avsim_image_prep; av_aloha_amd.imgprep.prep_reference's
+        bits).  img: a tensor on the env's device, uint8 [n, H, W, 3] or float32 [n, 3, H, W] -- an observation, a decode_jpeg result --; lut:
+        a float32 tensor [nlut, 3, 256] (or [3, 256]) there; box: HOST int rows (x0, y0, flip), one per output; lut_index / src_index: HOST
+        int arrays, the table / the source image of every output (None: table 0 / image i), all checked on the host (ValueError) and copied
+        by the library before the call returns.  -> float32 [nout, 3, oh, ow] on the device (out: the tensor to write).  Does not synchronise."""
+        torch = self.torch
+        self._bind_stream()
+        sf, (n, H, W) = self._canvas_of(img)
+        assert isinstance(lut, torch.Tensor) and lut.dtype == torch.float32 and lut.device == self.device and lut.is_contiguous() \
+            and lut.numel() % 768 == 0 and tuple(lut.shape[-2:]) == (3, 256), "prep_images(lut=...): a contiguous float32 [nlut, 3, 256] tensor on the env's device"
+        b = np.ascontiguousarray(box, dtype=np.int32).reshape(-1, 3)
+        li = None if lut_index is None else np.ascontiguousarray(lut_index, dtype=np.int32).reshape(len(b))
+        si = None if src_index is None else np.ascontiguousarray(src_index, dtype=np.int32).reshape(len(b))
+        oh, ow = int(out_hw[0]), int(out_hw[1])
+        if out is None:
+            out = torch.empty((len(b), 3, max(oh, 0), max(ow, 0)), dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.device == self.device and tuple(out.shape) == (len(b), 3, oh, ow) and out.is_contiguous()
+        self._compose_check(self.L.avsim_image_prep(self.h.h, img.data_ptr(), sf, n, H, W, lut.data_ptr(), lut.numel() // 768, _ffi.ptr(li), b.ctypes.data,
+                                                    len(b), _ffi.ptr(si), oh, ow, out.data_ptr()))
+        return out
+
     def check_render_overflow(self):
         """Overflow flags of the last colour render (bit 0 triangle records, bit 1 tile lists; 0 = complete images): warns when set.
         Synchronises, so it is read once at the end of an evaluation rather than per step."""

@@ -279,6 +279,28 @@ int avsim_compose_label(avsim_t* h, void* canvas, int canvas_fmt, int nout, int 
                         const char* prefix, const int64_t* value, uint32_t rgb);
 void avsim_compose_font(uint8_t rows[128][7]);
 
+/* Training batches on the device (csrc/avsim_imgprep.hip.h); av_aloha_amd/imgprep.py is the specification, and both calls
+ * equal it bit for bit.  Images are fmt 0: u8 [n][H][W][3] or fmt 1: float32 [n][3][H][W] in [0, 1], read as u8 by (int)(v * 255 + 0.5f)
+ * as avsim_jpeg_encode does.
+ * avsim_image_stats: out[i][c] = (sum, sum of squares, min, max) of the u8 values of channel c of image index[i] (index NULL: image i), as
+ * uint64 -- the integers a data set's mean / std / min / max are made of (imgprep.combine_stats), exact and the same on every run.  img,
+ * index and out follow the handle's I/O mode; a host caller's index is checked (negative: AVSIM_EINVAL) and says how many images img
+ * holds, a device caller's is not read by the host.  AVSIM_EINVAL, with nothing launched and out untouched: fmt other than 0 / 1, height or
+ * width outside 1..65535, nimg < 1.
+ * avsim_image_prep: out[i][c][y][x] = lut[lut_index[i]][c][u8(img[src_index[i]])[y0 + y][x0 + (flip ? out_w - 1 - x : x)][c]] with
+ * (x0, y0, flip) = box[i]: a crop, an optional mirror and a per-channel table look-up in one pass -- normalisation ((u / 255 - mean) / std
+ * tabulated, imgprep.normalise_lut), brightness, gamma, any per-channel curve.  lut: float32 [nlut][3][256]; lut_index NULL: table 0 for every
+ * output; src_index NULL: output i reads image i.  img, lut and out follow the handle's I/O mode; box, lut_index and src_index are HOST arrays
+ * in both modes (as avsim_compose's places), checked before anything is launched and copied into pinned staging of the library's own before
+ * the call returns -- the caller may change or free them at once.  The staging is reused behind events: with AVSIM_IO_DEVICE a call does not
+ * synchronise the stream once a call of the same sizes has run.  AVSIM_EINVAL, with nothing launched and out untouched: fmt other than 0 / 1,
+ * an image or output size outside 1..65535, a crop that does not lie inside the source, a flip other than 0 / 1, a lut_index outside
+ * [0, nlut), a src_index outside [0, nsrc), nsrc, nout or nlut < 1 (nlut at most 2^20). */
+int avsim_image_stats(avsim_t* h, const void* img, int fmt, const int32_t* index, int nimg, int height, int width, uint64_t* out /* [nimg][3][4] */);
+int avsim_image_prep(avsim_t* h, const void* img, int fmt, int nsrc, int height, int width, const float* lut, int nlut, const int32_t* lut_index,
+                     const int32_t* box /* [nout][3] */, int nout, const int32_t* src_index, int out_h, int out_w,
+                     float* out /* [nout][3][out_h][out_w] */);
+
 /* Per-env episodes on the device (a vector env with gymnasium's NEXT_STEP autoreset; av_aloha_amd/vec_env.py).  Pointers follow the
  * handle's I/O mode, except box / share of the set-up (host pointers).  In device mode no step, reset, sample or render call
  * synchronises; avsim_episode_setup does (it reallocates the records: once per evaluation), and so do avsim_episode_log /

@@ -1,0 +1,177 @@
+"""av_aloha_amd/imgprep.py, the specification of avsim_image_stats / avsim_image_prep and of the action chunks, against arithmetic written
+out here; the draw order of dataset.TrainingBatches; and that the library declares and exports the two entry points.  No device needed."""
+import ctypes as C
+import math
+import os
+import re
+from fractions import Fraction
+
+import numpy as np
+
+from av_aloha_amd import dataset, imgprep
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def noise(shape, seed):
+    return np.random.default_rng(seed).integers(0, 256, shape, dtype=np.uint8)
+
+
+def test_stats_reference_is_numpy_sums():
+    img = noise((5, 13, 17, 3), 1)
+    st = imgprep.stats_reference(img)
+    assert st.dtype == np.uint64 and st.shape == (5, 3, 4)
+    for i in range(5):
+        for c in range(3):
+            v = img[i, :, :, c]
+            assert st[i, c, 0] == np.sum(v, dtype=np.uint64)
+            assert st[i, c, 1] == np.sum(v.astype(np.uint64) ** 2, dtype=np.uint64)
+            assert st[i, c, 2] == v.min() and st[i, c, 3] == v.max()
+    idx = [4, 0, 0, 2]
+    assert np.array_equal(imgprep.stats_reference(img, idx), st[idx])
+    f = (np.transpose(img, (0, 3, 1, 2)).astype(np.float32) / np.float32(255)).copy()
+    assert np.array_equal(imgprep.stats_reference(f), st)
+
+
+def _is_rounded_sqrt(d, var):
+    """d is the double nearest to sqrt(var): var lies between the squares of the midpoints to d's neighbours."""
+    if var == 0:
+        return d == 0.0
+    lo, hi = (Fraction(math.nextafter(d, 0.0)) + Fraction(d)) / 2, (Fraction(math.nextafter(d, math.inf)) + Fraction(d)) / 2
+    return lo * lo <= var <= hi * hi
+
+
+def _check_combine(img):
+    n, H, W, _ = img.shape
+    got = imgprep.combine_stats(imgprep.stats_reference(img), H * W)
+    N = n * H * W
+    for c in range(3):
+        v = [int(x) for x in img[..., c].reshape(-1)]
+        S, Q = sum(v), sum(x * x for x in v)
+        mean, var = Fraction(S, 255 * N), Fraction(N * Q - S * S, (255 * N) ** 2)
+        assert var == sum((Fraction(x, 255) - mean) ** 2 for x in v) / N            # the population variance
+        assert got["mean"][c, 0, 0] == np.float32(float(mean))
+        std64 = float(np.float64(got["std"][c, 0, 0]))
+        assert got["std"].dtype == np.float32
+        # the float32 is the rounding of the correctly rounded double: find that double from the candidates around the float32
+        cands = [float(np.float64(math.sqrt(float(var))))]
+        cands += [math.nextafter(cands[0], 0.0), math.nextafter(cands[0], math.inf)]
+        exact = [d for d in cands if _is_rounded_sqrt(d, var)]
+        assert len(exact) >= 1 and np.float32(exact[0]) == got["std"][c, 0, 0], (std64, exact)
+        assert got["min"][c, 0, 0] == np.float32(float(Fraction(min(v), 255))) and got["max"][c, 0, 0] == np.float32(float(Fraction(max(v), 255)))
+    for k in ("mean", "std", "min", "max"):
+        assert got[k].shape == (3, 1, 1) and got[k].dtype == np.float32
+    return got
+
+
+def test_combine_stats_is_exact_rational_arithmetic():
+    const = np.empty((2, 5, 7, 3), dtype=np.uint8)
+    const[...] = [17, 128, 201]
+    got = _check_combine(const)
+    assert (got["std"] == 0).all()                                        # exactly: N Q - S^2 = 0 in integers
+    got = _check_combine(np.full((3, 4, 6, 3), 255, dtype=np.uint8))
+    assert (got["mean"] == 1).all() and (got["std"] == 0).all() and (got["min"] == 1).all()
+    _check_combine(noise((3, 9, 11, 3), 2))
+
+
+def test_to_u8_round_trips_all_levels():
+    u = np.arange(256, dtype=np.uint8)
+    f = (u.astype(np.float32) / np.float32(255)).reshape(1, 1, 16, 16)
+    f = np.ascontiguousarray(np.repeat(f, 3, axis=1))
+    back = imgprep.to_u8(f)
+    assert back.dtype == np.uint8 and back.shape == (1, 16, 16, 3)
+    assert np.array_equal(back[0, :, :, 0].reshape(-1), u) and np.array_equal(back[0, :, :, 2].reshape(-1), u)
+    img = noise((2, 3, 4, 3), 3)
+    assert imgprep.to_u8(img) is img
+
+
+def test_normalise_lut_is_the_float32_expression():
+    mean, std = np.array([0.485, 0.456, 0.406], np.float32), np.array([0.229, 0.224, 0.225], np.float32)
+    lut = imgprep.normalise_lut(mean.reshape(3, 1, 1), std.reshape(3, 1, 1))
+    assert lut.dtype == np.float32 and lut.shape == (3, 256)
+    img = noise((1, 6, 5, 3), 4)
+    want = (img[0].astype(np.float32) / np.float32(255) - mean) / std             # [H, W, 3], every operation in float32
+    assert want.dtype == np.float32
+    got = imgprep.prep_reference(img, lut[None], None, [(0, 0, 0)], (6, 5))[0]
+    assert np.array_equal(got.view(np.uint32), np.transpose(want, (2, 0, 1)).copy().view(np.uint32))
+    ident = imgprep.identity_lut()
+    assert np.array_equal(ident[1], np.arange(256, dtype=np.float32) / np.float32(255)) and ident.shape == (3, 256)
+
+
+def test_prep_reference_against_a_triple_loop():
+    img = noise((2, 7, 9, 3), 5)
+    lut = np.random.default_rng(6).standard_normal((2, 3, 256)).astype(np.float32)
+    oh, ow = 4, 5
+    box = [(3, 2, 0), (4, 3, 1), (0, 0, 1)]
+    src_index, lut_index = [1, 0, 1], [0, 1, 1]
+    got = imgprep.prep_reference(img, lut, lut_index, box, (oh, ow), src_index)
+    assert got.shape == (3, 3, oh, ow) and got.dtype == np.float32
+    for i, (x0, y0, flip) in enumerate(box):
+        for c in range(3):
+            for y in range(oh):
+                for x in range(ow):
+                    u = img[src_index[i], y0 + y, x0 + (ow - 1 - x if flip else x), c]
+                    assert got[i, c, y, x] == lut[lut_index[i], c, u]
+    full = imgprep.prep_reference(img, lut, None, [(0, 0, 0), (0, 0, 1)], (7, 9))
+    for c in range(3):
+        assert np.array_equal(full[0, c], lut[0, c][img[0, :, :, c]]) and np.array_equal(full[1, c], lut[0, c][img[1, :, ::-1, c]])
+    for bad in ([(5, 0, 0)], [(0, 4, 0)], [(-1, 0, 0)], [(0, 0, 2)]):
+        try:
+            imgprep.prep_reference(img[:1], lut, None, bad, (oh, ow))
+        except ValueError:
+            continue
+        raise AssertionError(f"box {bad} must be refused")
+
+
+def test_chunk_index_against_brute_force():
+    lens = [5, 7]
+    starts = [0, 5]
+    for chunk in (4, 9):
+        frames = np.arange(12)
+        index, pad = imgprep.chunk_index(starts, lens, frames, chunk)
+        assert index.dtype == np.int64 and pad.dtype == np.bool_ and index.shape == pad.shape == (12, chunk)
+        for f in range(12):
+            e = 0 if f < 5 else 1
+            s, T = starts[e], lens[e]
+            t = f - s
+            for k in range(chunk):
+                assert index[f, k] == s + min(t + k, T - 1)
+                assert pad[f, k] == (t + k > T - 1)
+    index, pad = imgprep.chunk_index(starts, lens, [11, 0], 2)
+    assert index.tolist() == [[11, 11], [0, 1]] and pad.tolist() == [[False, True], [False, False]]
+
+
+def test_training_batches_draw_order():
+    sizes = {"a": (16, 24), "b": (24, 32)}
+    crop = (12, 20)
+    p0 = dataset.epoch_plan(12, 5, sizes, crop, "random", seed=3, epoch=0)
+    again = dataset.epoch_plan(12, 5, sizes, crop, "random", seed=3, epoch=0)
+    p1 = dataset.epoch_plan(12, 5, sizes, crop, "random", seed=3, epoch=1)
+    assert len(p0) == 2 and all(len(part) == 5 for part, _ in p0)                 # drop_last
+    for (a, ba), (b, bb) in zip(p0, again):
+        assert np.array_equal(a, b) and all(np.array_equal(ba[c], bb[c]) for c in sizes)
+    assert any(not np.array_equal(a, b) or any(not np.array_equal(ba[c], bb[c]) for c in sizes) for (a, ba), (b, bb) in zip(p0, p1))
+    # the documented order, drawn here: the permutation, then per batch and camera y0, then x0
+    rng = np.random.default_rng([3, 0])
+    order = rng.permutation(12)
+    for i, (part, boxes) in enumerate(p0):
+        assert np.array_equal(part, order[5 * i:5 * i + 5])
+        for c, (H, W) in sizes.items():
+            y0 = rng.integers(0, H - crop[0] + 1, 5)
+            x0 = rng.integers(0, W - crop[1] + 1, 5)
+            assert np.array_equal(boxes[c][:, 1], y0) and np.array_equal(boxes[c][:, 0], x0) and (boxes[c][:, 2] == 0).all()
+    keep = dataset.epoch_plan(12, 5, sizes, crop, "random", seed=3, epoch=0, drop_last=False)
+    assert [len(p) for p, _ in keep] == [5, 5, 2] and keep[2][1]["b"].shape == (2, 3)
+    center = dataset.epoch_plan(12, 5, sizes, crop, "center", seed=3, epoch=0)
+    assert (center[0][1]["a"] == [2, 2, 0]).all() and (center[1][1]["b"] == [6, 6, 0]).all()
+    assert np.array_equal(center[0][0], p0[0][0])                                # the same permutation
+
+
+def test_new_entry_points_declared_and_exported():
+    txt = open(os.path.join(ROOT, "include", "avsim.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    from av_aloha_amd.build import build_hip
+    L = C.CDLL(build_hip())
+    for name in ("avsim_image_stats", "avsim_image_prep"):
+        assert re.search(r"\bint\s+%s\s*\(" % name, txt), f"include/avsim.h does not declare {name}"
+        assert hasattr(L, name), f"libavsim.so lacks {name}"
