@@ -17,8 +17,9 @@ def _stale(target, sources):
 
 
 def build_hip(force=False, verbose=False):
-    """hipcc --offload-arch=gfx950: avsim_api.hip (C-ABI, f32 product kernels, IK, render) and avsim_phys_f64.hip (the f64 parity
-    kernel, -ffp-contract=off so that it rounds like the oracle) compiled side by side, linked into libavsim.so."""
+    """hipcc --offload-arch=gfx950: avsim_api.hip (C-ABI, f32 product kernels, IK, render), avsim_phys_spec.hip (the f32 physics
+    kernel specialised per model) and avsim_phys_f64.hip (the f64 parity kernel, -ffp-contract=off so that it rounds like the oracle)
+    compiled side by side, linked into libavsim.so."""
     srcs = [os.path.join(SRC, f) for f in sorted(os.listdir(SRC)) if not f.endswith(".o") and not f.startswith(".")] + [os.path.join(ROOT, "include", "avsim.h"), os.path.abspath(__file__)]       # (this file holds the flags: a library built with other flags is stale too)
     if not force and not _stale(LIB, srcs):
         return LIB
@@ -34,6 +35,8 @@ def build_hip(force=False, verbose=False):
 def _build_hip_locked(verbose):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     common = [hipcc, "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-c"]
+    F32_FLAGS = ["-O2", "-fno-hip-fp32-correctly-rounded-divide-sqrt", "-fgpu-flush-denormals-to-zero", "-fno-slp-vectorize", "-fno-vectorize",
+                 "-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]
     units = [
         # f32 divide / sqrt through v_rcp / v_rsq (~1 ulp) instead of the correctly rounded 10-instruction sequences; the f64
         # parity mode is unaffected and the f32 tolerances of tests/test_gpu_physics.py are stated against the f64 oracle
@@ -45,8 +48,9 @@ def _build_hip_locked(verbose):
         # together 1006 k -> 1023 k (tools/exp_flags_multi.sh, profiles/r03_experiments.txt); -O3 was the setting until then
         # -amdgpu-sched-strategy=max-ilp: the machine scheduler orders for instruction-level parallelism instead of for occupancy, which the kernels fix
         # themselves (waves_per_eu): config 2 1 028 -> 1 039 k, f64 428 -> 436 k on one box (tools/exp_flags_ab.sh, profiles/r05_experiments.txt 7b)
-        ("avsim_api", ["-O2", "-fno-hip-fp32-correctly-rounded-divide-sqrt", "-fgpu-flush-denormals-to-zero", "-fno-slp-vectorize", "-fno-vectorize",
-                       "-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-mllvm", "-amdgpu-sched-strategy=max-ilp"] + (["-DAVSIM_RENDER_STATS"] if os.environ.get("AVSIM_RENDER_STATS") else []) + os.environ.get("AVSIM_EXTRA_FLAGS", "").split()),
+        ("avsim_api", F32_FLAGS + (["-DAVSIM_RENDER_STATS"] if os.environ.get("AVSIM_RENDER_STATS") else []) + os.environ.get("AVSIM_EXTRA_FLAGS", "").split()),
+        # the f32 physics kernel once more per model of csrc/avsim_phys_specs.h, layout and table offsets compiled in: the same flags as the generic one
+        ("avsim_phys_spec", F32_FLAGS + os.environ.get("AVSIM_EXTRA_FLAGS", "").split()),
         # the f64 unit is built -ffp-contract=off: the oracle's roundings.  Round 6 measured the fused build (AVSIM_EXTRA_FLAGS_F64=-ffp-contract=fast): + 4 %
         # (434 -> 452 k env-steps/s) and every f64 parity test of tests/test_gpu_physics.py / test_gpu_boxbox.py / test_gpu_configs.py / test_gpu_episode_parity.py
         # unchanged -- but the scripted closed-loop episodes become other trajectories (GradIK amplifies a rounding), and on the new SlotInsertion episodes the

@@ -595,9 +595,14 @@ int avsim_render_kernel_time(avsim_t* h, int reset, double* total_ms, int64_t* l
     return AVSIM_OK;
 }
 
+// option "phys_specialised" = 2: a call whose physics launch would take the generic kernel fails HERE, before the call's first enqueue
+// (the reset kernel, the state conversion and the Cartesian step's IK all write state ahead of the physics launch)
+#define AVS_PHYS_GATE(h) do { if ((h)->phys.refuses((h)->err)) return AVSIM_EINVAL; } while (0)
+
 int avsim_observe(avsim_t* h, double* agent_pos, int32_t* reward, uint8_t* success) {
     if (!h) return AVSIM_EINVAL;
     AVS_ON_DEVICE(h);
+    AVS_PHYS_GATE(h);
     int rc;
     void *dap = nullptr, *drw = nullptr, *dsu = nullptr;
     size_t N = h->N;
@@ -685,6 +690,7 @@ extern "C" {
 int avsim_reset(avsim_t* h, const uint8_t* mask, const double* obj_qpos) {
     if (!h || !obj_qpos) { if (h) h->set_error("avsim_reset: obj_qpos is required"); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
+    AVS_PHYS_GATE(h);
     h->state_ver++;
     return h->f64 ? reset_impl<double>(h, mask, obj_qpos) : reset_impl<float>(h, mask, obj_qpos);
 }
@@ -727,6 +733,7 @@ static int step_common(avsim_t* h, const float* d_action, int nsub, double* agen
 int avsim_step(avsim_t* h, const float* action, int nsub, double* agent_pos, int32_t* reward, uint8_t* success) {
     if (!h || !action || nsub < 0) { if (h) h->set_error("avsim_step: bad arguments"); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
+    AVS_PHYS_GATE(h);
     const void* da;
     int rc;
     if ((rc = h->in(0, action, sizeof(float) * h->N * h->nj, &da))) return rc;
@@ -736,6 +743,7 @@ int avsim_step(avsim_t* h, const float* action, int nsub, double* agent_pos, int
 int avsim_step_ctrl(avsim_t* h, int nsub, double* agent_pos, int32_t* reward, uint8_t* success) {
     if (!h || nsub < 0) { if (h) h->set_error("avsim_step_ctrl: bad arguments"); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
+    AVS_PHYS_GATE(h);
     return step_common(h, nullptr, nsub, agent_pos, reward, success);
 }
 
@@ -747,6 +755,7 @@ int avsim_step_cartesian(avsim_t* h, const double* action23, int ik_mode, int ns
     }
     if (h->num_arms != 3) { h->set_error("avsim_step_cartesian: the 23-D Cartesian action drives three arms (sim_env.py:277-282)"); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
+    AVS_PHYS_GATE(h);
     const void* da;
     int rc;
     if ((rc = h->in(0, action23, sizeof(double) * h->N * 23, &da))) return rc;
@@ -807,6 +816,7 @@ int avsim_get_state(avsim_t* h, double* qpos, double* qvel, double* ctrl, double
 int avsim_set_state(avsim_t* h, const double* qpos, const double* qvel, const double* ctrl, const double* warm) {
     if (!h) return AVSIM_EINVAL;
     AVS_ON_DEVICE(h);
+    AVS_PHYS_GATE(h);
     h->state_ver++;
     size_t N = h->N;
     int rc;

@@ -695,8 +695,8 @@ AVS_DEV void ncomp_subst(const NewtonArgs<real>& A, const NComp& c, int lane) {
 // NCH = contact chunks of 64 (one contact per lane and chunk): 1 when the model's contact cap is <= 64
 // COUPLED: some row reaches into two kinematic trees (the caller looks: solve_i) -- two instances, so that the solves of scenes
 // without such rows carry nothing of the dense path (its call alone costs the Newton loop SGPRs: 1 % of the headline configuration)
-template <typename real, int NCH, bool COUPLED>
-__device__ __attribute__((always_inline)) int newton_solve(KPtr<real> ka, GLB_PTR(const real) rows, LDS_PTR(real) r_, LDS_PTR(int) ii_, LDS_PTR(const int) li_, int nefc, int ncon, int nlead,
+template <typename real, int NCH, bool COUPLED, typename KA>
+__device__ __attribute__((always_inline)) int newton_solve(KA ka, GLB_PTR(const real) rows, LDS_PTR(real) r_, LDS_PTR(int) ii_, LDS_PTR(const int) li_, int nefc, int ncon, int nlead,
                                                       int iters, real tol, real scale, int profiling) {
     const int lane = threadIdx.x & 63;
     NewtonArgs<real> A;
@@ -706,18 +706,16 @@ __device__ __attribute__((always_inline)) int newton_solve(KPtr<real> ka, GLB_PT
         LDS_PTR(int) ii = (LDS_PTR(int))(unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)ii_);
         LDS_PTR(const int) li = (LDS_PTR(const int))(unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)li_);
         tol = lane_get(tol, 0); scale = lane_get(scale, 0);
-        const Layout __attribute__((address_space(4)))* L = &ka->lay;
-        const MOff __attribute__((address_space(4)))* O = &ka->mo;
-        A.rowS = r + L->rowS; A.rowI = ii + L->rowI; A.rmeta = ii + L->rmeta;
+        A.rowS = r + ka->lay.rowS; A.rowI = ii + ka->lay.rowI; A.rmeta = ii + ka->lay.rmeta;
         {   // the row pointer is wave-uniform: back to SGPRs
             const unsigned long long p_ = (unsigned long long)rows;
             A.rJ = (GLB_PTR(const real))(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(p_ >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)p_));
         }
-        A.M = r + L->M; A.a = r + L->qacc; A.as = r + L->asm_;
-        A.H = r + L->nH; A.g = r + L->ng; A.dl = r + L->ndl; A.jv = r + L->njv;
-        A.cefc = ii + L->cefc;
-        A.prof = profiling ? ii + L->nprof : (LDS_PTR(int))nullptr;
-        A.tree_dofadr = li + O->tree_dofadr; A.tree_dofnum = li + O->tree_dofnum; A.tree_madr = li + O->tree_madr; A.dof_tree = li + O->dof_tree;
+        A.M = r + ka->lay.M; A.a = r + ka->lay.qacc; A.as = r + ka->lay.asm_;
+        A.H = r + ka->lay.nH; A.g = r + ka->lay.ng; A.dl = r + ka->lay.ndl; A.jv = r + ka->lay.njv;
+        A.cefc = ii + ka->lay.cefc;
+        A.prof = profiling ? ii + ka->lay.nprof : (LDS_PTR(int))nullptr;
+        A.tree_dofadr = li + ka->mo.tree_dofadr; A.tree_dofnum = li + ka->mo.tree_dofnum; A.tree_madr = li + ka->mo.tree_madr; A.dof_tree = li + ka->mo.dof_tree;
         A.nv = __builtin_amdgcn_readfirstlane(ka->m.nv); A.ntree = __builtin_amdgcn_readfirstlane(ka->m.ntree);
         A.nefc = __builtin_amdgcn_readfirstlane(nefc); A.ncon = __builtin_amdgcn_readfirstlane(ncon);
         A.nlead = __builtin_amdgcn_readfirstlane(nlead); A.iters = __builtin_amdgcn_readfirstlane(iters);
@@ -1043,8 +1041,8 @@ __device__ __attribute__((always_inline)) int newton_solve(KPtr<real> ka, GLB_PT
 
 // The coupled instances as functions of their own: what they keep in registers (the component, the batched Hessian rows) then
 // does not weigh on the register allocation of Env::solve, where the uncoupled instance of the headline scene is inlined.
-template <typename real, int NCH>
-__device__ AVS_OUTLINE_5 int newton_solve_coupled(KPtr<real> ka, GLB_PTR(const real) rows, LDS_PTR(real) r_, LDS_PTR(int) ii_, LDS_PTR(const int) li_, int nefc, int ncon, int nlead,
+template <typename real, int NCH, typename KA>
+__device__ AVS_OUTLINE_5 int newton_solve_coupled(KA ka, GLB_PTR(const real) rows, LDS_PTR(real) r_, LDS_PTR(int) ii_, LDS_PTR(const int) li_, int nefc, int ncon, int nlead,
                                                               int iters, real tol, real scale, int profiling) {
     return newton_solve<real, NCH, true>(ka, rows, r_, ii_, li_, nefc, ncon, nlead, iters, tol, scale, profiling);
 }

@@ -21,6 +21,7 @@
 #include "avsim_collide.hip.h"
 #include "avsim_math.hip.h"
 #include "avsim_model.h"
+#include "avsim_phys_layout.h"
 
 namespace avs {
 
@@ -31,10 +32,8 @@ constexpr int ROW_W = 2 * TREE_W;
 // LDS stride of the per-row solver record: odd, so that the row-per-lane loops (lane i reads word k of row i) spread over
 // all 32 banks instead of hammering 4 of them (stride 8)
 constexpr int ROW_S = ROW_W;       // Jacobian rows live in global memory (L2-resident scratch): 64-byte rows, no banks to dodge
-constexpr int RS_S = 9;            // solver record: 8 words used
 constexpr int CAND_MAX = 256;  // exact broad-phase survivors per substep (narrow-phase work list, global scratch)
 constexpr int PROF_W = 26;   // words per env of the phase profile: 8 phases, broad / narrow, 16 solver / probe slots
-constexpr int ANC_MAX = 64;    // LDS ints of the kinematics' pointer-jumping table (one per body)
 constexpr int NEAR_MAX = 512;  // Verlet neighbour list: pairs within reach + skin, rebuilt when a geom moved > skin/2
 
 template <typename real>
@@ -160,77 +159,7 @@ struct DevModel {
     GLB_PTR(const real) obs_scale;
 };
 
-struct MOff {
-    int nreal, nint;
-    int body_parent;
-    int body_jntadr;
-    int body_jntnum;
-    int body_dofadr;
-    int body_dofnum;
-    int body_tree;
-    int body_dofmask;
-    int body_last;
-    int tree_bodyadr;
-    int tree_bodylist;
-    int tree_dofadr;
-    int tree_dofnum;
-    int tree_madr;
-    int jnt_type;
-    int jnt_qposadr;
-    int jnt_dofadr;
-    int jnt_actfrclimited;
-    int limited_jnt;
-    int dof_body;
-    int dof_parent;
-    int dof_tree;
-    int dof_jnt;
-    int floss_dof;
-    int ment_i;
-    int ment_j;
-    int act_dof;
-    int act_qposadr;
-    int act_ctrllimited;
-    int geom_type;
-    int geom_body;
-    int geom_static;
-    int body_pos;
-    int body_quat;
-    int body_mass;
-    int body_ipos;
-    int body_inertia;
-    int body_invweight0;
-    int jnt_pos;
-    int jnt_axis;
-    int jnt_range;
-    int jnt_actfrcrange;
-    int jnt_margin;
-    int dof_armature;
-    int dof_damping;
-    int dof_frictionloss;
-    int dof_invweight0;
-    int act_kp;
-    int act_kv;
-    int act_gear;
-    int act_ctrlrange;
-    int geom_cpos;
-    int geom_rbound;
-};
-
-// per-env LDS layout (offsets in reals / ints)
-struct Layout {
-    int qpos, qvel, ctrl, warm, xpos, xmat, xipos, cdof, gcen, M, L, Minv, bias, fsm, asm_, qacc, fcon, nH, ng, ndl, njv, U, nreal;
-    // scratch union U, phase A
-    int cinert, cvel, cacc, cfrc, binert;   // binert: the bodies' own spatial inertias (cinert becomes the composites)
-    // phase B
-    int cdist, cpos, cnrm, rowS, scr;   // scr: narrow-phase scratch (overlays rowS: 64 result slots of 20 words + 9 box work areas)
-    // ints
-    int cand, cpair, cefc, rmeta, rowI, gI, misc, nprof, nint;
-    int maxgrp;
-    int maxcon, maxefc;
-    int expcon;                   // stride of the contact export arrays (the full capacity, whatever this layout's own)
-    int gefc, ggrp;               // rows / groups per env in the global scratch (the full capacities)
-    int bytes_per_env;
-};
+static_assert(NARROW_SCR_W == 64 * SLOT_W + 4 * 56, "avsim_phys_layout.h: narrow-phase scratch");
 
 // everything the kernel needs to know about the model: read through a constant-address-space pointer, so that the ~90 table
 // pointers and ~100 offsets are scalar-loaded where they are used instead of being held (and spilled) for the whole kernel
@@ -242,6 +171,31 @@ struct KArgs {
 };
 template <typename real>
 using KPtr = const KArgs<real> __attribute__((address_space(4)))*;
+
+// Layout policy of Env / k_phys: where `ka->lay.X` and `ka->mo.X` come from.  GenericSpec: `ka` IS the KPtr, every offset is a scalar
+// load where it is used (any model, any capacities).  A fixed spec (avsim_phys_spec.hip) carries the Layout and the MOff of one
+// committed model as static constexpr members lay / mo: `ka` is then a KFixed, whose -> hands out the spec's constants for lay and
+// mo -- they end up in the immediate offsets of the ds_read / ds_write instructions -- and the handle's run-time values for `m` (what options
+// can change: tolerances, solver flags, the table pointers).  The host launches such a kernel only for a handle whose own Layout, MOff and
+// dims equal the spec's (PhysHost::launch_t).
+struct GenericSpec {};
+template <typename real, typename SPEC>
+struct KFixed {
+    KPtr<real> p;
+    struct View {
+        const DevModel<real> __attribute__((address_space(4)))& m;
+        static constexpr Layout lay = SPEC::lay;
+        static constexpr MOff mo = SPEC::mo;
+        AVS_DEV const View* operator->() const { return this; }
+    };
+    AVS_DEV KFixed(KPtr<real> p_) : p(p_) {}
+    AVS_DEV explicit KFixed(unsigned long long v) : p((KPtr<real>)v) {}            // (PHASE_LAUNDER)
+    AVS_DEV explicit operator unsigned long long() const { return (unsigned long long)p; }
+    AVS_DEV View operator->() const { return View{p->m}; }
+};
+template <typename real, typename SPEC> struct KRefOf { using type = KFixed<real, SPEC>; };
+template <typename real> struct KRefOf<real, GenericSpec> { using type = KPtr<real>; };
+template <typename real, typename SPEC> using KRef = typename KRefOf<real, SPEC>::type;
 // start of a phase: forget what was loaded through ka so far (keeps the live ranges of model scalars inside one phase)
 #define PHASE_LAUNDER()                                                                                \
     do {                                                                                               \
@@ -1687,8 +1641,8 @@ struct SInert {
 };
 
 // spatial inertia of body b about the world origin in world axes
-template <typename real>
-AVS_DEV void body_inertia(KPtr<real> ka, const real* xmat, const real* xipos, int b, SInert<real>& s) {
+template <typename real, typename KA>
+AVS_DEV void body_inertia(KA ka, const real* xmat, const real* xipos, int b, SInert<real>& s) {
     const real* R = xmat + 9 * b;
     GLB_PTR(const real) Ib = ka->m.body_inertia + 6 * b;
     real I3[9] = {Ib[0], Ib[3], Ib[4], Ib[3], Ib[1], Ib[5], Ib[4], Ib[5], Ib[2]}, T[9], Ic[9];
@@ -1845,7 +1799,7 @@ AVS_DEV int reward_from_flags(int f, int t, int* latch) {
     return rw;
 }
 // get_reward on explicit contact lists (one thread per list): geom id pairs int[n][cap][2], -1 = unused slot
-#ifndef AVSIM_TU_F64
+#if !defined(AVSIM_TU_F64) && !defined(AVSIM_NO_F32_LAUNCH)      // (avsim_api.hip's)
 __global__ void k_reward_pairs(GLB_PTR(const int) geom_class, int ngeom, int task_id, const int* __restrict__ pairs, int n, int cap, int* __restrict__ latch, int* __restrict__ reward) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -1862,9 +1816,9 @@ __global__ void k_reward_pairs(GLB_PTR(const int) geom_class, int ngeom, int tas
 #endif
 
 
-template <typename real, int G>
+template <typename real, int G, typename SPEC = GenericSpec>
 struct Env {
-    KPtr<real> ka;   // model, LDS layout and table offsets: one struct in constant memory, re-read per phase (PHASE_BEGIN)
+    KRef<real, SPEC> ka;   // model, LDS layout and table offsets: one struct in constant memory, re-read per phase (PHASE_BEGIN)
     int env = 0;                    // global env index (row buffer addressing)
     int diverged = 0;               // the state left the representable range during this launch and was put back to the home pose
     int nit_sum = 0, nit_max = 0;   // Newton iterations over the launch's substeps (diagnostics)
@@ -1875,7 +1829,7 @@ struct Env {
     const real* lr;
     const int* li;
     long long t_broad = 0, t_narrow = 0;
-    __device__ Env(KPtr<real> ka_, real* r_, int* i_, int lane_, int grp_, const real* lr_, const int* li_)
+    __device__ Env(KRef<real, SPEC> ka_, real* r_, int* i_, int lane_, int grp_, const real* lr_, const int* li_)
         : ka(ka_), r(r_), ii(i_), lane(lane_), grp(grp_), lr(lr_), li(li_) {}
     // hot model tables live in LDS (copied once per block); the accessors rebuild the pointer from the kernarg offset
     AVS_DEV const int* LI() const { const int* p = li; AVS_ASSUME_LDS(p); return p; }
@@ -2377,7 +2331,7 @@ struct Env {
     // entry 1 + pert of that slot (1e30: none).  Out of line with register arguments only: the MPR code
     // is 27 KB, and as a call of mpr_perturbed itself the two Shapes went through the wave's private segment -- 79 dwords per lane,
     // 20 KB written and read back per narrow-phase pass, most of the kernel's spill traffic (profiles/r05_experiments.txt section 7).
-    __device__ AVS_OUTLINE_0 static void multi_perturb(KPtr<real> ka_, real* r_, int* i_, int lane_, int grp_, const real* lr_, const int* li_, int env_,
+    __device__ AVS_OUTLINE_0 static void multi_perturb(KRef<real, SPEC> ka_, real* r_, int* i_, int lane_, int grp_, const real* lr_, const int* li_, int env_,
                                                                    int pga, int pgb, int src, int pert) {
         Env e(ka_, r_, i_, lane_, grp_, lr_, li_);       // (an Env by value is an aggregate of 22 dwords: passed in memory)
         e.env = env_;
@@ -3257,7 +3211,7 @@ struct Env {
 #ifndef AVSIM_PHYS_MAXW
 #define AVSIM_PHYS_MAXW 8
 #endif
-template <typename real, int G, int MAXW, bool RETRY>
+template <typename real, int G, int MAXW, bool RETRY, typename SPEC = GenericSpec>
 #ifndef AVSIM_PHYS_ATTR
 #ifdef AVSIM_TU_F64
 #define AVSIM_PHYS_ATTR
@@ -3266,13 +3220,14 @@ template <typename real, int G, int MAXW, bool RETRY>
 #define AVSIM_PHYS_ATTR __attribute__((amdgpu_waves_per_eu(2)))
 #endif
 #endif
-__global__ void __launch_bounds__(64 * MAXW) AVSIM_PHYS_ATTR k_phys(KPtr<real> ka_small, const real* __restrict__ img_real, const int* __restrict__ img_int, int N, int nsub, int pgs_iters, const float* __restrict__ action,
+__global__ void __launch_bounds__(64 * MAXW) AVSIM_PHYS_ATTR k_phys(KPtr<real> ka_small_, const real* __restrict__ img_real, const int* __restrict__ img_int, int N, int nsub, int pgs_iters, const float* __restrict__ action,
                                              int want_reward, real* __restrict__ g_qpos, real* __restrict__ g_qvel, real* __restrict__ g_ctrl,
                                              real* __restrict__ g_warm, int* __restrict__ g_latch, double* __restrict__ o_agent,
                                              int* __restrict__ o_reward, unsigned char* __restrict__ o_success, int* __restrict__ o_ncon,
                                              int* __restrict__ o_cpairs, double* __restrict__ o_cdist, int* __restrict__ o_diag, int max_reward, int export_contacts, long long* __restrict__ o_prof, float* __restrict__ o_xpose,
                                              const int* __restrict__ env_order, int* __restrict__ o_cost, int* __restrict__ work_head, int* __restrict__ work_next,
-                                             int* __restrict__ retry, int retry_mode, KPtr<real> ka_big) {
+                                             int* __restrict__ retry, int retry_mode, KPtr<real> ka_big_) {
+    const KRef<real, SPEC> ka_small(ka_small_), ka_big(ka_big_);      // (a fixed SPEC: the layout and the table offsets are its constants)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // Two passes over a launch's envs (PhysHost::launch_t).  The first runs every env with the SMALL contact / row capacities -- the
     // LDS record that lets the most envs share a CU; an env that runs out of them in any substep is abandoned before anything of it is
@@ -3382,12 +3337,12 @@ __global__ void __launch_bounds__(64 * MAXW) AVSIM_PHYS_ATTR k_phys(KPtr<real> k
         }
         if (polls >= (1 << 15)) { lds_put(&pair_want[pr], 0); to_list(env); continue; }      // (never seen: a partner's env-step is ~2000 polls; the claim is withdrawn first, its grant can never match another)
     }
-    KPtr<real> ka = (RETRY && big) ? ka_big : ka_small;
+    KRef<real, SPEC> ka = (RETRY && big) ? ka_big : ka_small;
     const long long t_launch = __builtin_readcyclecounter();
     real* r = reinterpret_cast<real*>(smem + (size_t)((RETRY && big) ? (wave & ~1) : wave) * ka_small->lay.bytes_per_env);
     int* ii = reinterpret_cast<int*>(r + ka->lay.nreal);
     bool beyond = false;      // this env needed more than the small capacities in some substep
-    Env<real, G> E(ka, r, ii, lane, grp, lr, li);
+    Env<real, G, SPEC> E(ka, r, ii, lane, grp, lr, li);
     E.env = env;
 
     // ---- load state (coalesced: consecutive lanes read consecutive words of this env's record) ----
@@ -3417,7 +3372,7 @@ __global__ void __launch_bounds__(64 * MAXW) AVSIM_PHYS_ATTR k_phys(KPtr<real> k
         PROF(0, E.pre_phases());
 #else
         {
-            Env<real, G> e(E);
+            Env<real, G, SPEC> e(E);
             PROF(0, e.kinematics());
             PROF(1, e.crb());
             PROF(2, e.rne_bias());
@@ -3432,7 +3387,7 @@ __global__ void __launch_bounds__(64 * MAXW) AVSIM_PHYS_ATTR k_phys(KPtr<real> k
         PROF(7, E.post_phases());
 #else
         {
-            Env<real, G> e(E);
+            Env<real, G, SPEC> e(E);
             PROF(7, e.euler());
             e.check_divergence();
             E.diverged = e.diverged;
@@ -3544,6 +3499,9 @@ struct PhysHost;
 // narrow phase's support-vertex and clipping tie-breaks then fall the same way on both sides
 int phys_launch_f64(PhysHost& ph, hipStream_t st, int nsub, const float* action, void* qpos, void* qvel, void* ctrl, void* warm, int* latch,
                     double* agent, int32_t* reward, uint8_t* success, std::string& err);
+// The kernels compiled for one committed model each (avsim_phys_spec.hip, a translation unit of its own): the host stub of the
+// one-pass f32 k_phys whose spec equals the handle's Layout, MOff and dims word for word, or null (`name`: the spec's model)
+const void* phys_spec_kernel(const PhysHost& ph, const char** name);
 
 struct PhysHost {
     int maxcon = 48, maxefc = 144, pgs_iters = 20, group = 64, export_contacts = 1, force_reward = 0, wpb_override = 0;
@@ -3553,6 +3511,8 @@ struct PhysHost {
     // results are those of the full capacities, the common case runs at the residency of the small ones.  Equal tiers: one pass.
     int maxcon1 = 48, maxefc1 = 144;
     bool f64 = false;
+    int specialised = 1;            // option "phys_specialised": 0 never, 1 the kernel compiled for the model when one matches, 2 require one
+    bool host_only = false;         // build() assembles the table image and the offsets without a device (tools/gen_phys_specs)
     int N = 0, max_reward = 0;
     std::vector<void*> allocs;
     DevModel<float> mf;
@@ -3597,6 +3557,7 @@ struct PhysHost {
     DevPtr<T> up(const std::vector<T>& v) {
         void* p = nullptr;
         size_t n = (v.size() ? v.size() : 1) * sizeof(T);
+        if (host_only) return DevPtr<T>{nullptr};
         if (hipMalloc(&p, n) != hipSuccess) throw std::runtime_error("hipMalloc failed while uploading the model");
         if (v.size() && hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("hipMemcpy failed while uploading the model");
         allocs.push_back(p);
@@ -3826,6 +3787,22 @@ struct PhysHost {
         d_img_int = up(img_int);
     }
 
+    // Which kernel a one-pass launch of this handle takes as it stands: the one compiled for its model, or null = the generic one.
+    // Host only: no launch, no allocation.
+    const void* spec_kernel(const char** name) const {
+        if (f64 || specialised == 0 || two_pass()) return nullptr;
+        return phys_spec_kernel(*this, name);
+    }
+    // "phys_specialised" = 2: a launch that would take the generic kernel is refused.  Asked by launch_t and, before their first
+    // enqueue, by the API entry points that change state ahead of the physics launch (reset, set_state, the Cartesian step's IK).
+    bool refuses(std::string& err) const {
+        if (specialised != 2 || spec_kernel(nullptr)) return false;
+        err = std::string("phys_specialised = 2: no kernel compiled for this handle's model and layout (") +
+              (f64 ? "f64 handle" : two_pass() ? "two capacity tiers" : "Layout, table offsets or dims match no spec of avsim_phys_specs.h") + "); the launch would take the generic k_phys";
+        return true;
+    }
+    int spec_note = 0;
+
     void make_layout(int nq, int nv, int nu, int nb, int ng, int msize, int ntree) {
         if (maxcon1 > maxcon) maxcon1 = maxcon;
         if (maxefc1 > maxefc) maxefc1 = maxefc;
@@ -3834,44 +3811,12 @@ struct PhysHost {
     }
     void make_layout_of(Layout& L, const int maxcon, const int maxefc, int nq, int nv, int nu, int nb, int ng, int msize, int ntree) {
         kargs_dirty = true;
-        int o = 0;
-        auto R = [&](int n) { int a = o; o += n; return a; };
-        L.qpos = R(nq); L.qvel = R(nv); L.ctrl = R(nu); L.warm = R(nv);
-        L.xpos = R(3 * nb); L.xmat = R(9 * nb); L.xipos = R(3 * nb); L.cdof = R(6 * nv); L.gcen = R(3 * ng);
-        L.M = R(msize); L.L = R(msize); o = (o + 3) & ~3; L.Minv = R(64 * ntree);
-        L.bias = R(nv); L.fsm = R(nv); L.asm_ = R(nv); L.qacc = R(nv); L.fcon = R(nv);
-        // Newton scratch (packed Hessian, gradient, direction, per-row J.dl) lives over xpos..gcen where it fits: every
-        // position-derived quantity is dead between make_constraints and the next substep's kinematics
-        {
-            int nvh = nv * (nv + 1) / 2, need1 = nvh + 2 * nv, need2 = need1 + maxefc, avail = 15 * nb + 6 * nv + 3 * ng;
-            int base = need1 <= avail ? L.xpos : R(need1);
-            L.nH = base; L.ng = base + nvh; L.ndl = L.ng + nv;
-            L.njv = need2 <= avail ? L.ndl + nv : R(maxefc);
-        }
-        L.U = o;
-        int a = o;
-        L.cinert = a; a += 10 * nb; L.binert = a; a += 10 * nb; L.cvel = a; a += 6 * nb; L.cacc = a; a += 6 * nb; L.cfrc = a; a += 6 * nb;
-        int bq = o;
-        L.cdist = bq; bq += maxcon; L.cpos = bq; bq += 3 * maxcon; L.cnrm = bq; bq += 3 * maxcon;
-        bq = (bq + 3) & ~3; L.rowS = bq; L.scr = bq; bq += RS_S * maxefc;
-        L.maxgrp = maxefc / 3 + 8;
-        if (bq < L.scr + 64 * SLOT_W + 4 * 56) bq = L.scr + 64 * SLOT_W + 4 * 56;     // narrow phase: 64 result slots + 4 box work areas
-        o = a > bq ? a : bq;
-        L.nreal = (o + 3) & ~3;
-        int io = 0;
-        auto Iq = [&](int n) { int x = io; io += n; return x; };
-        L.cand = Iq(ANC_MAX); L.cpair = Iq(maxcon); L.cefc = Iq(maxcon); L.rmeta = Iq(maxefc); L.rowI = Iq(maxefc); L.gI = Iq(maxefc / 3 + 8); L.misc = Iq(12); L.nprof = Iq(16);
-        L.nint = (io + 3) & ~3;
-        L.maxcon = maxcon;
-        L.maxefc = maxefc;
-        L.expcon = this->maxcon;
-        L.gefc = this->maxefc;
-        L.ggrp = this->maxefc / 3 + 8;
-        size_t rs = f64 ? 8 : 4;
-        L.bytes_per_env = (int)((L.nreal * rs + (size_t)L.nint * 4 + 15) & ~(size_t)15);
-        if (getenv("AVSIM_DEBUG_LAYOUT"))
+        L = avs::make_layout_of(maxcon, maxefc, this->maxcon, this->maxefc, nq, nv, nu, nb, ng, msize, ntree, f64 ? 8 : 4);
+        if (getenv("AVSIM_DEBUG_LAYOUT")) {
+            const int pb = L.rowS + RS_S * maxefc > L.scr + NARROW_SCR_W ? L.rowS + RS_S * maxefc : L.scr + NARROW_SCR_W;
             fprintf(stderr, "avsim layout: %d reals + %d ints = %d B per env (U at %d: phase A %d, phase B %d words); tables %zu B\n", L.nreal, L.nint,
-                    L.bytes_per_env, L.U, a - L.U, bq - L.U, (size_t)moff.nreal * rs + (size_t)moff.nint * 4);
+                    L.bytes_per_env, L.U, 38 * nb, pb - L.U, (size_t)moff.nreal * (f64 ? 8 : 4) + (size_t)moff.nint * 4);
+        }
     }
 
     int dims[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -3913,14 +3858,8 @@ struct PhysHost {
             static const int mx[5] = {4, 4, 5, 3, 4};
             max_reward = mx[b.scalar("task_id")];
             int ms = f64 ? md.msize : mf.msize;
-            // row / contact capacities per task: every box of a compound object resting on the condim-6 table
-            // contributes 4 contacts x 6 rows (SewNeedle 24 contacts / 128 rows, TubeTransfer 40 / 248 at rest)
-            // Two tiers where the smaller first one lets more envs share a CU (SewNeedle: 7 instead of 6 -- the scripted grasp of
-            // BASELINE config 3 reaches 194 rows / 35 contacts in most envs at once, so the first tier must hold that: with 176 rows,
-            // 8 per CU, nearly every env needed the full record during the grasp; TubeTransfer): the second pass costs a launch and,
-            // when its list is not empty, the latency of one env-step, so the other tasks keep one tier.
-            static const int cap_efc[5] = {176, 176, 336, 480, 176}, cap_con[5] = {48, 48, 72, 96, 48};
-            static const int cap_efc1[5] = {176, 176, 224, 288, 176}, cap_con1[5] = {48, 48, 56, 64, 48};
+            // row / contact capacities per task, in two tiers (avsim_phys_layout.h)
+            const int *cap_efc = CAP_EFC, *cap_con = CAP_CON, *cap_efc1 = CAP_EFC1, *cap_con1 = CAP_CON1;
             maxefc = cap_efc[b.scalar("task_id")];
             maxcon = cap_con[b.scalar("task_id")];
             maxefc1 = cap_efc1[b.scalar("task_id")];
@@ -3965,6 +3904,7 @@ struct PhysHost {
         if (n == "export_contacts") { export_contacts = v != 0; return true; }
         if (n == "num_joints") { if (v != 14 && v != 21) return false; mf.nj = md.nj = (int)v; return true; }
         if (n == "order_envs") { order_envs = v != 0; return true; }
+        if (n == "phys_specialised") { if (v != 0 && v != 1 && v != 2) return false; specialised = (int)v; return true; }
         if (n == "pair_waves") { pair_waves = v != 0; return true; }
         if (n == "qcqp_tridiag") { mf.qcqp_tridiag = md.qcqp_tridiag = v < 0 ? 0 : (v > 2 ? 2 : (int)v); return true; }
         if (n == "noslip_per_tree") { mf.noslip_per_tree = md.noslip_per_tree = v != 0; return true; }
@@ -4008,6 +3948,15 @@ struct PhysHost {
         const size_t tables = (size_t)moff.nreal * sizeof(real) + (size_t)moff.nint * 4;
         auto kern1 = k_phys<real, G, MAXW, false>;      // one pass
         auto kern2 = k_phys<real, G, MAXW, true>;       // the two passes of the two-tier capacities
+        // The kernel compiled for this very model (option "phys_specialised"): only a one-pass f32 launch whose Layout, MOff and dims equal
+        // the spec's takes it; every other launch -- another model, capacities changed by option, f64, two tiers -- the generic one
+        const char* spec_name = nullptr;
+        const void* kspec = sizeof(real) == 4 && MAXW == AVSIM_PHYS_MAXW ? spec_kernel(&spec_name) : nullptr;
+        if (refuses(err)) return -1;      // (before anything is enqueued; the API's entry points ask the same question before THEIR first enqueue)
+        if (spec_note != (kspec ? 1 : 2) && getenv("AVSIM_DEBUG_LAYOUT")) {      // which kernel the handle's launches take, once per change
+            fprintf(stderr, "avsim: k_phys %s%s\n", kspec ? "specialised for " : "generic", kspec ? spec_name : "");
+            spec_note = kspec ? 1 : 2;
+        }
         if (!attr_done) {    // once per handle (= per device): a second handle on another GPU of the same process sets its own
             hipError_t e = hipFuncSetAttribute((const void*)kern1, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (e == hipSuccess) e = hipFuncSetAttribute((const void*)kern2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -4021,6 +3970,14 @@ struct PhysHost {
                 (void)hipMemset(d_head, 0, 2 * sizeof(int));
             }
             attr_done = 1;
+        }
+        if (kspec) {      // same signature as the generic one-pass kernel: launched through its own unit's host stub
+            if (!(attr_done & 2)) {
+                const hipError_t e = hipFuncSetAttribute(kspec, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                if (e != hipSuccess) { err = std::string("hipFuncSetAttribute(") + spec_name + "): " + hipGetErrorString(e); return -3; }
+                attr_done |= 2;
+            }
+            kern1 = (decltype(kern1))kspec;
         }
         const bool two = two_pass();
         int wpb = waves_per_block<real, MAXW>(lay);
@@ -4088,7 +4045,7 @@ struct PhysHost {
         return 0;
     }
 
-#ifndef AVSIM_TU_F64
+#if !defined(AVSIM_TU_F64) && !defined(AVSIM_NO_F32_LAUNCH)      // (a unit that defines the latter does not instantiate the generic f32 kernels)
     int launch(hipStream_t st, int N_, int nsub, const float* action, int nj, void* qpos, void* qvel, void* ctrl, void* warm, int* latch,
                double* agent, int32_t* reward, uint8_t* success, std::string& err) {
         (void)N_; (void)nj;
