@@ -18,8 +18,8 @@ def _stale(target, sources):
 
 def build_hip(force=False, verbose=False):
     """hipcc --offload-arch=gfx950: avsim_api.hip (C-ABI, f32 product kernels, IK, render), avsim_phys_spec.hip (the f32 physics
-    kernel specialised per model) and avsim_phys_f64.hip (the f64 parity kernel, -ffp-contract=off so that it rounds like the oracle)
-    compiled side by side, linked into libavsim.so."""
+    kernel specialised per model), avsim_phys_f64.hip (the f64 parity kernel, -ffp-contract=off so that it rounds like the oracle) and
+    avsim_imgaug.hip (the image augmentation, which rounds like its numpy specification) compiled side by side, linked into libavsim.so."""
     srcs = [os.path.join(SRC, f) for f in sorted(os.listdir(SRC)) if not f.endswith(".o") and not f.startswith(".")] + [os.path.join(ROOT, "include", "avsim.h"), os.path.abspath(__file__)]       # (this file holds the flags: a library built with other flags is stale too)
     if not force and not _stale(LIB, srcs):
         return LIB
@@ -57,6 +57,11 @@ def _build_hip_locked(verbose):
         # device's contact counts differ from the FULL-hull oracle's in 1.8 % of the env-steps where tests/test_gpu_fidelity.py asserts <= 1 % (0.29 % on the unfused
         # build's episodes): not adopted (profiles/r06_experiments.txt 5)
         ("avsim_phys_f64", ["-O3", "-ffp-contract=off", "-mllvm", "-amdgpu-sched-strategy=max-ilp"] + os.environ.get("AVSIM_EXTRA_FLAGS_F64", "").split()),
+        # the image augmentation equals its numpy specification (av_aloha_amd/imgaug.py) bit for bit, which F32_FLAGS cannot give: -ffp-contract=off keeps
+        # a * f + b * g two multiplications and an addition; -fhip-fp32-correctly-rounded-divide-sqrt (the compiler's default, named so that it stays) makes
+        # x / y the IEEE sequence v_div_scale / v_rcp / v_fma x 4 / v_div_fmas / v_div_fixup; -fno-gpu-flush-denormals-to-zero (also the default for
+        # gfx950) keeps f32 denormals: the kernels' descriptors carry float_denorm_mode_32 = 3 and the division needs no mode switch
+        ("avsim_imgaug", ["-O3", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-gpu-flush-denormals-to-zero"] + os.environ.get("AVSIM_EXTRA_FLAGS_IMGAUG", "").split()),
     ]
     procs = []
     for name, extra in units:

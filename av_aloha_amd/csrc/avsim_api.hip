@@ -15,6 +15,7 @@
 #include "../../include/avsim.h"
 #include "avsim_compose.hip.h"
 #include "avsim_imgprep.hip.h"
+#include "avsim_imgaug.hip.h"
 #include "avsim_episode.hip.h"
 #include "avsim_ik.hip.h"
 #include "avsim_jpeg.hip.h"
@@ -82,6 +83,9 @@ struct avsim {
     JpegDecHost jpegdec; // and those streams back into images: Huffman lookup tables, the coefficients' staging area
     ComposeHost compose; // views resampled into a canvas, labels (avsim_compose.hip.h): coefficient tables per size pair, the validated placements
     ImgPrepHost imgprep; // image statistics, crops through tables (avsim_imgprep.hip.h): the pinned staging of a call's host arrays
+    unsigned long long* aug_sum = nullptr;   // avsim_image_jitter: the gray sums behind contrast, one slot per output (csrc/avsim_imgaug.hip); grows on demand
+    size_t aug_sum_cap = 0;
+    int aug_sum_n = 0;                       // the outputs of the last call
     bool jpegdec_events = false;   // option "jpeg_decode_events": avsim_jpeg_decode records ev[12..15] around its three kernels
     // the state's version: bumped by everything that writes qpos (reset, the steps, set_state); the image calls skip their pose pass and the shadow
     // map when they already hold this version's (a facade that fetches its cameras one call at a time repeats neither)
@@ -478,6 +482,7 @@ void avsim_destroy(avsim_t* h) {
     h->jpegdec.destroy();
     h->compose.destroy();
     h->imgprep.destroy();
+    if (h->aug_sum) (void)hipFree(h->aug_sum);
     for (void* p : {h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, (void*)h->d_latch})
         if (p) (void)hipFree(p);
     for (void* p : h->d_io)
@@ -1165,6 +1170,60 @@ int avsim_image_prep(avsim_t* h, const void* img, int fmt, int nsrc, int height,
     if (h->imgprep.launch(h->stream, dimg, fmt, height, width, (const float*)dlut, lut_index, box, nout, src_index, out_h, out_w, (float*)dout, h->err)) return AVSIM_EHIP;
     if ((rc = h->out_end(10, out, obytes))) return rc;
     return h->finish();
+}
+
+// Colour and sharpness augmentation (av_aloha_amd/imgaug.py is the specification; the kernels: csrc/avsim_imgaug.hip, a unit of its own flags).
+// The host arrays go through the staging slots avsim_image_prep uses.
+int avsim_image_jitter(avsim_t* h, const void* img, int nsrc, int height, int width, const int32_t* box_mask, const float* factor,
+                       const int32_t* src_index, int nout, const float* mean_std, int out_h, int out_w, float* out) {
+    if (!h) return AVSIM_EINVAL;
+    if (!img || !box_mask || !factor || !out || nsrc < 1 || nout < 1) { h->set_error("avsim_image_jitter: bad arguments"); return AVSIM_EINVAL; }
+    if (height < 1 || width < 1 || height > 65535 || width > 65535 || out_h < 1 || out_w < 1 || out_h > 65535 || out_w > 65535) {
+        h->set_error("avsim_image_jitter: image sizes %d x %d, %d x %d outside 1..65535", height, width, out_h, out_w);
+        return AVSIM_EINVAL;
+    }
+    {   // the host arrays are checked before anything moves or is launched
+        std::string why;
+        if (imgaug_validate(nsrc, height, width, box_mask, factor, src_index, nout, mean_std, out_h, out_w, why)) { h->set_error("%s", why.c_str()); return AVSIM_EINVAL; }
+    }
+    AVS_ON_DEVICE(h);
+    int rc;
+    const void* dimg = nullptr;
+    void* dout = nullptr;
+    const size_t obytes = sizeof(float) * 3 * (size_t)nout * out_h * out_w;
+    if ((rc = h->in(8, img, (size_t)nsrc * height * width * 3, &dimg))) return rc;
+    if ((rc = h->out_begin(10, out, obytes, &dout))) return rc;
+    if (h->aug_sum_cap < (size_t)nout) {
+        if (h->aug_sum) (void)hipFree(h->aug_sum);
+        h->aug_sum = nullptr;
+        h->aug_sum_cap = 0;
+        const size_t cap = ((size_t)nout + 511) & ~(size_t)511;
+        HIPCHK(h, hipMalloc((void**)&h->aug_sum, sizeof(unsigned long long) * cap));
+        h->aug_sum_cap = cap;
+    }
+    const size_t sbytes = imgaug_stage_bytes(nout);
+    ImgPrepHost::Slot* s = h->imgprep.acquire(sbytes, h->err);
+    if (!s) return AVSIM_EHIP;
+    const int ncon = imgaug_pack(s->pin, box_mask, factor, src_index, nout, mean_std);
+    HIPCHK(h, hipMemcpyAsync(s->dev, s->pin, sbytes, hipMemcpyHostToDevice, h->stream));
+    const int lrc = imgaug_launch(h->stream, dimg, height, width, s->dev, nout, ncon, mean_std != nullptr, out_h, out_w, h->aug_sum, (float*)dout, h->err);
+    // (the event also after a failed launch: the copy above may be in flight)
+    const hipError_t e = hipEventRecord(s->done, h->stream);
+    s->busy = e == hipSuccess;
+    if (lrc) return AVSIM_EHIP;
+    HIPCHK(h, e);
+    h->aug_sum_n = nout;
+    if ((rc = h->out_end(10, out, obytes))) return rc;
+    return h->finish();
+}
+
+int avsim_image_jitter_sums(avsim_t* h, uint64_t* sums, int nout) {
+    if (!h) return AVSIM_EINVAL;
+    if (!sums || nout < 1 || nout > h->aug_sum_n) { h->set_error("avsim_image_jitter_sums: %d sums asked for, the last avsim_image_jitter made %d outputs", nout, h->aug_sum_n); return AVSIM_EINVAL; }
+    AVS_ON_DEVICE(h);
+    HIPCHK(h, hipMemcpyAsync(sums, h->aug_sum, sizeof(uint64_t) * (size_t)nout, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return AVSIM_OK;
 }
 
 // The visual scene of avsim_render_rgb: the mesh library (models/visual_meshes.avv, compiler/vismesh.py) against the instances the

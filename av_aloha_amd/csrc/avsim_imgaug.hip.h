@@ -1,0 +1,93 @@
+// avsim_imgaug.hip.h -- colour and sharpness augmentation of training images on the device (avsim_image_jitter): what
+// avsim_api.hip needs of the unit csrc/avsim_imgaug.hip -- the record of an output, the checks on the caller's host arrays and the launcher.
+//
+// av_aloha_amd/imgaug.py is the specification, and the device equals it bit for bit.  That needs every float32 operation rounded on its own
+// and correctly -- no fused multiply-add, IEEE division, denormals kept --, which avsim_api.hip's flags do not give (build.py, F32_FLAGS):
+// the kernels live in a unit of their own, built as avsim_phys_f64.hip is, and are reached through imgaug_launch (the build is -fno-gpu-rdc).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <string>
+
+namespace avs {
+
+constexpr int IAG_THREADS = 256;
+constexpr int IAG_TX = 64, IAG_TY = 16;      // k_aug_apply's tile of the output crop: 16 lanes of four pixels across, 16 rows
+constexpr int IAG_BRIGHTNESS = 1, IAG_CONTRAST = 2, IAG_SATURATION = 4, IAG_HUE = 8, IAG_SHARPNESS = 16;
+
+// One output image as the kernels read it (validated by the host): the source image, the box's corner, flip | mask << 1, the five factors
+struct AugItem {
+    int src, x0, y0, fm;
+    float f[5];
+    int pad[3];
+};
+static_assert(sizeof(AugItem) == 48, "AugItem is twelve words");
+
+// the bytes of a call's staging: the items, the outputs that have the contrast bit, mean and std
+inline size_t imgaug_stage_bytes(int nout) { return (size_t)nout * (sizeof(AugItem) + sizeof(int)) + 8 * sizeof(float); }
+
+// the conditions of the header on the host arrays; -1 and err says which
+inline int imgaug_validate(int nsrc, int SH, int SW, const int32_t* box_mask, const float* factor, const int32_t* src_index, int nout,
+                           const float* mean_std, int oh, int ow, std::string& err) {
+    static const char* const opname[5] = {"brightness", "contrast", "saturation", "hue", "sharpness"};
+    char buf[240];
+    if (mean_std)
+        for (int c = 0; c < 3; c++) {
+            if (!std::isfinite(mean_std[3 + c]) || mean_std[3 + c] == 0.0f) { err = "avsim_image_jitter: a std that is 0 or not finite"; return -1; }
+        }
+    for (int i = 0; i < nout; i++) {
+        const int32_t* b = box_mask + 4 * (size_t)i;
+        const long long x0 = b[0], y0 = b[1], fl = b[2], mask = b[3], s = src_index ? src_index[i] : i;
+        const char* what = nullptr;
+        if (s < 0 || s >= nsrc) what = "source image out of range";
+        else if (fl != 0 && fl != 1) what = "flip is 0 or 1";
+        else if (mask < 0 || mask > 31) what = "mask outside 0..31";
+        else if (x0 < 0 || y0 < 0 || x0 + ow > SW || y0 + oh > SH) what = "the crop does not lie inside the source";
+        if (what) {
+            snprintf(buf, sizeof buf, "avsim_image_jitter: output %d (source %lld, box %lld %lld %lld, mask %lld): %s", i, s, x0, y0, fl, mask, what);
+            err = buf;
+            return -1;
+        }
+        for (int k = 0; k < 5; k++) {
+            if (!((mask >> k) & 1)) continue;      // factors of unset bits are not looked at
+            const float f = factor[5 * (size_t)i + k];
+            const float lo = k == 3 ? -0.5f : 0.0f, hi = k == 3 ? 0.5f : 16.0f;
+            if (!std::isfinite(f) || f < lo || f > hi) {
+                snprintf(buf, sizeof buf, "avsim_image_jitter: output %d: the %s factor %g is not a finite value in [%g, %g]", i, opname[k], (double)f, (double)lo, (double)hi);
+                err = buf;
+                return -1;
+            }
+        }
+    }
+    return 0;
+}
+
+// packs a validated call into `pin` (imgaug_stage_bytes(nout) bytes) -> the number of outputs that have the contrast bit
+inline int imgaug_pack(void* pin, const int32_t* box_mask, const float* factor, const int32_t* src_index, int nout, const float* mean_std) {
+    AugItem* it = (AugItem*)pin;
+    int* cidx = (int*)(it + nout);
+    float* ms = (float*)(cidx + nout);
+    int ncon = 0;
+    for (int i = 0; i < nout; i++) {
+        const int32_t* b = box_mask + 4 * (size_t)i;
+        AugItem a{};
+        a.src = src_index ? src_index[i] : i;
+        a.x0 = b[0]; a.y0 = b[1]; a.fm = b[2] | (b[3] << 1);
+        for (int k = 0; k < 5; k++) a.f[k] = ((b[3] >> k) & 1) ? factor[5 * (size_t)i + k] : 0.0f;
+        it[i] = a;
+        if (b[3] & IAG_CONTRAST) cidx[ncon++] = i;
+    }
+    for (int k = 0; k < 6; k++) ms[k] = mean_std ? mean_std[k] : (k < 3 ? 0.0f : 1.0f);
+    ms[6] = ms[7] = 0.0f;
+    return ncon;
+}
+
+// csrc/avsim_imgaug.hip.  stage: the device copy of what imgaug_pack wrote; gsum: nout 64-bit slots of the library's; src, out: device
+// pointers.  Zeroes gsum, runs k_aug_gray_sum for the ncon outputs that have the contrast bit and k_aug_apply for all.  -3: HIP
+int imgaug_launch(hipStream_t stream, const void* src, int SH, int SW, const void* stage, int nout, int ncon, bool normalise, int oh, int ow,
+                  unsigned long long* gsum, float* out, std::string& err);
+
+}  // namespace avs

@@ -277,15 +277,13 @@ struct ImgPrepHost {
         return 0;
     }
 
-    // src, lut, out: device pointers; the three arrays: host, validated.  -3: HIP
-    int launch(hipStream_t stream, const void* src, int sf, int SH, int SW, const float* lut, const int32_t* lut_index, const int32_t* box, int nout,
-               const int32_t* src_index, int oh, int ow, float* out, std::string& err) {
+    // the next slot, idle (its last call's event waited for) and holding at least `bytes` of pinned and of device memory; nullptr: HIP, err says what
+    Slot* acquire(size_t bytes, std::string& err) {
         Slot& s = slot[next];
         next = (next + 1) % NSLOT;
         hipError_t e = hipSuccess;
         if (s.busy) e = hipEventSynchronize(s.done);      // (the call four calls back: long done in a training loop)
         s.busy = false;
-        const size_t bytes = (size_t)nout * sizeof(PrepItem);
         if (e == hipSuccess && s.cap < bytes) {
             if (s.pin) (void)hipHostFree(s.pin);
             if (s.dev) (void)hipFree(s.dev);
@@ -297,7 +295,18 @@ struct ImgPrepHost {
             if (e == hipSuccess) s.cap = cap;
         }
         if (e == hipSuccess && !s.done) e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming);
-        if (e != hipSuccess) { err = std::string("image prep staging: ") + hipGetErrorString(e); return -3; }
+        if (e != hipSuccess) { err = std::string("image prep staging: ") + hipGetErrorString(e); return nullptr; }
+        return &s;
+    }
+
+    // src, lut, out: device pointers; the three arrays: host, validated.  -3: HIP
+    int launch(hipStream_t stream, const void* src, int sf, int SH, int SW, const float* lut, const int32_t* lut_index, const int32_t* box, int nout,
+               const int32_t* src_index, int oh, int ow, float* out, std::string& err) {
+        const size_t bytes = (size_t)nout * sizeof(PrepItem);
+        Slot* sp = acquire(bytes, err);
+        if (!sp) return -3;
+        Slot& s = *sp;
+        hipError_t e = hipSuccess;
         PrepItem* it = (PrepItem*)s.pin;
         for (int i = 0; i < nout; i++)
             it[i] = PrepItem{src_index ? src_index[i] : i, box[3 * (size_t)i], box[3 * (size_t)i + 1], box[3 * (size_t)i + 2] | ((lut_index ? lut_index[i] : 0) << 1)};

@@ -6,7 +6,7 @@ import json
 
 import numpy as np
 
-from . import _ffi, imgprep, jpeg
+from . import _ffi, imgaug, imgprep, jpeg
 from .harness import load_episode
 
 
@@ -223,11 +223,16 @@ class TrainingBatches:
                                   episode's last (imgprep.chunk_index, LeRobot's delta_timestamps), normalised alike
       "action_is_pad"             bool [B, chunk_size]: the clamped ones
       "episode_index", "frame_index"  int64 [B]
+    augment: None (the default): nothing below applies.  True, or a dict laid over imgaug.DEFAULT_CFG: every camera's images go through
+    avsim_image_jitter instead -- LeRobot's image_transforms (brightness, contrast, saturation, hue, sharpness; a random subset per image,
+    drawn by imgaug.augment_plan from a stream of its own) applied to the whole decoded frame, then the same crop and normalisation; the bits
+    of imgaug.jitter_reference with plan(epoch)'s boxes and augment_plan(epoch)'s parameters.
     stats: CompressedDataset.stats()'s (or load_stats'); a dimension whose std is 0 normalises to nan / inf, as the formula says.
     Like batch(), an iteration step does not wait for the device."""
 
-    def __init__(self, ds, batch_size, chunk_size, stats, crop=None, crop_mode="random", normalise=True, seed=0, drop_last=True):
+    def __init__(self, ds, batch_size, chunk_size, stats, crop=None, crop_mode="random", normalise=True, seed=0, drop_last=True, augment=None):
         torch = ds.torch
+        self.augment = None if augment is None or augment is False else imgaug.make_cfg(augment)
         self.ds, self.batch_size, self.chunk_size = ds, int(batch_size), int(chunk_size)
         self.crop, self.crop_mode, self.normalise, self.seed, self.drop_last = crop, crop_mode, bool(normalise), int(seed), bool(drop_last)
         if self.batch_size < 1 or self.chunk_size < 1:
@@ -240,6 +245,11 @@ class TrainingBatches:
             st = stats[f"observation.images.{c}"]
             lut = imgprep.normalise_lut(st["mean"], st["std"]) if self.normalise else imgprep.identity_lut()
             self.lut[c] = torch.from_numpy(np.ascontiguousarray(lut, dtype=np.float32).reshape(1, 3, 256)).to(ds.device)
+        self.mean_std = {}
+        if self.augment is not None and self.normalise:
+            for c in ds.cameras:
+                st = stats[f"observation.images.{c}"]
+                self.mean_std[c] = imgaug.mean_std(st["mean"], st["std"])
         for key in ("observation.state", "action"):
             self.norm[key] = (torch.from_numpy(np.asarray(stats[key]["mean"], dtype=np.float32)).to(ds.device),
                               torch.from_numpy(np.asarray(stats[key]["std"], dtype=np.float32)).to(ds.device))
@@ -250,8 +260,20 @@ class TrainingBatches:
     def plan(self, epoch):
         return epoch_plan(self.ds.n, self.batch_size, self.sizes, self.crop, self.crop_mode, self.seed, epoch, self.drop_last)
 
+    def augment_plan(self, epoch):
+        """The augmentation of one epoch, batch after batch of plan(epoch): [{camera: (mask int32 [B], factor float32 [B, 5])}], drawn by
+        imgaug.augment_plan(B, cfg, seed, epoch, batch, the camera's index in the data set's cameras).  None without augment."""
+        if self.augment is None:
+            return None
+        return [{c: imgaug.augment_plan(len(part), self.augment, self.seed, epoch, b, k) for k, c in enumerate(self.ds.cameras)}
+                for b, (part, _) in enumerate(self.plan(epoch))]
+
     def __iter__(self):
         epoch, self.epoch = self.epoch, self.epoch + 1
+        if self.augment is not None:
+            for (part, boxes), aug in zip(self.plan(epoch), self.augment_plan(epoch)):
+                yield self.make(part, boxes, aug)
+            return
         for part, boxes in self.plan(epoch):
             yield self.make(part, boxes)
 
@@ -261,8 +283,9 @@ class TrainingBatches:
         mean, std = self.norm[key]
         return (x - mean) / std
 
-    def make(self, part, boxes):
-        """The batch of the frames `part` with the crop boxes {camera: int32 [B, 3]}."""
+    def make(self, part, boxes, aug=None):
+        """The batch of the frames `part` with the crop boxes {camera: int32 [B, 3]}; aug: {camera: (mask, factor)} (augment_plan's), the
+        images then go through avsim_image_jitter."""
         ds, torch = self.ds, self.ds.torch
         raw = ds.batch(part, fmt="gym")
         B = len(part)
@@ -277,6 +300,16 @@ class TrainingBatches:
             h, w = (H, W) if self.crop is None else (int(self.crop[0]), int(self.crop[1]))
             box = np.ascontiguousarray(boxes[c], dtype=np.int32).reshape(B, 3)
             img = torch.empty((B, 3, h, w), dtype=torch.float32, device=ds.device)
+            if aug is not None:
+                bm, fac = imgaug.pack_params(box, *aug[c])
+                ms = self.mean_std.get(c)
+                rc = ds.h.L.avsim_image_jitter(ds.h.h, raw[f"observation.images.{c}"].data_ptr(), B, H, W, bm.ctypes.data, fac.ctypes.data, None, B,
+                                               None if ms is None else ms.ctypes.data, h, w, img.data_ptr())
+                if rc == -1:
+                    raise ValueError(ds.h.L.avsim_last_error(ds.h.h).decode())
+                ds.h.check(rc)
+                out[f"observation.images.{c}"] = img
+                continue
             rc = ds.h.L.avsim_image_prep(ds.h.h, raw[f"observation.images.{c}"].data_ptr(), 0, B, H, W, self.lut[c].data_ptr(), 1, None, box.ctypes.data,
                                          B, None, h, w, img.data_ptr())
             if rc == -1:          # AVSIM_EINVAL: nothing was launched

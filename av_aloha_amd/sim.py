@@ -340,6 +340,35 @@ class BatchedSim:
                                                       len(b), _ffi.ptr(si), oh, ow, out.ctypes.data))
         return out
 
+    def jitter_images(self, img, params, out_hw, mean=None, std=None, src_index=None, out=None):
+        """float32 [nout, 3, oh, ow]: brightness, contrast, saturation, hue and sharpness jitter of img, cropped, mirrored and normalised in one
+        pass (avsim_image_jitter): the bits of av_aloha_amd.imgaug.jitter_reference.  img: u8 [n, H, W, 3]; params: imgaug.PARAMS_DTYPE rows or
+        the pair (int32 [nout, 4] = (x0, y0, flip, mask), float32 [nout, 5] = the factors); mean / std: three values each, or None: the output
+        stays in [0, 1]; src_index: the source image of every output (None: image i).  ValueError for what the library refuses."""
+        from . import imgaug
+        img = np.ascontiguousarray(img)
+        if not (img.dtype == np.uint8 and img.ndim == 4 and img.shape[3] == 3):
+            raise ValueError("jitter_images: the images are a u8 [n, H, W, 3] array")
+        n, H, W = img.shape[:3]
+        bm, fac = imgaug.split_params(params)
+        si = None if src_index is None else np.ascontiguousarray(src_index, dtype=np.int32).reshape(len(bm))
+        ms = imgaug.mean_std(mean, std)
+        oh, ow = int(out_hw[0]), int(out_hw[1])
+        if out is None:
+            out = np.empty((len(bm), 3, max(oh, 0), max(ow, 0)), dtype=np.float32)
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (len(bm), 3, oh, ow)):
+            raise ValueError("jitter_images: out is a C-contiguous float32 [nout, 3, oh, ow] array")
+        self._compose_check(self.h.L.avsim_image_jitter(self.h.h, img.ctypes.data, n, H, W, bm.ctypes.data, fac.ctypes.data, _ffi.ptr(si), len(bm), _ffi.ptr(ms), oh, ow,
+                                                        out.ctypes.data))
+        return out
+
+    def jitter_gray_sums(self, nout):
+        """uint64 [nout]: the integer sums behind the contrast means of the last jitter_images call (avsim_image_jitter_sums;
+        imgaug.gray_sum_reference's), meaningful for the outputs that had the contrast bit.  For tests."""
+        sums = np.zeros(int(nout), dtype=np.uint64)
+        self._compose_check(self.h.L.avsim_image_jitter_sums(self.h.h, sums.ctypes.data, int(nout)))
+        return sums
+
     def reward_from_pairs(self, geom_pairs, latch=None):
         """The task's get_reward (env.py:425-863) on explicit contact lists: geom_pairs int [nsets, cap, 2] (collision
         geom ids, negative = empty slot); latch int32 [nsets] is updated in place.  Returns int32 [nsets]."""

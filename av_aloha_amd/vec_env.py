@@ -425,6 +425,30 @@ class VecEnv:
                                                     len(b), _ffi.ptr(si), oh, ow, out.data_ptr()))
         return out
 
+    def jitter_images(self, img, params, out_hw, mean=None, std=None, src_index=None, out=None):
+        """Brightness, contrast, saturation, hue and sharpness jitter of img, cropped, mirrored and normalised in one pass (avsim_image_jitter;
+        av_aloha_amd.imgaug.jitter_reference's bits).  img: a uint8 [n, H, W, 3] tensor on the env's device -- an observation, a decode_jpeg
+        result --; params: HOST imgaug.PARAMS_DTYPE rows or the pair (int32 [nout, 4] = (x0, y0, flip, mask), float32 [nout, 5]); mean / std:
+        three HOST values each, or None: the output stays in [0, 1]; src_index: a HOST int array, the source image of every output (None: image
+        i).  All host arrays are checked (ValueError) and copied by the library before the call returns.  -> float32 [nout, 3, oh, ow] on the
+        device (out: the tensor to write).  Does not synchronise."""
+        from . import imgaug
+        torch = self.torch
+        self._bind_stream()
+        assert isinstance(img, torch.Tensor) and img.dtype == torch.uint8 and img.device == self.device and img.ndim == 4 and img.shape[3] == 3 \
+            and img.is_contiguous(), "jitter_images(img=...): a contiguous uint8 [n, H, W, 3] tensor on the env's device"
+        n, H, W = (int(v) for v in img.shape[:3])
+        bm, fac = imgaug.split_params(params)
+        si = None if src_index is None else np.ascontiguousarray(src_index, dtype=np.int32).reshape(len(bm))
+        ms = imgaug.mean_std(mean, std)
+        oh, ow = int(out_hw[0]), int(out_hw[1])
+        if out is None:
+            out = torch.empty((len(bm), 3, max(oh, 0), max(ow, 0)), dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.device == self.device and tuple(out.shape) == (len(bm), 3, oh, ow) and out.is_contiguous()
+        self._compose_check(self.L.avsim_image_jitter(self.h.h, img.data_ptr(), n, H, W, bm.ctypes.data, fac.ctypes.data, _ffi.ptr(si), len(bm), _ffi.ptr(ms), oh, ow,
+                                                      out.data_ptr()))
+        return out
+
     def check_render_overflow(self):
         """Overflow flags of the last colour render (bit 0 triangle records, bit 1 tile lists; 0 = complete images): warns when set.
         Synchronises, so it is read once at the end of an evaluation rather than per step."""

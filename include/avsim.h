@@ -308,6 +308,30 @@ int avsim_image_prep(avsim_t* h, const void* img, int fmt, int nsrc, int height,
                      const int32_t* box /* [nout][3] */, int nout, const int32_t* src_index, int out_h, int out_w,
                      float* out /* [nout][3][out_h][out_w] */);
 
+/* Colour and sharpness augmentation of training images on the device (csrc/avsim_imgaug.hip); av_aloha_amd/imgaug.py is the
+ * specification, and the call equals it bit for bit (-0 and +0 aside).
+ * avsim_image_jitter: output i is image src_index[i] (NULL: image i) of img with the operations of mask = box_mask[i][3] applied to the WHOLE
+ * image -- bit 0 brightness, 1 contrast, 2 saturation, 3 hue, 4 sharpness, in that order, with the factors factor[i] = (fb, fc, fs, fh, fsh),
+ * torchvision's adjust_* arithmetic for float images in float32, floats carried from one operation to the next --, then cropped and
+ * mirrored by (x0, y0, flip) = box_mask[i][0..2] as avsim_image_prep crops, then normalised per channel as (v - mean[c]) / std[c] with
+ * mean_std = (mean[3], std[3]); mean_std NULL: the values stay in [0, 1].  Contrast blends with the mean gray of the whole source image
+ * (after brightness), reduced in integers first; sharpness blends with a 3 x 3 blur whose border is the source image's, not the crop's.
+ * Only u8 [nsrc][H][W][3] images are read (the float CHW format stays with avsim_image_prep).  img and out follow the handle's I/O mode;
+ * box_mask, factor, src_index and mean_std are HOST arrays in both modes, checked before anything is launched and copied into the pinned
+ * staging avsim_image_prep uses before the call returns -- the caller may change or free them at once.  With AVSIM_IO_DEVICE a call does
+ * not synchronise the stream once a call of the same sizes has run.  AVSIM_EINVAL, with nothing launched and out untouched: an image or
+ * output size outside 1..65535, nsrc or nout < 1, a crop that does not lie inside the source, a flip other than 0 / 1, a mask outside 0..31, a
+ * src_index outside [0, nsrc), a factor of a set bit that is not finite, a brightness, contrast, saturation or sharpness factor of a set bit
+ * outside [0, 16], a hue factor of a set bit outside [-0.5, 0.5], a std that is 0 or not finite.  Factors of unset bits are not looked at.
+ * avsim_image_jitter_sums (for tests): sums[i] = the integer S behind output i's contrast mean in the last avsim_image_jitter call of this
+ * handle, m = float(double(S) / double(H W 2^20)), for the outputs that had the contrast bit (the other slots hold nothing meant); sums: a HOST
+ * array of nout <= that call's nout values in both modes.  Synchronises the stream. */
+int avsim_image_jitter(avsim_t* h, const void* img /* u8 [nsrc][H][W][3] */, int nsrc, int height, int width,
+                       const int32_t* box_mask /* [nout][4]: x0, y0, flip, mask */, const float* factor /* [nout][5] */,
+                       const int32_t* src_index /* or NULL */, int nout, const float* mean_std /* [2][3] or NULL: [0,1] output */,
+                       int out_h, int out_w, float* out /* [nout][3][out_h][out_w] */);
+int avsim_image_jitter_sums(avsim_t* h, uint64_t* sums /* [nout] */, int nout);
+
 /* Per-env episodes on the device (a vector env with gymnasium's NEXT_STEP autoreset; av_aloha_amd/vec_env.py).  Pointers follow the
  * handle's I/O mode, except box / share of the set-up (host pointers).  In device mode no step, reset, sample or render call
  * synchronises; avsim_episode_setup does (it reallocates the records: once per evaluation), and so do avsim_episode_log /
