@@ -82,10 +82,8 @@ struct avsim {
     JpegHost jpeg;       // JPEG streams of such images (avsim_jpeg.hip.h): tables per shape, the intervals' staging area
     JpegDecHost jpegdec; // and those streams back into images: Huffman lookup tables, the coefficients' staging area
     ComposeHost compose; // views resampled into a canvas, labels (avsim_compose.hip.h): coefficient tables per size pair, the validated placements
-    ImgPrepHost imgprep; // image statistics, crops through tables (avsim_imgprep.hip.h): the pinned staging of a call's host arrays
-    unsigned long long* aug_sum = nullptr;   // avsim_image_jitter: the gray sums behind contrast, one slot per output (csrc/avsim_imgaug.hip); grows on demand
-    size_t aug_sum_cap = 0;
-    int aug_sum_n = 0;                       // the outputs of the last call
+    StageRing stage;     // the pinned staging of a call's host arrays (avsim_stage.h): avsim_image_prep's and avsim_image_jitter's
+    ImgAugHost imgaug;   // colour and sharpness jitter (avsim_imgaug.hip.h): the gray sums behind contrast
     bool jpegdec_events = false;   // option "jpeg_decode_events": avsim_jpeg_decode records ev[12..15] around its three kernels
     // the state's version: bumped by everything that writes qpos (reset, the steps, set_state); the image calls skip their pose pass and the shadow
     // map when they already hold this version's (a facade that fetches its cameras one call at a time repeats neither)
@@ -481,8 +479,8 @@ void avsim_destroy(avsim_t* h) {
     h->jpeg.destroy();
     h->jpegdec.destroy();
     h->compose.destroy();
-    h->imgprep.destroy();
-    if (h->aug_sum) (void)hipFree(h->aug_sum);
+    h->stage.destroy();
+    h->imgaug.destroy();
     for (void* p : {h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, (void*)h->d_latch})
         if (p) (void)hipFree(p);
     for (void* p : h->d_io)
@@ -957,6 +955,35 @@ int avsim_render_rgb_f32(avsim_t* h, const int32_t* cam_ids, int ncam, int heigh
     return render_images(h, cam_ids, ncam, height, width, out, true, true);
 }
 
+// ---- the image calls: what they share.  The staging slots (d_io) they use, by what a slot carries -- names that hold within the image calls
+// only: the episode calls further down use 8..11 for their own outputs
+enum ImgSlot { IMG_IN = 8, IMG_INDEX = 9, IMG_RESULT = 10, IMG_LEN_OUT = 11, IMG_LEN_IN = 12, IMG_TILE = 13 };
+// bytes per pixel of format 0 (u8 HWC) / 1 (float32 CHW)
+static size_t img_bpp(int fmt) { return fmt ? 12 : 3; }
+// refuses a format other than 0 / 1 and a size outside 1..65535, of the call's image and of its second one where it has two (a call whose
+// image has one format only passes that format)
+static int img_args(avsim_t* h, const char* who, int fmt, int64_t ht, int64_t wd, int fmt2 = 0, int64_t ht2 = 1, int64_t wd2 = 1) {
+    if ((fmt != 0 && fmt != 1) || (fmt2 != 0 && fmt2 != 1)) { h->set_error("%s: a format is 0 (u8 HWC) or 1 (float32 CHW)", who); return AVSIM_EINVAL; }
+    const bool first = ht < 1 || wd < 1 || ht > 65535 || wd > 65535;
+    if (first || ht2 < 1 || wd2 < 1 || ht2 > 65535 || wd2 > 65535) {
+        h->set_error("%s: image size %lld x %lld outside 1..65535", who, (long long)(first ? ht : ht2), (long long)(first ? wd : wd2));
+        return AVSIM_EINVAL;
+    }
+    return AVSIM_OK;
+}
+// rows: the images (streams) the input holds -- nimg, but a host caller's index says how many
+static int index_rows(avsim_t* h, const char* who, const int32_t* index, int nimg, size_t* rows) {
+    *rows = (size_t)nimg;
+    if (h->io_device || !index) return AVSIM_OK;
+    int top = 0;
+    for (int i = 0; i < nimg; i++) {
+        if (index[i] < 0) { h->set_error("%s: negative index", who); return AVSIM_EINVAL; }
+        top = index[i] > top ? index[i] : top;
+    }
+    *rows = (size_t)top + 1;
+    return AVSIM_OK;
+}
+
 // JPEG streams of a batch of images (av_aloha_amd/jpeg.py is the specification; csrc/avsim_jpeg.hip.h)
 int64_t avsim_jpeg_bound(int height, int width) {
     if (height < 1 || width < 1 || height > 65535 || width > 65535) return AVSIM_EINVAL;
@@ -966,28 +993,22 @@ int avsim_jpeg_encode(avsim_t* h, const void* img, int fmt, const int32_t* index
                       int64_t stride, int32_t* out_len) {
     if (!h) return AVSIM_EINVAL;
     if (!img || !out || !out_len || nimg < 0 || stride < 0) { h->set_error("avsim_jpeg_encode: bad arguments"); return AVSIM_EINVAL; }
-    if (fmt != 0 && fmt != 1) { h->set_error("avsim_jpeg_encode: fmt is 0 (u8 HWC) or 1 (float32 CHW)"); return AVSIM_EINVAL; }
-    if (quality < 1 || quality > 100) { h->set_error("avsim_jpeg_encode: quality %d outside 1..100", quality); return AVSIM_EINVAL; }
-    if (height < 1 || width < 1 || height > 65535 || width > 65535) { h->set_error("avsim_jpeg_encode: image size %d x %d outside 1..65535", height, width); return AVSIM_EINVAL; }
-    if (nimg == 0) return AVSIM_OK;
-    AVS_ON_DEVICE(h);
     int rc;
+    if ((rc = img_args(h, "avsim_jpeg_encode", fmt, height, width))) return rc;
+    if (quality < 1 || quality > 100) { h->set_error("avsim_jpeg_encode: quality %d outside 1..100", quality); return AVSIM_EINVAL; }
+    if (nimg == 0) return AVSIM_OK;
+    size_t rows;
+    if ((rc = index_rows(h, "avsim_jpeg_encode", index, nimg, &rows))) return rc;
+    AVS_ON_DEVICE(h);
     const void *dimg = nullptr, *dindex = nullptr;
     void *dout = nullptr, *dlen = nullptr;
-    if (!h->io_device && index) {          // (a host caller's index says how many images `img` holds)
-        int top = 0;
-        for (int i = 0; i < nimg; i++) {
-            if (index[i] < 0) { h->set_error("avsim_jpeg_encode: negative index"); return AVSIM_EINVAL; }
-            top = index[i] > top ? index[i] : top;
-        }
-        if ((rc = h->in(8, img, (size_t)(top + 1) * height * width * (fmt ? 12 : 3), &dimg))) return rc;
-    } else if ((rc = h->in(8, img, (size_t)nimg * height * width * (fmt ? 12 : 3), &dimg))) return rc;
-    if (index && (rc = h->in(9, index, sizeof(int32_t) * (size_t)nimg, &dindex))) return rc;
-    if ((rc = h->out_begin(10, out, (size_t)nimg * stride, &dout))) return rc;
-    if ((rc = h->out_begin(11, out_len, sizeof(int32_t) * (size_t)nimg, &dlen))) return rc;
+    if ((rc = h->in(IMG_IN, img, rows * (size_t)height * width * img_bpp(fmt), &dimg))) return rc;
+    if (index && (rc = h->in(IMG_INDEX, index, sizeof(int32_t) * (size_t)nimg, &dindex))) return rc;
+    if ((rc = h->out_begin(IMG_RESULT, out, (size_t)nimg * stride, &dout))) return rc;
+    if ((rc = h->out_begin(IMG_LEN_OUT, out_len, sizeof(int32_t) * (size_t)nimg, &dlen))) return rc;
     if ((rc = h->jpeg.launch(h->stream, dimg, fmt, (const int*)dindex, nimg, height, width, quality, (uint8_t*)dout, stride, (int*)dlen, h->err))) return AVSIM_EHIP;
-    if ((rc = h->out_end(10, out, (size_t)nimg * stride))) return rc;
-    if ((rc = h->out_end(11, out_len, sizeof(int32_t) * (size_t)nimg))) return rc;
+    if ((rc = h->out_end(IMG_RESULT, out, (size_t)nimg * stride))) return rc;
+    if ((rc = h->out_end(IMG_LEN_OUT, out_len, sizeof(int32_t) * (size_t)nimg))) return rc;
     return h->finish();
 }
 
@@ -998,24 +1019,24 @@ int avsim_render_jpeg(avsim_t* h, const int32_t* cam_ids, int ncam, int height, 
     if (!h) return AVSIM_EINVAL;
     if (!cam_ids || !out || !out_len || ncam < 1 || stride < 0) { h->set_error("avsim_render_jpeg: bad arguments"); return AVSIM_EINVAL; }
     if (quality < 1 || quality > 100) { h->set_error("avsim_render_jpeg: quality %d outside 1..100", quality); return AVSIM_EINVAL; }
-    const int64_t iw = tile ? (int64_t)width * ncam : width;
-    if (height < 1 || width < 1 || height > 65535 || iw > 65535) { h->set_error("avsim_render_jpeg: image size %d x %lld outside 1..65535", height, (long long)iw); return AVSIM_EINVAL; }
+    const int64_t iw = tile ? (int64_t)width * ncam : width;      // (below 1 where width is: ncam >= 1)
+    int rc;
+    if ((rc = img_args(h, "avsim_render_jpeg", 0, height, iw))) return rc;
     if (!(h->vis.loaded && !h->render_proxies)) { h->set_error("avsim_render_jpeg draws the visual scene only (avsim_load_visual, render_proxies 0)"); return AVSIM_EINVAL; }
     if (tile && h->vis.cam_major) { h->set_error("avsim_render_jpeg: tile puts the views of an env side by side (render_cam_major 0)"); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
-    int rc;
     const int nstream = tile ? h->N : h->N * ncam;
     const size_t bytes = (size_t)3 * h->N * ncam * height * width;
     void *dimg = nullptr, *dtile = nullptr, *dout = nullptr, *dlen = nullptr;
     if ((rc = h->io_buf(7, bytes, &dimg))) return rc;
     if ((rc = render_to(h, cam_ids, ncam, height, width, dimg, true, false))) return rc;
     if (tile && ncam > 1) {
-        if ((rc = h->io_buf(13, bytes, &dtile))) return rc;
+        if ((rc = h->io_buf(IMG_TILE, bytes, &dtile))) return rc;
         if (jpeg_tile(h->stream, dimg, dtile, h->N, ncam, height, width, h->err)) return AVSIM_EHIP;
         dimg = dtile;
     }
-    if ((rc = h->out_begin(10, out, (size_t)nstream * stride, &dout))) return rc;
-    if ((rc = h->out_begin(11, out_len, sizeof(int32_t) * (size_t)nstream, &dlen))) return rc;
+    if ((rc = h->out_begin(IMG_RESULT, out, (size_t)nstream * stride, &dout))) return rc;
+    if ((rc = h->out_begin(IMG_LEN_OUT, out_len, sizeof(int32_t) * (size_t)nstream, &dlen))) return rc;
     if (h->jpeg.launch(h->stream, dimg, 0, nullptr, nstream, height, (int)iw, quality, (uint8_t*)dout, stride, (int*)dlen, h->err)) return AVSIM_EHIP;
     if (h->io_device) return AVSIM_OK;
     HIPCHK(h, hipMemcpyAsync(out_len, dlen, sizeof(int32_t) * (size_t)nstream, hipMemcpyDeviceToHost, h->stream));
@@ -1032,32 +1053,24 @@ int avsim_jpeg_decode(avsim_t* h, const uint8_t* in, int64_t stride, const int32
                       int fmt, int upsample, void* out, int32_t* status) {
     if (!h) return AVSIM_EINVAL;
     if (!in || !in_len || !out || !status || nimg < 0 || stride < 1) { h->set_error("avsim_jpeg_decode: bad arguments"); return AVSIM_EINVAL; }
-    if (fmt != 0 && fmt != 1) { h->set_error("avsim_jpeg_decode: fmt is 0 (u8 HWC) or 1 (float32 CHW)"); return AVSIM_EINVAL; }
-    if (upsample != 0 && upsample != 1) { h->set_error("avsim_jpeg_decode: upsample is 0 (replicate) or 1 (triangle)"); return AVSIM_EINVAL; }
-    if (height < 1 || width < 1 || height > 65535 || width > 65535) { h->set_error("avsim_jpeg_decode: image size %d x %d outside 1..65535", height, width); return AVSIM_EINVAL; }
-    if (nimg == 0) return AVSIM_OK;
-    AVS_ON_DEVICE(h);
     int rc;
-    size_t rows = (size_t)nimg;            // (a host caller's index says how many streams `in` holds)
-    if (!h->io_device && index) {
-        int top = 0;
-        for (int i = 0; i < nimg; i++) {
-            if (index[i] < 0) { h->set_error("avsim_jpeg_decode: negative index"); return AVSIM_EINVAL; }
-            top = index[i] > top ? index[i] : top;
-        }
-        rows = (size_t)top + 1;
-    }
+    if ((rc = img_args(h, "avsim_jpeg_decode", fmt, height, width))) return rc;
+    if (upsample != 0 && upsample != 1) { h->set_error("avsim_jpeg_decode: upsample is 0 (replicate) or 1 (triangle)"); return AVSIM_EINVAL; }
+    if (nimg == 0) return AVSIM_OK;
+    size_t rows;
+    if ((rc = index_rows(h, "avsim_jpeg_decode", index, nimg, &rows))) return rc;
+    AVS_ON_DEVICE(h);
     const void *din = nullptr, *dlen = nullptr, *dindex = nullptr;
     void *dout = nullptr, *dstatus = nullptr;
-    const size_t bytes = (size_t)nimg * height * width * (fmt ? 12 : 3);
-    if ((rc = h->in(8, in, rows * (size_t)stride, &din))) return rc;
-    if ((rc = h->in(12, in_len, sizeof(int32_t) * rows, &dlen))) return rc;
-    if (index && (rc = h->in(9, index, sizeof(int32_t) * (size_t)nimg, &dindex))) return rc;
-    if ((rc = h->out_begin(10, out, bytes, &dout))) return rc;
-    if ((rc = h->out_begin(11, status, sizeof(int32_t) * (size_t)nimg, &dstatus))) return rc;
+    const size_t bytes = (size_t)nimg * height * width * img_bpp(fmt);
+    if ((rc = h->in(IMG_IN, in, rows * (size_t)stride, &din))) return rc;
+    if ((rc = h->in(IMG_LEN_IN, in_len, sizeof(int32_t) * rows, &dlen))) return rc;
+    if (index && (rc = h->in(IMG_INDEX, index, sizeof(int32_t) * (size_t)nimg, &dindex))) return rc;
+    if ((rc = h->out_begin(IMG_RESULT, out, bytes, &dout))) return rc;
+    if ((rc = h->out_begin(IMG_LEN_OUT, status, sizeof(int32_t) * (size_t)nimg, &dstatus))) return rc;
     if ((rc = h->jpegdec.launch(h->stream, (const uint8_t*)din, stride, (const int*)dlen, (const int*)dindex, nimg, height, width, fmt, upsample, dout, (int*)dstatus, h->err, h->jpegdec_events ? h->ev + 12 : nullptr))) return AVSIM_EHIP;
-    if ((rc = h->out_end(10, out, bytes))) return rc;
-    if ((rc = h->out_end(11, status, sizeof(int32_t) * (size_t)nimg))) return rc;
+    if ((rc = h->out_end(IMG_RESULT, out, bytes))) return rc;
+    if ((rc = h->out_end(IMG_LEN_OUT, status, sizeof(int32_t) * (size_t)nimg))) return rc;
     return h->finish();
 }
 
@@ -1066,26 +1079,22 @@ int avsim_compose(avsim_t* h, const void* src, int src_fmt, int nsrc, int src_h,
                   const int32_t* places, int nplace, int clear, uint32_t clear_rgb) {
     if (!h) return AVSIM_EINVAL;
     if (!src || !canvas || nplace < 0 || (nplace > 0 && !places) || nsrc < 1 || nout < 1) { h->set_error("avsim_compose: bad arguments"); return AVSIM_EINVAL; }
-    if ((src_fmt != 0 && src_fmt != 1) || (canvas_fmt != 0 && canvas_fmt != 1)) { h->set_error("avsim_compose: a format is 0 (u8 HWC) or 1 (float32 CHW)"); return AVSIM_EINVAL; }
-    if (src_h < 1 || src_w < 1 || src_h > 65535 || src_w > 65535 || canvas_h < 1 || canvas_w < 1 || canvas_h > 65535 || canvas_w > 65535) {
-        h->set_error("avsim_compose: image sizes %d x %d, %d x %d outside 1..65535", src_h, src_w, canvas_h, canvas_w);
-        return AVSIM_EINVAL;
-    }
+    int rc;
+    if ((rc = img_args(h, "avsim_compose", src_fmt, src_h, src_w, canvas_fmt, canvas_h, canvas_w))) return rc;
     if (!h->io_device) {          // (the arguments are checked before a host caller's pixels move)
         std::string why;
         if (ComposeHost::validate(nsrc, src_h, src_w, nout, canvas_h, canvas_w, places, nplace, why)) { h->set_error("%s", why.c_str()); return AVSIM_EINVAL; }
     }
     AVS_ON_DEVICE(h);
-    int rc;
     const void* dsrc = nullptr;
     void* dcanvas = nullptr;
-    const size_t sbytes = (size_t)nsrc * src_h * src_w * (src_fmt ? 12 : 3), cbytes = (size_t)nout * canvas_h * canvas_w * (canvas_fmt ? 12 : 3);
-    if ((rc = h->in(8, src, sbytes, &dsrc))) return rc;
-    if ((rc = h->out_begin(10, canvas, cbytes, &dcanvas))) return rc;
+    const size_t sbytes = (size_t)nsrc * src_h * src_w * img_bpp(src_fmt), cbytes = (size_t)nout * canvas_h * canvas_w * img_bpp(canvas_fmt);
+    if ((rc = h->in(IMG_IN, src, sbytes, &dsrc))) return rc;
+    if ((rc = h->out_begin(IMG_RESULT, canvas, cbytes, &dcanvas))) return rc;
     if (!h->io_device && !clear) HIPCHK(h, hipMemcpyAsync(dcanvas, canvas, cbytes, hipMemcpyHostToDevice, h->stream));
     if ((rc = h->compose.launch(h->stream, dsrc, src_fmt, nsrc, src_h, src_w, dcanvas, canvas_fmt, nout, canvas_h, canvas_w, places, nplace, clear, clear_rgb, h->err)))
         return rc == -1 ? AVSIM_EINVAL : AVSIM_EHIP;
-    if ((rc = h->out_end(10, canvas, cbytes))) return rc;
+    if ((rc = h->out_end(IMG_RESULT, canvas, cbytes))) return rc;
     return h->finish();
 }
 
@@ -1093,20 +1102,19 @@ int avsim_compose_label(avsim_t* h, void* canvas, int canvas_fmt, int nout, int 
                         const int64_t* value, uint32_t rgb) {
     if (!h) return AVSIM_EINVAL;
     if (!canvas || nlabel < 0 || (nlabel > 0 && !where) || nout < 1) { h->set_error("avsim_compose_label: bad arguments"); return AVSIM_EINVAL; }
-    if (canvas_fmt != 0 && canvas_fmt != 1) { h->set_error("avsim_compose_label: canvas_fmt is 0 (u8 HWC) or 1 (float32 CHW)"); return AVSIM_EINVAL; }
-    if (canvas_h < 1 || canvas_w < 1 || canvas_h > 65535 || canvas_w > 65535) { h->set_error("avsim_compose_label: canvas size %d x %d outside 1..65535", canvas_h, canvas_w); return AVSIM_EINVAL; }
+    int rc;
+    if ((rc = img_args(h, "avsim_compose_label", canvas_fmt, canvas_h, canvas_w))) return rc;
     if (nlabel == 0) return AVSIM_OK;
     AVS_ON_DEVICE(h);
-    int rc;
     void* dcanvas = nullptr;
     const void* dvalue = nullptr;
-    const size_t cbytes = (size_t)nout * canvas_h * canvas_w * (canvas_fmt ? 12 : 3);
-    if ((rc = h->out_begin(10, canvas, cbytes, &dcanvas))) return rc;
+    const size_t cbytes = (size_t)nout * canvas_h * canvas_w * img_bpp(canvas_fmt);
+    if ((rc = h->out_begin(IMG_RESULT, canvas, cbytes, &dcanvas))) return rc;
     if (!h->io_device) HIPCHK(h, hipMemcpyAsync(dcanvas, canvas, cbytes, hipMemcpyHostToDevice, h->stream));
-    if (value && (rc = h->in(9, value, sizeof(int64_t) * (size_t)nlabel, &dvalue))) return rc;
+    if (value && (rc = h->in(IMG_INDEX, value, sizeof(int64_t) * (size_t)nlabel, &dvalue))) return rc;
     if ((rc = h->compose.label(h->stream, dcanvas, canvas_fmt, nout, canvas_h, canvas_w, where, nlabel, prefix, (const long long*)dvalue, rgb, h->err)))
         return rc == -1 ? AVSIM_EINVAL : AVSIM_EHIP;
-    if ((rc = h->out_end(10, canvas, cbytes))) return rc;
+    if ((rc = h->out_end(IMG_RESULT, canvas, cbytes))) return rc;
     return h->finish();
 }
 
@@ -1122,27 +1130,19 @@ void avsim_compose_font(uint8_t rows[128][7]) {
 int avsim_image_stats(avsim_t* h, const void* img, int fmt, const int32_t* index, int nimg, int height, int width, uint64_t* out) {
     if (!h) return AVSIM_EINVAL;
     if (!img || !out || nimg < 1) { h->set_error("avsim_image_stats: bad arguments"); return AVSIM_EINVAL; }
-    if (fmt != 0 && fmt != 1) { h->set_error("avsim_image_stats: fmt is 0 (u8 HWC) or 1 (float32 CHW)"); return AVSIM_EINVAL; }
-    if (height < 1 || width < 1 || height > 65535 || width > 65535) { h->set_error("avsim_image_stats: image size %d x %d outside 1..65535", height, width); return AVSIM_EINVAL; }
-    size_t rows = (size_t)nimg;            // (a host caller's index says how many images `img` holds)
-    if (!h->io_device && index) {
-        int top = 0;
-        for (int i = 0; i < nimg; i++) {
-            if (index[i] < 0) { h->set_error("avsim_image_stats: negative index"); return AVSIM_EINVAL; }
-            top = index[i] > top ? index[i] : top;
-        }
-        rows = (size_t)top + 1;
-    }
-    AVS_ON_DEVICE(h);
     int rc;
+    if ((rc = img_args(h, "avsim_image_stats", fmt, height, width))) return rc;
+    size_t rows;
+    if ((rc = index_rows(h, "avsim_image_stats", index, nimg, &rows))) return rc;
+    AVS_ON_DEVICE(h);
     const void *dimg = nullptr, *dindex = nullptr;
     void* dout = nullptr;
     const size_t obytes = sizeof(uint64_t) * 12 * (size_t)nimg;
-    if ((rc = h->in(8, img, rows * (size_t)height * width * (fmt ? 12 : 3), &dimg))) return rc;
-    if (index && (rc = h->in(9, index, sizeof(int32_t) * (size_t)nimg, &dindex))) return rc;
-    if ((rc = h->out_begin(10, out, obytes, &dout))) return rc;
+    if ((rc = h->in(IMG_IN, img, rows * (size_t)height * width * img_bpp(fmt), &dimg))) return rc;
+    if (index && (rc = h->in(IMG_INDEX, index, sizeof(int32_t) * (size_t)nimg, &dindex))) return rc;
+    if ((rc = h->out_begin(IMG_RESULT, out, obytes, &dout))) return rc;
     if (ImgPrepHost::stats(h->stream, dimg, fmt, (const int*)dindex, nimg, height, width, (unsigned long long*)dout, h->err)) return AVSIM_EHIP;
-    if ((rc = h->out_end(10, out, obytes))) return rc;
+    if ((rc = h->out_end(IMG_RESULT, out, obytes))) return rc;
     return h->finish();
 }
 
@@ -1150,78 +1150,51 @@ int avsim_image_prep(avsim_t* h, const void* img, int fmt, int nsrc, int height,
                      const int32_t* box, int nout, const int32_t* src_index, int out_h, int out_w, float* out) {
     if (!h) return AVSIM_EINVAL;
     if (!img || !lut || !box || !out || nsrc < 1 || nout < 1 || nlut < 1 || nlut > (1 << 20)) { h->set_error("avsim_image_prep: bad arguments"); return AVSIM_EINVAL; }
-    if (fmt != 0 && fmt != 1) { h->set_error("avsim_image_prep: fmt is 0 (u8 HWC) or 1 (float32 CHW)"); return AVSIM_EINVAL; }
-    if (height < 1 || width < 1 || height > 65535 || width > 65535 || out_h < 1 || out_w < 1 || out_h > 65535 || out_w > 65535) {
-        h->set_error("avsim_image_prep: image sizes %d x %d, %d x %d outside 1..65535", height, width, out_h, out_w);
-        return AVSIM_EINVAL;
-    }
+    int rc;
+    if ((rc = img_args(h, "avsim_image_prep", fmt, height, width, 1, out_h, out_w))) return rc;
     {   // the host arrays are checked before anything moves or is launched
         std::string why;
         if (ImgPrepHost::validate(nsrc, height, width, nlut, lut_index, box, nout, src_index, out_h, out_w, why)) { h->set_error("%s", why.c_str()); return AVSIM_EINVAL; }
     }
     AVS_ON_DEVICE(h);
-    int rc;
     const void *dimg = nullptr, *dlut = nullptr;
     void* dout = nullptr;
     const size_t obytes = sizeof(float) * 3 * (size_t)nout * out_h * out_w;
-    if ((rc = h->in(8, img, (size_t)nsrc * height * width * (fmt ? 12 : 3), &dimg))) return rc;
-    if ((rc = h->in(9, lut, sizeof(float) * 768 * (size_t)nlut, &dlut))) return rc;
-    if ((rc = h->out_begin(10, out, obytes, &dout))) return rc;
-    if (h->imgprep.launch(h->stream, dimg, fmt, height, width, (const float*)dlut, lut_index, box, nout, src_index, out_h, out_w, (float*)dout, h->err)) return AVSIM_EHIP;
-    if ((rc = h->out_end(10, out, obytes))) return rc;
+    if ((rc = h->in(IMG_IN, img, (size_t)nsrc * height * width * img_bpp(fmt), &dimg))) return rc;
+    if ((rc = h->in(IMG_INDEX, lut, sizeof(float) * 768 * (size_t)nlut, &dlut))) return rc;
+    if ((rc = h->out_begin(IMG_RESULT, out, obytes, &dout))) return rc;
+    if (ImgPrepHost::launch(h->stage, h->stream, dimg, fmt, height, width, (const float*)dlut, lut_index, box, nout, src_index, out_h, out_w, (float*)dout, h->err)) return AVSIM_EHIP;
+    if ((rc = h->out_end(IMG_RESULT, out, obytes))) return rc;
     return h->finish();
 }
 
-// Colour and sharpness augmentation (av_aloha_amd/imgaug.py is the specification; the kernels: csrc/avsim_imgaug.hip, a unit of its own flags).
-// The host arrays go through the staging slots avsim_image_prep uses.
+// Colour and sharpness augmentation (av_aloha_amd/imgaug.py is the specification; the kernels: csrc/avsim_imgaug.hip, a unit of its own flags)
 int avsim_image_jitter(avsim_t* h, const void* img, int nsrc, int height, int width, const int32_t* box_mask, const float* factor,
                        const int32_t* src_index, int nout, const float* mean_std, int out_h, int out_w, float* out) {
     if (!h) return AVSIM_EINVAL;
     if (!img || !box_mask || !factor || !out || nsrc < 1 || nout < 1) { h->set_error("avsim_image_jitter: bad arguments"); return AVSIM_EINVAL; }
-    if (height < 1 || width < 1 || height > 65535 || width > 65535 || out_h < 1 || out_w < 1 || out_h > 65535 || out_w > 65535) {
-        h->set_error("avsim_image_jitter: image sizes %d x %d, %d x %d outside 1..65535", height, width, out_h, out_w);
-        return AVSIM_EINVAL;
-    }
+    int rc;
+    if ((rc = img_args(h, "avsim_image_jitter", 0, height, width, 1, out_h, out_w))) return rc;
     {   // the host arrays are checked before anything moves or is launched
         std::string why;
         if (imgaug_validate(nsrc, height, width, box_mask, factor, src_index, nout, mean_std, out_h, out_w, why)) { h->set_error("%s", why.c_str()); return AVSIM_EINVAL; }
     }
     AVS_ON_DEVICE(h);
-    int rc;
     const void* dimg = nullptr;
     void* dout = nullptr;
     const size_t obytes = sizeof(float) * 3 * (size_t)nout * out_h * out_w;
-    if ((rc = h->in(8, img, (size_t)nsrc * height * width * 3, &dimg))) return rc;
-    if ((rc = h->out_begin(10, out, obytes, &dout))) return rc;
-    if (h->aug_sum_cap < (size_t)nout) {
-        if (h->aug_sum) (void)hipFree(h->aug_sum);
-        h->aug_sum = nullptr;
-        h->aug_sum_cap = 0;
-        const size_t cap = ((size_t)nout + 511) & ~(size_t)511;
-        HIPCHK(h, hipMalloc((void**)&h->aug_sum, sizeof(unsigned long long) * cap));
-        h->aug_sum_cap = cap;
-    }
-    const size_t sbytes = imgaug_stage_bytes(nout);
-    ImgPrepHost::Slot* s = h->imgprep.acquire(sbytes, h->err);
-    if (!s) return AVSIM_EHIP;
-    const int ncon = imgaug_pack(s->pin, box_mask, factor, src_index, nout, mean_std);
-    HIPCHK(h, hipMemcpyAsync(s->dev, s->pin, sbytes, hipMemcpyHostToDevice, h->stream));
-    const int lrc = imgaug_launch(h->stream, dimg, height, width, s->dev, nout, ncon, mean_std != nullptr, out_h, out_w, h->aug_sum, (float*)dout, h->err);
-    // (the event also after a failed launch: the copy above may be in flight)
-    const hipError_t e = hipEventRecord(s->done, h->stream);
-    s->busy = e == hipSuccess;
-    if (lrc) return AVSIM_EHIP;
-    HIPCHK(h, e);
-    h->aug_sum_n = nout;
-    if ((rc = h->out_end(10, out, obytes))) return rc;
+    if ((rc = h->in(IMG_IN, img, (size_t)nsrc * height * width * img_bpp(0), &dimg))) return rc;
+    if ((rc = h->out_begin(IMG_RESULT, out, obytes, &dout))) return rc;
+    if (h->imgaug.launch(h->stage, h->stream, dimg, height, width, box_mask, factor, src_index, nout, mean_std, out_h, out_w, (float*)dout, h->err)) return AVSIM_EHIP;
+    if ((rc = h->out_end(IMG_RESULT, out, obytes))) return rc;
     return h->finish();
 }
 
 int avsim_image_jitter_sums(avsim_t* h, uint64_t* sums, int nout) {
     if (!h) return AVSIM_EINVAL;
-    if (!sums || nout < 1 || nout > h->aug_sum_n) { h->set_error("avsim_image_jitter_sums: %d sums asked for, the last avsim_image_jitter made %d outputs", nout, h->aug_sum_n); return AVSIM_EINVAL; }
+    if (!sums || nout < 1 || nout > h->imgaug.nout) { h->set_error("avsim_image_jitter_sums: %d sums asked for, the last avsim_image_jitter made %d outputs", nout, h->imgaug.nout); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
-    HIPCHK(h, hipMemcpyAsync(sums, h->aug_sum, sizeof(uint64_t) * (size_t)nout, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(sums, h->imgaug.gsum, sizeof(uint64_t) * (size_t)nout, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return AVSIM_OK;
 }

@@ -12,6 +12,8 @@
 #include <cstdio>
 #include <string>
 
+#include "avsim_stage.h"
+
 namespace avs {
 
 constexpr int IAG_THREADS = 256;
@@ -89,5 +91,41 @@ inline int imgaug_pack(void* pin, const int32_t* box_mask, const float* factor, 
 // pointers.  Zeroes gsum, runs k_aug_gray_sum for the ncon outputs that have the contrast bit and k_aug_apply for all.  -3: HIP
 int imgaug_launch(hipStream_t stream, const void* src, int SH, int SW, const void* stage, int nout, int ncon, bool normalise, int oh, int ow,
                   unsigned long long* gsum, float* out, std::string& err);
+
+// The host side of avsim_image_jitter: the gray sums behind contrast, one 64-bit slot per output, grown on demand and kept for
+// avsim_image_jitter_sums; the per-call arrays go through the library's pinned staging like avsim_image_prep's
+struct ImgAugHost {
+    unsigned long long* gsum = nullptr;
+    size_t gsum_cap = 0;
+    int nout = 0;      // the outputs of the last call
+
+    void destroy() {
+        if (gsum) (void)hipFree(gsum);
+        *this = ImgAugHost{};
+    }
+
+    // src, out: device pointers; the four arrays: host, validated.  -3: HIP
+    int launch(StageRing& ring, hipStream_t stream, const void* src, int SH, int SW, const int32_t* box_mask, const float* factor, const int32_t* src_index,
+               int n, const float* mean_std, int oh, int ow, float* out, std::string& err) {
+        hipError_t e = hipSuccess;
+        if (gsum_cap < (size_t)n) {
+            destroy();
+            const size_t cap = ((size_t)n + 511) & ~(size_t)511;
+            if ((e = hipMalloc((void**)&gsum, sizeof(unsigned long long) * cap)) != hipSuccess) { gsum = nullptr; err = std::string("image jitter sums: ") + hipGetErrorString(e); return -3; }
+            gsum_cap = cap;
+        }
+        const size_t bytes = imgaug_stage_bytes(n);
+        StageRing::Slot* s = ring.acquire(bytes, err);
+        if (!s) return -3;
+        const int ncon = imgaug_pack(s->pin, box_mask, factor, src_index, n, mean_std);
+        if (ring.upload(*s, bytes, stream, err)) return -3;
+        std::string lerr;
+        const int lrc = imgaug_launch(stream, src, SH, SW, s->dev, n, ncon, mean_std != nullptr, oh, ow, gsum, out, lerr);
+        const int rc = ring.release(*s, stream, err);
+        if (lrc) { err = lerr; return lrc; }
+        if (rc == 0) nout = n;
+        return rc;
+    }
+};
 
 }  // namespace avs

@@ -22,6 +22,7 @@
 #include <string>
 
 #include "avsim_jpeg.hip.h"
+#include "avsim_stage.h"
 
 namespace avs {
 
@@ -233,29 +234,8 @@ __global__ void __launch_bounds__(IPR_THREADS) k_image_prep(const void* __restri
     }
 }
 
-// The host side: the per-call arrays (box, lut_index, src_index) go through pinned staging of the library's own, four slots reused behind events
+// The host side: the per-call arrays (box, lut_index, src_index) go through the library's pinned staging (avsim_stage.h)
 struct ImgPrepHost {
-    static constexpr int NSLOT = 4;
-    struct Slot {
-        void* pin = nullptr;
-        void* dev = nullptr;
-        size_t cap = 0;
-        hipEvent_t done = nullptr;
-        bool busy = false;
-    };
-    Slot slot[NSLOT];
-    int next = 0;
-
-    void destroy() {
-        for (auto& s : slot) {
-            if (s.busy) (void)hipEventSynchronize(s.done);
-            if (s.pin) (void)hipHostFree(s.pin);
-            if (s.dev) (void)hipFree(s.dev);
-            if (s.done) (void)hipEventDestroy(s.done);
-            s = Slot{};
-        }
-    }
-
     // the conditions of the header on the host arrays; -1 and err says which
     static int validate(int nsrc, int SH, int SW, int nlut, const int32_t* lut_index, const int32_t* box, int nout, const int32_t* src_index, int oh,
                         int ow, std::string& err) {
@@ -277,41 +257,17 @@ struct ImgPrepHost {
         return 0;
     }
 
-    // the next slot, idle (its last call's event waited for) and holding at least `bytes` of pinned and of device memory; nullptr: HIP, err says what
-    Slot* acquire(size_t bytes, std::string& err) {
-        Slot& s = slot[next];
-        next = (next + 1) % NSLOT;
-        hipError_t e = hipSuccess;
-        if (s.busy) e = hipEventSynchronize(s.done);      // (the call four calls back: long done in a training loop)
-        s.busy = false;
-        if (e == hipSuccess && s.cap < bytes) {
-            if (s.pin) (void)hipHostFree(s.pin);
-            if (s.dev) (void)hipFree(s.dev);
-            s.pin = s.dev = nullptr;
-            s.cap = 0;
-            const size_t cap = (bytes + 4095) & ~(size_t)4095;
-            e = hipHostMalloc(&s.pin, cap, hipHostMallocDefault);
-            if (e == hipSuccess) e = hipMalloc(&s.dev, cap);
-            if (e == hipSuccess) s.cap = cap;
-        }
-        if (e == hipSuccess && !s.done) e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming);
-        if (e != hipSuccess) { err = std::string("image prep staging: ") + hipGetErrorString(e); return nullptr; }
-        return &s;
-    }
-
     // src, lut, out: device pointers; the three arrays: host, validated.  -3: HIP
-    int launch(hipStream_t stream, const void* src, int sf, int SH, int SW, const float* lut, const int32_t* lut_index, const int32_t* box, int nout,
-               const int32_t* src_index, int oh, int ow, float* out, std::string& err) {
+    static int launch(StageRing& ring, hipStream_t stream, const void* src, int sf, int SH, int SW, const float* lut, const int32_t* lut_index, const int32_t* box,
+                      int nout, const int32_t* src_index, int oh, int ow, float* out, std::string& err) {
         const size_t bytes = (size_t)nout * sizeof(PrepItem);
-        Slot* sp = acquire(bytes, err);
+        StageRing::Slot* sp = ring.acquire(bytes, err);
         if (!sp) return -3;
-        Slot& s = *sp;
-        hipError_t e = hipSuccess;
+        StageRing::Slot& s = *sp;
         PrepItem* it = (PrepItem*)s.pin;
         for (int i = 0; i < nout; i++)
             it[i] = PrepItem{src_index ? src_index[i] : i, box[3 * (size_t)i], box[3 * (size_t)i + 1], box[3 * (size_t)i + 2] | ((lut_index ? lut_index[i] : 0) << 1)};
-        e = hipMemcpyAsync(s.dev, s.pin, bytes, hipMemcpyHostToDevice, stream);
-        if (e != hipSuccess) { err = std::string("image prep staging: ") + hipGetErrorString(e); return -3; }
+        if (ring.upload(s, bytes, stream, err)) return -3;
         const int G = (ow + 3) / 4;
         const int rb = std::min(oh, std::max(1, (4 * IPR_THREADS + G - 1) / G));      // some four items per lane
         const int bands = (oh + rb - 1) / rb;
@@ -320,11 +276,10 @@ struct ImgPrepHost {
             if (sf == 0) hipLaunchKernelGGL(k_image_prep<0>, grid, dim3(IPR_THREADS), 0, stream, src, SH, SW, lut, (const PrepItem*)s.dev, i0, oh, ow, rb, out);
             else hipLaunchKernelGGL(k_image_prep<1>, grid, dim3(IPR_THREADS), 0, stream, src, SH, SW, lut, (const PrepItem*)s.dev, i0, oh, ow, rb, out);
         }
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(s.done, stream);
+        const hipError_t e = hipGetLastError();
+        const int rc = ring.release(s, stream, err);
         if (e != hipSuccess) { err = std::string("image prep kernel: ") + hipGetErrorString(e); return -3; }
-        s.busy = true;
-        return 0;
+        return rc;
     }
 
     // img, index, out: device pointers

@@ -6,8 +6,9 @@ import json
 
 import numpy as np
 
-from . import _ffi, imgaug, imgprep, jpeg
+from . import imgaug, imgprep, jpeg
 from .harness import load_episode
+from .images import DeviceImages
 
 
 class CompressedDataset:
@@ -29,7 +30,6 @@ class CompressedDataset:
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("CompressedDataset decodes on the GPU: device is a cuda device")
-        torch.zeros(1, device=self.device)           # torch's runtime comes up first (vec_env.py)
         state, action, ep_idx, fr_idx = [], [], [], []
         streams = {c: [] for c in self.cameras}
         for e, path in enumerate(paths):
@@ -66,10 +66,7 @@ class CompressedDataset:
             self.buf[c] = flat
             self.size[c] = jpeg.stream_size(ss[0].tobytes())
             self.stride[c] = (int(ln.max()) + 255) // 256 * 256
-        import os
-        from .constants import MODEL_DIR             # the smallest handle the library offers: the decoder needs none of the model
-        with open(os.path.join(MODEL_DIR, "insert_peg_3arms.avm"), "rb") as f:
-            self.h = _ffi.Handle(f.read(), 2, self.device.index or 0, _ffi.AVSIM_IO_DEVICE)
+        self.img = DeviceImages(self.device)         # the image calls
         self._stage, self._pending = {}, []
 
     def __len__(self):
@@ -85,14 +82,13 @@ class CompressedDataset:
         t_idx = torch.from_numpy(idx).to(self.device, non_blocking=True)
         out = {"observation.state": self.state[t_idx], "action": self.action[t_idx], "episode_index": self.episode_index[t_idx],
                "frame_index": self.frame_index[t_idx]}
-        self.h.check(self.h.L.avsim_set_stream(self.h.h, torch.cuda.current_stream(self.device).cuda_stream))
         self._check_pending()
         for c in self.cameras:
             out[f"observation.images.{c}"] = self._decode(c, idx, fmt)
         return out
 
     def _decode(self, c, idx, fmt):
-        """The frames idx of camera c, decoded on the handle's stream: float32 [B, 3, H, W] (fmt "lerobot") or uint8 [B, H, W, 3] ("gym")."""
+        """The frames idx of camera c, decoded on torch's current stream: float32 [B, 3, H, W] (fmt "lerobot") or uint8 [B, H, W, 3] ("gym")."""
         torch = self.torch
         B = len(idx)
         ln = self.len[c][idx]
@@ -108,11 +104,7 @@ class CompressedDataset:
         d_rows, d_len = rows.to(self.device, non_blocking=True), lens.to(self.device, non_blocking=True)
         done.record()
         H, W = self.size[c]
-        img = torch.empty((B, 3, H, W), dtype=torch.float32, device=self.device) if fmt == "lerobot" else \
-            torch.empty((B, H, W, 3), dtype=torch.uint8, device=self.device)
-        status = torch.empty(B, dtype=torch.int32, device=self.device)
-        self.h.check(self.h.L.avsim_jpeg_decode(self.h.h, d_rows.data_ptr(), self.stride[c], d_len.data_ptr(), None, B, H, W, 1 if fmt == "lerobot" else 0,
-                                                1 if self.upsample == "triangle" else 0, img.data_ptr(), status.data_ptr()))
+        img, status = self.img.decode_jpeg(d_rows, d_len, height=H, width=W, upsample=self.upsample, fmt=fmt)
         if self.check:
             self._pending.append((status, idx, c))
         return img
@@ -123,7 +115,6 @@ class CompressedDataset:
         (avsim_image_stats), the integer sums combined exactly (imgprep.combine_stats: no float accumulation, the same result for every
         batch_size) --, and of "observation.state" and "action" per dimension, in float64.  std is the population std."""
         torch = self.torch
-        self.h.check(self.h.L.avsim_set_stream(self.h.h, torch.cuda.current_stream(self.device).cuda_stream))
         self._check_pending()
         out = {}
         for c in self.cameras:
@@ -131,8 +122,7 @@ class CompressedDataset:
             sums = torch.empty((self.n, 3, 4), dtype=torch.int64, device=self.device)
             for i0 in range(0, self.n, int(batch_size)):
                 idx = np.arange(i0, min(self.n, i0 + int(batch_size)), dtype=np.int64)
-                img = self._decode(c, idx, "gym")
-                self.h.check(self.h.L.avsim_image_stats(self.h.h, img.data_ptr(), 0, None, len(idx), H, W, sums[i0:i0 + len(idx)].data_ptr()))
+                self.img.image_stats(self._decode(c, idx, "gym"), out=sums[i0:i0 + len(idx)])
             out[f"observation.images.{c}"] = imgprep.combine_stats(sums.cpu().numpy().view(np.uint64), H * W)
             self._check_pending()
         for key, t in (("observation.state", self.state), ("action", self.action)):
@@ -160,12 +150,12 @@ class CompressedDataset:
             yield self.batch(part)
 
     def close(self):
-        if getattr(self, "h", None) is not None:
+        if getattr(self, "img", None) is not None:
             try:
                 self._check_pending()
             finally:
-                self.h.close()
-                self.h = None
+                self.img.close()
+                self.img = None
 
 
 def save_stats(stats, path):
@@ -249,7 +239,7 @@ class TrainingBatches:
         if self.augment is not None and self.normalise:
             for c in ds.cameras:
                 st = stats[f"observation.images.{c}"]
-                self.mean_std[c] = imgaug.mean_std(st["mean"], st["std"])
+                self.mean_std[c] = (st["mean"], st["std"])
         for key in ("observation.state", "action"):
             self.norm[key] = (torch.from_numpy(np.asarray(stats[key]["mean"], dtype=np.float32)).to(ds.device),
                               torch.from_numpy(np.asarray(stats[key]["std"], dtype=np.float32)).to(ds.device))
@@ -299,21 +289,10 @@ class TrainingBatches:
             H, W = self.sizes[c]
             h, w = (H, W) if self.crop is None else (int(self.crop[0]), int(self.crop[1]))
             box = np.ascontiguousarray(boxes[c], dtype=np.int32).reshape(B, 3)
-            img = torch.empty((B, 3, h, w), dtype=torch.float32, device=ds.device)
+            src = raw[f"observation.images.{c}"]
             if aug is not None:
-                bm, fac = imgaug.pack_params(box, *aug[c])
-                ms = self.mean_std.get(c)
-                rc = ds.h.L.avsim_image_jitter(ds.h.h, raw[f"observation.images.{c}"].data_ptr(), B, H, W, bm.ctypes.data, fac.ctypes.data, None, B,
-                                               None if ms is None else ms.ctypes.data, h, w, img.data_ptr())
-                if rc == -1:
-                    raise ValueError(ds.h.L.avsim_last_error(ds.h.h).decode())
-                ds.h.check(rc)
-                out[f"observation.images.{c}"] = img
-                continue
-            rc = ds.h.L.avsim_image_prep(ds.h.h, raw[f"observation.images.{c}"].data_ptr(), 0, B, H, W, self.lut[c].data_ptr(), 1, None, box.ctypes.data,
-                                         B, None, h, w, img.data_ptr())
-            if rc == -1:          # AVSIM_EINVAL: nothing was launched
-                raise ValueError(ds.h.L.avsim_last_error(ds.h.h).decode())
-            ds.h.check(rc)
-            out[f"observation.images.{c}"] = img
+                ms = self.mean_std.get(c, (None, None))
+                out[f"observation.images.{c}"] = ds.img.jitter_images(src, imgaug.pack_params(box, *aug[c]), (h, w), mean=ms[0], std=ms[1])
+            else:
+                out[f"observation.images.{c}"] = ds.img.prep_images(src, self.lut[c], box, (h, w))
         return out

@@ -162,6 +162,7 @@ class _GridRecorder:
 
     def __init__(self, env, path, camera, k, cols, cell, quality, fps):
         from .compose import layout_grid
+        from .images import default_stride
         from .mjpeg import AviWriter
         import torch
         self.env, self.k, self.quality = env, int(k), int(quality)
@@ -173,7 +174,7 @@ class _GridRecorder:
         self.canvas = torch.zeros((1, CH, CW, 3), dtype=torch.uint8, device=env.device)
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         self.writer = AviWriter(path, CW, CH, fps=fps)
-        stride = int(min(env.L.avsim_jpeg_bound(CH, CW), (CH * CW * 3 // 2 + 4095) // 4096 * 4096))
+        stride = default_stride(env.L, CH, CW, 2)
         self.chunk = max(1, min(64, (256 << 20) // stride))
         self.buf = torch.empty((self.chunk, 1, stride), dtype=torch.uint8, device=env.device)
         self.len = torch.zeros((self.chunk, 1), dtype=torch.int32, device=env.device)
@@ -633,21 +634,19 @@ class _HostComposer:
 
 
 class _DeviceComposer:
-    """The same steps on the device (a camera-less VecEnv's handle: avsim_jpeg_decode, avsim_compose, avsim_compose_label, avsim_jpeg_encode):
+    """The same steps on the device (images.DeviceImages: avsim_jpeg_decode, avsim_compose, avsim_compose_label, avsim_jpeg_encode):
     streams or raw frames go in, streams come out, and no decoded or composed pixel leaves the device."""
 
     def __init__(self, device):
-        from .vec_env import VecEnv
-        import torch
-        self.torch = torch
-        torch.zeros(1, device=torch.device("cuda", int(device)))        # torch's runtime first (vec_env.py)
-        self.env = VecEnv("insert_peg", 3, 1, 1, device=int(device))
+        from .images import DeviceImages
+        self.img = DeviceImages(int(device))
+        self.torch = self.img.torch
         self.bytes_to_device = self.bytes_from_device = 0
         self._status = []          # of the decode calls since the last encode, read when that waits for the stream anyway
 
     def _up(self, a):
         self.bytes_to_device += a.nbytes
-        return self.torch.from_numpy(a).to(self.env.device)
+        return self.torch.from_numpy(a).to(self.img.device)
 
     def images(self, frames=None, streams=None):
         from . import jpeg
@@ -658,23 +657,23 @@ class _DeviceComposer:
         buf, ln = np.zeros((len(streams), stride), np.uint8), np.array([len(x) for x in streams], np.int32)
         for i, x in enumerate(streams):
             buf[i, :len(x)] = np.frombuffer(x, np.uint8)
-        out, status = self.env.decode_jpeg(self._up(buf), self._up(ln), height=H, width=W, fmt="gym")
+        out, status = self.img.decode_jpeg(self._up(buf), self._up(ln), height=H, width=W, fmt="gym")
         self._status.append(status)
         return out
 
     def compose(self, src, places, canvas, canvas_hw, n):
-        return self.env.compose(src, places, out=canvas, canvas_hw=canvas_hw, nout=n, clear=0 if canvas is None else None)
+        return self.img.compose(src, places, out=canvas, canvas_hw=canvas_hw, nout=n, clear=0 if canvas is None else None)
 
     def label(self, canvas, where, prefix, values):
         v = None if values is None else self._up(np.ascontiguousarray(values, dtype=np.int64))
-        return self.env.compose_label(canvas, where, prefix, v, 0xFFFFFF)
+        return self.img.compose_label(canvas, where, prefix, v, 0xFFFFFF)
 
     def encode(self, canvas, quality):
-        out, ln = self.env.encode_images(canvas, quality)
+        out, ln = self.img.encode_images(canvas, quality)
         n = ln.cpu().numpy()                                       # (waits for the stream)
         if int(n.max()) > out.shape[1]:                            # some stream did not fit: its length says what it needs
-            out = self.torch.empty((len(n), int(n.max())), dtype=self.torch.uint8, device=self.env.device)
-            out, ln = self.env.encode_images(canvas, quality, out=out)
+            out = self.torch.empty((len(n), int(n.max())), dtype=self.torch.uint8, device=self.img.device)
+            out, ln = self.img.encode_images(canvas, quality, out=out)
             n = ln.cpu().numpy()
         status, self._status = self._status, []
         if any(bool(st.any().item()) for st in status):
@@ -684,7 +683,7 @@ class _DeviceComposer:
         return [data[i, :n[i]].tobytes() for i in range(len(n))]
 
     def close(self):
-        self.env.close()
+        self.img.close()
 
 
 def _visualize(episodes, video_path, cameras, stride, prefix, numbered, quality, fps, device, chunk_bytes):

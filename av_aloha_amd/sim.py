@@ -8,7 +8,7 @@ import os
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, images
 from .constants import MODEL_DIR, SIM_PHYSICS_ENV_STEP_RATIO
 
 TASK_KEYS = ("insert_peg", "slot_insertion", "sew_needle", "tube_transfer", "hook_package")
@@ -122,8 +122,7 @@ class BatchedSim:
     def render_depth(self, cameras, height, width):
         """Depth images float32 [N, len(cameras), height, width] (metres along the optical axis) of the named cameras
         (names from the manifest's camera table, or indices) at the current state."""
-        names = self.manifest["camera_names"]
-        ids = np.array([names.index(c) if isinstance(c, str) else int(c) for c in cameras], dtype=np.int32)
+        ids = images.camera_ids(self.manifest, cameras)
         out = np.empty((self.N, len(ids), height, width), dtype=np.float32)
         self.h.check(self.h.L.avsim_render_depth(self.h.h, ids.ctypes.data, len(ids), height, width, out.ctypes.data))
         return out
@@ -152,8 +151,7 @@ class BatchedSim:
             self.load_visual()
         self.set_option("render_proxies", 0 if visual else 1)
         self.set_option("render_cam_major", 1 if (cam_major and visual) else 0)      # [len(cameras), N, height, width, 3]: every camera's batch contiguous
-        names = self.manifest["camera_names"]
-        ids = np.array([names.index(c) if isinstance(c, str) else int(c) for c in cameras], dtype=np.int32)
+        ids = images.camera_ids(self.manifest, cameras)
         shape = (len(ids), self.N, height, width, 3) if (cam_major and visual) else (self.N, len(ids), height, width, 3)
         if out is None:
             out = np.empty(shape, dtype=np.uint8)
@@ -190,7 +188,7 @@ class BatchedSim:
             return buf, ln
         for i0 in range(0, n, batch):
             frames = f[i0:i0 + batch]
-            buf, ln = run(frames, min(bound, (H * W * 3 // 4 + 4095) // 4096 * 4096))
+            buf, ln = run(frames, images.default_stride(L, H, W, 4))
             if int(ln.max()) > buf.shape[1]:          # some stream did not fit: its length says what it needs
                 buf, ln = run(frames, int(ln.max()))
             out += [buf[i, :ln[i]].tobytes() for i in range(len(frames))]
@@ -204,8 +202,7 @@ class BatchedSim:
             self.load_visual()
         self.set_option("render_proxies", 0)
         self.set_option("render_cam_major", 0)
-        names = self.manifest["camera_names"]
-        ids = np.array([names.index(c) if isinstance(c, str) else int(c) for c in cameras], dtype=np.int32)
+        ids = images.camera_ids(self.manifest, cameras)
         L = self.h.L
         iw = width * len(ids) if tile else width
         bound = int(L.avsim_jpeg_bound(height, iw))
@@ -214,13 +211,13 @@ class BatchedSim:
         n = self.N if tile else self.N * len(ids)
         key = (height, iw, int(quality))
         strides = self._jpeg_stride
-        stride = strides.get(key, min(bound, (height * iw * 3 // 8 + 4095) // 4096 * 4096))
+        stride = strides.get(key) or images.default_stride(L, height, iw, 8)
         while True:
             buf, ln = np.empty((n, stride), dtype=np.uint8), np.empty(n, dtype=np.int32)
             self.h.check(L.avsim_render_jpeg(self.h.h, ids.ctypes.data, len(ids), height, width, 1 if tile else 0, int(quality), buf.ctypes.data, stride, ln.ctypes.data))
             if int(ln.max()) <= stride:
                 break
-            stride = strides[key] = min(bound, (int(ln.max()) * 5 // 4 + 4095) // 4096 * 4096)        # some stream did not fit: its length says what it needs
+            stride = strides[key] = min(bound, int(ln.max()) * 5 // 4)        # some stream did not fit: its length says what it needs
         if self.visual_info()["overflow"]:
             import warnings
             warnings.warn(f"avsim_render_jpeg: a view ran out of triangle records or tile-list entries at {height}x{width}: triangles were dropped from the image", RuntimeWarning, stacklevel=2)
@@ -256,11 +253,6 @@ class BatchedSim:
                                                      "1 header, 2 marker structure or length, 4 entropy-coded data)")
         return out
 
-    def _compose_check(self, rc):
-        if rc == -1:          # AVSIM_EINVAL: the library launched nothing
-            raise ValueError(self.h.L.avsim_last_error(self.h.h).decode())
-        self.h.check(rc)
-
     def compose(self, src, places, out=None, canvas_hw=None, nout=None, clear=None):
         """Images resampled into rectangles of a canvas on the device (avsim_compose): the pixels of av_aloha_amd.compose.compose_reference.
         src: u8 [n, H, W, 3] or float32 [n, 3, H, W] in [0, 1]; places: int rows (out image, src image, x0, y0, w, h).  out: the canvas to
@@ -269,41 +261,32 @@ class BatchedSim:
         nothing is said).  ValueError for what the library refuses (a rectangle outside the canvas, overlaps, a shrink of more than 16)."""
         src = np.ascontiguousarray(src)
         p = np.ascontiguousarray(places, dtype=np.int32).reshape(-1, 6)
-        if src.dtype == np.uint8 and src.ndim == 4 and src.shape[3] == 3:
-            sf, (n, H, W) = 0, src.shape[:3]
-        elif src.dtype == np.float32 and src.ndim == 4 and src.shape[1] == 3:
-            sf, (n, H, W) = 1, (src.shape[0],) + src.shape[2:]
-        else:
-            raise ValueError("compose takes u8 [n, H, W, 3] or float32 [n, 3, H, W] images")
+        sf, n, H, W = images.layout(src)
         if out is None:
             if canvas_hw is None:
                 raise ValueError("compose: give a canvas (out=...) or its size (canvas_hw=...)")
             nout = int(p[:, 0].max()) + 1 if nout is None and len(p) else int(nout or 1)
             out = np.empty((nout, int(canvas_hw[0]), int(canvas_hw[1]), 3), dtype=np.uint8)
             clear = 0 if clear is None else clear
-        df, (no, CH, CW) = self._canvas(out)
-        self._compose_check(self.h.L.avsim_compose(self.h.h, src.ctypes.data, sf, n, H, W, out.ctypes.data, df, no, CH, CW, p.ctypes.data, len(p),
-                                                  0 if clear is None else 1, int(clear or 0) & 0xFFFFFF))
+        df, no, CH, CW = self._canvas(out)
+        images.check_call(self.h, self.h.L.avsim_compose(self.h.h, src.ctypes.data, sf, n, H, W, out.ctypes.data, df, no, CH, CW, p.ctypes.data, len(p),
+                                                         0 if clear is None else 1, int(clear or 0) & 0xFFFFFF))
         return out
 
     @staticmethod
     def _canvas(out):
-        if not (isinstance(out, np.ndarray) and out.flags.c_contiguous and out.ndim == 4):
+        if not (isinstance(out, np.ndarray) and out.flags.c_contiguous):
             raise ValueError("compose: the canvas is a C-contiguous u8 [n, H, W, 3] or float32 [n, 3, H, W] array")
-        if out.dtype == np.uint8 and out.shape[3] == 3:
-            return 0, out.shape[:3]
-        if out.dtype == np.float32 and out.shape[1] == 3:
-            return 1, (out.shape[0],) + out.shape[2:]
-        raise ValueError("compose: the canvas is a C-contiguous u8 [n, H, W, 3] or float32 [n, 3, H, W] array")
+        return images.layout(out)
 
     def compose_label(self, canvas, where, prefix="", values=None, rgb=0xFFFFFF):
         """prefix + str(values[i]) painted onto the canvas at where[i] = (out image, x, y, scale) in the colour rgb (avsim_compose_label):
         the pixels of av_aloha_amd.compose.label_reference.  The canvas (compose's) is written in place and returned."""
-        df, (no, CH, CW) = self._canvas(canvas)
+        df, no, CH, CW = self._canvas(canvas)
         w = np.ascontiguousarray(where, dtype=np.int32).reshape(-1, 4)
         v = None if values is None else np.ascontiguousarray(values, dtype=np.int64).reshape(len(w))
-        self._compose_check(self.h.L.avsim_compose_label(self.h.h, canvas.ctypes.data, df, no, CH, CW, w.ctypes.data, len(w), prefix.encode("ascii", "replace"),
-                                                        _ffi.ptr(v), int(rgb) & 0xFFFFFF))
+        images.check_call(self.h, self.h.L.avsim_compose_label(self.h.h, canvas.ctypes.data, df, no, CH, CW, w.ctypes.data, len(w), prefix.encode("ascii", "replace"),
+                                                               _ffi.ptr(v), int(rgb) & 0xFFFFFF))
         return canvas
 
     def image_stats(self, img, index=None):
@@ -311,13 +294,13 @@ class BatchedSim:
         (avsim_image_stats): the integers of av_aloha_amd.imgprep.stats_reference.  img: u8 [n, H, W, 3] or float32 [n, 3, H, W]; index: the
         images to reduce, in this order (None: all)."""
         img = np.ascontiguousarray(img)
-        sf, (n, H, W) = self._canvas(img)
+        sf, n, H, W = self._canvas(img)
         idx = None if index is None else np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
         if idx is not None and len(idx) and (idx.min() < 0 or idx.max() >= n):
             raise ValueError(f"image_stats: index outside [0, {n})")
         m = n if idx is None else len(idx)
         out = np.empty((m, 3, 4), dtype=np.uint64)
-        self._compose_check(self.h.L.avsim_image_stats(self.h.h, img.ctypes.data, sf, _ffi.ptr(idx), m, H, W, out.ctypes.data))
+        images.check_call(self.h, self.h.L.avsim_image_stats(self.h.h, img.ctypes.data, sf, _ffi.ptr(idx), m, H, W, out.ctypes.data))
         return out
 
     def prep_images(self, img, lut, box, out_hw, lut_index=None, src_index=None, out=None):
@@ -326,7 +309,7 @@ class BatchedSim:
         int rows (x0, y0, flip), one per output; lut_index / src_index: the table / the source image of every output (None: table 0 /
         image i).  ValueError for what the library refuses (a crop outside the source, an index out of range)."""
         img = np.ascontiguousarray(img)
-        sf, (n, H, W) = self._canvas(img)
+        sf, n, H, W = self._canvas(img)
         lut = np.ascontiguousarray(lut, dtype=np.float32).reshape(-1, 3, 256)
         b = np.ascontiguousarray(box, dtype=np.int32).reshape(-1, 3)
         li = None if lut_index is None else np.ascontiguousarray(lut_index, dtype=np.int32).reshape(len(b))
@@ -336,8 +319,8 @@ class BatchedSim:
             out = np.empty((len(b), 3, max(oh, 0), max(ow, 0)), dtype=np.float32)
         if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (len(b), 3, oh, ow)):
             raise ValueError("prep_images: out is a C-contiguous float32 [nout, 3, oh, ow] array")
-        self._compose_check(self.h.L.avsim_image_prep(self.h.h, img.ctypes.data, sf, n, H, W, lut.ctypes.data, len(lut), _ffi.ptr(li), b.ctypes.data,
-                                                      len(b), _ffi.ptr(si), oh, ow, out.ctypes.data))
+        images.check_call(self.h, self.h.L.avsim_image_prep(self.h.h, img.ctypes.data, sf, n, H, W, lut.ctypes.data, len(lut), _ffi.ptr(li), b.ctypes.data,
+                                                             len(b), _ffi.ptr(si), oh, ow, out.ctypes.data))
         return out
 
     def jitter_images(self, img, params, out_hw, mean=None, std=None, src_index=None, out=None):
@@ -358,15 +341,15 @@ class BatchedSim:
             out = np.empty((len(bm), 3, max(oh, 0), max(ow, 0)), dtype=np.float32)
         if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (len(bm), 3, oh, ow)):
             raise ValueError("jitter_images: out is a C-contiguous float32 [nout, 3, oh, ow] array")
-        self._compose_check(self.h.L.avsim_image_jitter(self.h.h, img.ctypes.data, n, H, W, bm.ctypes.data, fac.ctypes.data, _ffi.ptr(si), len(bm), _ffi.ptr(ms), oh, ow,
-                                                        out.ctypes.data))
+        images.check_call(self.h, self.h.L.avsim_image_jitter(self.h.h, img.ctypes.data, n, H, W, bm.ctypes.data, fac.ctypes.data, _ffi.ptr(si), len(bm), _ffi.ptr(ms), oh, ow,
+                                                               out.ctypes.data))
         return out
 
     def jitter_gray_sums(self, nout):
         """uint64 [nout]: the integer sums behind the contrast means of the last jitter_images call (avsim_image_jitter_sums;
         imgaug.gray_sum_reference's), meaningful for the outputs that had the contrast bit.  For tests."""
         sums = np.zeros(int(nout), dtype=np.uint64)
-        self._compose_check(self.h.L.avsim_image_jitter_sums(self.h.h, sums.ctypes.data, int(nout)))
+        images.check_call(self.h, self.h.L.avsim_image_jitter_sums(self.h.h, sums.ctypes.data, int(nout)))
         return sums
 
     def reward_from_pairs(self, geom_pairs, latch=None):

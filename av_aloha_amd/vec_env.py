@@ -29,6 +29,7 @@ import numpy as np
 from . import _ffi
 from .constants import CAMERAS, MODEL_DIR, SIM_PHYSICS_ENV_STEP_RATIO
 from .env import ENVS
+from .images import DeviceImageOps, camera_ids, default_stride
 from .sim import load_blob
 
 # Initial positions of the free objects in qpos order: (lo xyz, hi xyz) of the reference's uniform draws (env.py:474-501, 513-543,
@@ -78,8 +79,9 @@ def sample_poses(task, seed, episode_ids):
     return out
 
 
-class VecEnv:
-    """num_envs envs of one task on one GPU; see the module's docstring for the semantics."""
+class VecEnv(DeviceImageOps):
+    """num_envs envs of one task on one GPU; see the module's docstring for the semantics.  The image calls on any tensor of the env's device
+    -- decode_jpeg, encode_images, compose, compose_label, image_stats, prep_images, jitter_images -- are images.DeviceImageOps's."""
 
     metadata = {"autoreset_mode": "NextStep", "render_modes": []}
 
@@ -107,9 +109,7 @@ class VecEnv:
         options = {"render_shadows": 1, "render_samples": 4, "render_smooth": 1, **(options or {})}
         for k, v in options.items():
             self.h.check(self.L.avsim_set_option(self.h.h, k.encode(), float(v)))
-        names = self.manifest["camera_names"]
-        self._cam_ids = np.array([names.index(c) for c in self.cameras], dtype=np.int32)
-        self._depth_ids = np.array([names.index(c) for c in self.depth_cameras], dtype=np.int32)
+        self._cam_ids, self._depth_ids = camera_ids(self.manifest, self.cameras), camera_ids(self.manifest, self.depth_cameras)
         if self.cameras:
             with open(os.path.join(MODEL_DIR, "visual_meshes.avv"), "rb") as f:
                 lib = f.read()
@@ -143,12 +143,6 @@ class VecEnv:
         self._setup(self.seed, 0)
 
     # -- plumbing ----------------------------------------------------------------------------------
-    def _bind_stream(self):
-        s = self.torch.cuda.current_stream(self.device)
-        if self._stream is None or s.cuda_stream != self._stream.cuda_stream:
-            self.h.check(self.L.avsim_set_stream(self.h.h, s.cuda_stream))
-            self._stream = s
-
     def _setup(self, seed, log_capacity):
         self._bind_stream()
         self.seed, self._log_capacity = int(seed), int(log_capacity)
@@ -243,8 +237,7 @@ class VecEnv:
     def jpeg_stride(self, quality=90):
         """Bytes encode_jpeg reserves per stream by default: half the raw frame, never more than the worst case (avsim_jpeg_bound).  A
         rendered 480 x 640 frame takes 31 KB at quality 90 and 95 KB at 100."""
-        H, W = self.observation_height, self.observation_width
-        return int(min(self.L.avsim_jpeg_bound(H, W), (H * W * 3 // 2 + 4095) // 4096 * 4096))
+        return default_stride(self.L, self.observation_height, self.observation_width, 2)
 
     def encode_jpeg(self, camera, envs=None, quality=90, out=None, out_len=None):
         """JPEG streams of `camera`'s CURRENT observation (the images the last reset / step returned), encoded on the device from the
@@ -268,186 +261,14 @@ class VecEnv:
                 "encode_jpeg(envs=...): an int32 index tensor on the env's device"
             index = envs.clamp(0, self.num_envs - 1).contiguous()
             n = int(index.shape[0])
-        if out is None:
-            out = torch.empty((n, self.jpeg_stride(quality)), dtype=torch.uint8, device=self.device)
-        if out_len is None:
-            out_len = torch.empty(n, dtype=torch.int32, device=self.device)
-        assert out.dtype == torch.uint8 and out.device == self.device and out.ndim == 2 and out.shape[0] == n and out.is_contiguous()
-        assert out_len.dtype == torch.int32 and out_len.device == self.device and tuple(out_len.shape) == (n,) and out_len.is_contiguous()
-        img = self._img[self.cameras.index(camera)]
-        self.h.check(self.L.avsim_jpeg_encode(self.h.h, img.data_ptr(), 1 if self.obs_format == "lerobot" else 0, _ffi.ptr(index), n,
-                                              self.observation_height, self.observation_width, int(quality), out.data_ptr(), int(out.shape[1]),
-                                              out_len.data_ptr()))
-        return out, out_len
-
-    def decode_jpeg(self, buf, lengths, height=None, width=None, upsample="replicate", fmt=None, out=None, status=None):
-        """The inverse of encode_jpeg on the device (avsim_jpeg_decode): buf uint8 [n, stride] and lengths int32 [n] as encode_jpeg
-        returns them -> (images, status int32 [n]).  height / width default to the observation size, fmt to the env's observation format:
-        "lerobot" float32 [n, 3, H, W] in [0, 1], "gym" uint8 [n, H, W, 3].  The pixels are av_aloha_amd.jpeg.decode_reference's;
-        status[i] != 0 flags a stream that is not this encoder's (avsim.h), whose image is unspecified.  out / status: buffers to write
-        into.  Does not synchronise -- so it does not raise for a flagged stream either: read `status` when the host next waits."""
-        torch = self.torch
-        self._bind_stream()
-        if upsample not in ("replicate", "triangle"):
-            raise ValueError(f"upsample {upsample!r}: 'replicate' or 'triangle'")
-        fmt = self.obs_format if fmt is None else fmt
-        if fmt not in ("lerobot", "gym"):
-            raise ValueError(f"fmt {fmt!r}: 'lerobot' or 'gym'")
-        H = self.observation_height if height is None else int(height)
-        W = self.observation_width if width is None else int(width)
-        assert buf.dtype == torch.uint8 and buf.device == self.device and buf.ndim == 2 and buf.is_contiguous()
-        n = int(buf.shape[0])
-        assert lengths.dtype == torch.int32 and lengths.device == self.device and tuple(lengths.shape) == (n,) and lengths.is_contiguous()
-        shape, dtype = ((n, 3, H, W), torch.float32) if fmt == "lerobot" else ((n, H, W, 3), torch.uint8)
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=self.device)
-        if status is None:
-            status = torch.empty(n, dtype=torch.int32, device=self.device)
-        assert out.dtype == dtype and out.device == self.device and tuple(out.shape) == shape and out.is_contiguous()
-        assert status.dtype == torch.int32 and status.device == self.device and tuple(status.shape) == (n,) and status.is_contiguous()
-        self.h.check(self.L.avsim_jpeg_decode(self.h.h, buf.data_ptr(), int(buf.shape[1]), lengths.data_ptr(), None, n, H, W,
-                                              1 if fmt == "lerobot" else 0, 1 if upsample == "triangle" else 0, out.data_ptr(), status.data_ptr()))
-        return out, status
+        return self._encode(self._img[self.cameras.index(camera)], 1 if self.obs_format == "lerobot" else 0, index, n, self.observation_height,
+                            self.observation_width, quality, out, out_len)
 
     def camera_images(self, camera):
         """The buffer that holds `camera`'s current observation of all envs: float32 [N, 3, H, W] (lerobot) or uint8 [N, H, W, 3] (gym)."""
         if camera not in self.cameras:
             raise ValueError(f"the env does not render {camera!r} (cameras: {self.cameras})")
         return self._img[self.cameras.index(camera)]
-
-    def encode_images(self, images, quality=90, out=None, out_len=None):
-        """JPEG streams of any image batch on the env's device -- uint8 [n, H, W, 3] or float32 [n, 3, H, W], a compose() canvas for one --
-        through avsim_jpeg_encode: -> (out uint8 [n, stride], out_len int32 [n]) as encode_jpeg returns them.  Does not synchronise."""
-        torch = self.torch
-        self._bind_stream()
-        fmt, (n, H, W) = self._canvas_of(images)
-        if out is None:
-            out = torch.empty((n, int(min(self.L.avsim_jpeg_bound(H, W), (H * W * 3 // 2 + 4095) // 4096 * 4096))), dtype=torch.uint8, device=self.device)
-        if out_len is None:
-            out_len = torch.empty(n, dtype=torch.int32, device=self.device)
-        assert out.dtype == torch.uint8 and out.device == self.device and out.ndim == 2 and out.shape[0] == n and out.is_contiguous()
-        assert out_len.dtype == torch.int32 and out_len.device == self.device and tuple(out_len.shape) == (n,) and out_len.is_contiguous()
-        self.h.check(self.L.avsim_jpeg_encode(self.h.h, images.data_ptr(), fmt, None, n, H, W, int(quality), out.data_ptr(), int(out.shape[1]), out_len.data_ptr()))
-        return out, out_len
-
-    def _canvas_of(self, t):
-        torch = self.torch
-        assert isinstance(t, torch.Tensor) and t.device == self.device and t.is_contiguous() and t.ndim == 4, "a contiguous 4-D tensor on the env's device"
-        if t.dtype == torch.uint8 and t.shape[3] == 3:
-            return 0, (int(t.shape[0]), int(t.shape[1]), int(t.shape[2]))
-        if t.dtype == torch.float32 and t.shape[1] == 3:
-            return 1, (int(t.shape[0]), int(t.shape[2]), int(t.shape[3]))
-        raise ValueError("compose: images are uint8 [n, H, W, 3] or float32 [n, 3, H, W]")
-
-    def _compose_check(self, rc):
-        if rc == -1:          # AVSIM_EINVAL: nothing was launched
-            raise ValueError(self.L.avsim_last_error(self.h.h).decode())
-        self.h.check(rc)
-
-    def compose(self, src, places, out=None, canvas_hw=None, nout=None, clear=None, fmt=None):
-        """Images resampled into rectangles of a canvas (avsim_compose; av_aloha_amd.compose.compose_reference's pixels).  src: a tensor on
-        the env's device, uint8 [n, H, W, 3] or float32 [n, 3, H, W] -- an observation of this env, a decode_jpeg result --; places: HOST int
-        rows (out image, src image, x0, y0, w, h), checked on the host (ValueError).  out: the canvas tensor (either format), written in
-        place; None: one of canvas_hw = (CH, CW) and nout images is allocated in format fmt ("gym" u8 HWC, the default, or "lerobot" float32
-        CHW) and cleared.  clear: 0xRRGGBB to fill the canvas with first.  Does not synchronise."""
-        torch = self.torch
-        self._bind_stream()
-        p = np.ascontiguousarray(places, dtype=np.int32).reshape(-1, 6)
-        sf, (n, H, W) = self._canvas_of(src)
-        if out is None:
-            if canvas_hw is None:
-                raise ValueError("compose: give a canvas (out=...) or its size (canvas_hw=...)")
-            if fmt not in (None, "gym", "lerobot"):
-                raise ValueError(f"fmt {fmt!r}: 'lerobot' or 'gym'")
-            nout = int(p[:, 0].max()) + 1 if nout is None and len(p) else int(nout or 1)
-            CH, CW = int(canvas_hw[0]), int(canvas_hw[1])
-            out = torch.empty((nout, 3, CH, CW), dtype=torch.float32, device=self.device) if fmt == "lerobot" else \
-                torch.empty((nout, CH, CW, 3), dtype=torch.uint8, device=self.device)
-            clear = 0 if clear is None else clear
-        df, (no, CH, CW) = self._canvas_of(out)
-        self._compose_check(self.L.avsim_compose(self.h.h, src.data_ptr(), sf, n, H, W, out.data_ptr(), df, no, CH, CW, p.ctypes.data, len(p),
-                                                0 if clear is None else 1, int(clear or 0) & 0xFFFFFF))
-        return out
-
-    def compose_label(self, canvas, where, prefix="", values=None, rgb=0xFFFFFF):
-        """prefix + the decimal digits of values[i] painted at where[i] = (out image, x, y, scale) (avsim_compose_label;
-        av_aloha_amd.compose.label_reference's pixels).  values: an int64 tensor [len(where)] on the env's device -- info["episode_id"], read by
-        the kernel --, or None: the prefix alone; where: HOST rows.  Writes the canvas in place; does not synchronise."""
-        torch = self.torch
-        self._bind_stream()
-        df, (no, CH, CW) = self._canvas_of(canvas)
-        w = np.ascontiguousarray(where, dtype=np.int32).reshape(-1, 4)
-        if values is not None:
-            assert isinstance(values, torch.Tensor) and values.dtype == torch.int64 and values.device == self.device and tuple(values.shape) == (len(w),) \
-                and values.is_contiguous(), "compose_label(values=...): a contiguous int64 tensor on the env's device, one value per label"
-        self._compose_check(self.L.avsim_compose_label(self.h.h, canvas.data_ptr(), df, no, CH, CW, w.ctypes.data, len(w), prefix.encode("ascii", "replace"),
-                                                      _ffi.ptr(values), int(rgb) & 0xFFFFFF))
-        return canvas
-
-    def image_stats(self, img, index=None, out=None):
-        """(sum, sum of squares, min, max) of the u8 values per image and channel (avsim_image_stats; av_aloha_amd.imgprep.stats_reference's
-        integers): img a tensor on the env's device, uint8 [n, H, W, 3] or float32 [n, 3, H, W]; index: an int32 tensor there, the images to
-        reduce in this order (values outside [0, n) are clamped), None: all.  -> int64 [m, 3, 4] on the device (the values are below 2^63).
-        Does not synchronise."""
-        torch = self.torch
-        self._bind_stream()
-        sf, (n, H, W) = self._canvas_of(img)
-        if index is not None:
-            assert isinstance(index, torch.Tensor) and index.dtype == torch.int32 and index.device == self.device and index.ndim == 1, \
-                "image_stats(index=...): an int32 index tensor on the env's device"
-            index = index.clamp(0, n - 1).contiguous()
-        m = n if index is None else int(index.shape[0])
-        if out is None:
-            out = torch.empty((m, 3, 4), dtype=torch.int64, device=self.device)
-        assert out.dtype == torch.int64 and out.device == self.device and tuple(out.shape) == (m, 3, 4) and out.is_contiguous()
-        self._compose_check(self.L.avsim_image_stats(self.h.h, img.data_ptr(), sf, _ffi.ptr(index), m, H, W, out.data_ptr()))
-        return out
-
-    def prep_images(self, img, lut, box, out_hw, lut_index=None, src_index=None, out=None):
-        """Crops of img, mirrored where box says so, every channel through a table (avsim_image_prep; av_aloha_amd.imgprep.prep_reference's
-        bits).  img: a tensor on the env's device, uint8 [n, H, W, 3] or float32 [n, 3, H, W] -- an observation, a decode_jpeg result --; lut:
-        a float32 tensor [nlut, 3, 256] (or [3, 256]) there; box: HOST int rows (x0, y0, flip), one per output; lut_index / src_index: HOST
-        int arrays, the table / the source image of every output (None: table 0 / image i), all checked on the host (ValueError) and copied
-        by the library before the call returns.  -> float32 [nout, 3, oh, ow] on the device (out: the tensor to write).  Does not synchronise."""
-        torch = self.torch
-        self._bind_stream()
-        sf, (n, H, W) = self._canvas_of(img)
-        assert isinstance(lut, torch.Tensor) and lut.dtype == torch.float32 and lut.device == self.device and lut.is_contiguous() \
-            and lut.numel() % 768 == 0 and tuple(lut.shape[-2:]) == (3, 256), "prep_images(lut=...): a contiguous float32 [nlut, 3, 256] tensor on the env's device"
-        b = np.ascontiguousarray(box, dtype=np.int32).reshape(-1, 3)
-        li = None if lut_index is None else np.ascontiguousarray(lut_index, dtype=np.int32).reshape(len(b))
-        si = None if src_index is None else np.ascontiguousarray(src_index, dtype=np.int32).reshape(len(b))
-        oh, ow = int(out_hw[0]), int(out_hw[1])
-        if out is None:
-            out = torch.empty((len(b), 3, max(oh, 0), max(ow, 0)), dtype=torch.float32, device=self.device)
-        assert out.dtype == torch.float32 and out.device == self.device and tuple(out.shape) == (len(b), 3, oh, ow) and out.is_contiguous()
-        self._compose_check(self.L.avsim_image_prep(self.h.h, img.data_ptr(), sf, n, H, W, lut.data_ptr(), lut.numel() // 768, _ffi.ptr(li), b.ctypes.data,
-                                                    len(b), _ffi.ptr(si), oh, ow, out.data_ptr()))
-        return out
-
-    def jitter_images(self, img, params, out_hw, mean=None, std=None, src_index=None, out=None):
-        """Brightness, contrast, saturation, hue and sharpness jitter of img, cropped, mirrored and normalised in one pass (avsim_image_jitter;
-        av_aloha_amd.imgaug.jitter_reference's bits).  img: a uint8 [n, H, W, 3] tensor on the env's device -- an observation, a decode_jpeg
-        result --; params: HOST imgaug.PARAMS_DTYPE rows or the pair (int32 [nout, 4] = (x0, y0, flip, mask), float32 [nout, 5]); mean / std:
-        three HOST values each, or None: the output stays in [0, 1]; src_index: a HOST int array, the source image of every output (None: image
-        i).  All host arrays are checked (ValueError) and copied by the library before the call returns.  -> float32 [nout, 3, oh, ow] on the
-        device (out: the tensor to write).  Does not synchronise."""
-        from . import imgaug
-        torch = self.torch
-        self._bind_stream()
-        assert isinstance(img, torch.Tensor) and img.dtype == torch.uint8 and img.device == self.device and img.ndim == 4 and img.shape[3] == 3 \
-            and img.is_contiguous(), "jitter_images(img=...): a contiguous uint8 [n, H, W, 3] tensor on the env's device"
-        n, H, W = (int(v) for v in img.shape[:3])
-        bm, fac = imgaug.split_params(params)
-        si = None if src_index is None else np.ascontiguousarray(src_index, dtype=np.int32).reshape(len(bm))
-        ms = imgaug.mean_std(mean, std)
-        oh, ow = int(out_hw[0]), int(out_hw[1])
-        if out is None:
-            out = torch.empty((len(bm), 3, max(oh, 0), max(ow, 0)), dtype=torch.float32, device=self.device)
-        assert out.dtype == torch.float32 and out.device == self.device and tuple(out.shape) == (len(bm), 3, oh, ow) and out.is_contiguous()
-        self._compose_check(self.L.avsim_image_jitter(self.h.h, img.data_ptr(), n, H, W, bm.ctypes.data, fac.ctypes.data, _ffi.ptr(si), len(bm), _ffi.ptr(ms), oh, ow,
-                                                      out.data_ptr()))
-        return out
 
     def check_render_overflow(self):
         """Overflow flags of the last colour render (bit 0 triangle records, bit 1 tile lists; 0 = complete images): warns when set.
@@ -460,12 +281,6 @@ class VecEnv:
             warnings.warn(f"vector env: a view ran out of triangle records / tile-list entries (flags {int(info[2])}): triangles were "
                           "dropped from some images", RuntimeWarning, stacklevel=2)
         return int(info[2])
-
-    def close(self):
-        if getattr(self, "h", None) is not None:
-            self.h.check(self.L.avsim_sync(self.h.h))
-            self.h.close()
-            self.h = None
 
 
 def make_vec(env_id, num_envs, max_episode_steps, device=None, cameras=None, depth_cameras=(), obs_format="lerobot", seed=0,

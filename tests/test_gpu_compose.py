@@ -300,6 +300,95 @@ def test_vec_env_compose():
         env.close()
 
 
+DEVICE_IMAGES_ALONE = r"""
+import numpy as np
+import torch
+from av_aloha_amd import compose, imgaug, imgprep, jpeg
+from av_aloha_amd.images import DeviceImages
+from av_aloha_amd.vec_env import make_vec
+
+H, W, Q = 37, 53, 90
+yy, xx = np.mgrid[0:H, 0:W]
+u8 = np.stack([np.stack([(4 * xx + 40 * i) % 256, (5 * yy + 9 * i) % 256, (xx + yy + 30 * i) % 256], -1) for i in range(2)]).astype(np.uint8)
+u8 ^= np.random.default_rng(0).integers(0, 8, u8.shape, dtype=np.uint8)
+places = [(0, 0, 3, 1, W, H), (0, 1, 60, 2, 40, 30)]                   # a copy and a shrink, side by side on a 40 x 120 canvas
+where, values, rgb = [(0, 5, 30, 1), (0, 62, 3, 2)], np.array([7, 123456], np.int64), 0x40FF80
+box, mean, std = [(3, 2, 0), (13, 13, 1)], [0.4, 0.5, 0.6], [0.2, 0.25, 0.3]      # the second box flipped, flush with the corner
+lut = np.ascontiguousarray(imgprep.normalise_lut(mean, std), dtype=np.float32)
+params = (np.array([b[:2] + (b[2], 31) for b in box], np.int32), np.array([[1.2, 0.7, 1.4, 0.1, 1.8], [0.6, 1.5, 0.3, -0.2, 0.4]], np.float32))
+
+# the numpy specifications, once
+streams = [jpeg.encode_reference(f, Q) for f in u8]
+dec = np.stack([jpeg.decode_reference(x) for x in streams])
+want = {"gym": dec, "lerobot": dec.transpose(0, 3, 1, 2).astype(np.float32) / np.float32(255),
+        "canvas": compose.compose_reference(np.zeros((1, 40, 120, 3), np.uint8), dec, places)}
+want["label"] = compose.label_reference(want["canvas"].copy(), where, "E", values, rgb)
+want["stats"] = imgprep.stats_reference(want["label"])
+want["prep"] = imgprep.prep_reference(dec, lut, None, box, (24, 40))
+want["jitter"] = imgaug.jitter_reference(dec, params, (24, 40), mean=mean, std=std)
+
+ops = DeviceImages()                                                     # no env, no other handle: it brings torch's GPU up itself
+dev = ops.device
+t_u8, t_values, t_lut = (torch.from_numpy(a).to(dev) for a in (u8, values, lut))
+
+
+def chain():
+    out, ln = ops.encode_images(t_u8, Q)
+    got = {"lerobot": ops.decode_jpeg(out, ln, height=H, width=W), "gym": ops.decode_jpeg(out, ln, height=H, width=W, fmt="gym")}
+    img = got["gym"][0]
+    got["canvas"] = ops.compose(img, places, canvas_hw=(40, 120)).clone()
+    got["label"] = ops.compose_label(got["canvas"].clone(), where, "E", t_values, rgb)
+    got["stats"] = ops.image_stats(got["label"])
+    got["prep"] = ops.prep_images(img, t_lut, box, (24, 40))
+    got["jitter"] = ops.jitter_images(img, params, (24, 40), mean=mean, std=std)
+    n = ln.cpu().numpy()
+    assert n.max() <= out.shape[1]
+    assert [out[i, :n[i]].cpu().numpy().tobytes() for i in range(2)] == streams
+    for k in ("lerobot", "gym"):
+        assert not got[k][1].cpu().numpy().any()
+        got[k] = got[k][0]
+    for k, w in want.items():
+        g = got[k].cpu().numpy()
+        assert g.dtype == (np.int64 if k == "stats" else w.dtype) and g.shape == w.shape, k
+        assert np.array_equal(g.view(w.dtype), w), k                      # (nothing here is a nan: bit for bit)
+
+
+side = torch.cuda.Stream(device=dev)
+side.wait_stream(torch.cuda.current_stream(dev))
+with torch.cuda.stream(side):
+    chain()
+    assert ops._stream.cuda_stream == side.cuda_stream
+side.synchronize()
+chain()                                                                  # torch's current stream changed: the handle follows it
+assert ops._stream.cuda_stream == torch.cuda.current_stream(dev).cuda_stream != side.cuda_stream
+try:
+    ops.decode_jpeg(*ops.encode_images(t_u8, Q))                          # no observation size to default to
+    raise AssertionError("decode_jpeg without a size went through")
+except ValueError:
+    pass
+ops.close()
+ops.close()
+
+env = make_vec("gym_guided_vision/InsertPeg-3Arms-v0", num_envs=2, max_episode_steps=5, cameras=[])
+obs, info = env.reset(seed=1)
+obs, reward, terminated, truncated, info = env.step(obs["observation.state"].clone())
+assert info["elapsed_steps"].tolist() == [1, 1] and bool(torch.isfinite(obs["observation.state"]).all())
+env.close()
+print("device images alone: ok")
+"""
+
+
+def test_device_images_without_an_env():
+    """images.DeviceImages in a process of its own, where no env and no other handle exists: the seven image calls on a side stream and then on
+    torch's default stream, every result equal to its numpy specification bit for bit; close() twice; a VecEnv made afterwards steps."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([root, os.environ.get("PYTHONPATH", "")]))
+    p = subprocess.run([sys.executable, "-c", DEVICE_IMAGES_ALONE], capture_output=True, text=True, env=env, cwd=root, timeout=300)
+    assert p.returncode == 0 and "device images alone: ok" in p.stdout, p.stdout + p.stderr
+
+
 def synthetic_episode(seed, T=3):
     rng = np.random.default_rng(seed)
     yy, xx = np.mgrid[0:36, 0:48]

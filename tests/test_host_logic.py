@@ -144,6 +144,37 @@ def test_data_collection_model_variant():
             assert len(changed) > 0 and all(g in a["pair_geom"].reshape(-1, 2)[p] for p in changed)                      # only pairs of that geom
 
 
+def test_image_layout_and_check_call():
+    """images.layout reads the two image formats off anything with dtype / shape / ndim; images.check_call turns the library's "refused,
+    nothing launched" (-1) into a ValueError that carries its message."""
+    from av_aloha_amd import images
+    assert images.layout(np.zeros((2, 5, 7, 3), np.uint8)) == (0, 2, 5, 7)
+    assert images.layout(np.zeros((4, 3, 5, 7), np.float32)) == (1, 4, 5, 7)
+    assert images.layout(np.zeros((3, 3, 5, 3), np.uint8)) == (0, 3, 3, 5) and images.layout(np.zeros((3, 3, 5, 3), np.float32)) == (1, 3, 5, 3)
+    for bad in (np.zeros((5, 7, 3), np.uint8), np.zeros((2, 5, 7, 4), np.uint8), np.zeros((2, 4, 5, 7), np.float32), np.zeros((2, 5, 7, 3), np.float64)):
+        with pytest.raises(ValueError):
+            images.layout(bad)
+
+    class FakeLib:
+        @staticmethod
+        def avsim_last_error(h):
+            return b"avsim_compose: place 0 lies outside the canvas"
+
+    class FakeHandle:
+        L, h, checked = FakeLib, object(), []
+
+        def check(self, rc):
+            self.checked.append(rc)
+
+    handle = FakeHandle()
+    with pytest.raises(ValueError, match="avsim_compose: place 0 lies outside the canvas"):
+        images.check_call(handle, -1)
+    assert handle.checked == []
+    assert images.check_call(handle, 0) is None and handle.checked == [0]
+    images.check_call(handle, -3)                     # every other status is Handle.check's to raise
+    assert handle.checked == [0, -3]
+
+
 def test_bench_gpus_flag_refuses_a_node_with_fewer_gpus():
     """bench.py --gpus N starts N ranks itself (one process per GPU); on a node with fewer GPUs it must fail loudly and
     print no line (it used to ignore the flag and report n_gpus: 1)."""
