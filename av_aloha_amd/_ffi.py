@@ -79,6 +79,11 @@ def lib():
         L.avsim_episode_step.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
         L.avsim_episode_log.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp]
         L.avsim_episode_count.argtypes = [vp, vp]
+        L.avsim_chunk_setup.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
+        L.avsim_chunk_reset.argtypes = [vp]
+        L.avsim_chunk_need.argtypes = [vp, vp, vp, vp, vp]
+        L.avsim_chunk_step.argtypes = [vp, vp, vp, vp, vp]
+        L.avsim_chunk_starved.argtypes = [vp, vp]
         L.avsim_sync.argtypes = [vp]
         L.avsim_set_stream.argtypes = [vp, vp]
         L.avsim_event_record.argtypes = [vp, i32]

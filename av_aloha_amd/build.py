@@ -18,8 +18,9 @@ def _stale(target, sources):
 
 def build_hip(force=False, verbose=False):
     """hipcc --offload-arch=gfx950: avsim_api.hip (C-ABI, f32 product kernels, IK, render), avsim_phys_spec.hip (the f32 physics
-    kernel specialised per model), avsim_phys_f64.hip (the f64 parity kernel, -ffp-contract=off so that it rounds like the oracle) and
-    avsim_imgaug.hip (the image augmentation, which rounds like its numpy specification) compiled side by side, linked into libavsim.so."""
+    kernel specialised per model), avsim_phys_f64.hip (the f64 parity kernel, -ffp-contract=off so that it rounds like the oracle) ,
+    avsim_imgaug.hip (the image augmentation, which rounds like its numpy specification) and avsim_chunks.hip (the execution of action
+    chunks, likewise) compiled side by side, linked into libavsim.so."""
     srcs = [os.path.join(SRC, f) for f in sorted(os.listdir(SRC)) if not f.endswith(".o") and not f.startswith(".")] + [os.path.join(ROOT, "include", "avsim.h"), os.path.abspath(__file__)]       # (this file holds the flags: a library built with other flags is stale too)
     if not force and not _stale(LIB, srcs):
         return LIB
@@ -62,6 +63,8 @@ def _build_hip_locked(verbose):
         # x / y the IEEE sequence v_div_scale / v_rcp / v_fma x 4 / v_div_fmas / v_div_fixup; -fno-gpu-flush-denormals-to-zero (also the default for
         # gfx950) keeps f32 denormals: the kernels' descriptors carry float_denorm_mode_32 = 3 and the division needs no mode switch
         ("avsim_imgaug", ["-O3", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-gpu-flush-denormals-to-zero"] + os.environ.get("AVSIM_EXTRA_FLAGS_IMGAUG", "").split()),
+        # the execution of action chunks equals ITS numpy specification (av_aloha_amd/chunks.py) bit for bit: the same flags for the same reasons
+        ("avsim_chunks", ["-O3", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-gpu-flush-denormals-to-zero"] + os.environ.get("AVSIM_EXTRA_FLAGS_CHUNKS", "").split()),
     ]
     procs = []
     for name, extra in units:

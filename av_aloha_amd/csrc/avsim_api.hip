@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/avsim.h"
+#include "avsim_chunks.hip.h"
 #include "avsim_compose.hip.h"
 #include "avsim_imgprep.hip.h"
 #include "avsim_imgaug.hip.h"
@@ -84,6 +85,7 @@ struct avsim {
     ComposeHost compose; // views resampled into a canvas, labels (avsim_compose.hip.h): coefficient tables per size pair, the validated placements
     StageRing stage;     // the pinned staging of a call's host arrays (avsim_stage.h): avsim_image_prep's and avsim_image_jitter's
     ImgAugHost imgaug;   // colour and sharpness jitter (avsim_imgaug.hip.h): the gray sums behind contrast
+    ChunkHost chunks;    // per-env execution of action chunks (avsim_chunks.hip.h), once avsim_chunk_setup has run
     bool jpegdec_events = false;   // option "jpeg_decode_events": avsim_jpeg_decode records ev[12..15] around its three kernels
     // the state's version: bumped by everything that writes qpos (reset, the steps, set_state); the image calls skip their pose pass and the shadow
     // map when they already hold this version's (a facade that fetches its cameras one call at a time repeats neither)
@@ -481,6 +483,7 @@ void avsim_destroy(avsim_t* h) {
     h->compose.destroy();
     h->stage.destroy();
     h->imgaug.destroy();
+    h->chunks.destroy();
     for (void* p : {h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, (void*)h->d_latch})
         if (p) (void)hipFree(p);
     for (void* p : h->d_io)
@@ -1451,6 +1454,82 @@ int avsim_episode_count(avsim_t* h, int64_t count[2]) {
     bool host = false;
     if ((rc = ep_copy(h, count, h->ep.count, 2 * sizeof(int64_t), &host))) return rc;
     if (host) HIPCHK(h, hipStreamSynchronize(h->stream));
+    return AVSIM_OK;
+}
+
+}  // extern "C"
+
+// ---- per-env execution of action chunks (av_aloha_amd/chunks.py is the specification; the kernels: csrc/avsim_chunks.hip, a unit of its own flags) ----
+extern "C" {
+
+int avsim_chunk_setup(avsim_t* h, int chunk_size, int action_dim, int mode, int n_action_steps, int first, const float* tables, const float* mean_std) {
+    if (!h) return AVSIM_EINVAL;
+    {
+        std::string why;
+        if (chunk_validate(chunk_size, action_dim, mode, n_action_steps, first, tables, mean_std, why)) { h->set_error("%s", why.c_str()); return AVSIM_EINVAL; }
+    }
+    AVS_ON_DEVICE(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // (buffers of an earlier set-up may still be in use)
+    if (h->chunks.setup(h->stream, h->N, chunk_size, action_dim, mode, n_action_steps, first, tables, mean_std, h->err)) return AVSIM_EHIP;
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // (the tables are on the device: the caller's arrays are free)
+    return AVSIM_OK;
+}
+
+int avsim_chunk_reset(avsim_t* h) {
+    if (!h) return AVSIM_EINVAL;
+    if (!h->chunks.ready) { h->set_error("avsim_chunk_reset: call avsim_chunk_setup first"); return AVSIM_EINVAL; }
+    AVS_ON_DEVICE(h);
+    HIPCHK(h, hipMemsetAsync(h->chunks.P.stepped, 0, sizeof(int) * (size_t)h->N, h->stream));
+    return h->finish();
+}
+
+int avsim_chunk_need(avsim_t* h, const int64_t* episode_id, const int32_t* elapsed, uint8_t* need, int32_t* any) {
+    if (!h) return AVSIM_EINVAL;
+    if (!h->chunks.ready) { h->set_error("avsim_chunk_need: call avsim_chunk_setup first"); return AVSIM_EINVAL; }
+    if (!episode_id || !elapsed) { h->set_error("avsim_chunk_need: episode_id and elapsed are required"); return AVSIM_EINVAL; }
+    AVS_ON_DEVICE(h);
+    const size_t N = h->N;
+    int rc;
+    const void *did, *del;
+    void *dn = nullptr, *da = nullptr;
+    if ((rc = h->in(1, episode_id, sizeof(int64_t) * N, &did))) return rc;
+    if ((rc = h->in(2, elapsed, sizeof(int32_t) * N, &del))) return rc;
+    if (need && (rc = h->out_begin(5, need, N, &dn))) return rc;
+    if (any && (rc = h->out_begin(6, any, sizeof(int32_t), &da))) return rc;
+    chunk_launch_book(h->stream, h->chunks.P, 0, 0, (const int64_t*)did, (const int*)del, (uint8_t*)dn, (int*)da);
+    HIPCHK(h, hipGetLastError());
+    if ((rc = h->out_end(5, need, N))) return rc;
+    if ((rc = h->out_end(6, any, sizeof(int32_t)))) return rc;
+    return h->finish();
+}
+
+int avsim_chunk_step(avsim_t* h, const float* chunks, const int64_t* episode_id, const int32_t* elapsed, float* action) {
+    if (!h) return AVSIM_EINVAL;
+    if (!h->chunks.ready) { h->set_error("avsim_chunk_step: call avsim_chunk_setup first"); return AVSIM_EINVAL; }
+    if (!episode_id || !elapsed || !action) { h->set_error("avsim_chunk_step: episode_id, elapsed and action are required"); return AVSIM_EINVAL; }
+    const ChunkArgs& P = h->chunks.P;
+    if (!chunks && P.mode == CHK_ENSEMBLE) { h->set_error("avsim_chunk_step: ensemble mode needs a chunk in every call"); return AVSIM_EINVAL; }
+    AVS_ON_DEVICE(h);
+    const size_t N = h->N;
+    int rc;
+    const void *dc = nullptr, *did, *del;
+    void* dact;
+    if (chunks && (rc = h->in(0, chunks, sizeof(float) * N * P.CA, &dc))) return rc;
+    if ((rc = h->in(1, episode_id, sizeof(int64_t) * N, &did))) return rc;
+    if ((rc = h->in(2, elapsed, sizeof(int32_t) * N, &del))) return rc;
+    if ((rc = h->out_begin(4, action, sizeof(float) * N * P.A, &dact))) return rc;
+    chunk_launch_step(h->stream, P, (const float*)dc, (const int64_t*)did, (const int*)del, (float*)dact);
+    HIPCHK(h, hipGetLastError());
+    if ((rc = h->out_end(4, action, sizeof(float) * N * P.A))) return rc;
+    return h->finish();
+}
+
+int avsim_chunk_starved(avsim_t* h, uint64_t* count) {
+    if (!h || !count) return AVSIM_EINVAL;
+    if (!h->chunks.ready) { h->set_error("avsim_chunk_starved: call avsim_chunk_setup first"); return AVSIM_EINVAL; }
+    AVS_ON_DEVICE(h);
+    HIPCHK(h, hipMemcpyAsync(count, h->chunks.P.starved, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return AVSIM_OK;
 }
 

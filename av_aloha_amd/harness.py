@@ -315,6 +315,36 @@ def make_preprocessor(venv, stats, crop=None):
     return pre
 
 
+def chunked_policy(venv, predict_chunk, chunk_size, ensemble=None, n_action_steps=None, first=0, stats=None, predict="when_needed"):
+    """(select_action, executor) for evaluate_vec and a policy that predicts action CHUNKS (ACT, diffusion policies trained by
+    dataset.TrainingBatches(chunk_size=...)): predict_chunk(obs, info) -> float32 [N, chunk_size, nj] on the env's device, normalised when
+    `stats` (CompressedDataset.stats()'s) are given.  The executor (chunks.ActionChunks on venv) keeps the state PER ENV and starts an env's
+    state anew when its episode does (a new info["episode_id"] or elapsed_steps 0), which a policy's own select_action with one queue or one
+    ensembler for the batch does not: that is only right while all envs' episodes are in phase.
+    ensemble = a coefficient (ACT's 0.01): LeRobot's temporal ensembling; predict_chunk runs in every call and nothing synchronises.
+    ensemble None: a queue of n_action_steps (default chunk_size) rows from row `first` (a diffusion policy: n_obs_steps - 1).  predict =
+    "when_needed": predict_chunk runs, for the whole batch, only in the calls where some env needs a chunk; select_action reads the executor's
+    4-byte `any` flag to know -- the ONE synchronisation per call of this function.  predict = "always": it runs in every call, the envs
+    that need no chunk ignore theirs, and nothing synchronises.  Neither setting can starve an env (executor.starved() stays 0).
+    An evaluation's first call sees elapsed_steps 0 everywhere and so starts every env afresh; select_action cannot check that without a
+    synchronisation and does not try: call executor.reset() before evaluate_vec when the executor has run before -- the explicit form of it."""
+    from .chunks import ActionChunks
+    if predict not in ("when_needed", "always"):
+        raise ValueError(f"predict {predict!r}: 'when_needed' or 'always'")
+    executor = ActionChunks(venv, chunk_size, None, ensemble, n_action_steps, first, stats)
+    ask = ensemble is None and predict == "when_needed"
+
+    def select_action(obs, info):
+        if ask:
+            _, flag = executor.need(info)
+            chunks = predict_chunk(obs, info) if int(flag.item()) else None          # (.item() waits for the stream)
+        else:
+            chunks = predict_chunk(obs, info)
+        return executor.step(chunks, info)
+
+    return select_action, executor
+
+
 def record_episode(env, actions23) -> dict:
     """Steps a Cartesian-action env (av_aloha_amd.sim_env) through `actions23` [T-1, 23] and returns the episode arrays."""
     ts = env.get_obs()

@@ -352,6 +352,55 @@ class BatchedSim:
         images.check_call(self.h, self.h.L.avsim_image_jitter_sums(self.h.h, sums.ctypes.data, int(nout)))
         return sums
 
+    def chunk_setup(self, chunk_size, action_dim=None, ensemble=None, n_action_steps=None, first=0, mean=None, std=None):
+        """Per-env execution of action chunks on host arrays (avsim_chunk_setup; av_aloha_amd.chunks is the specification and
+        chunks.ActionChunks the torch front): ensemble None -> a queue of n_action_steps (default chunk_size) rows from row `first`, a
+        coefficient -> temporal ensembling with chunks.ensemble_tables; mean / std un-normalise the chunks.  ValueError for what the library
+        refuses.  -> the keyword arguments of a chunks.ChunkReference(N, C, A, ...) of the same set-up."""
+        from . import chunks
+        C, A = int(chunk_size), int(self.nj if action_dim is None else action_dim)
+        if ensemble is None:
+            mode, tables, n_action_steps = "queue", None, (C if n_action_steps is None else n_action_steps)
+        else:
+            mode, tables = "ensemble", (chunks.ensemble_tables(C, ensemble) if 1 <= C <= chunks.MAX_CHUNK else None)
+        ms = chunks.mean_std(mean, std, A)
+        images.check_call(self.h, self.h.L.avsim_chunk_setup(self.h.h, C, A, chunks.MODES[mode], int(n_action_steps or 0), int(first), _ffi.ptr(tables), _ffi.ptr(ms)))
+        self._chunk_shape = (C, A)
+        return dict(mode=mode, tables=tables, n_action_steps=n_action_steps, first=first, mean=None if ms is None else ms[0], std=None if ms is None else ms[1])
+
+    def _chunk_ids(self, episode_id, elapsed):
+        eid = np.ascontiguousarray(episode_id, dtype=np.int64).reshape(self.N)
+        return eid, np.ascontiguousarray(elapsed, dtype=np.int32).reshape(self.N)
+
+    def chunk_need(self, episode_id, elapsed):
+        """(need bool [N], any bool): the envs that need a chunk in the next chunk_step given these ids and elapsed steps (avsim_chunk_need)."""
+        eid, el = self._chunk_ids(episode_id, elapsed)
+        need, flag = np.zeros(self.N, dtype=np.uint8), np.zeros(1, dtype=np.int32)
+        images.check_call(self.h, self.h.L.avsim_chunk_need(self.h.h, eid.ctypes.data, el.ctypes.data, need.ctypes.data, flag.ctypes.data))
+        return need.astype(bool), bool(flag[0])
+
+    def chunk_step(self, chunks, episode_id, elapsed):
+        """float32 [N, A]: the actions of this call (avsim_chunk_step).  chunks: float32 [N, C, A], or None in queue mode."""
+        if not hasattr(self, "_chunk_shape"):
+            raise ValueError("chunk_step: call chunk_setup first")
+        C, A = self._chunk_shape
+        eid, el = self._chunk_ids(episode_id, elapsed)
+        if chunks is not None:
+            chunks = np.ascontiguousarray(chunks, dtype=np.float32)
+            if chunks.shape != (self.N, C, A):
+                raise ValueError(f"chunk_step: chunks of shape {chunks.shape}, expected {(self.N, C, A)}")
+        action = np.zeros((self.N, A), dtype=np.float32)
+        images.check_call(self.h, self.h.L.avsim_chunk_step(self.h.h, _ffi.ptr(chunks), eid.ctypes.data, el.ctypes.data, action.ctypes.data))
+        return action
+
+    def chunk_reset(self):
+        images.check_call(self.h, self.h.L.avsim_chunk_reset(self.h.h))
+
+    def chunk_starved(self):
+        c = np.zeros(1, dtype=np.uint64)
+        images.check_call(self.h, self.h.L.avsim_chunk_starved(self.h.h, c.ctypes.data))
+        return int(c[0])
+
     def reward_from_pairs(self, geom_pairs, latch=None):
         """The task's get_reward (env.py:425-863) on explicit contact lists: geom_pairs int [nsets, cap, 2] (collision
         geom ids, negative = empty slot); latch int32 [nsets] is updated in place.  Returns int32 [nsets]."""

@@ -11,7 +11,8 @@ per-env episodes and gymnasium's NEXT_STEP autoreset done by the library's kerne
 * Every tensor returned is a preallocated buffer that the next reset / step overwrites: clone what must outlive the call.
 * NEXT_STEP: an env whose episode ended (terminated or truncated) in call t starts its next episode in call t + 1, whose action does
   not reach it; that call reports reward 0, flags 0, elapsed 0, the new `info["episode_id"]` and the new episode's first observation.
-  A change of an env's episode id is the signal for per-env policy state.
+  A change of an env's episode id is the signal for per-env policy state (chunks.ActionChunks / harness.chunked_policy keep a chunked
+  policy's queue or temporal ensembler per env on the device and restart it on that signal).
 * Initial object poses come from Philox4x32-10 keyed by (seed, episode id) inside the library (OBJECT_BOXES below), not from the global
   numpy RNG that env.py's sample_object_poses consumes like the reference: an episode's poses do not depend on the batch size.
 * torch's GPU must be initialised in the process before the first libavsim handle is created (torch ships its own HIP runtime

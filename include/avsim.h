@@ -366,6 +366,35 @@ int avsim_episode_log(avsim_t* h, int64_t n, double* ret, int32_t* length, int32
 /* count = {episodes started, episodes finished} since avsim_episode_setup */
 int avsim_episode_count(avsim_t* h, int64_t count[2]);
 
+/* Per-env execution of a policy's action chunks on the device (csrc/avsim_chunks.hip); av_aloha_amd/chunks.py is the
+ * specification, and the calls equal it bit for bit.  One state per handle, sized to its num_envs.  A policy predicts chunks
+ * float [N][C][A] of normalised actions, row k of env i its action k steps from now; avsim_chunk_step turns them into the float [N][A]
+ * action of avsim_episode_step.  Env i is FRESH in a call when it has not been stepped since the set-up / avsim_chunk_reset, or
+ * elapsed[i] == 0, or episode_id[i] differs from the id the previous call saw: its state starts empty.  Every value is un-normalised first,
+ * y = x * std[a] + mean[a] (two float32 operations; mean_std NULL: y = x).
+ * mode 0, ensemble (LeRobot's ACTTemporalEnsembler, online): with u = the env's updates since fresh, for k in 0 .. C-1, c = min(u, C-1-k),
+ * slot j = (u + k) mod C: ens[j] = y[k] if c == 0, else (ens[j] * cum[c-1] + y[k] * w[c]) / cum[c], every operation a float32 one rounded
+ * on its own; the action is ens[u mod C].  tables = (w[C], cum[C]) are the caller's (chunks.ensemble_tables): the library computes no exp.
+ * mode 1, queue: an env NEEDS a chunk when it is fresh or its queue is empty; it then takes rows [first, first + n_action_steps) of its
+ * chunk and returns them one per call.  With chunks NULL such an env is STARVED: it repeats its previous action (zeros if fresh), its queue
+ * stays empty and the counter of avsim_chunk_starved goes up by one.  An env that does not need a chunk ignores the one given.
+ * avsim_chunk_setup: tables and mean_std are HOST arrays, copied before the call returns; everything is checked before anything is
+ * allocated or enqueued -- AVSIM_EINVAL: chunk_size outside 1..1024, action_dim outside 1..64, mode other than 0 / 1, queue: n_action_steps
+ * < 1, first < 0, first + n_action_steps > chunk_size; ensemble: tables NULL, an entry not finite, a cum[c] <= 0; a mean or std not finite.
+ * (Re)initialises the state: all envs unstepped, the starved counter 0.  Synchronises.  avsim_chunk_reset: all envs unstepped.
+ * avsim_chunk_need: need uint8 [N] and any int32 [1] (1 when some env needs; either may be NULL) from one kernel; changes no state; in
+ * ensemble mode every env needs a chunk in every call.  avsim_chunk_step: chunks NULL in ensemble mode, or any of these calls before the
+ * set-up, is AVSIM_EINVAL with nothing enqueued and the state untouched.  The array pointers of need / step follow the handle's I/O mode;
+ * the work goes on the handle's stream, and with AVSIM_IO_DEVICE neither synchronises.  avsim_chunk_starved: count is a HOST pointer;
+ * synchronises, like avsim_episode_count. */
+int avsim_chunk_setup(avsim_t* h, int chunk_size, int action_dim, int mode, int n_action_steps, int first,
+                      const float* tables /* host [2][C] or NULL */, const float* mean_std /* host [2][A] or NULL */);
+int avsim_chunk_reset(avsim_t* h);
+int avsim_chunk_need(avsim_t* h, const int64_t* episode_id, const int32_t* elapsed, uint8_t* need /* [N] */, int32_t* any /* [1] */);
+int avsim_chunk_step(avsim_t* h, const float* chunks /* [N][C][A] or NULL */, const int64_t* episode_id /* [N] */,
+                     const int32_t* elapsed /* [N] */, float* action /* [N][A] */);
+int avsim_chunk_starved(avsim_t* h, uint64_t* count);
+
 /* get_reward of the handle's task (gym_guided_vision/gym_guided_vision/env.py:425-863, five subclasses) evaluated on
  * caller-supplied contact lists instead of the simulator's own contacts: geom_pairs = int32[nsets][cap][2], ids into the
  * model's collision geom table (manifest "geom_names"), a slot with a negative id is empty.  The kernel applies the same

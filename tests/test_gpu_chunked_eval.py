@@ -1,0 +1,118 @@
+"""harness.chunked_policy under harness.evaluate_vec: five InsertPeg envs, episodes of six steps, twelve episodes, a deterministic chunk
+predictor.  Every call's chunks, ids, elapsed steps and returned action are recorded and replayed through the specification
+(av_aloha_amd.chunks.ChunkReference): the actions are equal bit for bit, no env starves, and in "when_needed" mode the predictor ran in exactly
+the calls the specification's need().any() names.
+
+Two envs are put out of phase by a masked reset before the run, as a user's code may leave them.  evaluate_vec itself starts every env anew
+(start_log, reset), which puts them back in phase, and with equal episode lengths they would stay there; so the recorder also does a masked
+reset DURING the run, in a call where the two envs hold episode ids past the twelve that are evaluated (an abandoned episode is never logged,
+and evaluate_vec waits for every id below twelve): from there on their episodes run two steps off the others'."""
+import numpy as np
+import pytest
+
+from av_aloha_amd import chunks as ck
+from av_aloha_amd.harness import chunked_policy, evaluate_vec
+from av_aloha_amd.vec_env import make_vec
+
+pytestmark = pytest.mark.gpu
+
+
+def _torch_runtime_first():
+    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
+    import torch as t
+    if t.cuda.is_available():
+        t.zeros(1, device="cuda")
+
+
+_torch_runtime_first()
+
+PEG = "gym_guided_vision/InsertPeg-3Arms-v0"
+N, STEPS, EPISODES, C = 5, 6, 12, 4
+RESET_AT, RESET_ENVS = 16, (3, 4)          # the 17th select_action call: every env holds an id in 10 .. 14, envs 3 and 4 those past 11
+
+
+@pytest.fixture(scope="module")
+def venv():
+    env = make_vec(PEG, N, STEPS, cameras=[])
+    yield env
+    env.close()
+
+
+def make_predictor(venv, log):
+    import torch
+    k = torch.arange(C, dtype=torch.float32, device=venv.device)[None, :, None]
+    a = torch.arange(venv.nj, dtype=torch.float32, device=venv.device)[None, None, :]
+
+    def predict_chunk(obs, info):
+        """a small wave around the current joint state, its phase set by the episode id: inside the joint ranges"""
+        state = obs["observation.state"][:, None, :]
+        x = (state + 0.02 * torch.sin(0.7 * k + 0.3 * a + 0.5 * info["episode_id"][:, None, None].to(torch.float32))).contiguous()
+        log["chunks"] = x.clone()
+        return x
+    return predict_chunk
+
+
+def evaluate(venv, **kw):
+    """-> (the executor, the records of evaluate_vec, one dict per select_action call)"""
+    import torch
+    log, calls = {}, []
+    venv.reset(seed=3)
+    mask = torch.zeros(N, dtype=torch.bool, device=venv.device)
+    mask[list(RESET_ENVS)] = True
+    venv.reset(options={"reset_mask": mask})
+    select, executor = chunked_policy(venv, make_predictor(venv, log), C, **kw)
+    executor.reset()
+
+    def recording(obs, info):
+        if len(calls) == RESET_AT:
+            venv.reset(options={"reset_mask": mask})          # (obs and info are the env's own buffers: they now hold the new episodes)
+        log["chunks"] = None
+        action = select(obs, info)
+        calls.append({"chunks": None if log["chunks"] is None else log["chunks"].cpu().numpy(), "ids": info["episode_id"].cpu().numpy().copy(),
+                      "elapsed": info["elapsed_steps"].cpu().numpy().copy(), "action": action.cpu().numpy().copy()})
+        return action
+    records = evaluate_vec(venv, recording, EPISODES, seed=3)
+    return executor, records, calls
+
+
+def replay(executor, calls, when_needed=False):
+    ref = executor.reference()
+    for t, c in enumerate(calls):
+        if when_needed:
+            assert (c["chunks"] is not None) == bool(ref.need(c["ids"], c["elapsed"]).any()), t
+        want = ref.step(c["chunks"], c["ids"], c["elapsed"])
+        assert c["action"].dtype == np.float32 and not np.isnan(c["action"]).any() and np.array_equal(c["action"], want), t
+    assert ref.starved == 0
+
+
+def check_run(records, calls):
+    assert len(records) == EPISODES and all(r["length"] == STEPS for r in records)
+    assert len(calls) > RESET_AT
+    assert all((c["ids"][list(RESET_ENVS)] >= EPISODES).all() for c in calls[RESET_AT - 1:RESET_AT])          # the abandoned episodes are not evaluated ones
+    assert any(len(set(c["elapsed"].tolist())) > 1 for c in calls), "the envs' episodes never ran out of phase"
+
+
+def test_ensemble(venv):
+    executor, records, calls = evaluate(venv, ensemble=0.01)
+    check_run(records, calls)
+    assert all(c["chunks"] is not None for c in calls)
+    replay(executor, calls)
+    assert executor.starved() == 0
+
+
+@pytest.mark.parametrize("predict", ["when_needed", "always"])
+def test_queue(venv, predict):
+    executor, records, calls = evaluate(venv, n_action_steps=3, predict=predict)
+    check_run(records, calls)
+    if predict == "always":
+        assert all(c["chunks"] is not None for c in calls)
+    else:
+        assert any(c["chunks"] is None for c in calls)
+    replay(executor, calls, when_needed=predict == "when_needed")
+    assert executor.starved() == 0
+
+
+def test_an_unknown_predict_setting_is_refused(venv):
+    with pytest.raises(ValueError):
+        chunked_policy(venv, lambda obs, info: None, C, predict="sometimes")
+    assert ck.MODES["queue"] == 1
