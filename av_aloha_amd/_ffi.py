@@ -84,6 +84,9 @@ def lib():
         L.avsim_chunk_need.argtypes = [vp, vp, vp, vp, vp]
         L.avsim_chunk_step.argtypes = [vp, vp, vp, vp, vp]
         L.avsim_chunk_starved.argtypes = [vp, vp]
+        L.avsim_obs_history_setup.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, vp, vp, i32, i32]
+        L.avsim_obs_history_reset.argtypes = [vp]
+        L.avsim_obs_history_push.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.avsim_sync.argtypes = [vp]
         L.avsim_set_stream.argtypes = [vp, vp]
         L.avsim_event_record.argtypes = [vp, i32]

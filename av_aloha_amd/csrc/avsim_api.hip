@@ -16,6 +16,7 @@
 #include "avsim_chunks.hip.h"
 #include "avsim_compose.hip.h"
 #include "avsim_imgprep.hip.h"
+#include "avsim_obshist.hip.h"
 #include "avsim_imgaug.hip.h"
 #include "avsim_episode.hip.h"
 #include "avsim_ik.hip.h"
@@ -86,6 +87,7 @@ struct avsim {
     StageRing stage;     // the pinned staging of a call's host arrays (avsim_stage.h): avsim_image_prep's and avsim_image_jitter's
     ImgAugHost imgaug;   // colour and sharpness jitter (avsim_imgaug.hip.h): the gray sums behind contrast
     ChunkHost chunks;    // per-env execution of action chunks (avsim_chunks.hip.h), once avsim_chunk_setup has run
+    ObsHistHost obshist; // per-env observation histories (avsim_obshist.hip.h), once avsim_obs_history_setup has run
     bool jpegdec_events = false;   // option "jpeg_decode_events": avsim_jpeg_decode records ev[12..15] around its three kernels
     // the state's version: bumped by everything that writes qpos (reset, the steps, set_state); the image calls skip their pose pass and the shadow
     // map when they already hold this version's (a facade that fetches its cameras one call at a time repeats neither)
@@ -484,6 +486,7 @@ void avsim_destroy(avsim_t* h) {
     h->stage.destroy();
     h->imgaug.destroy();
     h->chunks.destroy();
+    h->obshist.destroy();
     for (void* p : {h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, (void*)h->d_latch})
         if (p) (void)hipFree(p);
     for (void* p : h->d_io)
@@ -1531,6 +1534,73 @@ int avsim_chunk_starved(avsim_t* h, uint64_t* count) {
     HIPCHK(h, hipMemcpyAsync(count, h->chunks.P.starved, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return AVSIM_OK;
+}
+
+}  // extern "C"
+
+// ---- per-env observation histories (av_aloha_amd/obshist.py is the specification; the kernels: csrc/avsim_obshist.hip, a unit of its own flags) ----
+extern "C" {
+
+int avsim_obs_history_setup(avsim_t* h, int n_obs_steps, int state_dim, const float* state_mean_std, int ncam, int fmt, int height, int width, const float* lut,
+                            const int32_t* box, int out_h, int out_w) {
+    if (!h) return AVSIM_EINVAL;
+    {
+        std::string why;
+        if (obs_validate(n_obs_steps, state_dim, state_mean_std, ncam, fmt, height, width, lut, box, out_h, out_w, why)) { h->set_error("%s", why.c_str()); return AVSIM_EINVAL; }
+    }
+    AVS_ON_DEVICE(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // (buffers of an earlier set-up may still be in use)
+    if (h->obshist.setup(h->stream, h->N, n_obs_steps, state_dim, state_mean_std, ncam, fmt, height, width, lut, box, out_h, out_w, !h->io_device, h->err)) return AVSIM_EHIP;
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // (the tables are on the device: the caller's arrays are free)
+    return AVSIM_OK;
+}
+
+int avsim_obs_history_reset(avsim_t* h) {
+    if (!h) return AVSIM_EINVAL;
+    if (!h->obshist.ready) { h->set_error("avsim_obs_history_reset: call avsim_obs_history_setup first"); return AVSIM_EINVAL; }
+    AVS_ON_DEVICE(h);
+    HIPCHK(h, hipMemsetAsync(h->obshist.P.pushed, 0, sizeof(int) * (size_t)h->N, h->stream));
+    return h->finish();
+}
+
+int avsim_obs_history_push(avsim_t* h, const int64_t* episode_id, const int32_t* elapsed, const float* state, float* state_hist, const void* const* img,
+                           float* const* img_hist) {
+    if (!h) return AVSIM_EINVAL;
+    ObsHistHost& O = h->obshist;
+    if (!O.ready) { h->set_error("avsim_obs_history_push: call avsim_obs_history_setup first"); return AVSIM_EINVAL; }
+    const ObsArgs& P = O.P;
+    if (!episode_id || !elapsed) { h->set_error("avsim_obs_history_push: episode_id and elapsed are required"); return AVSIM_EINVAL; }
+    if (P.D > 0 && (!state || !state_hist)) { h->set_error("avsim_obs_history_push: state and state_hist are required (state_dim %d)", P.D); return AVSIM_EINVAL; }
+    if (P.ncam > 0 && (!img || !img_hist)) { h->set_error("avsim_obs_history_push: img and img_hist are required (%d cameras)", P.ncam); return AVSIM_EINVAL; }
+    for (int c = 0; c < P.ncam; c++)
+        if (!img[c] || !img_hist[c]) { h->set_error("avsim_obs_history_push: camera %d: a NULL pointer", c); return AVSIM_EINVAL; }
+    AVS_ON_DEVICE(h);
+    const size_t N = h->N;
+    ObsPtrs Q{};
+    if (h->io_device) {
+        for (int c = 0; c < P.ncam; c++) { Q.img[c] = img[c]; Q.hist[c] = img_hist[c]; }
+        obs_launch_push(h->stream, P, Q, episode_id, elapsed, state, state_hist);
+        HIPCHK(h, hipGetLastError());
+        return AVSIM_OK;
+    }
+    // host I/O: every array in, the histories out again (for tests and numpy callers: the histories cross twice per call)
+    HIPCHK(h, hipMemcpyAsync(O.m_id, episode_id, sizeof(int64_t) * N, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(O.m_el, elapsed, sizeof(int32_t) * N, hipMemcpyHostToDevice, h->stream));
+    if (P.D > 0) {
+        HIPCHK(h, hipMemcpyAsync(O.m_state, state, sizeof(float) * N * P.D, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(O.m_shist, state_hist, O.shist_bytes(), hipMemcpyHostToDevice, h->stream));
+    }
+    for (int c = 0; c < P.ncam; c++) {
+        HIPCHK(h, hipMemcpyAsync(O.m_img[c], img[c], O.src_bytes(), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(O.m_hist[c], img_hist[c], O.hist_bytes(), hipMemcpyHostToDevice, h->stream));
+        Q.img[c] = O.m_img[c];
+        Q.hist[c] = (float*)O.m_hist[c];
+    }
+    obs_launch_push(h->stream, P, Q, (const int64_t*)O.m_id, (const int*)O.m_el, (const float*)O.m_state, (float*)O.m_shist);
+    HIPCHK(h, hipGetLastError());
+    if (P.D > 0) HIPCHK(h, hipMemcpyAsync(state_hist, O.m_shist, O.shist_bytes(), hipMemcpyDeviceToHost, h->stream));
+    for (int c = 0; c < P.ncam; c++) HIPCHK(h, hipMemcpyAsync(img_hist[c], O.m_hist[c], O.hist_bytes(), hipMemcpyDeviceToHost, h->stream));
+    return h->finish();
 }
 
 }  // extern "C"

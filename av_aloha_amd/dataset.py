@@ -217,11 +217,21 @@ class TrainingBatches:
     avsim_image_jitter instead -- LeRobot's image_transforms (brightness, contrast, saturation, hue, sharpness; a random subset per image,
     drawn by imgaug.augment_plan from a stream of its own) applied to the whole decoded frame, then the same crop and normalisation; the bits
     of imgaug.jitter_reference with plan(epoch)'s boxes and augment_plan(epoch)'s parameters.
+    n_obs_steps: None (the default): nothing below applies.  K >= 1: for a policy that reads K observations, the image and state entries
+    gain an axis -- "observation.images.<cam>" float32 [B, K, 3, h, w], "observation.state" float32 [B, K, D] --, slot K-1 the item's frame
+    and slot k the frame K-1-k steps before it, clamped to the episode's first (imgprep.history_index, LeRobot's negative delta_timestamps);
+    "observation.state_is_pad" and "observation.images.<cam>_is_pad" bool [B, K] name the clamped ones.  The K frames of an item share its
+    crop box and its augmentation parameters (LeRobot transforms a stacked item with one draw); they go through the same avsim_image_prep /
+    avsim_image_jitter call as B K outputs.  What obshist.ObsHistory stacks at evaluation.
     stats: CompressedDataset.stats()'s (or load_stats'); a dimension whose std is 0 normalises to nan / inf, as the formula says.
     Like batch(), an iteration step does not wait for the device."""
 
-    def __init__(self, ds, batch_size, chunk_size, stats, crop=None, crop_mode="random", normalise=True, seed=0, drop_last=True, augment=None):
+    def __init__(self, ds, batch_size, chunk_size, stats, crop=None, crop_mode="random", normalise=True, seed=0, drop_last=True, augment=None,
+                 n_obs_steps=None):
         torch = ds.torch
+        self.n_obs_steps = None if n_obs_steps is None else int(n_obs_steps)
+        if self.n_obs_steps is not None and self.n_obs_steps < 1:
+            raise ValueError("TrainingBatches: n_obs_steps is at least 1 (or None)")
         self.augment = None if augment is None or augment is False else imgaug.make_cfg(augment)
         self.ds, self.batch_size, self.chunk_size = ds, int(batch_size), int(chunk_size)
         self.crop, self.crop_mode, self.normalise, self.seed, self.drop_last = crop, crop_mode, bool(normalise), int(seed), bool(drop_last)
@@ -277,6 +287,8 @@ class TrainingBatches:
         """The batch of the frames `part` with the crop boxes {camera: int32 [B, 3]}; aug: {camera: (mask, factor)} (augment_plan's), the
         images then go through avsim_image_jitter."""
         ds, torch = self.ds, self.ds.torch
+        if self.n_obs_steps is not None:
+            return self._make_history(part, boxes, aug)
         raw = ds.batch(part, fmt="gym")
         B = len(part)
         out = {"observation.state": self._norm("observation.state", raw["observation.state"]), "episode_index": raw["episode_index"],
@@ -295,4 +307,32 @@ class TrainingBatches:
                 out[f"observation.images.{c}"] = ds.img.jitter_images(src, imgaug.pack_params(box, *aug[c]), (h, w), mean=ms[0], std=ms[1])
             else:
                 out[f"observation.images.{c}"] = ds.img.prep_images(src, self.lut[c], box, (h, w))
+        return out
+
+    def _make_history(self, part, boxes, aug):
+        """make() with n_obs_steps = K: the B K frames of history_index through the same calls, every item's box and parameters K times."""
+        ds, torch = self.ds, self.ds.torch
+        B, K = len(part), self.n_obs_steps
+        hidx, hpad = imgprep.history_index(ds.ep_start, ds.ep_len, part, K)
+        raw = ds.batch(hidx.reshape(-1), fmt="gym")
+        t_pad = torch.from_numpy(hpad).to(ds.device, non_blocking=True)
+        out = {"observation.state": self._norm("observation.state", raw["observation.state"]).reshape(B, K, -1), "observation.state_is_pad": t_pad,
+               "episode_index": raw["episode_index"].reshape(B, K)[:, K - 1], "frame_index": raw["frame_index"].reshape(B, K)[:, K - 1]}
+        index, pad = imgprep.chunk_index(ds.ep_start, ds.ep_len, part, self.chunk_size)
+        t_index = torch.from_numpy(index).to(ds.device, non_blocking=True)
+        out["action"] = self._norm("action", ds.action[t_index])
+        out["action_is_pad"] = torch.from_numpy(pad).to(ds.device, non_blocking=True)
+        for c in ds.cameras:
+            H, W = self.sizes[c]
+            h, w = (H, W) if self.crop is None else (int(self.crop[0]), int(self.crop[1]))
+            box = np.repeat(np.ascontiguousarray(boxes[c], dtype=np.int32).reshape(B, 3), K, axis=0)
+            src = raw[f"observation.images.{c}"]
+            if aug is not None:
+                ms = self.mean_std.get(c, (None, None))
+                mask, factor = aug[c]
+                img = ds.img.jitter_images(src, imgaug.pack_params(box, np.repeat(mask, K, axis=0), np.repeat(factor, K, axis=0)), (h, w), mean=ms[0], std=ms[1])
+            else:
+                img = ds.img.prep_images(src, self.lut[c], box, (h, w))
+            out[f"observation.images.{c}"] = img.reshape(B, K, 3, h, w)
+            out[f"observation.images.{c}_is_pad"] = t_pad
         return out

@@ -315,19 +315,22 @@ def make_preprocessor(venv, stats, crop=None):
     return pre
 
 
-def chunked_policy(venv, predict_chunk, chunk_size, ensemble=None, n_action_steps=None, first=0, stats=None, predict="when_needed"):
+def chunked_policy(venv, predict_chunk, chunk_size, ensemble=None, n_action_steps=None, first=0, stats=None, predict="when_needed", observe=None):
     """(select_action, executor) for evaluate_vec and a policy that predicts action CHUNKS (ACT, diffusion policies trained by
     dataset.TrainingBatches(chunk_size=...)): predict_chunk(obs, info) -> float32 [N, chunk_size, nj] on the env's device, normalised when
     `stats` (CompressedDataset.stats()'s) are given.  The executor (chunks.ActionChunks on venv) keeps the state PER ENV and starts an env's
     state anew when its episode does (a new info["episode_id"] or elapsed_steps 0), which a policy's own select_action with one queue or one
     ensembler for the batch does not: that is only right while all envs' episodes are in phase.
     ensemble = a coefficient (ACT's 0.01): LeRobot's temporal ensembling; predict_chunk runs in every call and nothing synchronises.
-    ensemble None: a queue of n_action_steps (default chunk_size) rows from row `first` (a diffusion policy: n_obs_steps - 1).  predict =
+    ensemble None: a queue of n_action_steps (default chunk_size) rows from row `first` (a diffusion policy: n_obs_steps - 1, with `observe`).  predict =
     "when_needed": predict_chunk runs, for the whole batch, only in the calls where some env needs a chunk; select_action reads the executor's
     4-byte `any` flag to know -- the ONE synchronisation per call of this function.  predict = "always": it runs in every call, the envs
     that need no chunk ignore theirs, and nothing synchronises.  Neither setting can starve an env (executor.starved() stays 0).
     An evaluation's first call sees elapsed_steps 0 everywhere and so starts every env afresh; select_action cannot check that without a
-    synchronisation and does not try: call executor.reset() before evaluate_vec when the executor has run before -- the explicit form of it."""
+    synchronisation and does not try: call executor.reset() before evaluate_vec when the executor has run before -- the explicit form of it.
+    observe: a callable (obs, info) -> obs', run in EVERY call, before the decision whether to predict; predict_chunk receives its result.
+    history_preprocessor's is the one for a policy with n_obs_steps > 1, whose history must see every observation although the policy itself
+    is skipped in most calls.  None: predict_chunk receives the env's observation."""
     from .chunks import ActionChunks
     if predict not in ("when_needed", "always"):
         raise ValueError(f"predict {predict!r}: 'when_needed' or 'always'")
@@ -335,6 +338,8 @@ def chunked_policy(venv, predict_chunk, chunk_size, ensemble=None, n_action_step
     ask = ensemble is None and predict == "when_needed"
 
     def select_action(obs, info):
+        if observe is not None:
+            obs = observe(obs, info)
         if ask:
             _, flag = executor.need(info)
             chunks = predict_chunk(obs, info) if int(flag.item()) else None          # (.item() waits for the stream)
@@ -343,6 +348,21 @@ def chunked_policy(venv, predict_chunk, chunk_size, ensemble=None, n_action_step
         return executor.step(chunks, info)
 
     return select_action, executor
+
+
+def history_preprocessor(venv, stats, crop=None, n_obs_steps=2):
+    """(observe, history) for chunked_policy(..., observe=observe) and a policy that reads n_obs_steps observations: history is an
+    obshist.ObsHistory on venv with make_preprocessor's numbers (stats: CompressedDataset.stats()'s; crop = (h, w): the centred box), kept PER
+    ENV -- an env that starts a new episode starts with n_obs_steps copies of its reset frame --, and observe(obs, info) pushes the env's
+    observation and returns {"observation.state": float32 [N, K, D], "observation.images.<cam>": float32 [N, K, 3, h, w]}, slot K-1 the
+    newest: what dataset.TrainingBatches(n_obs_steps=K, crop_mode="center") trains on.  Nothing synchronises.  Call history.reset() before
+    evaluate_vec when the history has run before (chunked_policy's docstring says why)."""
+    from .obshist import ObsHistory
+    H, W = venv.observation_height, venv.observation_width
+    if crop is not None and not (1 <= int(crop[0]) <= H and 1 <= int(crop[1]) <= W):
+        raise ValueError(f"crop {tuple(crop)} does not fit the env's {H} x {W} images")
+    history = ObsHistory(venv, n_obs_steps, stats=stats, crop=crop)
+    return history.push, history
 
 
 def record_episode(env, actions23) -> dict:

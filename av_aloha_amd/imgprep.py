@@ -8,7 +8,8 @@ csrc/avsim_imgprep.hip.h) in numpy, bit for bit, and the index arithmetic of act
   float is accumulated anywhere, so there is no tolerance to state.  std is the population std, as LeRobot's compute_stats uses.
 * `normalise_lut`, `identity_lut`: the tables; `prep_reference`: crop + optional mirror + look-up,
   out[i, c, y, x] = lut[lut_index[i], c, u8(img[i])[y0 + y, x0 + (flip ? ow - 1 - x : x), c]].
-* `chunk_index`: LeRobot's delta_timestamps clamping -- the frames of an action chunk and which of them are padding."""
+* `chunk_index`: LeRobot's delta_timestamps clamping -- the frames of an action chunk and which of them are padding; `history_index`:
+  the same for the frames in front of one (n_obs_steps > 1)."""
 from fractions import Fraction
 
 import numpy as np
@@ -149,3 +150,21 @@ def chunk_index(ep_start, ep_len, frame, chunk):
     s, T = ep_start[e][:, None], ep_len[e][:, None]
     tk = (f[:, None] - s) + np.arange(int(chunk), dtype=np.int64)[None, :]
     return s + np.minimum(tk, T - 1), tk > T - 1
+
+
+def history_index(ep_start, ep_len, frame, n_obs_steps):
+    """(index int64 [B, K], is_pad bool [B, K]) of the observation histories that END at the global frames `frame` (K = n_obs_steps; slot
+    K-1 is the frame itself): for frame f at position t of an episode starting at s, index[k] = s + max(t - (K-1) + k, 0) and is_pad[k] =
+    t - (K-1) + k < 0 -- LeRobot's clamping of negative delta_timestamps, the counterpart of chunk_index."""
+    ep_start = np.asarray(ep_start, dtype=np.int64)
+    ep_len = np.asarray(ep_len, dtype=np.int64)
+    f = np.asarray(frame, dtype=np.int64).reshape(-1)
+    e = np.searchsorted(ep_start, f, side="right") - 1
+    if len(f) and (f.min() < 0 or (f >= ep_start[e] + ep_len[e]).any()):
+        raise IndexError("history_index: a frame outside the episodes")
+    K = int(n_obs_steps)
+    if K < 1:
+        raise ValueError("history_index: n_obs_steps >= 1")
+    s = ep_start[e][:, None]
+    tk = (f[:, None] - s) - (K - 1) + np.arange(K, dtype=np.int64)[None, :]
+    return s + np.maximum(tk, 0), tk < 0

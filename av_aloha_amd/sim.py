@@ -401,6 +401,54 @@ class BatchedSim:
         images.check_call(self.h, self.h.L.avsim_chunk_starved(self.h.h, c.ctypes.data))
         return int(c[0])
 
+    def obs_history_setup(self, n_obs_steps, state_dim=None, mean=None, std=None, fmt=0, src_hw=None, out_hw=None, lut=None, box=None):
+        """Per-env observation histories on host arrays (avsim_obs_history_setup; av_aloha_amd.obshist is the specification and
+        obshist.ObsHistory the torch front).  state_dim defaults to the joint count (0: no state); mean / std normalise the state; lut float32
+        [ncam, 3, 256] and box int (x0, y0, flip) rows: one table and one crop of out_hw = (h, w) per camera of src_hw = (H, W) images in
+        format fmt (0: u8 HWC, 1: float32 CHW); lut None: no cameras.  ValueError for what the library refuses.  -> the keyword arguments of an
+        obshist.ObsHistoryReference(N, K, D, ...) of the same set-up.  The histories live in this object (NaN until an env's first push)."""
+        from . import obshist
+        K, D = int(n_obs_steps), int(self.nj if state_dim is None else state_dim)
+        ms = obshist.mean_std(mean, std, D) if D > 0 else None
+        lut = None if lut is None else np.ascontiguousarray(lut, dtype=np.float32).reshape(-1, 3, 256)
+        ncam = 0 if lut is None else len(lut)
+        box = None if box is None else np.ascontiguousarray(box, dtype=np.int32).reshape(-1, 3)
+        if ncam and (box is None or len(box) != ncam or src_hw is None or out_hw is None):
+            raise ValueError("obs_history_setup: cameras need src_hw, out_hw and one box per table")
+        fmt = obshist.FORMATS.get(fmt, fmt)
+        (H, W), (h, w) = (src_hw, out_hw) if ncam else ((0, 0), (0, 0))
+        images.check_call(self.h, self.h.L.avsim_obs_history_setup(self.h.h, K, D, _ffi.ptr(ms), ncam, int(fmt) if ncam else 0, int(H), int(W), _ffi.ptr(lut), _ffi.ptr(box),
+                                                                   int(h), int(w)))
+        self._obs_hist = (np.full((self.N, K, D), np.nan, dtype=np.float32), [np.full((self.N, K, 3, int(h), int(w)), np.nan, dtype=np.float32) for _ in range(ncam)])
+        self._obs_src = ((self.N, int(H), int(W), 3), np.uint8) if fmt == 0 else ((self.N, 3, int(H), int(W)), np.float32)
+        return dict(cams=ncam, fmt=fmt, src_hw=src_hw, out_hw=out_hw, lut=lut, box=box, mean=None if ms is None else ms[0], std=None if ms is None else ms[1])
+
+    def obs_history_push(self, state, imgs, episode_id, elapsed):
+        """(state_hist float32 [N, K, D], [img_hist float32 [N, K, 3, h, w] per camera]) after this call's observations (avsim_obs_history_push):
+        this object's arrays, updated in place.  state: float32 [N, D] (None with state_dim 0); imgs: one batch per camera."""
+        import ctypes
+        if not hasattr(self, "_obs_hist"):
+            raise ValueError("obs_history_push: call obs_history_setup first")
+        sh, ih = self._obs_hist
+        eid, el = self._chunk_ids(episode_id, elapsed)
+        D = sh.shape[2]
+        if D > 0:
+            state = np.ascontiguousarray(state, dtype=np.float32)
+            if state.shape != (self.N, D):
+                raise ValueError(f"obs_history_push: state of shape {state.shape}, expected {(self.N, D)}")
+        imgs = [] if imgs is None else [np.ascontiguousarray(a) for a in imgs]
+        shape, dtype = self._obs_src
+        if len(imgs) != len(ih) or any(a.shape != shape or a.dtype != dtype for a in imgs):
+            raise ValueError(f"obs_history_push: {len(ih)} image batches of shape {shape} and type {np.dtype(dtype).name}")
+        src = (ctypes.c_void_p * max(len(ih), 1))(*[a.ctypes.data for a in imgs])
+        dst = (ctypes.c_void_p * max(len(ih), 1))(*[a.ctypes.data for a in ih])
+        images.check_call(self.h, self.h.L.avsim_obs_history_push(self.h.h, eid.ctypes.data, el.ctypes.data, state.ctypes.data if D > 0 else None,
+                                                                  sh.ctypes.data if D > 0 else None, src, dst))
+        return sh, ih
+
+    def obs_history_reset(self):
+        images.check_call(self.h, self.h.L.avsim_obs_history_reset(self.h.h))
+
     def reward_from_pairs(self, geom_pairs, latch=None):
         """The task's get_reward (env.py:425-863) on explicit contact lists: geom_pairs int [nsets, cap, 2] (collision
         geom ids, negative = empty slot); latch int32 [nsets] is updated in place.  Returns int32 [nsets]."""

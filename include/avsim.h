@@ -395,6 +395,31 @@ int avsim_chunk_step(avsim_t* h, const float* chunks /* [N][C][A] or NULL */, co
                      const int32_t* elapsed /* [N] */, float* action /* [N][A] */);
 int avsim_chunk_starved(avsim_t* h, uint64_t* count);
 
+/* Per-env observation histories on the device (csrc/avsim_obshist.hip); av_aloha_amd/obshist.py is the specification, and the
+ * calls equal it bit for bit.  One state per handle, sized to its num_envs.  A policy with n_obs_steps = K reads [N][K][...]: slot K-1 is
+ * the newest observation.  Env i is FRESH in a call exactly as for avsim_chunk_step: not pushed since the set-up / avsim_obs_history_reset,
+ * or elapsed[i] == 0, or episode_id[i] differs from the id the previous call saw.  Per call and env, the new state is (x - mean[d]) / std[d]
+ * (two float32 operations; state_mean_std NULL: x) and the new image of camera c is avsim_image_prep's with table lut[c] and box[c] =
+ * (x0, y0, flip), from img[c] in format fmt (0: uint8 [N][height][width][3], 1: float32 [N][3][height][width]).  A fresh env: all K slots
+ * become the new value and the old contents are not read; otherwise slot[k] = slot[k+1] for k < K-1 and slot[K-1] = new.
+ * avsim_obs_history_setup: state_mean_std, lut and box are HOST arrays, copied before the call returns; everything is checked before
+ * anything is allocated or enqueued -- AVSIM_EINVAL: n_obs_steps outside 1..16, state_dim outside 0..256, ncam outside 0..8, state_dim 0
+ * with ncam 0, and with cameras: fmt other than 0 / 1, a size outside 1..65535, lut or box NULL, a crop not inside the source, a flip
+ * other than 0 / 1; a mean not finite, a std 0 or not finite.  (Re)initialises the state: all envs unpushed.  Synchronises.
+ * avsim_obs_history_push: img and img_hist are HOST arrays of ncam pointers; the arrays they name, and state float [N][D], state_hist float
+ * [N][K][D], img_hist[c] float [N][K][3][out_h][out_w], episode_id and elapsed, follow the handle's I/O mode.  The histories are the
+ * caller's memory, updated in place.  AVSIM_EINVAL, with nothing enqueued and the state untouched: a push or reset before the set-up, a NULL
+ * id array, a NULL state or state_hist with state_dim > 0, a NULL camera pointer.  The work goes on the handle's stream; with
+ * AVSIM_IO_DEVICE neither push nor reset synchronises.  Without it every array, the histories included, is copied to the device and the
+ * histories back around the pass: that mode is for tests and numpy callers.  16-byte history accesses when out_h out_w is a multiple of
+ * four and every img_hist[c] is 16-byte aligned, single floats otherwise. */
+int avsim_obs_history_setup(avsim_t* h, int n_obs_steps, int state_dim, const float* state_mean_std /* host [2][D] or NULL */, int ncam, int fmt,
+                            int height, int width, const float* lut /* host [ncam][3][256] */, const int32_t* box /* host [ncam][3] */,
+                            int out_h, int out_w);
+int avsim_obs_history_reset(avsim_t* h);
+int avsim_obs_history_push(avsim_t* h, const int64_t* episode_id /* [N] */, const int32_t* elapsed /* [N] */, const float* state,
+                           float* state_hist, const void* const* img /* host [ncam] */, float* const* img_hist /* host [ncam] */);
+
 /* get_reward of the handle's task (gym_guided_vision/gym_guided_vision/env.py:425-863, five subclasses) evaluated on
  * caller-supplied contact lists instead of the simulator's own contacts: geom_pairs = int32[nsets][cap][2], ids into the
  * model's collision geom table (manifest "geom_names"), a slot with a negative id is empty.  The kernel applies the same
