@@ -15,7 +15,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+#include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "avsim_collide.hip.h"
@@ -36,8 +39,18 @@ constexpr int CAND_MAX = 256;  // exact broad-phase survivors per substep (narro
 constexpr int PROF_W = 26;   // words per env of the phase profile: 8 phases, broad / narrow, 16 solver / probe slots
 constexpr int NEAR_MAX = 512;  // Verlet neighbour list: pairs within reach + skin, rebuilt when a geom moved > skin/2
 
+// every integer of DevHead, by name: what a per-model kernel has as constants and what the host compares before it launches one
+#define AVSIM_HEAD_INTS(X)                                                                                                              \
+    X(nq) X(nv) X(nu) X(nbody) X(njnt) X(ngeom) X(npair) X(ntree) X(neq) X(nfloss) X(nlimited) X(nment) X(task_id) X(nj) X(msize)        \
+    X(noslip_iters) X(noslip_trees) X(qcqp_tridiag) X(newton_early_exit) X(newton_component) X(noslip_per_tree) X(solver) X(newton_iters) \
+    X(ls_iterations)
+// ... and the two that sit further down in the model, next to the tables they describe (Env::nobj_ / hull_ovf_)
+#define AVSIM_BODY_INTS(X) X(nobj) X(hull_ovf)
+// The head of the model: its integer dims, the solver configuration and the real-valued options.  The generic kernel reads them through
+// `ka->m.X` as scalar loads; the kernel compiled for one model (KFixed below) sees the same words through FixedHead, whose integer members
+// are constants of the model's spec.
 template <typename real>
-struct DevModel {
+struct DevHead {
     int nq, nv, nu, nbody, njnt, ngeom, npair, ntree, neq, nfloss, nlimited, nment, task_id, nj, msize;
     real timestep, gravity[3], impratio, grip_lo, grip_hi;
     int noslip_iters;
@@ -50,6 +63,24 @@ struct DevModel {
     real newton_tol, nscale;      // MuJoCo tolerance and 1/(meaninertia*nv) scaling of the termination tests
     real ls_tolerance;            // Newton's line search stops at |phi'(alpha)| < ls_tolerance |phi'(0)| (option "ls_tolerance"; default 1e-10 in f64, 1e-4 in f32 -- MuJoCo's mjOption.ls_tolerance is 0.01 of another scale [EXT])
     int ls_iterations;            // ... after at most this many evaluations beyond phi'(0) (option "ls_iterations"; default 50 = MuJoCo's mjOption.ls_iterations [EXT])
+};
+// The same words with every integer a constant of SPEC (avsim_phys_specs.h: the model's dims and the solver configuration of a default
+// f32 handle); the reals stay the handle's run-time values.  PhysHost launches such a kernel only while the handle's own integers equal
+// the spec's (avsim_phys_spec.hip), so the words behind the pads hold exactly these values.
+template <typename real, typename SPEC>
+struct FixedHead {
+    int pad_dims_[15];
+    real timestep, gravity[3], impratio, grip_lo, grip_hi;
+    int pad_flags_[8];
+    real newton_tol, nscale;
+    real ls_tolerance;
+    int pad_tail_;
+#define AVS_FIXED_INT(x) static constexpr int x = SPEC::x;
+    AVSIM_HEAD_INTS(AVS_FIXED_INT)
+#undef AVS_FIXED_INT
+};
+template <typename real, typename HEAD>
+struct DevModelT : HEAD {
     // bodies
     GLB_PTR(const int) body_parent;
     GLB_PTR(const int) body_jntadr;
@@ -159,6 +190,8 @@ struct DevModel {
     GLB_PTR(const real) obs_scale;
 };
 
+template <typename real> using DevModel = DevModelT<real, DevHead<real>>;
+
 static_assert(NARROW_SCR_W == 64 * SLOT_W + 4 * 56, "avsim_phys_layout.h: narrow-phase scratch");
 
 // everything the kernel needs to know about the model: read through a constant-address-space pointer, so that the ~90 table
@@ -175,15 +208,24 @@ using KPtr = const KArgs<real> __attribute__((address_space(4)))*;
 // Layout policy of Env / k_phys: where `ka->lay.X` and `ka->mo.X` come from.  GenericSpec: `ka` IS the KPtr, every offset is a scalar
 // load where it is used (any model, any capacities).  A fixed spec (avsim_phys_spec.hip) carries the Layout and the MOff of one
 // committed model as static constexpr members lay / mo: `ka` is then a KFixed, whose -> hands out the spec's constants for lay and
-// mo -- they end up in the immediate offsets of the ds_read / ds_write instructions -- and the handle's run-time values for `m` (what options
-// can change: tolerances, solver flags, the table pointers).  The host launches such a kernel only for a handle whose own Layout, MOff and
-// dims equal the spec's (PhysHost::launch_t).
+// mo -- they end up in the immediate offsets of the ds_read / ds_write instructions.  Of `m` it hands out the spec's constants for every
+// integer (dims: the trip counts of the phases' loops; solver configuration: the paths a default handle never takes are not compiled in)
+// and the handle's run-time values for the reals and the table pointers.  Such a kernel also keeps its table image at LDS offset 0, in
+// front of the env records, so that the base of every table read is a constant too (Env::LR / LI).  The host launches it only for a
+// handle whose own Layout, MOff and integers equal the spec's at that launch (PhysHost::launch_t, spec_matches).
 struct GenericSpec {};
+template <typename SPEC> constexpr bool spec_fixed = !std::is_same<SPEC, GenericSpec>::value;
 template <typename real, typename SPEC>
 struct KFixed {
+    using Model = DevModelT<real, FixedHead<real, SPEC>>;
+    using FH = FixedHead<real, SPEC>;
+    using DH = DevHead<real>;
+    static_assert(sizeof(FH) == sizeof(DH) && alignof(FH) == alignof(DH) && sizeof(Model) == sizeof(DevModel<real>) && offsetof(FH, timestep) == offsetof(DH, timestep) &&
+                      offsetof(FH, newton_tol) == offsetof(DH, newton_tol) && offsetof(FH, pad_tail_) == offsetof(DH, ls_iterations),
+                  "FixedHead: the words of DevHead");
     KPtr<real> p;
     struct View {
-        const DevModel<real> __attribute__((address_space(4)))& m;
+        const Model __attribute__((address_space(4)))& m;      // (integers: the spec's constants; reals and pointers: the handle's)
         static constexpr Layout lay = SPEC::lay;
         static constexpr MOff mo = SPEC::mo;
         AVS_DEV const View* operator->() const { return this; }
@@ -191,7 +233,7 @@ struct KFixed {
     AVS_DEV KFixed(KPtr<real> p_) : p(p_) {}
     AVS_DEV explicit KFixed(unsigned long long v) : p((KPtr<real>)v) {}            // (PHASE_LAUNDER)
     AVS_DEV explicit operator unsigned long long() const { return (unsigned long long)p; }
-    AVS_DEV View operator->() const { return View{p->m}; }
+    AVS_DEV View operator->() const { return View{reinterpret_cast<const Model __attribute__((address_space(4)))&>(p->m)}; }
 };
 template <typename real, typename SPEC> struct KRefOf { using type = KFixed<real, SPEC>; };
 template <typename real> struct KRefOf<real, GenericSpec> { using type = KPtr<real>; };
@@ -211,6 +253,9 @@ template <typename real, typename SPEC> using KRef = typename KRefOf<real, SPEC>
 #else
 #define AVS_ASSUME_LDS(p) ((void)(p))
 #endif
+// the LDS word at a byte offset of the workgroup's allocation (through a parameter: a literal 0 would be the null pointer, which is not address 0 there)
+template <typename T>
+AVS_DEV T* lds_at(unsigned byte_off) { return (T*)(__attribute__((address_space(3))) T*)(size_t)byte_off; }
 #define LDS_BASES()                                                                       \
     real* const r = this->r; AVS_ASSUME_LDS(r);     \
     int* const ii = this->ii; AVS_ASSUME_LDS(ii);   \
@@ -1832,10 +1877,24 @@ struct Env {
     __device__ Env(KRef<real, SPEC> ka_, real* r_, int* i_, int lane_, int grp_, const real* lr_, const int* li_)
         : ka(ka_), r(r_), ii(i_), lane(lane_), grp(grp_), lr(lr_), li(li_) {}
     // hot model tables live in LDS (copied once per block); the accessors rebuild the pointer from the kernarg offset
-    AVS_DEV const int* LI() const { const int* p = li; AVS_ASSUME_LDS(p); return p; }
-    AVS_DEV const real* LR() const { const real* p = lr; AVS_ASSUME_LDS(p); return p; }
+    // (a fixed spec: the image is at LDS offset 0 -- k_phys puts it there -- and these are constants)
+    AVS_DEV const int* LI() const {
+        const int* p = li;
+        if constexpr (spec_fixed<SPEC>) p = lds_at<const int>((unsigned)(ka->mo.nreal * sizeof(real)));
+        AVS_ASSUME_LDS(p);
+        return p;
+    }
+    AVS_DEV const real* LR() const {
+        const real* p = lr;
+        if constexpr (spec_fixed<SPEC>) p = lds_at<const real>(0u);
+        AVS_ASSUME_LDS(p);
+        return p;
+    }
     // (the env's share of the global scratch is sized by the FULL capacities in both layouts of a two-tier handle: envs stepped with
     // the small and with the full record run side by side)
+    // (the model's two integers outside its head: the spec's constants in a per-model kernel)
+    AVS_DEV int nobj_() const { if constexpr (spec_fixed<SPEC>) return SPEC::nobj; else return ka->m.nobj; }
+    AVS_DEV int hull_ovf_() const { if constexpr (spec_fixed<SPEC>) return SPEC::hull_ovf; else return ka->m.hull_ovf; }
     AVS_DEV GLB_PTR(real) rows_() const { return (GLB_PTR(real))ka->m.rJ_glob + (size_t)env * ka->lay.gefc * ROW_S; }
     AVS_DEV GLB_PTR(real) rowsB_() const { return (GLB_PTR(real))ka->m.rB_glob + (size_t)env * ka->lay.gefc * ROW_S; }
     AVS_DEV GLB_PTR(real) coup_() const { return (GLB_PTR(real))ka->m.gA_glob + (size_t)env * ka->lay.ggrp * GA_W; }
@@ -2306,7 +2365,7 @@ struct Env {
         s.hull = ka->m.hull_vert;
         s.hbase = ka->m.geom_hull[2 * g];
         s.hR = ka->m.geom_hull[2 * g + 1];
-        s.hovf = ka->m.hull_ovf;
+        s.hovf = hull_ovf_();
         s.nh = 0;
         for (int k = 0; k < 3; k++) { s.lc[k] = ka->m.geom_lbox[6 * g + k]; s.lh[k] = ka->m.geom_lbox[6 * g + 3 + k]; }
         if (geom_static_()[g]) {
@@ -2395,6 +2454,9 @@ struct Env {
         int nnear = misc[6];
         if (rebuild) {
             nnear = 0;
+            // (not unrolled: with npair a constant of a per-model kernel the optimiser unrolls the 28 passes of hook_package_2arms in full,
+            // 7 000 instructions and 160 scalar loads more in collide; the same for the overflow loop below)
+#pragma unroll 1
             for (int base = 0; base < ka->m.npair; base += G) {
                 int p = base + lane;
                 bool hit = p < ka->m.npair && pair_hit(p, skin);
@@ -2417,6 +2479,7 @@ struct Env {
             }
         } else {
             // neighbour list overflow: exact test over the whole compiled pair list
+#pragma unroll 1
             for (int base = 0; base < ka->m.npair; base += G) {
                 int p = base + lane;
                 bool hit = p < ka->m.npair && pair_hit(p, real(0));
@@ -3033,6 +3096,7 @@ struct Env {
     // the call goes through a throw-away copy: the caller's object never has its address taken and stays in registers too
     __device__ __attribute__((always_inline)) void solve_i(int pgs_iters, int solver, int newton_iters, real newton_tol, real scale) {
         PHASE_BEGIN();
+        if constexpr (spec_fixed<SPEC>) { solver = ka->m.solver; newton_iters = ka->m.newton_iters; }      // (the spec's constants: the other solver is not compiled in)
         int *misc = ii + ka->lay.misc, *rmeta = ii + ka->lay.rmeta, *cefc = ii + ka->lay.cefc, *rowI = ii + ka->lay.rowI;
         real *qacc = r + ka->lay.qacc, *as = r + ka->lay.asm_, *rowS = r + ka->lay.rowS, *fcon = r + ka->lay.fcon;
         GLB_PTR(real) rJ = rows_();
@@ -3050,7 +3114,7 @@ struct Env {
             bool two_ = false;
             for (int i = lane; i < nefc; i += G) two_ = two_ || ((rowI[i] >> 19) & 15) != 0;
             const bool coupled = __any(two_) != 0 || ka->m.ntree > 8;
-#define AVS_NEWTON_ARGS ka, (GLB_PTR(const real))rJ, (LDS_PTR(real))r, (LDS_PTR(int))ii, (LDS_PTR(const int))li, nefc, ncon, misc[4], newton_iters, newton_tol, scale, profiling ? 1 : 0
+#define AVS_NEWTON_ARGS ka, (GLB_PTR(const real))rJ, (LDS_PTR(real))r, (LDS_PTR(int))ii, (LDS_PTR(const int))LI(), nefc, ncon, misc[4], newton_iters, newton_tol, scale, profiling ? 1 : 0
             int used = __builtin_amdgcn_readfirstlane(ncon) <= 64 ? (coupled ? newton_solve_coupled<real, 1>(AVS_NEWTON_ARGS) : newton_solve<real, 1, false>(AVS_NEWTON_ARGS))
                                                                   : (coupled ? newton_solve_coupled<real, 2>(AVS_NEWTON_ARGS) : newton_solve<real, 2, false>(AVS_NEWTON_ARGS));
 #undef AVS_NEWTON_ARGS
@@ -3131,7 +3195,7 @@ struct Env {
         diverged = 1;
         for (int i = lane; i < ka->m.nq; i += G) qpos[i] = ka->m.qpos_home[i];
         GSYNC();
-        for (int i = lane; i < ka->m.nobj * 7; i += G) qpos[ka->m.obj_qadr[i / 7] + i % 7] = (real)ka->m.obj_reset[((size_t)env * ka->m.nobj) * 7 + i];
+        for (int i = lane; i < nobj_() * 7; i += G) qpos[ka->m.obj_qadr[i / 7] + i % 7] = (real)ka->m.obj_reset[((size_t)env * nobj_()) * 7 + i];
         for (int i = lane; i < ka->m.nv; i += G) { qvel[i] = 0; warm[i] = 0; }
         if (lane == 0) (ii + ka->lay.misc)[7] = 0;      // the Verlet list is stale
         GSYNC();
@@ -3265,7 +3329,16 @@ __global__ void __launch_bounds__(64 * MAXW) AVSIM_PHYS_ATTR k_phys(KPtr<real> k
     const int wpb = blockDim.x >> 6;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, grp = 0;
     // hot model tables -> LDS, once per block
-    real* lr = reinterpret_cast<real*>(smem + (size_t)wpb * ka_small->lay.bytes_per_env);
+    // (a fixed spec: the image FIRST, the records behind it -- its base is then offset 0 whatever wpb is, and Env::LR / LI say so)
+    constexpr bool FIXED = spec_fixed<SPEC>;
+    static_assert(!(FIXED && RETRY), "the per-model kernels are one-pass");
+    size_t rec0 = 0;
+    if constexpr (FIXED) {
+        rec0 = (((size_t)ka_small->mo.nreal * sizeof(real) + (size_t)ka_small->mo.nint * 4) + 15) & ~(size_t)15;
+        // (no static LDS in this kernel, so the dynamic part starts at 0; were that ever not so the launch steps nothing, which every test of the kernel notices)
+        if ((unsigned)(size_t)(LDS_PTR(unsigned char))smem != 0u) return;
+    }
+    real* lr = reinterpret_cast<real*>(smem + (FIXED ? (size_t)0 : (size_t)wpb * ka_small->lay.bytes_per_env));
     int* li = reinterpret_cast<int*>(lr + ka_small->mo.nreal);
     for (int i = threadIdx.x; i < ka_small->mo.nreal; i += blockDim.x) lr[i] = img_real[i];
     for (int i = threadIdx.x; i < ka_small->mo.nint; i += blockDim.x) li[i] = img_int[i];
@@ -3339,7 +3412,7 @@ __global__ void __launch_bounds__(64 * MAXW) AVSIM_PHYS_ATTR k_phys(KPtr<real> k
     }
     KRef<real, SPEC> ka = (RETRY && big) ? ka_big : ka_small;
     const long long t_launch = __builtin_readcyclecounter();
-    real* r = reinterpret_cast<real*>(smem + (size_t)((RETRY && big) ? (wave & ~1) : wave) * ka_small->lay.bytes_per_env);
+    real* r = reinterpret_cast<real*>(smem + rec0 + (size_t)((RETRY && big) ? (wave & ~1) : wave) * ka_small->lay.bytes_per_env);
     int* ii = reinterpret_cast<int*>(r + ka->lay.nreal);
     bool beyond = false;      // this env needed more than the small capacities in some substep
     Env<real, G, SPEC> E(ka, r, ii, lane, grp, lr, li);
@@ -3500,7 +3573,8 @@ struct PhysHost;
 int phys_launch_f64(PhysHost& ph, hipStream_t st, int nsub, const float* action, void* qpos, void* qvel, void* ctrl, void* warm, int* latch,
                     double* agent, int32_t* reward, uint8_t* success, std::string& err);
 // The kernels compiled for one committed model each (avsim_phys_spec.hip, a translation unit of its own): the host stub of the
-// one-pass f32 k_phys whose spec equals the handle's Layout, MOff and dims word for word, or null (`name`: the spec's model)
+// one-pass f32 k_phys whose spec equals the handle's Layout, MOff, dims and every integer of its model head (DevHead: dims and solver
+// configuration, as the handle's options have them at this launch) word for word, or null (`name`: the spec's model)
 const void* phys_spec_kernel(const PhysHost& ph, const char** name);
 
 struct PhysHost {
@@ -3512,7 +3586,7 @@ struct PhysHost {
     int maxcon1 = 48, maxefc1 = 144;
     bool f64 = false;
     int specialised = 1;            // option "phys_specialised": 0 never, 1 the kernel compiled for the model when one matches, 2 require one
-    bool host_only = false;         // build() assembles the table image and the offsets without a device (tools/gen_phys_specs)
+    bool host_only = false;         // init() assembles the table image, the offsets and the layouts without a device (tools/gen_phys_specs)
     int N = 0, max_reward = 0;
     std::vector<void*> allocs;
     DevModel<float> mf;
@@ -3798,7 +3872,7 @@ struct PhysHost {
     bool refuses(std::string& err) const {
         if (specialised != 2 || spec_kernel(nullptr)) return false;
         err = std::string("phys_specialised = 2: no kernel compiled for this handle's model and layout (") +
-              (f64 ? "f64 handle" : two_pass() ? "two capacity tiers" : "Layout, table offsets or dims match no spec of avsim_phys_specs.h") + "); the launch would take the generic k_phys";
+              (f64 ? "f64 handle" : two_pass() ? "two capacity tiers" : "Layout, table offsets, dims or solver options (solver, noslip_*, qcqp_tridiag, newton_*, ls_iterations, num_joints) match no spec of avsim_phys_specs.h") + "); the launch would take the generic k_phys";
         return true;
     }
     int spec_note = 0;
@@ -3826,6 +3900,7 @@ struct PhysHost {
     int* d_near = nullptr;
     void* d_gref = nullptr;
     void alloc_contacts() {
+        if (host_only) return;
         if (d_rows) (void)hipFree(d_rows);
         d_rows = nullptr;
         if (hipMalloc(&d_rows, (size_t)N * maxefc * ROW_S * (f64 ? 8 : 4) * 2) != hipSuccess) throw std::runtime_error("hipMalloc of the constraint row buffers failed");
@@ -3907,6 +3982,7 @@ struct PhysHost {
         if (n == "phys_specialised") { if (v != 0 && v != 1 && v != 2) return false; specialised = (int)v; return true; }
         if (n == "pair_waves") { pair_waves = v != 0; return true; }
         if (n == "qcqp_tridiag") { mf.qcqp_tridiag = md.qcqp_tridiag = v < 0 ? 0 : (v > 2 ? 2 : (int)v); return true; }
+        if (n == "noslip_iters") { if (v < 0 || v > 100) return false; mf.noslip_iters = md.noslip_iters = (int)v; return true; }
         if (n == "noslip_per_tree") { mf.noslip_per_tree = md.noslip_per_tree = v != 0; return true; }
         if (n == "noslip_trees") { mf.noslip_trees = md.noslip_trees = v != 0; return true; }
         if (n == "newton_component") { mf.newton_component = md.newton_component = v != 0; return true; }
@@ -3948,8 +4024,9 @@ struct PhysHost {
         const size_t tables = (size_t)moff.nreal * sizeof(real) + (size_t)moff.nint * 4;
         auto kern1 = k_phys<real, G, MAXW, false>;      // one pass
         auto kern2 = k_phys<real, G, MAXW, true>;       // the two passes of the two-tier capacities
-        // The kernel compiled for this very model (option "phys_specialised"): only a one-pass f32 launch whose Layout, MOff and dims equal
-        // the spec's takes it; every other launch -- another model, capacities changed by option, f64, two tiers -- the generic one
+        // The kernel compiled for this very model (option "phys_specialised"): only a one-pass f32 launch whose Layout, MOff, dims and solver
+        // configuration equal the spec's takes it; every other launch -- another model, capacities or a solver option changed, f64, two
+        // tiers -- the generic one
         const char* spec_name = nullptr;
         const void* kspec = sizeof(real) == 4 && MAXW == AVSIM_PHYS_MAXW ? spec_kernel(&spec_name) : nullptr;
         if (refuses(err)) return -1;      // (before anything is enqueued; the API's entry points ask the same question before THEIR first enqueue)
@@ -3987,6 +4064,8 @@ struct PhysHost {
         // (round 6).  One-tier launches only (the wave pairs of the two-tier launch want their even / odd partners).
         if (!two && wpb_override <= 0 && num_cu > 0 && N < num_cu * wpb) { wpb = (N + num_cu - 1) / num_cu; if (wpb < 1) wpb = 1; }
         const size_t pairflags = two ? 2 * (MAXW / 2 > 0 ? MAXW / 2 : 1) * sizeof(int) : 0;
+        // (the per-model kernel puts the tables FIRST and the records behind them, rounded up to 16 bytes: both image halves are multiples
+        // of four words (build), so its total is this one too)
         const size_t shmem = (size_t)lay.bytes_per_env * wpb + tables + pairflags, shmem2 = (size_t)lay2.bytes_per_env * wpb2 + tables + pairflags;
         // pairs of waves take the envs that need the full capacities inside the first pass when the full record fits two small ones
         const int pairing = (two && wpb >= 2 && lay2.bytes_per_env <= 2 * lay.bytes_per_env && pair_waves) ? 8 : 0;
@@ -4059,5 +4138,24 @@ struct PhysHost {
     }
 #endif
 };
+
+// Does the handle, as its options stand now, hold exactly what the kernel compiled for SPEC has as constants?  Host only (asked at every launch
+// and by PhysHost::refuses; tests/test_phys_spec2_host.py runs it without a device).
+template <typename SPEC>
+inline bool spec_matches(const PhysHost& ph) {
+    static_assert(sizeof(Layout) == LAYOUT_WORDS * sizeof(int) && sizeof(MOff) == MOFF_WORDS * sizeof(int), "structs of ints, no padding");
+    static constexpr Layout lay = SPEC::lay;
+    static constexpr MOff mo = SPEC::mo;
+    static_assert(((size_t)mo.nreal * sizeof(float) + (size_t)mo.nint * 4) % 16 == 0, "the records behind the table image start 16-byte aligned without padding");
+    if (std::memcmp(&ph.lay, &lay, sizeof(Layout)) != 0 || std::memcmp(&ph.lay2, &lay, sizeof(Layout)) != 0 || std::memcmp(&ph.moff, &mo, sizeof(MOff)) != 0 ||
+        std::memcmp(ph.dims, SPEC::dims, sizeof(ph.dims)) != 0)
+        return false;
+    // every integer the kernel has as a constant, against what the handle holds NOW (options change them after construction)
+#define AVSIM_SPEC_INT(x) if (ph.mf.x != SPEC::x) return false;
+    AVSIM_HEAD_INTS(AVSIM_SPEC_INT)
+    AVSIM_BODY_INTS(AVSIM_SPEC_INT)
+#undef AVSIM_SPEC_INT
+    return true;
+}
 
 }  // namespace avs

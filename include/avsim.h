@@ -81,13 +81,17 @@ int avsim_dims(const avsim_t* h, int32_t dims[AVSIM_NDIMS]);
  *   "num_joints"        14 | 21: width of the action / agent_pos rows, whatever the blob's arm count (a 3-arm env whose camera
  *                       arm was parked by hide_middle_arm, env.py:394-395, keeps its 21-D action on the 2-arm model)
  *   "waves_per_block"   envs per workgroup, 0 = as many as fit in 160 KiB of LDS (<= 8)
- *   "phys_specialised"  1 (default): a one-pass f32 launch takes the physics kernel compiled for the handle's model (LDS layout and
- *                       table offsets as compile-time constants; csrc/avsim_phys_specs.h lists the models) when the handle's layout,
- *                       table offsets and dims equal that kernel's exactly, the generic kernel otherwise; 0 = always the generic
- *                       kernel; 2 = require: a step whose launch would take the generic kernel (another model, capacities changed
- *                       by "maxefc" / "maxcon", f64, two capacity tiers) fails with AVSIM_EINVAL before anything is enqueued -- avsim_step*,
+ *   "phys_specialised"  1 (default): a one-pass f32 launch takes the physics kernel compiled for the handle's model (LDS layout, table
+ *                       offsets, dims and the default solver configuration as compile-time constants; csrc/avsim_phys_specs.h lists the
+ *                       models and the values) when the handle's layout, table offsets, dims and integer solver options ("solver",
+ *                       "newton_iters", "noslip_iters", "noslip_trees", "noslip_per_tree", "qcqp_tridiag", "newton_early_exit",
+ *                       "newton_component", "ls_iterations", "num_joints") equal that kernel's exactly at the launch, the generic kernel
+ *                       otherwise; 0 = always the generic kernel; 2 = require: a step whose launch would take the generic kernel (another
+ *                       model, capacities changed by "maxefc" / "maxcon", one of those options off its default, f64, two capacity tiers)
+ *                       fails with AVSIM_EINVAL before anything is enqueued -- avsim_step*,
  *                       avsim_reset, avsim_set_state / avsim_set_qpos and avsim_observe ask before their IK / reset / conversion kernels.
  *                       Same results to the last bit in all three settings
+ *   "noslip_iters"      0 .. 100: sweeps of the noslip pass after the solver (default: the model's own, 3 in the committed models)
  *   "noslip_per_tree"   1 (default): the dry-friction rows of the noslip pass are relaxed per kinematic tree, all trees at once
  *                       (models with <= 8 trees); 0 = six rows at a time through the Gauss-Seidel groups (what models with more
  *                       trees get); same results to rounding

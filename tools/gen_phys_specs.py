@@ -1,5 +1,5 @@
 """Regenerates av_aloha_amd/csrc/avsim_phys_specs.h: builds tools/gen_phys_specs.cpp for the host (it includes the physics header and
-runs PhysHost::build without a device) and runs it on the models that get a k_phys compiled for them.
+runs PhysHost::init without a device) and runs it on the models that get a k_phys compiled for them.
 
     python tools/gen_phys_specs.py            # rewrites the committed header
     python tools/gen_phys_specs.py --out X.h  # writes elsewhere (tests/test_phys_spec_host.py compares that with the committed one)
