@@ -84,8 +84,8 @@ struct avsim {
     JpegHost jpeg;       // JPEG streams of such images (avsim_jpeg.hip.h): tables per shape, the intervals' staging area
     JpegDecHost jpegdec; // and those streams back into images: Huffman lookup tables, the coefficients' staging area
     ComposeHost compose; // views resampled into a canvas, labels (avsim_compose.hip.h): coefficient tables per size pair, the validated placements
-    StageRing stage;     // the pinned staging of a call's host arrays (avsim_stage.h): avsim_image_prep's and avsim_image_jitter's
-    ImgAugHost imgaug;   // colour and sharpness jitter (avsim_imgaug.hip.h): the gray sums behind contrast
+    StageRing stage;     // the pinned staging of a call's host arrays (avsim_stage.h): avsim_image_prep's, avsim_image_jitter's and avsim_image_augment's
+    ImgAugHost imgaug;   // colour, sharpness and affine augmentation (avsim_imgaug.hip.h): the gray sums behind contrast, the scratch images of sharpness + affine
     ChunkHost chunks;    // per-env execution of action chunks (avsim_chunks.hip.h), once avsim_chunk_setup has run
     ObsHistHost obshist; // per-env observation histories (avsim_obshist.hip.h), once avsim_obs_history_setup has run
     bool jpegdec_events = false;   // option "jpeg_decode_events": avsim_jpeg_decode records ev[12..15] around its three kernels
@@ -525,6 +525,7 @@ int avsim_set_option(avsim_t* h, const char* name, double value) {
     if (!std::strcmp(name, "render_chunk")) { if (value < 1) { h->set_error("render_chunk is a number of envs >= 1"); return AVSIM_EINVAL; } h->render.env_chunk = (int)value; return AVSIM_OK; }
     if (!std::strcmp(name, "jpeg_decode_events")) { h->jpegdec_events = value != 0; return AVSIM_OK; }
     if (!std::strcmp(name, "jpeg_decode_budget")) { if (value < 1) { h->set_error("jpeg_decode_budget is a number of bytes >= 1"); return AVSIM_EINVAL; } h->jpegdec.coef_budget = (size_t)value; return AVSIM_OK; }
+    if (!std::strcmp(name, "augment_scratch_bytes")) { if (!(value >= 1)) { h->set_error("augment_scratch_bytes is a number of bytes >= 1"); return AVSIM_EINVAL; } h->imgaug.scratch_limit = (size_t)value; return AVSIM_OK; }
     if (!std::strcmp(name, "diffik_iters")) { h->ik.diff_iters = (int)value; return AVSIM_OK; }
     if (!std::strcmp(name, "gradik_iters")) { h->ik.grad_iters = (int)value; return AVSIM_OK; }
     try {
@@ -1192,6 +1193,32 @@ int avsim_image_jitter(avsim_t* h, const void* img, int nsrc, int height, int wi
     if ((rc = h->in(IMG_IN, img, (size_t)nsrc * height * width * img_bpp(0), &dimg))) return rc;
     if ((rc = h->out_begin(IMG_RESULT, out, obytes, &dout))) return rc;
     if (h->imgaug.launch(h->stage, h->stream, dimg, height, width, box_mask, factor, src_index, nout, mean_std, out_h, out_w, (float*)dout, h->err)) return AVSIM_EHIP;
+    if ((rc = h->out_end(IMG_RESULT, out, obytes))) return rc;
+    return h->finish();
+}
+
+// avsim_image_jitter with the geometric op, bit 5.  Without the bit anywhere: avsim_image_jitter's launches
+int avsim_image_augment(avsim_t* h, const void* img, int nsrc, int height, int width, const int32_t* box_mask, const float* factor, const float* affine, int interp,
+                        const int32_t* src_index, int nout, const float* mean_std, int out_h, int out_w, float* out) {
+    if (!h) return AVSIM_EINVAL;
+    if (!img || !box_mask || !factor || !out || nsrc < 1 || nout < 1) { h->set_error("avsim_image_augment: bad arguments"); return AVSIM_EINVAL; }
+    int rc;
+    if ((rc = img_args(h, "avsim_image_augment", 0, height, width, 1, out_h, out_w))) return rc;
+    {   // the host arrays are checked before anything moves or is launched
+        std::string why;
+        if (imgaug_validate_affine(nsrc, height, width, box_mask, factor, affine, interp, src_index, nout, mean_std, out_h, out_w, why)) { h->set_error("%s", why.c_str()); return AVSIM_EINVAL; }
+    }
+    bool any = false;
+    for (int i = 0; i < nout && !any; i++) any = box_mask[4 * (size_t)i + 3] & IAG_AFFINE;
+    AVS_ON_DEVICE(h);
+    const void* dimg = nullptr;
+    void* dout = nullptr;
+    const size_t obytes = sizeof(float) * 3 * (size_t)nout * out_h * out_w;
+    if ((rc = h->in(IMG_IN, img, (size_t)nsrc * height * width * img_bpp(0), &dimg))) return rc;
+    if ((rc = h->out_begin(IMG_RESULT, out, obytes, &dout))) return rc;
+    if (any ? h->imgaug.launch_affine(h->stage, h->stream, dimg, height, width, box_mask, factor, affine, interp, src_index, nout, mean_std, out_h, out_w, (float*)dout, h->err)
+            : h->imgaug.launch(h->stage, h->stream, dimg, height, width, box_mask, factor, src_index, nout, mean_std, out_h, out_w, (float*)dout, h->err))
+        return AVSIM_EHIP;
     if ((rc = h->out_end(IMG_RESULT, out, obytes))) return rc;
     return h->finish();
 }

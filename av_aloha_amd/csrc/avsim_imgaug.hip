@@ -1,4 +1,4 @@
-// avsim_imgaug.hip -- the kernels of avsim_image_jitter: brightness, contrast, saturation, hue and sharpness of a decoded u8
+// avsim_imgaug.hip -- the kernels of avsim_image_jitter and avsim_image_augment: brightness, contrast, saturation, hue and sharpness of a decoded u8
 // frame, the crop, the mirror and the normalisation in one pass, plus the reduction contrast needs first.  av_aloha_amd/imgaug.py is the
 // specification; every float32 operation here is the one it names, rounded on its own.  The unit is built -ffp-contract=off with IEEE
 // division and denormals kept (av_aloha_amd/build.py): a * f + b * g is two v_mul and a v_add, x / y the v_div_scale / v_div_fmas /
@@ -17,7 +17,16 @@
 //                    image, not to the crop), keeps the three floats per pixel in LDS, and after a barrier every lane sums the eight
 //                    neighbours of its pixels in the specification's order.  The mirror, the normalisation and the stores are
 //                    k_image_prep's: a 16-byte store per plane where the address allows, single floats where it does not.  The mask is one
-//                    per output, so every branch on it is uniform in the workgroup.
+//                    per output, so every branch on it is uniform in the workgroup.  Its body is iag_apply_tile, which the two kernels below share.
+// The kernels of avsim_image_augment, which adds bit 5, an affine resampling of the whole image between sharpness and the crop:
+//   k_aug_apply_list k_aug_apply for a list of outputs: those of a call that have no bit 5, when others have.
+//   k_aug_affine<interp, format>  k_aug_apply's grid and tile; a lane makes four consecutive output pixels: the source position of each by
+//                    the specification's float32 steps, one tap (nearest) or four (bilinear), each tested against the image in float before an
+//                    index exists.  Format 0, outputs without sharpness: a tap is three bytes of the u8 image through the table and the
+//                    pointwise chain -- the chain commutes with the gather, and the contrast mean is k_aug_gray_sum's, the pre-affine image's.
+//                    Format 1, outputs with sharpness: a tap is three floats of the image k_aug_whole made.  A tap outside is 0.
+//   k_aug_whole      iag_apply_tile over the whole source image of an output that has sharpness and bit 5 -- no box, no mirror, no
+//                    normalisation -- into one of the float scratch images of ImgAugHost.
 #include "avsim_imgaug.hip.h"
 
 #include <algorithm>
@@ -149,15 +158,13 @@ __global__ void __launch_bounds__(IAG_THREADS) k_aug_gray_sum(const uint8_t* __r
     }
 }
 
-// grid = (tiles across, tiles down, outputs of this launch); ms: mean[3], std[3]; out: float32 [nout][3][oh][ow]
-__global__ void __launch_bounds__(IAG_THREADS) k_aug_apply(const uint8_t* __restrict__ src, int SH, int SW, const AugItem* __restrict__ items, int item0,
-                                                           const float* __restrict__ ms, int normalise, int oh, int ow,
-                                                           const unsigned long long* __restrict__ gsum, float* __restrict__ out) {
+// k_aug_apply's workgroup: the tile (blockIdx.x, blockIdx.y) of the output P, whose gray sum is *gs, into the image at oimg (three planes
+// of oh x ow).  ms: mean[3], std[3]
+__device__ __forceinline__ void iag_apply_tile(const uint8_t* __restrict__ src, int SH, int SW, const AugItem& P, const unsigned long long* __restrict__ gs,
+                                               const float* __restrict__ ms, int normalise, int oh, int ow, float* __restrict__ oimg) {
     __shared__ float s_tab[256];
     __shared__ float s_x[3 * IAG_SPLANE];
     const int tid = threadIdx.x;
-    const int i = item0 + blockIdx.z;
-    const AugItem P = items[i];
     const int flip = P.fm & 1;
     AugPoint A;
     A.mask = P.fm >> 1;
@@ -165,7 +172,7 @@ __global__ void __launch_bounds__(IAG_THREADS) k_aug_apply(const uint8_t* __rest
     A.gs = 1.0f - A.fs;
     A.mterm = 0.0f;
     if (A.mask & IAG_CONTRAST) {
-        const float m = (float)((double)gsum[i] / (double)((unsigned long long)SH * (unsigned long long)SW * 1048576ull));
+        const float m = (float)((double)*gs / (double)((unsigned long long)SH * (unsigned long long)SW * 1048576ull));
         A.mterm = m * (1.0f - A.fc);
     }
     const float fsh = P.f[4], gsh = 1.0f - fsh;
@@ -236,7 +243,7 @@ __global__ void __launch_bounds__(IAG_THREADS) k_aug_apply(const uint8_t* __rest
     }
     if (!mine) return;
     const size_t plane = (size_t)oh * ow;
-    float* o = out + (size_t)i * 3 * plane + (size_t)(ty0 + ly) * ow + (tx0 + lx);
+    float* o = oimg + (size_t)(ty0 + ly) * ow + (tx0 + lx);
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         float v0 = v[c][0], v1 = v[c][1], v2 = v[c][2], v3 = v[c][3];
@@ -253,6 +260,192 @@ __global__ void __launch_bounds__(IAG_THREADS) k_aug_apply(const uint8_t* __rest
     }
 }
 
+// grid = (tiles across, tiles down, outputs of this launch); ms: mean[3], std[3]; out: float32 [nout][3][oh][ow]
+__global__ void __launch_bounds__(IAG_THREADS) k_aug_apply(const uint8_t* __restrict__ src, int SH, int SW, const AugItem* __restrict__ items, int item0,
+                                                           const float* __restrict__ ms, int normalise, int oh, int ow,
+                                                           const unsigned long long* __restrict__ gsum, float* __restrict__ out) {
+    const int i = item0 + blockIdx.z;
+    const AugItem P = items[i];
+    iag_apply_tile(src, SH, SW, P, gsum + i, ms, normalise, oh, ow, out + (size_t)i * 3 * ((size_t)oh * ow));
+}
+
+// k_aug_apply for the outputs list[l0 + blockIdx.z]: those of an avsim_image_augment call that have no bit 5, when others have
+__global__ void __launch_bounds__(IAG_THREADS) k_aug_apply_list(const uint8_t* __restrict__ src, int SH, int SW, const AugItem* __restrict__ items,
+                                                                const int* __restrict__ list, int l0, const float* __restrict__ ms, int normalise, int oh, int ow,
+                                                                const unsigned long long* __restrict__ gsum, float* __restrict__ out) {
+    const int i = list[l0 + blockIdx.z];
+    const AugItem P = items[i];
+    iag_apply_tile(src, SH, SW, P, gsum + i, ms, normalise, oh, ow, out + (size_t)i * 3 * ((size_t)oh * ow));
+}
+
+// The colour ops and sharpness of the outputs list[l0 + blockIdx.z] over their WHOLE source images -- no box, no mirror, no normalisation --
+// into scratch: float32 [gridDim.z][3][SH][SW], which k_aug_affine<., 1> then gathers from.  grid = (tiles of the source, ., outputs of the group)
+__global__ void __launch_bounds__(IAG_THREADS) k_aug_whole(const uint8_t* __restrict__ src, int SH, int SW, const AugItem* __restrict__ items,
+                                                           const int* __restrict__ list, int l0, const unsigned long long* __restrict__ gsum,
+                                                           float* __restrict__ scratch) {
+    const int i = list[l0 + blockIdx.z];
+    AugItem P = items[i];
+    P.x0 = 0; P.y0 = 0; P.fm &= ~1;
+    iag_apply_tile(src, SH, SW, P, gsum + i, nullptr, 0, SH, SW, scratch + (size_t)blockIdx.z * 3 * ((size_t)SH * SW));
+}
+
+// One tap of the gather.  FMT 0: the u8 source pixel through the table and the pointwise chain; FMT 1: the three planes of a float image
+template <int FMT>
+__device__ __forceinline__ void iag_tap(const void* __restrict__ img, size_t HW, int SW, const float* s_tab, const AugPoint& A, float xi, float yi, float wlim, float hlim,
+                                        float& r, float& g, float& b) {
+    r = g = b = 0.0f;
+    if (xi >= 0.0f && xi <= wlim && yi >= 0.0f && yi <= hlim) {      // on the floats: no address is formed for a tap outside (or a NaN)
+        const size_t pix = (size_t)(int)yi * SW + (size_t)(int)xi;
+        if (FMT == 0) {
+            const uint8_t* q = (const uint8_t*)img + pix * 3;
+            r = s_tab[q[0]]; g = s_tab[q[1]]; b = s_tab[q[2]];
+            iag_point(A, r, g, b);
+        } else {
+            const float* q = (const float*)img + pix;
+            r = q[0]; g = q[HW]; b = q[2 * HW];
+        }
+    }
+}
+
+// grid = (tiles across, tiles down, outputs of this launch), k_aug_apply's tiles: the outputs list[l0 + blockIdx.z], which have bit 5.
+// FMT 0: src = the u8 images, the pointwise chain runs per tap (it commutes with the gather; the contrast mean is the pre-affine image's);
+// FMT 1: src = k_aug_whole's scratch, image blockIdx.z.  mats: float32 [nout][6]
+template <int INTERP, int FMT>
+__global__ void __launch_bounds__(IAG_THREADS) k_aug_affine(const void* __restrict__ src, int SH, int SW, const AugItem* __restrict__ items, const float* __restrict__ mats,
+                                                            const int* __restrict__ list, int l0, const float* __restrict__ ms, int normalise, int oh, int ow,
+                                                            const unsigned long long* __restrict__ gsum, float* __restrict__ out) {
+    __shared__ float s_tab[256];
+    const int tid = threadIdx.x;
+    const int i = list[l0 + blockIdx.z];
+    const AugItem P = items[i];
+    const int flip = P.fm & 1;
+    const size_t HW = (size_t)SH * SW;
+    AugPoint A;
+    A.mask = 0;
+    const void* img;
+    if (FMT == 0) {
+        A.mask = P.fm >> 1;
+        A.fb = P.f[0]; A.fc = P.f[1]; A.fs = P.f[2]; A.fh = P.f[3];
+        A.gs = 1.0f - A.fs;
+        A.mterm = 0.0f;
+        if (A.mask & IAG_CONTRAST) {
+            const float m = (float)((double)gsum[i] / (double)((unsigned long long)SH * (unsigned long long)SW * 1048576ull));
+            A.mterm = m * (1.0f - A.fc);
+        }
+        s_tab[tid] = (float)tid / 255.0f;
+        __syncthreads();
+        img = (const uint8_t*)src + (size_t)P.src * HW * 3;
+    } else {
+        img = (const float*)src + (size_t)blockIdx.z * 3 * HW;
+    }
+    const float* M = mats + 6 * (size_t)i;
+    const float m0 = M[0], m1 = M[1], m2 = M[2], m3 = M[3], m4 = M[4], m5 = M[5];
+    const int tx0 = blockIdx.x * IAG_TX, ty0 = blockIdx.y * IAG_TY;
+    const int ly = tid >> 4, lx = (tid & 15) * 4;
+    const int oy = ty0 + ly, ox = tx0 + lx;
+    if (oy >= oh || ox >= ow) return;
+    const int npx = min(4, ow - ox);
+    const float halfw = (float)SW / 2.0f, halfh = (float)SH / 2.0f;
+    const float backx = halfw - 0.5f, backy = halfh - 0.5f;
+    const float wlim = (float)(SW - 1), hlim = (float)(SH - 1);
+    const float yf = ((float)(P.y0 + oy) + 0.5f) - halfh;
+    float v[3][4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        v[0][k] = v[1][k] = v[2][k] = 0.0f;
+        if (k >= npx) continue;
+        const int X = P.x0 + (flip ? ow - 1 - (ox + k) : ox + k);      // the pixel of the whole image behind output column ox + k
+        const float xf = ((float)X + 0.5f) - halfw;
+        const float sx = (((m0 * xf) + (m1 * yf)) + m2) + backx;
+        const float sy = (((m3 * xf) + (m4 * yf)) + m5) + backy;
+        if (INTERP == 0) {
+            iag_tap<FMT>(img, HW, SW, s_tab, A, rintf(sx), rintf(sy), wlim, hlim, v[0][k], v[1][k], v[2][k]);
+        } else {
+            const float x0 = floorf(sx), y0 = floorf(sy);
+            const float wx = sx - x0, wy = sy - y0, ux = 1.0f - wx, uy = 1.0f - wy;
+            const float x1 = x0 + 1.0f, y1 = y0 + 1.0f;
+            float a[3], b[3], c[3], d[3];
+            iag_tap<FMT>(img, HW, SW, s_tab, A, x0, y0, wlim, hlim, a[0], a[1], a[2]);
+            iag_tap<FMT>(img, HW, SW, s_tab, A, x1, y0, wlim, hlim, b[0], b[1], b[2]);
+            iag_tap<FMT>(img, HW, SW, s_tab, A, x0, y1, wlim, hlim, c[0], c[1], c[2]);
+            iag_tap<FMT>(img, HW, SW, s_tab, A, x1, y1, wlim, hlim, d[0], d[1], d[2]);
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++) {
+                const float top = a[ch] * ux + b[ch] * wx, bot = c[ch] * ux + d[ch] * wx;
+                v[ch][k] = top * uy + bot * wy;
+            }
+        }
+    }
+    const size_t plane = (size_t)oh * ow;
+    float* o = out + (size_t)i * 3 * plane + (size_t)oy * ow + ox;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        float v0 = v[c][0], v1 = v[c][1], v2 = v[c][2], v3 = v[c][3];
+        if (normalise) {
+            const float mean = ms[c], sd = ms[3 + c];
+            v0 = (v0 - mean) / sd; v1 = (v1 - mean) / sd; v2 = (v2 - mean) / sd; v3 = (v3 - mean) / sd;
+        }
+        float* dst = o + c * plane;
+        if (npx == 4 && ((uintptr_t)dst & 15) == 0) {
+            *(float4*)dst = make_float4(v0, v1, v2, v3);
+        } else {
+            for (int j = 0; j < npx; j++) dst[j] = iag_pick(j, v0, v1, v2, v3);
+        }
+    }
+}
+
+// zeroes gsum and runs k_aug_gray_sum for the ncon outputs of cidx
+static void iag_sums(hipStream_t stream, const void* src, size_t HW, const AugItem* items, const int* cidx, int nout, int ncon, unsigned long long* gsum, hipError_t& e) {
+    e = hipMemsetAsync(gsum, 0, sizeof(unsigned long long) * (size_t)nout, stream);
+    if (e != hipSuccess) return;
+    // a slab: some eight units of 16 pixels per lane
+    const size_t units = 3 * HW / IAG_UNIT;
+    const int slabs = (int)std::min<size_t>(IAG_MAX_SLABS, std::max<size_t>(1, (units + 8 * IAG_THREADS - 1) / (8 * IAG_THREADS)));
+    for (int c0 = 0; c0 < ncon; c0 += 65535)
+        hipLaunchKernelGGL(k_aug_gray_sum, dim3(slabs, std::min(65535, ncon - c0)), dim3(IAG_THREADS), 0, stream, (const uint8_t*)src, HW, items, cidx, c0, gsum);
+}
+
+template <int FMT>
+static void iag_launch_affine(hipStream_t stream, int interp, dim3 grid, const void* src, int SH, int SW, const AugItem* items, const float* mats, const int* list, int l0,
+                              const float* ms, int normalise, int oh, int ow, const unsigned long long* gsum, float* out) {
+    if (interp == 0)
+        hipLaunchKernelGGL((k_aug_affine<0, FMT>), grid, dim3(IAG_THREADS), 0, stream, src, SH, SW, items, mats, list, l0, ms, normalise, oh, ow, gsum, out);
+    else
+        hipLaunchKernelGGL((k_aug_affine<1, FMT>), grid, dim3(IAG_THREADS), 0, stream, src, SH, SW, items, mats, list, l0, ms, normalise, oh, ow, gsum, out);
+}
+
+int imgaug_launch_affine(hipStream_t stream, const void* src, int SH, int SW, const void* stage, int nout, int ncon, const int count[3], int interp, bool normalise,
+                         int oh, int ow, unsigned long long* gsum, float* scratch, int group, float* out, std::string& err) {
+    const AugItem* items = (const AugItem*)stage;
+    const int* cidx = (const int*)(items + nout);
+    const float* ms = (const float*)(cidx + nout);
+    const float* mats = ms + 8;
+    const int* plain = (const int*)(mats + 6 * (size_t)nout);
+    const int *gather = plain + nout, *sharp = gather + nout;
+    const size_t HW = (size_t)SH * SW;
+    const int norm = normalise ? 1 : 0;
+    hipError_t e = hipSuccess;
+    if (ncon > 0) {
+        iag_sums(stream, src, HW, items, cidx, nout, ncon, gsum, e);
+        if (e != hipSuccess) { err = std::string("image augment sums: ") + hipGetErrorString(e); return -3; }
+    }
+    const dim3 tiles((ow + IAG_TX - 1) / IAG_TX, (oh + IAG_TY - 1) / IAG_TY), whole((SW + IAG_TX - 1) / IAG_TX, (SH + IAG_TY - 1) / IAG_TY);
+    for (int l0 = 0; l0 < count[0]; l0 += 65535)
+        hipLaunchKernelGGL(k_aug_apply_list, dim3(tiles.x, tiles.y, std::min(65535, count[0] - l0)), dim3(IAG_THREADS), 0, stream, (const uint8_t*)src, SH, SW, items, plain, l0,
+                           ms, norm, oh, ow, gsum, out);
+    for (int l0 = 0; l0 < count[1]; l0 += 65535)
+        iag_launch_affine<0>(stream, interp, dim3(tiles.x, tiles.y, std::min(65535, count[1] - l0)), src, SH, SW, items, mats, gather, l0, ms, norm, oh, ow, gsum, out);
+    // the outputs with sharpness and bit 5, `group` at a time through the scratch images: the stream orders a group's gather before the next group's fill
+    for (int l0 = 0; l0 < count[2]; l0 += group) {
+        const int n = std::min(group, count[2] - l0);
+        hipLaunchKernelGGL(k_aug_whole, dim3(whole.x, whole.y, n), dim3(IAG_THREADS), 0, stream, (const uint8_t*)src, SH, SW, items, sharp, l0, gsum, scratch);
+        iag_launch_affine<1>(stream, interp, dim3(tiles.x, tiles.y, n), scratch, SH, SW, items, mats, sharp, l0, ms, norm, oh, ow, gsum, out);
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) { err = std::string("image augment kernels: ") + hipGetErrorString(e); return -3; }
+    return 0;
+}
+
 int imgaug_launch(hipStream_t stream, const void* src, int SH, int SW, const void* stage, int nout, int ncon, bool normalise, int oh, int ow,
                   unsigned long long* gsum, float* out, std::string& err) {
     const AugItem* items = (const AugItem*)stage;
@@ -261,13 +454,8 @@ int imgaug_launch(hipStream_t stream, const void* src, int SH, int SW, const voi
     const size_t HW = (size_t)SH * SW;
     hipError_t e = hipSuccess;
     if (ncon > 0) {
-        e = hipMemsetAsync(gsum, 0, sizeof(unsigned long long) * (size_t)nout, stream);
+        iag_sums(stream, src, HW, items, cidx, nout, ncon, gsum, e);
         if (e != hipSuccess) { err = std::string("image jitter sums: ") + hipGetErrorString(e); return -3; }
-        // a slab: some eight units of 16 pixels per lane
-        const size_t units = 3 * HW / IAG_UNIT;
-        const int slabs = (int)std::min<size_t>(IAG_MAX_SLABS, std::max<size_t>(1, (units + 8 * IAG_THREADS - 1) / (8 * IAG_THREADS)));
-        for (int c0 = 0; c0 < ncon; c0 += 65535)
-            hipLaunchKernelGGL(k_aug_gray_sum, dim3(slabs, std::min(65535, ncon - c0)), dim3(IAG_THREADS), 0, stream, (const uint8_t*)src, HW, items, cidx, c0, gsum);
     }
     const dim3 tiles((ow + IAG_TX - 1) / IAG_TX, (oh + IAG_TY - 1) / IAG_TY);
     for (int i0 = 0; i0 < nout; i0 += 65535)

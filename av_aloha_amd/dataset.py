@@ -217,6 +217,9 @@ class TrainingBatches:
     avsim_image_jitter instead -- LeRobot's image_transforms (brightness, contrast, saturation, hue, sharpness; a random subset per image,
     drawn by imgaug.augment_plan from a stream of its own) applied to the whole decoded frame, then the same crop and normalisation; the bits
     of imgaug.jitter_reference with plan(epoch)'s boxes and augment_plan(epoch)'s parameters.
+    A config with an "affine" entry of weight > 0 (imgaug.LEROBOT_CFG) adds torchvision's RandomAffine as a sixth op: the images go through
+    avsim_image_augment with imgaug.augment_plan_affine's matrices (one interpolation per config), augment_plan(epoch) carries the matrix as
+    a third element, and the bits are imgaug.jitter_affine_reference's.
     n_obs_steps: None (the default): nothing below applies.  K >= 1: for a policy that reads K observations, the image and state entries
     gain an axis -- "observation.images.<cam>" float32 [B, K, 3, h, w], "observation.state" float32 [B, K, D] --, slot K-1 the item's frame
     and slot k the frame K-1-k steps before it, clamped to the episode's first (imgprep.history_index, LeRobot's negative delta_timestamps);
@@ -265,6 +268,9 @@ class TrainingBatches:
         imgaug.augment_plan(B, cfg, seed, epoch, batch, the camera's index in the data set's cameras).  None without augment."""
         if self.augment is None:
             return None
+        if imgaug.has_affine(self.augment):      # (mask, factor, matrix float32 [B, 6]) from augment_plan_affine, which needs the camera's size
+            return [{c: imgaug.augment_plan_affine(len(part), self.augment, self.seed, epoch, b, k, size=self.sizes[c])[:3] for k, c in enumerate(self.ds.cameras)}
+                    for b, (part, _) in enumerate(self.plan(epoch))]
         return [{c: imgaug.augment_plan(len(part), self.augment, self.seed, epoch, b, k) for k, c in enumerate(self.ds.cameras)}
                 for b, (part, _) in enumerate(self.plan(epoch))]
 
@@ -304,10 +310,18 @@ class TrainingBatches:
             src = raw[f"observation.images.{c}"]
             if aug is not None:
                 ms = self.mean_std.get(c, (None, None))
-                out[f"observation.images.{c}"] = ds.img.jitter_images(src, imgaug.pack_params(box, *aug[c]), (h, w), mean=ms[0], std=ms[1])
+                out[f"observation.images.{c}"] = self._augment(src, box, aug[c], 1, (h, w), ms)
             else:
                 out[f"observation.images.{c}"] = ds.img.prep_images(src, self.lut[c], box, (h, w))
         return out
+
+    def _augment(self, src, box, aug, K, out_hw, ms):
+        """One camera's images through avsim_image_jitter, or avsim_image_augment when the plan carries matrices; every item's parameters K times."""
+        rep = [np.repeat(a, K, axis=0) for a in aug] if K > 1 else list(aug)
+        params = imgaug.pack_params(box, rep[0], rep[1])
+        if len(rep) == 2:
+            return self.ds.img.jitter_images(src, params, out_hw, mean=ms[0], std=ms[1])
+        return self.ds.img.augment_images(src, params, rep[2], out_hw, interp=imgaug.interp_of(self.augment), mean=ms[0], std=ms[1])
 
     def _make_history(self, part, boxes, aug):
         """make() with n_obs_steps = K: the B K frames of history_index through the same calls, every item's box and parameters K times."""
@@ -329,8 +343,7 @@ class TrainingBatches:
             src = raw[f"observation.images.{c}"]
             if aug is not None:
                 ms = self.mean_std.get(c, (None, None))
-                mask, factor = aug[c]
-                img = ds.img.jitter_images(src, imgaug.pack_params(box, np.repeat(mask, K, axis=0), np.repeat(factor, K, axis=0)), (h, w), mean=ms[0], std=ms[1])
+                img = self._augment(src, box, aug[c], K, (h, w), ms)
             else:
                 img = ds.img.prep_images(src, self.lut[c], box, (h, w))
             out[f"observation.images.{c}"] = img.reshape(B, K, 3, h, w)

@@ -1,4 +1,4 @@
-"""The device image calls of libavsim (JPEG encode and decode, compose and label, image statistics, prep and jitter; include/avsim.h) from
+"""The device image calls of libavsim (JPEG encode and decode, compose and label, image statistics, prep, jitter and augment; include/avsim.h) from
 Python: what BatchedSim's numpy methods and the torch methods share, the torch methods themselves (DeviceImageOps, which VecEnv inherits)
 and DeviceImages, the same methods for a caller that has no env (a data set, a video tool)."""
 import numpy as np
@@ -213,6 +213,28 @@ class DeviceImageOps:
         assert out.dtype == torch.float32 and out.device == self.device and tuple(out.shape) == (len(bm), 3, oh, ow) and out.is_contiguous()
         check_call(self.h, self.L.avsim_image_jitter(self.h.h, img.data_ptr(), n, H, W, bm.ctypes.data, fac.ctypes.data, _ffi.ptr(si), len(bm), _ffi.ptr(ms), oh, ow,
                                                      out.data_ptr()))
+        return out
+
+    def augment_images(self, img, params, matrix, out_hw, interp=0, mean=None, std=None, src_index=None, out=None):
+        """jitter_images with the geometric op, mask bit 5 (avsim_image_augment; av_aloha_amd.imgaug.jitter_affine_reference's bits).  matrix:
+        HOST float32 [nout, 6], the inverse matrices (imgaug.affine_matrix) of the outputs that have the bit, or None when none has; interp: 0
+        nearest, 1 bilinear.  Everything else as jitter_images.  Does not synchronise."""
+        from . import imgaug
+        torch = self.torch
+        self._bind_stream()
+        assert isinstance(img, torch.Tensor) and img.dtype == torch.uint8 and img.device == self.device and img.ndim == 4 and img.shape[3] == 3 \
+            and img.is_contiguous(), "augment_images(img=...): a contiguous uint8 [n, H, W, 3] tensor on the env's device"
+        n, H, W = (int(v) for v in img.shape[:3])
+        bm, fac = imgaug.split_params(params)
+        mat = None if matrix is None else np.ascontiguousarray(matrix, dtype=np.float32).reshape(len(bm), 6)
+        si = None if src_index is None else np.ascontiguousarray(src_index, dtype=np.int32).reshape(len(bm))
+        ms = imgaug.mean_std(mean, std)
+        oh, ow = int(out_hw[0]), int(out_hw[1])
+        if out is None:
+            out = torch.empty((len(bm), 3, max(oh, 0), max(ow, 0)), dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.device == self.device and tuple(out.shape) == (len(bm), 3, oh, ow) and out.is_contiguous()
+        check_call(self.h, self.L.avsim_image_augment(self.h.h, img.data_ptr(), n, H, W, bm.ctypes.data, fac.ctypes.data, _ffi.ptr(mat), int(interp), _ffi.ptr(si), len(bm),
+                                                      _ffi.ptr(ms), oh, ow, out.data_ptr()))
         return out
 
 

@@ -345,6 +345,28 @@ class BatchedSim:
                                                                out.ctypes.data))
         return out
 
+    def augment_images(self, img, params, matrix, out_hw, interp=0, mean=None, std=None, src_index=None, out=None):
+        """float32 [nout, 3, oh, ow]: jitter_images with the geometric op, mask bit 5 (avsim_image_augment): the bits of
+        av_aloha_amd.imgaug.jitter_affine_reference.  matrix: float32 [nout, 6], the inverse matrices (imgaug.affine_matrix) of the outputs that
+        have the bit, or None when none has; interp: 0 nearest, 1 bilinear.  ValueError for what the library refuses."""
+        from . import imgaug
+        img = np.ascontiguousarray(img)
+        if not (img.dtype == np.uint8 and img.ndim == 4 and img.shape[3] == 3):
+            raise ValueError("augment_images: the images are a u8 [n, H, W, 3] array")
+        n, H, W = img.shape[:3]
+        bm, fac = imgaug.split_params(params)
+        mat = None if matrix is None else np.ascontiguousarray(matrix, dtype=np.float32).reshape(len(bm), 6)
+        si = None if src_index is None else np.ascontiguousarray(src_index, dtype=np.int32).reshape(len(bm))
+        ms = imgaug.mean_std(mean, std)
+        oh, ow = int(out_hw[0]), int(out_hw[1])
+        if out is None:
+            out = np.empty((len(bm), 3, max(oh, 0), max(ow, 0)), dtype=np.float32)
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (len(bm), 3, oh, ow)):
+            raise ValueError("augment_images: out is a C-contiguous float32 [nout, 3, oh, ow] array")
+        images.check_call(self.h, self.h.L.avsim_image_augment(self.h.h, img.ctypes.data, n, H, W, bm.ctypes.data, fac.ctypes.data, _ffi.ptr(mat), int(interp), _ffi.ptr(si),
+                                                                len(bm), _ffi.ptr(ms), oh, ow, out.ctypes.data))
+        return out
+
     def jitter_gray_sums(self, nout):
         """uint64 [nout]: the integer sums behind the contrast means of the last jitter_images call (avsim_image_jitter_sums;
         imgaug.gray_sum_reference's), meaningful for the outputs that had the contrast bit.  For tests."""

@@ -336,6 +336,23 @@ int avsim_image_jitter(avsim_t* h, const void* img /* u8 [nsrc][H][W][3] */, int
                        int out_h, int out_w, float* out /* [nout][3][out_h][out_w] */);
 int avsim_image_jitter_sums(avsim_t* h, uint64_t* sums /* [nout] */, int nout);
 
+/* avsim_image_jitter with the geometric op of LeRobot's image_transforms, torchvision's RandomAffine with fill 0 (csrc/avsim_imgaug.hip; DESIGN
+ * 8.af); av_aloha_amd/imgaug.py (jitter_affine_reference) is the specification, and the call equals it bit for bit (-0 and +0 aside).
+ * avsim_image_augment: everything as avsim_image_jitter, and mask bit 5 (32): after the colour operations and sharpness, still on the WHOLE
+ * image and before the crop, output i is resampled through the float32 inverse matrix M = affine[i]: with xf = (x + 0.5) - W / 2 and
+ * yf = (y + 0.5) - H / 2, the pixel (x, y) reads the source position sx = M0 xf + M1 yf + M2 + (W / 2 - 0.5), sy = M3 xf + M4 yf + M5 +
+ * (H / 2 - 0.5) (imgaug.py names every rounding; imgaug.affine_matrix makes M from an angle, a translation, a scale and shears).  interp, one
+ * per call: 0 the nearest pixel (half to even), 1 bilinear.  A tap outside the image is 0 in every channel, and is normalised like any other
+ * value.  affine is a HOST array like factor and may be NULL when no mask has bit 5; the entries of an output without the bit are not read.
+ * Without bit 5 anywhere the call runs avsim_image_jitter's kernels.  Outputs that have sharpness and bit 5 go through float images of the
+ * library's, at most 128 MiB of them at a time (option "augment_scratch_bytes"; one whole image at least), grown on demand.  AVSIM_EINVAL,
+ * with nothing launched and out untouched: avsim_image_jitter's conditions with masks 0..63, an interp other than 0 / 1, a matrix entry of a
+ * set bit 5 that is not finite or larger than 2^20 in magnitude, affine NULL with a bit 5 set.  avsim_image_jitter_sums reads this call's sums too. */
+int avsim_image_augment(avsim_t* h, const void* img /* u8 [nsrc][H][W][3] */, int nsrc, int height, int width,
+                        const int32_t* box_mask /* [nout][4]: x0, y0, flip, mask */, const float* factor /* [nout][5] */,
+                        const float* affine /* [nout][6] or NULL */, int interp, const int32_t* src_index /* or NULL */, int nout,
+                        const float* mean_std /* [2][3] or NULL: [0,1] output */, int out_h, int out_w, float* out /* [nout][3][out_h][out_w] */);
+
 /* Per-env episodes on the device (a vector env with gymnasium's NEXT_STEP autoreset; av_aloha_amd/vec_env.py).  Pointers follow the
  * handle's I/O mode, except box / share of the set-up (host pointers).  In device mode no step, reset, sample or render call
  * synchronises; avsim_episode_setup does (it reallocates the records: once per evaluation), and so do avsim_episode_log /

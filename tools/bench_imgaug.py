@@ -1,4 +1,4 @@
-"""What the device's colour and sharpness augmentation (avsim_image_jitter) costs next to the same arithmetic as torch tensor ops.  Writes
+"""What the device's colour, sharpness and affine augmentation (avsim_image_jitter, avsim_image_augment) costs next to the same arithmetic as torch tensor ops.  Writes
 profiles/imgaug_<tag>.json.
 
     python tools/bench_imgaug.py --frames 256 --tag r13
@@ -15,7 +15,18 @@ its contrast mean is the crop's and its blur stops at the crop's border, where (
 convolution also round in their own order.  So the largest absolute difference between the two (before the normalisation, over all pixels
 and over those not on the crop's border) is reported, not asserted -- tests/test_gpu_imgaug.py compares (b) with the specification for
 equality.  Bytes: (b) writes 12 B and reads 3 B per output pixel, and 3 B per source pixel of every image that has contrast; its rate is
-those bytes over the time of the call, against the 8 TB/s HBM roof."""
+those bytes over the time of the call, against the 8 TB/s HBM roof.
+
+The geometric op (avsim_image_augment), cases "affine" (bit 5 on all images, nearest), "affine_bilinear", "default+affine"
+(imgaug.LEROBOT_CFG's plan: 3 of 6 per image, nearest) and "sharpness+affine" (mask 48 on all images, nearest).  The op runs on the whole
+frame before the crop, so way (a) cannot start from the crop: it is u8 -> float32 CHW of the whole frames, the colour formulas on them,
+F.affine_grid + F.grid_sample(padding_mode="zeros", align_corners=False) with the same matrices (images without the bit get the identity),
+one gather for the boxes, (x - mean) / std; way (b) is the one call.  The two differ where a source coordinate rounds the other way
+(nearest) and by rounding (bilinear), so the largest difference and the share of values that differ by more than 1e-3 are reported.
+Bytes of (b), counted as what has to move, not what the caches saw: 12 B written per output value triple; read 3 B per output pixel (its
+taps lie next to its neighbours' -- bilinear's four are the same lines), 3 B per source pixel of an image that has contrast; an image
+with sharpness and bit 5 also reads its whole frame (3 B per pixel), writes and reads it as floats once (12 B per pixel written, 12 B per
+output pixel read back)."""
 import argparse
 import json
 import os
@@ -174,8 +185,76 @@ def bench(n, rounds, warmup):
                               "b_rate_TBps": (written + read) / (med * 1e-3) / 1e12, "b_rate_over_hbm_roof": (written + read) / (med * 1e-3) / HBM_ROOF,
                               "max_abs_diff_0_1": diff, "max_abs_diff_0_1_off_the_crop_border": diff_inside}
         print(name, json.dumps(res["cases"][name]), flush=True)
+    bench_affine(env, u8, box, ops, mean, std, out_b, ev, res, rng, warmup, rounds)
     env.close()
     return res
+
+
+def bench_affine(env, u8, box, ops, mean, std, out_b, ev, res, rng, warmup, rounds):
+    """The cases with the geometric op (module docstring)."""
+    import numpy as np
+    import torch
+    import torch.nn.functional as F
+    from av_aloha_amd import imgaug
+    n, dev = int(u8.shape[0]), u8.device
+    oh, ow = CROP
+    lerobot = imgaug.augment_plan_affine(n, imgaug.LEROBOT_CFG, seed=0, size=(H, W))
+    every = imgaug.augment_plan_affine(n, dict(imgaug.LEROBOT_CFG, max_num_transforms=6), seed=1, size=(H, W))      # a matrix for every image
+    cases = [("affine", np.full(n, 32, dtype=np.int32), every[1], every[2], 0), ("affine_bilinear", np.full(n, 32, dtype=np.int32), every[1], every[2], 1),
+             ("default+affine", lerobot[0], lerobot[1], lerobot[2], 0), ("sharpness+affine", np.full(n, 48, dtype=np.int32), every[1], every[2], 0)]
+    iy = torch.from_numpy(box[:, 1, None] + np.arange(oh)[None, :]).to(dev)[:, None, :, None]
+    ix = torch.from_numpy(box[:, 0, None] + np.arange(ow)[None, :]).to(dev)[:, None, None, :]
+    ii, ic = torch.arange(n, device=dev)[:, None, None, None], torch.arange(3, device=dev)[None, :, None, None]
+    for name, mask, fac, mat, interp in cases:
+        params = imgaug.pack_params(box, mask, fac)
+        t_fac = [torch.from_numpy(np.ascontiguousarray(fac[:, k])).to(dev).reshape(n, 1, 1, 1) for k in range(5)]
+        t_on = [torch.from_numpy(np.ascontiguousarray((mask >> k & 1).astype(bool))).to(dev).reshape(n, 1, 1, 1) for k in range(5)]
+        all_on = [bool((mask >> k & 1).all()) for k in range(5)]
+        some = [bool((mask >> k & 1).any()) for k in range(5)]
+        m = np.where((mask & 32).astype(bool)[:, None], mat, imgaug.IDENTITY_MATRIX).astype(np.float64)
+        theta = np.stack([np.stack([m[:, 0], m[:, 1] * H / W, m[:, 2] * 2 / W], axis=1), np.stack([m[:, 3] * W / H, m[:, 4], m[:, 5] * 2 / H], axis=1)], axis=1)
+        t_theta = torch.from_numpy(theta.astype(np.float32)).to(dev)
+
+        def way_a(normalise=True):
+            x = u8.permute(0, 3, 1, 2).to(torch.float32) / 255.0
+            for k in range(5):
+                if some[k]:
+                    y = ops[k](x, t_fac[k])
+                    x = y if all_on[k] else torch.where(t_on[k], y, x)
+            grid = F.affine_grid(t_theta, (n, 3, H, W), align_corners=False)
+            x = F.grid_sample(x, grid, mode="bilinear" if interp else "nearest", padding_mode="zeros", align_corners=False)
+            x = x[ii, ic, iy, ix]
+            return (x - mean) / std if normalise else x
+
+        def way_b(normalise=True):
+            return env.augment_images(u8, params, mat, (oh, ow), interp, MEAN if normalise else None, STD if normalise else None, out=out_b)
+
+        a, b = way_a(False), way_b(False)
+        torch.cuda.synchronize()
+        d = (a - b).abs()
+        diff, share = float(d.max()), float((d > 1e-3).float().mean())
+        del a, d
+        t = {"a_torch": [], "b_augment": []}
+        for r in range(warmup + rounds):
+            for key, way in (("a_torch", way_a), ("b_augment", way_b)):
+                ev[0].record()
+                y = way()
+                ev[1].record()
+                torch.cuda.synchronize()
+                del y
+                if r >= warmup:
+                    t[key].append(ev[0].elapsed_time(ev[1]))
+        med = statistics.median(t["b_augment"])
+        ncon, nboth = int((mask >> 1 & 1).sum()), int(((mask & 48) == 48).sum())
+        written = n * 3 * oh * ow * 4 + nboth * 12 * H * W
+        read = n * 3 * oh * ow + ncon * 3 * H * W + nboth * (3 * H * W + 12 * oh * ow - 3 * oh * ow)
+        res["cases"][name] = {**{k: summary(v) for k, v in t.items()}, "a_over_b": statistics.median(t["a_torch"]) / med,
+                              "a_spread": (max(t["a_torch"]) - min(t["a_torch"])) / statistics.median(t["a_torch"]), "interp": interp,
+                              "images_with_affine": int((mask >> 5 & 1).sum()), "images_with_contrast": ncon, "images_with_sharpness_and_affine": nboth,
+                              "b_bytes_written": written, "b_bytes_read": read,
+                              "b_rate_TBps": (written + read) / (med * 1e-3) / 1e12, "b_rate_over_hbm_roof": (written + read) / (med * 1e-3) / HBM_ROOF,
+                              "max_abs_diff_0_1": diff, "share_of_values_differing_by_more_than_1e-3": share}
+        print(name, json.dumps(res["cases"][name]), flush=True)
 
 
 def main():
