@@ -18,6 +18,7 @@
 #include "avsim_imgprep.hip.h"
 #include "avsim_obshist.hip.h"
 #include "avsim_imgaug.hip.h"
+#include "avsim_imgresize.hip.h"
 #include "avsim_episode.hip.h"
 #include "avsim_ik.hip.h"
 #include "avsim_jpeg.hip.h"
@@ -84,7 +85,7 @@ struct avsim {
     JpegHost jpeg;       // JPEG streams of such images (avsim_jpeg.hip.h): tables per shape, the intervals' staging area
     JpegDecHost jpegdec; // and those streams back into images: Huffman lookup tables, the coefficients' staging area
     ComposeHost compose; // views resampled into a canvas, labels (avsim_compose.hip.h): coefficient tables per size pair, the validated placements
-    StageRing stage;     // the pinned staging of a call's host arrays (avsim_stage.h): avsim_image_prep's, avsim_image_jitter's and avsim_image_augment's
+    StageRing stage;     // the pinned staging of a call's host arrays (avsim_stage.h): avsim_image_prep's, avsim_image_jitter's, avsim_image_augment's and avsim_image_resize's
     ImgAugHost imgaug;   // colour, sharpness and affine augmentation (avsim_imgaug.hip.h): the gray sums behind contrast, the scratch images of sharpness + affine
     ChunkHost chunks;    // per-env execution of action chunks (avsim_chunks.hip.h), once avsim_chunk_setup has run
     ObsHistHost obshist; // per-env observation histories (avsim_obshist.hip.h), once avsim_obs_history_setup has run
@@ -1219,6 +1220,28 @@ int avsim_image_augment(avsim_t* h, const void* img, int nsrc, int height, int w
     if (any ? h->imgaug.launch_affine(h->stage, h->stream, dimg, height, width, box_mask, factor, affine, interp, src_index, nout, mean_std, out_h, out_w, (float*)dout, h->err)
             : h->imgaug.launch(h->stage, h->stream, dimg, height, width, box_mask, factor, src_index, nout, mean_std, out_h, out_w, (float*)dout, h->err))
         return AVSIM_EHIP;
+    if ((rc = h->out_end(IMG_RESULT, out, obytes))) return rc;
+    return h->finish();
+}
+
+// Resizing into a rectangle of a padded output (av_aloha_amd/imgresize.py is the specification; the kernels: csrc/avsim_imgresize.hip, a unit of its own flags)
+int avsim_image_resize(avsim_t* h, const void* img, int fmt, int nsrc, int height, int width, const int32_t* src_box, const int32_t* dst, const int32_t* src_index, int nout,
+                       int antialias, const float* fill, const float* mean_std, int out_h, int out_w, float* out) {
+    if (!h) return AVSIM_EINVAL;
+    if (!img || !src_box || !dst || !out || nsrc < 1 || nout < 1) { h->set_error("avsim_image_resize: bad arguments"); return AVSIM_EINVAL; }
+    int rc;
+    if ((rc = img_args(h, "avsim_image_resize", fmt, height, width, 1, out_h, out_w))) return rc;
+    {   // the host arrays are checked before anything moves or is launched
+        std::string why;
+        if (imgresize_validate(nsrc, height, width, src_box, dst, src_index, nout, antialias, fill, mean_std, out_h, out_w, why)) { h->set_error("%s", why.c_str()); return AVSIM_EINVAL; }
+    }
+    AVS_ON_DEVICE(h);
+    const void* dimg = nullptr;
+    void* dout = nullptr;
+    const size_t obytes = sizeof(float) * 3 * (size_t)nout * out_h * out_w;
+    if ((rc = h->in(IMG_IN, img, (size_t)nsrc * height * width * img_bpp(fmt), &dimg))) return rc;
+    if ((rc = h->out_begin(IMG_RESULT, out, obytes, &dout))) return rc;
+    if (imgresize_run(h->stage, h->stream, dimg, fmt, height, width, src_box, dst, src_index, nout, antialias, fill, mean_std, out_h, out_w, (float*)dout, h->err)) return AVSIM_EHIP;
     if ((rc = h->out_end(IMG_RESULT, out, obytes))) return rc;
     return h->finish();
 }

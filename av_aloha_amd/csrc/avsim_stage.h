@@ -1,4 +1,4 @@
-// avsim_stage.h -- pinned staging of the per-call host arrays of avsim_image_prep, avsim_image_jitter and avsim_image_augment: four slots of pinned and of device
+// avsim_stage.h -- pinned staging of the per-call host arrays of avsim_image_prep, avsim_image_jitter, avsim_image_augment and avsim_image_resize: four slots of pinned and of device
 // memory, reused behind events.  Host code only (avsim_imgaug.hip.h, which a unit of other flags reads too, includes it).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -6,7 +6,7 @@ import json
 
 import numpy as np
 
-from . import imgaug, imgprep, jpeg
+from . import imgaug, imgprep, imgresize, jpeg
 from .harness import load_episode
 from .images import DeviceImages
 
@@ -226,11 +226,19 @@ class TrainingBatches:
     "observation.state_is_pad" and "observation.images.<cam>_is_pad" bool [B, K] name the clamped ones.  The K frames of an item share its
     crop box and its augmentation parameters (LeRobot transforms a stacked item with one draw); they go through the same avsim_image_prep /
     avsim_image_jitter call as B K outputs.  What obshist.ObsHistory stacks at evaluation.
+    resize: None (the default): nothing below applies.  (h, w): for a policy with a fixed input size, the crop box (random or centred, as above;
+    crop None: the whole image) becomes the SOURCE REGION of avsim_image_resize and the images are float32 [B, 3, h, w]: the region resized by
+    the triangle filter of interpolate(mode="bilinear", antialias=antialias) -- resize_mode "stretch": to the whole output; "pad": with its
+    aspect ratio kept, the zero padding on the left and on top (imgresize.resize_with_pad_plan, the VLA policies' resize_with_pad) --, then
+    normalised as (v - mean) / std, the padding included; the bits of imgresize.resize_reference.  Without augment that is ONE pass from the
+    decoded u8 frames.  With augment it is TWO: avsim_image_jitter / avsim_image_augment as above but without normalisation, into float32
+    crops, then avsim_image_resize on those floats (fmt 1, not quantised), which normalises.  With n_obs_steps the K frames of an item share
+    the region.  The plans and their draws do not depend on resize.
     stats: CompressedDataset.stats()'s (or load_stats'); a dimension whose std is 0 normalises to nan / inf, as the formula says.
     Like batch(), an iteration step does not wait for the device."""
 
     def __init__(self, ds, batch_size, chunk_size, stats, crop=None, crop_mode="random", normalise=True, seed=0, drop_last=True, augment=None,
-                 n_obs_steps=None):
+                 n_obs_steps=None, resize=None, resize_mode="stretch", antialias=True):
         torch = ds.torch
         self.n_obs_steps = None if n_obs_steps is None else int(n_obs_steps)
         if self.n_obs_steps is not None and self.n_obs_steps < 1:
@@ -243,13 +251,19 @@ class TrainingBatches:
         self.sizes = {c: tuple(ds.size[c]) for c in ds.cameras}
         epoch_plan(0, 1, self.sizes, crop, crop_mode)           # (the arguments' checks)
         self.epoch = 0
+        self.resize = None if resize is None else (int(resize[0]), int(resize[1]))
+        self.resize_mode, self.antialias = resize_mode, bool(antialias)
+        if self.resize is not None:
+            for c, (H, W) in self.sizes.items():           # (the arguments' checks: the mode, the sizes, the ratio cap)
+                sb, dst = imgresize.boxes([(0, 0, 0)], (H, W) if crop is None else crop, self.resize, resize_mode)
+                imgresize.check_resize((1, H, W), sb, dst, None, self.resize)
         self.lut, self.norm = {}, {}
         for c in ds.cameras:
             st = stats[f"observation.images.{c}"]
             lut = imgprep.normalise_lut(st["mean"], st["std"]) if self.normalise else imgprep.identity_lut()
             self.lut[c] = torch.from_numpy(np.ascontiguousarray(lut, dtype=np.float32).reshape(1, 3, 256)).to(ds.device)
         self.mean_std = {}
-        if self.augment is not None and self.normalise:
+        if (self.augment is not None or self.resize is not None) and self.normalise:
             for c in ds.cameras:
                 st = stats[f"observation.images.{c}"]
                 self.mean_std[c] = (st["mean"], st["std"])
@@ -308,7 +322,9 @@ class TrainingBatches:
             h, w = (H, W) if self.crop is None else (int(self.crop[0]), int(self.crop[1]))
             box = np.ascontiguousarray(boxes[c], dtype=np.int32).reshape(B, 3)
             src = raw[f"observation.images.{c}"]
-            if aug is not None:
+            if self.resize is not None:
+                out[f"observation.images.{c}"] = self._resize(src, box, None if aug is None else aug[c], 1, (h, w), self.mean_std.get(c, (None, None)))
+            elif aug is not None:
                 ms = self.mean_std.get(c, (None, None))
                 out[f"observation.images.{c}"] = self._augment(src, box, aug[c], 1, (h, w), ms)
             else:
@@ -322,6 +338,15 @@ class TrainingBatches:
         if len(rep) == 2:
             return self.ds.img.jitter_images(src, params, out_hw, mean=ms[0], std=ms[1])
         return self.ds.img.augment_images(src, params, rep[2], out_hw, interp=imgaug.interp_of(self.augment), mean=ms[0], std=ms[1])
+
+    def _resize(self, src, box, aug, K, crop_hw, ms):
+        """One camera's images through avsim_image_resize, the crop boxes as source regions: from the u8 frames, or, with aug, from the float
+        crops the augmentation made without normalising; mean / std are applied here."""
+        if aug is not None:
+            src = self._augment(src, box, aug, K, crop_hw, (None, None))
+            box = np.zeros((len(box), 3), dtype=np.int32)
+        sb, dst = imgresize.boxes(box, crop_hw, self.resize, self.resize_mode)
+        return self.ds.img.resize_images(src, sb, dst, self.resize, self.antialias, mean=ms[0], std=ms[1])
 
     def _make_history(self, part, boxes, aug):
         """make() with n_obs_steps = K: the B K frames of history_index through the same calls, every item's box and parameters K times."""
@@ -341,11 +366,13 @@ class TrainingBatches:
             h, w = (H, W) if self.crop is None else (int(self.crop[0]), int(self.crop[1]))
             box = np.repeat(np.ascontiguousarray(boxes[c], dtype=np.int32).reshape(B, 3), K, axis=0)
             src = raw[f"observation.images.{c}"]
-            if aug is not None:
+            if self.resize is not None:
+                img = self._resize(src, box, None if aug is None else aug[c], K, (h, w), self.mean_std.get(c, (None, None)))
+            elif aug is not None:
                 ms = self.mean_std.get(c, (None, None))
                 img = self._augment(src, box, aug[c], K, (h, w), ms)
             else:
                 img = ds.img.prep_images(src, self.lut[c], box, (h, w))
-            out[f"observation.images.{c}"] = img.reshape(B, K, 3, h, w)
+            out[f"observation.images.{c}"] = img.reshape(B, K, 3, *img.shape[2:])
             out[f"observation.images.{c}_is_pad"] = t_pad
         return out

@@ -283,24 +283,32 @@ def evaluate_vec(env, select_action, num_episodes: int, seed: int | None = None,
              "success": bool(log["success"][i]), "initial_object_poses": log["initial_object_poses"][i]} for i in range(num_episodes)]
 
 
-def make_preprocessor(venv, stats, crop=None):
+def make_preprocessor(venv, stats, crop=None, resize=None, resize_mode="stretch", antialias=True):
     """A function obs -> the policy's input for a VecEnv, with the numbers training used: dataset.TrainingBatches(crop_mode="center")'s.
     stats: CompressedDataset.stats()'s (dataset.load_stats'); crop = (h, w): the centred box (None: the whole image).  The function reads
     the env's own image buffers (VecEnv.camera_images, either observation format) through VecEnv.prep_images with
     imgprep.normalise_lut(stats) -- the bits of imgprep.prep_reference -- and normalises the state as (x - mean) / std in float32; it returns
     {"observation.images.<cam>": float32 [N, 3, h, w], "observation.state": float32 [N, D]} on the env's device and does not synchronise:
-    evaluate_vec(venv, lambda obs, info: policy(pre(obs)), ...)."""
+    evaluate_vec(venv, lambda obs, info: policy(pre(obs)), ...).
+    resize = (oh, ow): the centred box is the source region of VecEnv.resize_images (avsim_image_resize) instead, resize_mode "stretch" or
+    "pad" and antialias as in dataset.TrainingBatches(crop_mode="center", resize=...), whose numbers these are -- the bits of
+    imgresize.resize_reference; the images are float32 [N, 3, oh, ow]."""
     import torch
-    from . import imgprep
+    from . import imgprep, imgresize
     H, W = venv.observation_height, venv.observation_width
     h, w = (H, W) if crop is None else (int(crop[0]), int(crop[1]))
     if not (1 <= h <= H and 1 <= w <= W):
         raise ValueError(f"crop {(h, w)} does not fit the env's {H} x {W} images")
     x0, y0 = imgprep.center_box((H, W), (h, w))
     box = np.tile(np.array([[x0, y0, 0]], dtype=np.int32), (venv.num_envs, 1))
-    luts = {}
+    luts, mean_std = {}, {}
+    if resize is not None:
+        resize = (int(resize[0]), int(resize[1]))
+        src_box, dst = imgresize.boxes(box, (h, w), resize, resize_mode)
+        imgresize.check_resize((venv.num_envs, H, W), src_box, dst, None, resize)
     for c in venv.cameras:
         st = stats[f"observation.images.{c}"]
+        mean_std[c] = (st["mean"], st["std"])
         luts[c] = torch.from_numpy(np.ascontiguousarray(imgprep.normalise_lut(st["mean"], st["std"]), dtype=np.float32).reshape(1, 3, 256)).to(venv.device)
     mean = torch.from_numpy(np.asarray(stats["observation.state"]["mean"], dtype=np.float32)).to(venv.device)
     std = torch.from_numpy(np.asarray(stats["observation.state"]["std"], dtype=np.float32)).to(venv.device)
@@ -309,7 +317,10 @@ def make_preprocessor(venv, stats, crop=None):
         state = obs["observation.state"] if "observation.state" in obs else obs["agent_pos"].to(torch.float32)
         out = {"observation.state": (state - mean) / std}
         for c in venv.cameras:
-            out[f"observation.images.{c}"] = venv.prep_images(venv.camera_images(c), luts[c], box, (h, w))
+            if resize is not None:
+                out[f"observation.images.{c}"] = venv.resize_images(venv.camera_images(c), src_box, dst, resize, antialias, mean=mean_std[c][0], std=mean_std[c][1])
+            else:
+                out[f"observation.images.{c}"] = venv.prep_images(venv.camera_images(c), luts[c], box, (h, w))
         return out
 
     return pre
@@ -350,14 +361,17 @@ def chunked_policy(venv, predict_chunk, chunk_size, ensemble=None, n_action_step
     return select_action, executor
 
 
-def history_preprocessor(venv, stats, crop=None, n_obs_steps=2):
+def history_preprocessor(venv, stats, crop=None, n_obs_steps=2, resize=None):
     """(observe, history) for chunked_policy(..., observe=observe) and a policy that reads n_obs_steps observations: history is an
     obshist.ObsHistory on venv with make_preprocessor's numbers (stats: CompressedDataset.stats()'s; crop = (h, w): the centred box), kept PER
     ENV -- an env that starts a new episode starts with n_obs_steps copies of its reset frame --, and observe(obs, info) pushes the env's
     observation and returns {"observation.state": float32 [N, K, D], "observation.images.<cam>": float32 [N, K, 3, h, w]}, slot K-1 the
     newest: what dataset.TrainingBatches(n_obs_steps=K, crop_mode="center") trains on.  Nothing synchronises.  Call history.reset() before
-    evaluate_vec when the history has run before (chunked_policy's docstring says why)."""
+    evaluate_vec when the history has run before (chunked_policy's docstring says why).
+    resize: not built -- the observation-history kernel keeps the crop's pixel grid; anything but None raises ValueError."""
     from .obshist import ObsHistory
+    if resize is not None:
+        raise ValueError("history_preprocessor: resize is not supported with observation histories (make_preprocessor has it)")
     H, W = venv.observation_height, venv.observation_width
     if crop is not None and not (1 <= int(crop[0]) <= H and 1 <= int(crop[1]) <= W):
         raise ValueError(f"crop {tuple(crop)} does not fit the env's {H} x {W} images")

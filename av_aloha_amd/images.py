@@ -1,4 +1,4 @@
-"""The device image calls of libavsim (JPEG encode and decode, compose and label, image statistics, prep, jitter and augment; include/avsim.h) from
+"""The device image calls of libavsim (JPEG encode and decode, compose and label, image statistics, prep, jitter, augment and resize; include/avsim.h) from
 Python: what BatchedSim's numpy methods and the torch methods share, the torch methods themselves (DeviceImageOps, which VecEnv inherits)
 and DeviceImages, the same methods for a caller that has no env (a data set, a video tool)."""
 import numpy as np
@@ -237,6 +237,32 @@ class DeviceImageOps:
                                                       _ffi.ptr(ms), oh, ow, out.data_ptr()))
         return out
 
+
+    def resize_images(self, img, src_box, dst, out_hw, antialias=True, fill=None, mean=None, std=None, src_index=None, out=None):
+        """Regions of img resized by the triangle filter of interpolate(mode="bilinear", antialias=...) into rectangles of a padded output,
+        mirrored and normalised in one pass (avsim_image_resize; av_aloha_amd.imgresize.resize_reference's bits).  img: a tensor on the env's
+        device, uint8 [n, H, W, 3] or float32 [n, 3, H, W] (read as floats: a jitter_images result resizes without a loss); src_box: HOST int
+        rows (x0, y0, w, h, flip), the source regions; dst: HOST int rows (ox, oy, rw, rh), where the resized regions go in the oh x ow
+        output (imgresize.resize_with_pad_plan makes a letterbox); fill: three HOST values for every other pixel (None: 0); mean / std: three
+        HOST values each, or None; src_index: a HOST int array, the source image of every output (None: image i).  All host arrays are
+        checked (ValueError) and copied by the library before the call returns.  -> float32 [nout, 3, oh, ow] on the device (out: the tensor
+        to write).  Does not synchronise."""
+        from . import imgresize
+        torch = self.torch
+        self._bind_stream()
+        sf, (n, H, W) = self._canvas_of(img)
+        b = np.ascontiguousarray(src_box, dtype=np.int32).reshape(-1, 5)
+        d = np.ascontiguousarray(dst, dtype=np.int32).reshape(len(b), 4)
+        si = None if src_index is None else np.ascontiguousarray(src_index, dtype=np.int32).reshape(len(b))
+        fl = None if fill is None else np.ascontiguousarray(fill, dtype=np.float32).reshape(3)
+        ms = imgresize.mean_std(mean, std)
+        oh, ow = int(out_hw[0]), int(out_hw[1])
+        if out is None:
+            out = torch.empty((len(b), 3, max(oh, 0), max(ow, 0)), dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.device == self.device and tuple(out.shape) == (len(b), 3, oh, ow) and out.is_contiguous()
+        check_call(self.h, self.L.avsim_image_resize(self.h.h, img.data_ptr(), sf, n, H, W, b.ctypes.data, d.ctypes.data, _ffi.ptr(si), len(b), int(antialias),
+                                                     _ffi.ptr(fl), _ffi.ptr(ms), oh, ow, out.data_ptr()))
+        return out
 
 class DeviceImages(DeviceImageOps):
     """DeviceImageOps for a caller that has no env: images go in and come out as tensors on `device`, and nothing is simulated.  The library

@@ -367,6 +367,29 @@ class BatchedSim:
                                                                 len(bm), _ffi.ptr(ms), oh, ow, out.ctypes.data))
         return out
 
+    def resize_images(self, img, src_box, dst, out_hw, antialias=True, fill=None, mean=None, std=None, src_index=None, out=None):
+        """float32 [nout, 3, oh, ow]: regions of img resized by the triangle filter of interpolate(mode="bilinear", antialias=...) into
+        rectangles of a padded output, mirrored and normalised (avsim_image_resize): the bits of av_aloha_amd.imgresize.resize_reference.  img:
+        u8 [n, H, W, 3] or float32 [n, 3, H, W] (read as floats); src_box: int rows (x0, y0, w, h, flip); dst: int rows (ox, oy, rw, rh); fill:
+        three values for the pixels outside dst (None: 0); mean / std: three values each, or None; src_index: the source image of every output
+        (None: image i).  ValueError for what the library refuses."""
+        from . import imgresize
+        img = np.ascontiguousarray(img)
+        sf, n, H, W = self._canvas(img)
+        b = np.ascontiguousarray(src_box, dtype=np.int32).reshape(-1, 5)
+        d = np.ascontiguousarray(dst, dtype=np.int32).reshape(len(b), 4)
+        si = None if src_index is None else np.ascontiguousarray(src_index, dtype=np.int32).reshape(len(b))
+        fl = None if fill is None else np.ascontiguousarray(fill, dtype=np.float32).reshape(3)
+        ms = imgresize.mean_std(mean, std)
+        oh, ow = int(out_hw[0]), int(out_hw[1])
+        if out is None:
+            out = np.empty((len(b), 3, max(oh, 0), max(ow, 0)), dtype=np.float32)
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (len(b), 3, oh, ow)):
+            raise ValueError("resize_images: out is a C-contiguous float32 [nout, 3, oh, ow] array")
+        images.check_call(self.h, self.h.L.avsim_image_resize(self.h.h, img.ctypes.data, sf, n, H, W, b.ctypes.data, d.ctypes.data, _ffi.ptr(si), len(b), int(antialias),
+                                                               _ffi.ptr(fl), _ffi.ptr(ms), oh, ow, out.ctypes.data))
+        return out
+
     def jitter_gray_sums(self, nout):
         """uint64 [nout]: the integer sums behind the contrast means of the last jitter_images call (avsim_image_jitter_sums;
         imgaug.gray_sum_reference's), meaningful for the outputs that had the contrast bit.  For tests."""

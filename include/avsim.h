@@ -353,6 +353,30 @@ int avsim_image_augment(avsim_t* h, const void* img /* u8 [nsrc][H][W][3] */, in
                         const float* affine /* [nout][6] or NULL */, int interp, const int32_t* src_index /* or NULL */, int nout,
                         const float* mean_std /* [2][3] or NULL: [0,1] output */, int out_h, int out_w, float* out /* [nout][3][out_h][out_w] */);
 
+/* Resizing images on the device, antialiased, into a rectangle of a padded output (csrc/avsim_imgresize.hip);
+ * av_aloha_amd/imgresize.py (resize_reference) is the specification, and the call equals it bit for bit (-0 and +0 aside).
+ * avsim_image_resize: output i reads image src_index[i] (NULL: image i) of img -- fmt 0: u8 [nsrc][H][W][3] with value float(u) / 255, fmt 1:
+ * float32 [nsrc][3][H][W] read AS FLOATS (not quantised as avsim_image_prep quantises, so that an avsim_image_jitter output resizes without a
+ * loss).  src_box[i] = (x0, y0, w, h, flip) is the source region and dst[i] = (ox, oy, rw, rh) the rectangle of the out_h x out_w output
+ * that the resized region fills; every other output pixel is fill[c] (fill NULL: 0).  The filter is the separable triangle filter of torch's
+ * interpolate(mode="bilinear", align_corners=False, antialias=...): per axis and output index i, in float32, scale = n_in / n_out, support =
+ * scale when antialias and scale >= 1, else 1, center = scale (i + 0.5), the taps j from max(0, int(center - support + 0.5)) to min(n_in,
+ * int(center + support + 0.5)) with weights max(0, 1 - |(j - center + 0.5) inv|), inv = 1 / support, over their sum; n_in is the REGION's size, so no
+ * pixel outside the box is read and crop-then-resize equals resizing the crop.  The horizontal pass comes first, then the vertical one, each a
+ * sum of products in ascending j with no fused multiply-add.  flip mirrors the resized rectangle; last every output pixel, fill included,
+ * becomes (v - mean[c]) / std[c] with mean_std = (mean[3], std[3]) (NULL: the values stay).  Upscaling is allowed; a ratio w / rw or h / rh
+ * above 16 is refused.  img and out follow the handle's I/O mode; src_box, dst, src_index, fill and mean_std are HOST arrays in both modes,
+ * checked before anything is launched and copied (52 bytes per output and 48 per call) into the pinned staging avsim_image_prep uses before
+ * the call returns -- the caller may change or free them at once.  With AVSIM_IO_DEVICE a call does not synchronise the stream once a call
+ * of the same sizes has run.  AVSIM_EINVAL, with nothing launched and out untouched: a fmt other than 0 / 1, an image or output size outside
+ * 1..65535, nsrc or nout < 1, a source box that does not lie inside the image, a dst rectangle that does not lie inside the output, w, h, rw or
+ * rh < 1, a ratio above 16, a flip or an antialias other than 0 / 1, a src_index outside [0, nsrc), a fill that is not finite, a std that is 0
+ * or not finite. */
+int avsim_image_resize(avsim_t* h, const void* img, int fmt, int nsrc, int height, int width,
+                       const int32_t* src_box /* [nout][5]: x0, y0, w, h, flip */, const int32_t* dst /* [nout][4]: ox, oy, rw, rh */,
+                       const int32_t* src_index /* or NULL */, int nout, int antialias, const float* fill /* [3] or NULL: 0 */,
+                       const float* mean_std /* [2][3] or NULL */, int out_h, int out_w, float* out /* [nout][3][out_h][out_w] */);
+
 /* Per-env episodes on the device (a vector env with gymnasium's NEXT_STEP autoreset; av_aloha_amd/vec_env.py).  Pointers follow the
  * handle's I/O mode, except box / share of the set-up (host pointers).  In device mode no step, reset, sample or render call
  * synchronises; avsim_episode_setup does (it reallocates the records: once per evaluation), and so do avsim_episode_log /
