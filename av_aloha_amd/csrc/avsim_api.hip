@@ -19,6 +19,7 @@
 #include "avsim_obshist.hip.h"
 #include "avsim_imgaug.hip.h"
 #include "avsim_imgresize.hip.h"
+#include "avsim_pointcloud.hip.h"
 #include "avsim_episode.hip.h"
 #include "avsim_ik.hip.h"
 #include "avsim_jpeg.hip.h"
@@ -89,6 +90,7 @@ struct avsim {
     ImgAugHost imgaug;   // colour, sharpness and affine augmentation (avsim_imgaug.hip.h): the gray sums behind contrast, the scratch images of sharpness + affine
     ChunkHost chunks;    // per-env execution of action chunks (avsim_chunks.hip.h), once avsim_chunk_setup has run
     ObsHistHost obshist; // per-env observation histories (avsim_obshist.hip.h), once avsim_obs_history_setup has run
+    PcHost pointcloud;   // point clouds from depth images (avsim_pointcloud.hip.h): a chunk of envs' pose records and candidate lists
     bool jpegdec_events = false;   // option "jpeg_decode_events": avsim_jpeg_decode records ev[12..15] around its three kernels
     // the state's version: bumped by everything that writes qpos (reset, the steps, set_state); the image calls skip their pose pass and the shadow
     // map when they already hold this version's (a facade that fetches its cameras one call at a time repeats neither)
@@ -488,6 +490,7 @@ void avsim_destroy(avsim_t* h) {
     h->imgaug.destroy();
     h->chunks.destroy();
     h->obshist.destroy();
+    h->pointcloud.destroy();
     for (void* p : {h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, (void*)h->d_latch})
         if (p) (void)hipFree(p);
     for (void* p : h->d_io)
@@ -922,15 +925,20 @@ extern "C" {
 
 // E6 (env.py:180-188 get_obs pixels / :195-200 render) as depth images: forward pass of the physics kernel (nsub = 0) exports
 // the body poses, then the two render kernels run on the same stream.  render_to: into device memory, with the handle's device current.
-static int render_to(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, void* dout, bool rgb, bool f32) {
-    int rc;
-    if (h->xpose_ver != h->state_ver) {          // body poses of the current state (a forward pass of the physics kernel, no substep)
+// body poses of the current state into render.d_xpose, when those it holds are another state's (a forward pass of the physics kernel, no substep)
+static int refresh_xpose(avsim_t* h) {
+    if (h->xpose_ver != h->state_ver) {
         h->phys.d_xpose = h->render.d_xpose;
-        rc = h->phys.launch(h->stream, h->N, 0, nullptr, h->nj, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, nullptr, nullptr, nullptr, h->err);
+        const int rc = h->phys.launch(h->stream, h->N, 0, nullptr, h->nj, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, nullptr, nullptr, nullptr, h->err);
         h->phys.d_xpose = nullptr;
         if (rc) return rc;
         h->xpose_ver = h->state_ver;
     }
+    return 0;
+}
+static int render_to(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, void* dout, bool rgb, bool f32) {
+    int rc;
+    if ((rc = refresh_xpose(h))) return rc;
     if (rgb && h->vis.cam_major && !(h->vis.loaded && !h->render_proxies)) { h->set_error("option render_cam_major applies to the visual scene's images only (avsim_load_visual, render_proxies 0)"); return AVSIM_EINVAL; }
     if (rgb && h->vis.loaded && !h->render_proxies)
         rc = h->vis.launch(h->stream, h->N, h->render.d_xpose, (const int*)cam_ids, ncam, h->render.m.ncam, height, width, dout, h->err, h->state_ver, f32);
@@ -961,6 +969,61 @@ int avsim_render_rgb(avsim_t* h, const int32_t* cam_ids, int ncam, int height, i
 // the visual scene's colour images as a policy reads them (eval.py preprocess_observation): float32 planar CHW, (float)u8 / 255
 int avsim_render_rgb_f32(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, float* out) {
     return render_images(h, cam_ids, ncam, height, width, out, true, true);
+}
+
+// ---- point clouds from depth images (av_aloha_amd/pointcloud.py is the specification; the kernels: csrc/avsim_pointcloud.hip, a unit of its own flags)
+enum PcSlot { PC_DEPTH = 8, PC_XYZ = 10, PC_INDEX = 11, PC_COUNT = 12 };
+static PcModel pc_model(const avsim_t* h) {
+    const RenderModel& m = h->render.m;
+    return PcModel{h->render.d_xpose, m.cam_body, m.cam_pos, m.cam_mat, m.cam_fovy, m.nbody};
+}
+int avsim_camera_poses(avsim_t* h, const int32_t* cam_ids, int ncam, float* out) {
+    if (!h) return AVSIM_EINVAL;
+    if (!cam_ids || !out || ncam < 1 || ncam > PC_MAX_CAMS) { h->set_error("avsim_camera_poses: bad arguments (1..%d cameras)", PC_MAX_CAMS); return AVSIM_EINVAL; }
+    PcCall c{};
+    for (int k = 0; k < ncam; k++) {
+        if (cam_ids[k] < 0 || cam_ids[k] >= h->render.m.ncam) { h->set_error("avsim_camera_poses: camera index out of range"); return AVSIM_EINVAL; }
+        c.cam[k] = cam_ids[k];
+    }
+    c.ncam = ncam;
+    AVS_ON_DEVICE(h);
+    int rc;
+    void* dout = nullptr;
+    const size_t bytes = sizeof(float) * PC_POSE_W * (size_t)h->N * ncam;
+    if ((rc = h->out_begin(PC_XYZ, out, bytes, &dout))) return rc;
+    if ((rc = refresh_xpose(h))) return rc;
+    if (pointcloud_poses_launch(h->stream, pc_model(h), c, 0, h->N, (float*)dout, h->err)) return AVSIM_EHIP;
+    if ((rc = h->out_end(PC_XYZ, out, bytes))) return rc;
+    return h->finish();
+}
+
+int avsim_point_cloud(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, const float* depth, const float* bounds, float max_depth, int npoints, float* xyz,
+                      int32_t* index, int32_t* count) {
+    if (!h) return AVSIM_EINVAL;
+    if (!cam_ids || !depth || !bounds || !xyz || !index || !count) { h->set_error("avsim_point_cloud: a null pointer"); return AVSIM_EINVAL; }
+    {   // the host arrays are checked before anything moves or is launched
+        std::string why;
+        if (pointcloud_validate(h->render.m.ncam, cam_ids, ncam, height, width, bounds, max_depth, npoints, why)) { h->set_error("%s", why.c_str()); return AVSIM_EINVAL; }
+    }
+    PcCall c{};
+    for (int k = 0; k < ncam; k++) c.cam[k] = cam_ids[k];
+    c.ncam = ncam; c.H = height; c.W = width; c.P = npoints; c.max_depth = max_depth;
+    for (int k = 0; k < 3; k++) { c.lo[k] = bounds[k]; c.hi[k] = bounds[3 + k]; }
+    AVS_ON_DEVICE(h);
+    int rc;
+    const void* ddepth = nullptr;
+    void *dxyz = nullptr, *dindex = nullptr, *dcount = nullptr;
+    const size_t N = (size_t)h->N, bxyz = sizeof(float) * 3 * N * npoints, bindex = sizeof(int32_t) * N * npoints, bcount = sizeof(int32_t) * 2 * N;
+    if ((rc = h->in(PC_DEPTH, depth, sizeof(float) * N * ncam * height * width, &ddepth))) return rc;
+    if ((rc = h->out_begin(PC_XYZ, xyz, bxyz, &dxyz))) return rc;
+    if ((rc = h->out_begin(PC_INDEX, index, bindex, &dindex))) return rc;
+    if ((rc = h->out_begin(PC_COUNT, count, bcount, &dcount))) return rc;
+    if ((rc = refresh_xpose(h))) return rc;
+    if (h->pointcloud.run(h->stream, pc_model(h), c, h->N, (const float*)ddepth, (float*)dxyz, (int*)dindex, (int*)dcount, h->err)) return AVSIM_EHIP;
+    if ((rc = h->out_end(PC_XYZ, xyz, bxyz))) return rc;
+    if ((rc = h->out_end(PC_INDEX, index, bindex))) return rc;
+    if ((rc = h->out_end(PC_COUNT, count, bcount))) return rc;
+    return h->finish();
 }
 
 // ---- the image calls: what they share.  The staging slots (d_io) they use, by what a slot carries -- names that hold within the image calls

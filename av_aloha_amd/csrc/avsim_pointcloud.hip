@@ -1,0 +1,230 @@
+// avsim_pointcloud.hip -- the kernels of avsim_camera_poses and avsim_point_cloud: depth images deprojected into one world
+// frame, cropped to a box, capped and thinned by farthest point sampling.  av_aloha_amd/pointcloud.py is the specification; every float32
+// operation here is the one it names, rounded on its own.  The unit is built -ffp-contract=off with IEEE division and denormals kept
+// (av_aloha_amd/build.py): a * b + c is a v_mul and a v_add.
+//
+//   k_pc_poses   a lane per (env, camera slot): the camera's world pose from the body pose and the model's camera tables, a record of 16
+//       floats.  avsim_camera_poses returns these records; k_pc_cloud reads them.
+//   k_pc_cloud   a workgroup of 1024 per env, three phases.
+//       1. Ordered compaction.  Wave w owns the contiguous pixels [w per, (w + 1) per) of the env's ncam H W, per a multiple of 64.  It
+//          counts its candidates (a ballot per 64 pixels), the 16 counts are summed in LDS (M, and the wave's first position), and a second
+//          walk over the same pixels writes candidate `pos` to the env's list -- at pos, or with M > 16384 at i where (i M) / 16384 == pos,
+//          if there is such an i (at most one: M > 16384).  The order is the pixels': nothing is appended atomically.
+//       2. Farthest point sampling.  Candidate k = 1024 j + tid lives in lane tid's registers, trip j: xyz recomputed from the depth (the
+//          same function, the same bits) and the running squared distance, 64 registers for 16 trips.  An iteration updates the distances
+//          against the last selection and finds the arg-max as the maximum of a 64-bit key -- the distance's bits above the complement of
+//          the position, so that the larger distance wins and, among equals, the LOWER position: two DPP reductions per wave, the
+//          wave's winner and its coordinates into LDS, ONE barrier, then every lane takes the maximum of the 16 keys and reads the winner's
+//          coordinates (the winner's wave is a field of its position).  The LDS records alternate between two sets, which is what makes one
+//          barrier enough.  When the winning distance is 0 every distance is, and by the rule all further selections are candidate 0.
+//       3. The selected positions (LDS) become points and pixel indices, 1024 at a time.
+#include "avsim_pointcloud.hip.h"
+
+namespace avs {
+
+__global__ void __launch_bounds__(256) k_pc_poses(PcModel m, PcCall c, int e0, int n, float* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n * c.ncam) return;
+    const int e = i / c.ncam, s = i - e * c.ncam, cam = c.cam[s];
+    const float *pb = m.xpose + ((size_t)(e0 + e) * m.nbody + m.cam_body[cam]) * 12, *Rb = pb + 3, *cp = m.cam_pos + 3 * cam, *Rm = m.cam_mat + 9 * cam;
+    float* o = out + (size_t)i * PC_POSE_W;
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        o[r] = ((pb[r] + Rb[3 * r] * cp[0]) + Rb[3 * r + 1] * cp[1]) + Rb[3 * r + 2] * cp[2];
+#pragma unroll
+        for (int j = 0; j < 3; j++) o[3 + 3 * r + j] = (Rb[3 * r] * Rm[j] + Rb[3 * r + 1] * Rm[3 + j]) + Rb[3 * r + 2] * Rm[6 + j];
+    }
+    o[12] = m.cam_tan[cam];
+    o[13] = o[14] = o[15] = 0.0f;
+}
+
+// the crop box and what locates a pixel, in registers
+struct PcView {
+    int HW, W;
+    float hh, hw, lo[3], hi[3], max_depth;
+};
+
+// pixel `pix` of the env (slot H W + r W + c) as a world point; true when it is a candidate.  s_pose: the env's records, s_scale: 2 t / H per slot
+__device__ __forceinline__ bool pc_world(const PcView& v, const float* s_pose, const float* s_scale, const float* __restrict__ depth, int pix, float& wx, float& wy, float& wz) {
+    const int slot = pix / v.HW, rem = pix - slot * v.HW, r = rem / v.W, c = rem - r * v.W;
+    const float* P = s_pose + slot * PC_POSE_W;
+    const float sc = s_scale[slot], d = depth[pix];
+    const float x = (((float)c + 0.5f) - v.hw) * sc;
+    const float y = -((((float)r + 0.5f) - v.hh) * sc);
+    const float X = x * d, Y = y * d, Z = -d;
+    wx = ((P[0] + P[3] * X) + P[4] * Y) + P[5] * Z;
+    wy = ((P[1] + P[6] * X) + P[7] * Y) + P[8] * Z;
+    wz = ((P[2] + P[9] * X) + P[10] * Y) + P[11] * Z;
+    return d < v.max_depth && wx >= v.lo[0] && wx <= v.hi[0] && wy >= v.lo[1] && wy <= v.hi[1] && wz >= v.lo[2] && wz <= v.hi[2];
+}
+
+constexpr int PC_WAVES = PC_THREADS / 64, PC_TRIPS = PC_MAX_CANDIDATES / PC_THREADS;
+
+// the maximum over the 64 lanes of the wave, the same in every lane (through an SGPR): DPP moves, no LDS (avsim_phys.hip.h's wave_sum with max)
+__device__ __forceinline__ unsigned wave_umax(unsigned x) {
+    x = max(x, (unsigned)__builtin_amdgcn_mov_dpp((int)x, 0x128, 0xf, 0xf, true));          // row_ror:8
+    x = max(x, (unsigned)__builtin_amdgcn_mov_dpp((int)x, 0x124, 0xf, 0xf, true));          // row_ror:4
+    x = max(x, (unsigned)__builtin_amdgcn_mov_dpp((int)x, 0x122, 0xf, 0xf, true));          // row_ror:2
+    x = max(x, (unsigned)__builtin_amdgcn_mov_dpp((int)x, 0x121, 0xf, 0xf, true));          // row_ror:1: every lane of a row of 16 holds the row's
+    x = max(x, (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false));   // row_bcast:15 into rows 1, 3
+    x = max(x, (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false));   // row_bcast:31 into rows 2, 3
+    return (unsigned)__builtin_amdgcn_readlane((int)x, 63);
+}
+
+__global__ void __launch_bounds__(PC_THREADS) k_pc_cloud(PcCall c, const float* __restrict__ depth, const float* __restrict__ pose, int* list, int L, float* __restrict__ xyz,
+                                                         int* __restrict__ index, int* __restrict__ count) {
+    __shared__ float s_pose[PC_MAX_CAMS * PC_POSE_W];
+    __shared__ float s_scale[PC_MAX_CAMS];
+    __shared__ int s_cnt[PC_WAVES];
+    __shared__ unsigned long long s_key[2][PC_WAVES];
+    __shared__ float s_win[2][PC_WAVES][4];
+    __shared__ int s_sel[PC_MAX_POINTS];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, env = blockIdx.x;
+    const int P = c.P, Q = c.ncam * c.H * c.W;
+    depth += (size_t)env * Q;
+    pose += (size_t)env * c.ncam * PC_POSE_W;
+    list += (size_t)env * L;
+    xyz += (size_t)env * P * 3;
+    index += (size_t)env * P;
+    count += (size_t)env * 2;
+    PcView v;
+    v.HW = c.H * c.W; v.W = c.W; v.hh = 0.5f * (float)c.H; v.hw = 0.5f * (float)c.W; v.max_depth = c.max_depth;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { v.lo[k] = c.lo[k]; v.hi[k] = c.hi[k]; }
+    if (tid < c.ncam * PC_POSE_W) s_pose[tid] = pose[tid];
+    __syncthreads();
+    if (tid < c.ncam) s_scale[tid] = (2.0f * s_pose[tid * PC_POSE_W + 12]) / (float)c.H;
+    __syncthreads();
+
+    // ---- 1. ordered compaction: counts, a scan, a scatter
+    const int per = ((Q + PC_THREADS - 1) / PC_THREADS) * 64;
+    const int p0 = wv * per, p1 = p0 + per < Q ? p0 + per : Q;
+    int cnt = 0;
+    for (int b = p0; b < p1; b += 64) {
+        float wx, wy, wz;
+        const int pix = b + lane;
+        const bool ok = pix < p1 && pc_world(v, s_pose, s_scale, depth, pix, wx, wy, wz);
+        cnt += __popcll(__ballot(ok));
+    }
+    if (lane == 0) s_cnt[wv] = cnt;
+    __syncthreads();
+    int base = 0, M = 0;
+#pragma unroll
+    for (int w = 0; w < PC_WAVES; w++) {
+        const int n = s_cnt[w];
+        if (w < wv) base += n;
+        M += n;
+    }
+    const int Mp = M < PC_MAX_CANDIDATES ? M : PC_MAX_CANDIDATES;
+    if (tid == 0) { count[0] = M; count[1] = Mp < P ? Mp : P; }
+    if (M == 0) {          // (the same for every lane)
+        for (int p = tid; p < P; p += PC_THREADS) { xyz[3 * p] = 0.0f; xyz[3 * p + 1] = 0.0f; xyz[3 * p + 2] = 0.0f; index[p] = -1; }
+        return;
+    }
+    for (int b = p0; b < p1; b += 64) {
+        float wx, wy, wz;
+        const int pix = b + lane;
+        const bool ok = pix < p1 && pc_world(v, s_pose, s_scale, depth, pix, wx, wy, wz);
+        const unsigned long long mask = __ballot(ok);
+        if (ok) {
+            const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
+            if (M > PC_MAX_CANDIDATES) {
+                const long long i = ((long long)pos * PC_MAX_CANDIDATES + M - 1) / M;
+                if (i < PC_MAX_CANDIDATES && (i * M) / PC_MAX_CANDIDATES == pos) list[i] = pix;
+            } else {
+                list[pos] = pix;
+            }
+        }
+        base += __popcll(mask);
+    }
+    __threadfence_block();
+    __syncthreads();
+
+    // ---- 2. farthest point sampling over the Mp listed candidates
+    // (the trips are loaded by a ROLLED loop that shifts the four arrays down by one and puts the new trip last: trip t ends at index t, the
+    // arrays are only ever indexed by constants, and the body -- two integer divisions -- exists once.  Unrolled it spilled 3.9 K registers.)
+    float x[PC_TRIPS], y[PC_TRIPS], z[PC_TRIPS], md[PC_TRIPS];
+#pragma unroll
+    for (int j = 0; j < PC_TRIPS; j++) { x[j] = y[j] = z[j] = 0.0f; md[j] = -1.0f; }
+#pragma nounroll
+    for (int t = 0; t < PC_TRIPS; t++) {
+        const int k = t * PC_THREADS + tid;
+        float nx = 0.0f, ny = 0.0f, nz = 0.0f, nm = -1.0f;          // no candidate: never the arg-max
+        if (k < Mp) {
+            pc_world(v, s_pose, s_scale, depth, list[k], nx, ny, nz);
+            nm = __builtin_inff();
+        }
+#pragma unroll
+        for (int j = 0; j + 1 < PC_TRIPS; j++) { x[j] = x[j + 1]; y[j] = y[j + 1]; z[j] = z[j + 1]; md[j] = md[j + 1]; }
+        x[PC_TRIPS - 1] = nx; y[PC_TRIPS - 1] = ny; z[PC_TRIPS - 1] = nz; md[PC_TRIPS - 1] = nm;
+    }
+    if (tid == 0) { s_win[0][0][0] = x[0]; s_win[0][0][1] = y[0]; s_win[0][0][2] = z[0]; s_sel[0] = 0; }
+    __syncthreads();
+    float sx = s_win[0][0][0], sy = s_win[0][0][1], sz = s_win[0][0][2];
+    for (int p = 1; p < P; p++) {
+        const int buf = p & 1;
+        float bv = -1.0f, bx = 0.0f, by = 0.0f, bz = 0.0f;
+        int bp = 0;
+#pragma unroll
+        for (int j = 0; j < PC_TRIPS; j++) {
+            if (j * PC_THREADS < Mp) {          // (the same for the whole workgroup)
+                const float dx = x[j] - sx, dy = y[j] - sy, dz = z[j] - sz;
+                const float m = fminf(md[j], (dx * dx + dy * dy) + dz * dz);
+                md[j] = m;
+                if (m > bv) { bv = m; bp = j * PC_THREADS + tid; bx = x[j]; by = y[j]; bz = z[j]; }          // ascending positions: the first of equals stays
+            }
+        }
+        // the wave's arg-max in two reductions: the largest distance (its bits + 1; 0: the lane holds no candidate), then among the lanes that
+        // hold it the lowest position (the largest complement)
+        const unsigned hi_mine = bv < 0.0f ? 0u : __float_as_uint(bv) + 1u;
+        const unsigned hi = wave_umax(hi_mine);
+        const unsigned lo_mine = (hi_mine == hi && hi != 0u) ? ~(unsigned)bp : 0u;
+        const unsigned lo = wave_umax(lo_mine);
+        if (hi != 0u ? (hi_mine == hi && lo_mine == lo) : lane == 0) {          // the wave's winner (positions are distinct), or lane 0 of a wave without candidates
+            s_key[buf][wv] = ((unsigned long long)hi << 32) | lo;
+            s_win[buf][wv][0] = bx; s_win[buf][wv][1] = by; s_win[buf][wv][2] = bz;
+        }
+        __syncthreads();
+        unsigned long long best = 0ull;
+#pragma unroll
+        for (int w = 0; w < PC_WAVES; w++) {
+            const unsigned long long o = s_key[buf][w];
+            best = o > best ? o : best;
+        }
+        unsigned pos = ~(unsigned)best;
+        pos = pos < (unsigned)Mp ? pos : 0u;
+        const int ww = (pos & (PC_THREADS - 1)) >> 6;
+        sx = s_win[buf][ww][0]; sy = s_win[buf][ww][1]; sz = s_win[buf][ww][2];
+        if (tid == 0) s_sel[p] = (int)pos;
+        if ((unsigned)(best >> 32) <= 1u) {          // the largest distance is +0: every distance is, and candidate 0 wins from here on
+            for (int q = p + 1 + tid; q < P; q += PC_THREADS) s_sel[q] = 0;
+            break;
+        }
+    }
+    __syncthreads();
+
+    // ---- 3. the selections as points and pixels
+    for (int p = tid; p < P; p += PC_THREADS) {
+        const int pix = list[s_sel[p]];
+        float wx, wy, wz;
+        pc_world(v, s_pose, s_scale, depth, pix, wx, wy, wz);
+        xyz[3 * p] = wx; xyz[3 * p + 1] = wy; xyz[3 * p + 2] = wz;
+        index[p] = pix;
+    }
+}
+
+int pointcloud_poses_launch(hipStream_t stream, const PcModel& m, const PcCall& c, int e0, int n, float* out, std::string& err) {
+    hipLaunchKernelGGL(k_pc_poses, dim3((n * c.ncam + 255) / 256), dim3(256), 0, stream, m, c, e0, n, out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { err = std::string("camera pose kernel: ") + hipGetErrorString(e); return -3; }
+    return 0;
+}
+
+int pointcloud_launch(hipStream_t stream, const PcCall& c, int n, const float* depth, const float* pose, int* list, float* xyz, int* index, int* count, std::string& err) {
+    hipLaunchKernelGGL(k_pc_cloud, dim3(n), dim3(PC_THREADS), 0, stream, c, depth, pose, list, (int)PcHost::list_len(c), xyz, index, count);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { err = std::string("point cloud kernel: ") + hipGetErrorString(e); return -3; }
+    return 0;
+}
+
+}  // namespace avs

@@ -907,10 +907,54 @@ def rerender_episode(data, env_id: str, save_path: str | None = None, device: in
     return out
 
 
-def rerender_dataset(dataset_dir: str, env_id: str, episode_idx: int | None = None, device: int = 0, frames_per_batch: int = 128):
+def rerender_pointclouds(data, env_id: str, cameras, height: int, width: int, bounds, points: int, frames_per_batch: int = 128, max_depth=None, device: int = 0, sim=None):
+    """The point clouds of a recorded episode, as an evaluation with VecEnv(pointcloud=...) will see them: (xyz float32 [T, P, 3], count int32
+    [T, 2]).  Works as rerender_episode does -- every recorded full state `all_qpos[t]` is put back (`set_qpos`), T frames as T envs of one
+    batched handle, `frames_per_batch` at a time -- and calls BatchedSim.point_cloud (depth render + avsim_point_cloud) on each batch.
+    sim: a BatchedSim of env_id's task and arms to reuse (its num_envs is the batch then)."""
+    from .env import ENVS
+    from .sim import BatchedSim
+    from .vec_env import _TASK_OF_CLASS
+    if isinstance(data, str):
+        data = load_episode(data)
+    spec = ENVS[env_id]
+    all_qpos = np.asarray(data["/observations/all_qpos"], dtype=np.float64)
+    T = all_qpos.shape[0]
+    own = sim is None
+    B = max(1, min(int(frames_per_batch), T)) if own else sim.N
+    if own:
+        sim = BatchedSim(_TASK_OF_CLASS[spec["env"]], spec["num_arms"], B, device=device)
+    assert all_qpos.shape[1] == sim.nq, f"the episode's all_qpos has {all_qpos.shape[1]} columns, the model of {env_id} {sim.nq}"
+    xyz, count = np.empty((T, int(points), 3), dtype=np.float32), np.empty((T, 2), dtype=np.int32)
+    for t0 in range(0, T, B):
+        q = all_qpos[t0:t0 + B]
+        n = q.shape[0]
+        if n < B:                                   # the last chunk: the spare envs repeat its last frame
+            q = np.concatenate([q, np.repeat(q[-1:], B - n, 0)])
+        sim.set_qpos(q)
+        x, _, c = sim.point_cloud(cameras, height, width, bounds, points, max_depth=max_depth)
+        xyz[t0:t0 + n], count[t0:t0 + n] = x[:n], c[:n]
+    if own:
+        sim.h.close()
+    return xyz, count
+
+
+def parse_pointcloud_option(text: str) -> dict:
+    """"cams:h:w:P:xlo,ylo,zlo,xhi,yhi,zhi" (cams: comma-separated camera names) as rerender_pointclouds' keyword arguments."""
+    parts = text.split(":")
+    if len(parts) != 5:
+        raise ValueError("--pointcloud cams:h:w:P:xlo,ylo,zlo,xhi,yhi,zhi")
+    b = [float(v) for v in parts[4].split(",")]
+    if len(b) != 6:
+        raise ValueError("--pointcloud: six bounds xlo,ylo,zlo,xhi,yhi,zhi")
+    return {"cameras": [c for c in parts[0].split(",") if c], "height": int(parts[1]), "width": int(parts[2]), "points": int(parts[3]), "bounds": b}
+
+
+def rerender_dataset(dataset_dir: str, env_id: str, episode_idx: int | None = None, device: int = 0, frames_per_batch: int = 128, pointcloud: dict | None = None):
     """replay_sim_episode.py:92-113 `main`: every `episode_*.hdf5` of `dataset_dir` (or the one with `episode_idx`) re-rendered for
     `env_id` into `<dataset_dir>/<EnvName>/episode_<i>.hdf5` (EnvName = the id without its namespace).  Returns the written paths and
-    the frames per second over the whole run."""
+    the frames per second over the whole run.  pointcloud: rerender_pointclouds' cameras / height / width / bounds / points -- the clouds are
+    written as `/observations/pointcloud` (and `/observations/pointcloud_count`) next to the images."""
     import glob
     import time
     from .env import make
@@ -920,7 +964,13 @@ def rerender_dataset(dataset_dir: str, env_id: str, episode_idx: int | None = No
     written, frames, t0 = [], 0, time.time()
     for p in paths:
         save_path = os.path.join(dataset_dir, env_id.split("/")[-1], os.path.basename(p))
-        out = rerender_episode(p, env_id, save_path, env=env)
+        if pointcloud is None:
+            out = rerender_episode(p, env_id, save_path, env=env)
+        else:           # + /observations/pointcloud [T, P, 3] and /observations/pointcloud_count [T, 2] next to the images
+            out = rerender_episode(p, env_id, None, env=env)
+            out["/observations/pointcloud"], out["/observations/pointcloud_count"] = rerender_pointclouds(p, env_id, frames_per_batch=frames_per_batch, device=device, sim=env.sim, **pointcloud)
+            d, f = os.path.split(os.path.abspath(save_path))
+            save_episode(out, d, int(f[len("episode_"):-len(".hdf5")]))
         frames += out["/action"].shape[0]
         written.append(save_path)
     if env is not None:

@@ -127,6 +127,39 @@ class BatchedSim:
         self.h.check(self.h.L.avsim_render_depth(self.h.h, ids.ctypes.data, len(ids), height, width, out.ctypes.data))
         return out
 
+    def camera_poses(self, cameras):
+        """float32 [N, len(cameras), 16]: the world pose of the named cameras at the current state (avsim_camera_poses) -- position pc[3],
+        rotation Rc[9] (row major, camera frame to world, the camera looks along its -z), tan(fovy / 2), three zeros."""
+        ids = images.camera_ids(self.manifest, cameras)
+        out = np.empty((self.N, len(ids), 16), dtype=np.float32)
+        images.check_call(self.h, self.h.L.avsim_camera_poses(self.h.h, ids.ctypes.data, len(ids), out.ctypes.data))
+        return out
+
+    def point_cloud(self, cameras, height, width, bounds, npoints, max_depth=None, depth=None):
+        """(xyz float32 [N, P, 3], index int32 [N, P], count int32 [N, 2]): one cloud per env in the world frame from the depth images of the
+        named cameras, cropped to bounds (xlo ylo zlo xhi yhi zhi) and thinned by farthest point sampling (avsim_point_cloud): the bits of
+        av_aloha_amd.pointcloud.point_cloud_reference given camera_poses().  depth: float32 [N, len(cameras), height, width] of the CURRENT
+        state (None: rendered first); max_depth: None = the far plane, so that pixels that see nothing drop out.  index is the flat pixel
+        slot * H * W + r * W + c, count = (candidates, distinct points).  ValueError for what the library refuses."""
+        from . import pointcloud
+        ids = images.camera_ids(self.manifest, cameras)
+        if depth is None:
+            depth = self.render_depth(cameras, height, width)
+        d = np.ascontiguousarray(depth, dtype=np.float32)
+        if d.shape != (self.N, len(ids), height, width):
+            raise ValueError(f"point_cloud: depth is float32 {(self.N, len(ids), height, width)}, not {d.shape}")
+        b = np.ascontiguousarray(bounds, dtype=np.float32).reshape(-1)
+        if b.shape != (6,):
+            raise ValueError("point_cloud: bounds are xlo ylo zlo xhi yhi zhi")
+        P = int(npoints)
+        xyz = np.empty((self.N, max(P, 0), 3), dtype=np.float32)
+        index = np.empty((self.N, max(P, 0)), dtype=np.int32)
+        count = np.empty((self.N, 2), dtype=np.int32)
+        images.check_call(self.h, self.h.L.avsim_point_cloud(self.h.h, ids.ctypes.data, len(ids), height, width, d.ctypes.data, b.ctypes.data,
+                                                             pointcloud.FAR_PLANE if max_depth is None else float(max_depth), P, xyz.ctypes.data,
+                                                             index.ctypes.data, count.ctypes.data))
+        return xyz, index, count
+
     def load_visual(self, path=None):
         """The visual scene of render_rgb: the decimated mesh library models/visual_meshes.avv (compiler/vismesh.py) against the
         instances in the model blob; from then on render_rgb rasterises the visual meshes (robot, frame, textured table, task

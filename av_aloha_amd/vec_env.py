@@ -8,6 +8,11 @@ per-env episodes and gymnasium's NEXT_STEP autoreset done by the library's kerne
 * obs_format "lerobot" (eval.py:23-66 preprocess_observation, done by the rasteriser): `observation.images.<cam>` float32 [N, 3, H, W] in
   [0, 1] (a contiguous view of the camera-major image batch) and `observation.state` float32 [N, nj]; "gym": GuidedVisionEnv's keys,
   `pixels[cam]` uint8 [N, H, W, 3] and `agent_pos` float64 [N, nj].  depth_cameras adds `depth[cam]` float32 [N, H, W].
+* pointcloud={"cameras": [...], "height": h, "width": w, "bounds": (xlo, ylo, zlo, xhi, yhi, zhi), "points": P, "max_depth": None} adds
+  `observation.pointcloud` (gym format: `pointcloud`) float32 [N, P, 3]: the cameras' depth rendered at its own size into its own buffer,
+  deprojected into the world frame, cropped and thinned by farthest point sampling (avsim_point_cloud); `info["pointcloud_count"]` int32
+  [N, 2] = (candidates, distinct points) and `info["pointcloud_index"]` int32 [N, P], the flat pixels.  None (the default): no call, buffer
+  or key changes.
 * Every tensor returned is a preallocated buffer that the next reset / step overwrites: clone what must outlive the call.
 * NEXT_STEP: an env whose episode ended (terminated or truncated) in call t starts its next episode in call t + 1, whose action does
   not reach it; that call reports reward 0, flags 0, elapsed 0, the new `info["episode_id"]` and the new episode's first observation.
@@ -30,7 +35,7 @@ import numpy as np
 from . import _ffi
 from .constants import CAMERAS, MODEL_DIR, SIM_PHYSICS_ENV_STEP_RATIO
 from .env import ENVS
-from .images import DeviceImageOps, camera_ids, default_stride
+from .images import DeviceImageOps, camera_ids, check_call, default_stride
 from .sim import load_blob
 
 # Initial positions of the free objects in qpos order: (lo xyz, hi xyz) of the reference's uniform draws (env.py:474-501, 513-543,
@@ -87,7 +92,7 @@ class VecEnv(DeviceImageOps):
     metadata = {"autoreset_mode": "NextStep", "render_modes": []}
 
     def __init__(self, task, num_arms, num_envs, max_episode_steps, device=None, cameras=(), depth_cameras=(), obs_format="lerobot",
-                 seed=0, terminate_on_success=False, f64=False, options=None, observation_height=480, observation_width=640):
+                 seed=0, terminate_on_success=False, f64=False, options=None, observation_height=480, observation_width=640, pointcloud=None):
         import torch
         assert obs_format in ("lerobot", "gym"), obs_format
         assert all(c in CAMERAS for c in list(cameras) + list(depth_cameras)), "Invalid camera names"
@@ -140,6 +145,21 @@ class VecEnv(DeviceImageOps):
         else:
             self._img = torch.zeros((nc, N, H, W, 3), dtype=torch.uint8, device=dev) if nc else None
         self._depth = torch.zeros((N, len(self.depth_cameras), H, W), dtype=torch.float32, device=dev) if self.depth_cameras else None
+        self._pc = None
+        if pointcloud is not None:      # a fixed-size world-frame cloud per env as an observation: its own cameras, size and depth buffer
+            from . import pointcloud as pcspec
+            pc = dict(pointcloud)
+            cams = list(pc["cameras"])
+            assert all(c in CAMERAS for c in cams), "Invalid camera names"
+            ids = camera_ids(self.manifest, cams)
+            ph, pw, P = int(pc["height"]), int(pc["width"]), int(pc["points"])
+            b = np.ascontiguousarray(pc["bounds"], dtype=np.float32).reshape(-1)
+            md = float(pcspec.FAR_PLANE if pc.get("max_depth") is None else pc["max_depth"])
+            pcspec.check_point_cloud(len(self.manifest["camera_names"]), ids, ph, pw, b, md, P)
+            self._pc = {"cameras": cams, "ids": ids, "height": ph, "width": pw, "bounds": b, "points": P, "max_depth": md,
+                        "depth": torch.zeros((N, len(cams), ph, pw), dtype=torch.float32, device=dev),
+                        "xyz": torch.zeros((N, P, 3), dtype=torch.float32, device=dev), "index": torch.zeros((N, P), dtype=torch.int32, device=dev),
+                        "count": torch.zeros((N, 2), dtype=torch.int32, device=dev)}
         self._bind_stream()
         self._setup(self.seed, 0)
 
@@ -169,7 +189,55 @@ class VecEnv(DeviceImageOps):
             obs = {"pixels": {c: self._img[i] for i, c in enumerate(self.cameras)}, "agent_pos": self._ap}
         if self.depth_cameras:
             obs["depth"] = {c: self._depth[:, i] for i, c in enumerate(self.depth_cameras)}
+        if self._pc is not None:
+            pc = self._pc
+            ids, nc = pc["ids"].ctypes.data, len(pc["cameras"])
+            self.h.check(L.avsim_render_depth(h, ids, nc, pc["height"], pc["width"], pc["depth"].data_ptr()))
+            self.h.check(L.avsim_point_cloud(h, ids, nc, pc["height"], pc["width"], pc["depth"].data_ptr(), pc["bounds"].ctypes.data, pc["max_depth"], pc["points"],
+                                             pc["xyz"].data_ptr(), pc["index"].data_ptr(), pc["count"].data_ptr()))
+            obs["observation.pointcloud" if self.obs_format == "lerobot" else "pointcloud"] = pc["xyz"]
         return obs
+
+    def _pc_info(self, info):
+        if self._pc is not None:
+            info["pointcloud_count"], info["pointcloud_index"] = self._pc["count"], self._pc["index"]
+        return info
+
+    # -- camera poses and point clouds on demand ---------------------------------------------------
+    def camera_poses(self, cameras):
+        """float32 [N, len(cameras), 16] on the env's device: the world pose of the named cameras at the current state (avsim_camera_poses) --
+        position pc[3], rotation Rc[9] (row major, camera frame to world, the camera looks along its -z), tan(fovy / 2), three zeros.  Does
+        not synchronise."""
+        self._bind_stream()
+        ids = camera_ids(self.manifest, cameras)
+        out = self.torch.empty((self.num_envs, len(ids), 16), dtype=self.torch.float32, device=self.device)
+        check_call(self.h, self.L.avsim_camera_poses(self.h.h, ids.ctypes.data, len(ids), out.data_ptr()))
+        return out
+
+    def point_cloud(self, cameras, height, width, bounds, npoints, max_depth=None, depth=None):
+        """(xyz float32 [N, P, 3], index int32 [N, P], count int32 [N, 2]) on the env's device: the world-frame cloud of the named cameras'
+        depth images at the current state, cropped to bounds (xlo ylo zlo xhi yhi zhi) and thinned by farthest point sampling
+        (avsim_point_cloud; av_aloha_amd/pointcloud.py is the specification).  depth: a float32 [N, len(cameras), height, width] tensor of the
+        CURRENT state (None: rendered here); max_depth None: the far plane.  Does not synchronise once the sizes have been seen."""
+        from . import pointcloud as pcspec
+        torch = self.torch
+        self._bind_stream()
+        ids = camera_ids(self.manifest, cameras)
+        N, P = self.num_envs, int(npoints)
+        if depth is None:
+            depth = torch.empty((N, len(ids), int(height), int(width)), dtype=torch.float32, device=self.device)
+            self.h.check(self.L.avsim_render_depth(self.h.h, ids.ctypes.data, len(ids), int(height), int(width), depth.data_ptr()))
+        assert isinstance(depth, torch.Tensor) and depth.dtype == torch.float32 and depth.device == self.device and depth.is_contiguous() and \
+            tuple(depth.shape) == (N, len(ids), int(height), int(width)), "point_cloud(depth=...): a contiguous float32 [N, cameras, height, width] tensor on the env's device"
+        b = np.ascontiguousarray(bounds, dtype=np.float32).reshape(-1)
+        if b.shape != (6,):
+            raise ValueError("point_cloud: bounds are xlo ylo zlo xhi yhi zhi")
+        xyz = torch.empty((N, max(P, 0), 3), dtype=torch.float32, device=self.device)
+        index = torch.empty((N, max(P, 0)), dtype=torch.int32, device=self.device)
+        count = torch.empty((N, 2), dtype=torch.int32, device=self.device)
+        check_call(self.h, self.L.avsim_point_cloud(self.h.h, ids.ctypes.data, len(ids), int(height), int(width), depth.data_ptr(), b.ctypes.data,
+                                                    float(pcspec.FAR_PLANE if max_depth is None else max_depth), P, xyz.data_ptr(), index.data_ptr(), count.data_ptr()))
+        return xyz, index, count
 
     # -- gym API -------------------------------------------------------------------------------------
     def reset(self, seed=None, options=None):
@@ -185,7 +253,7 @@ class VecEnv(DeviceImageOps):
         self.h.check(self.L.avsim_episode_reset(self.h.h, _ffi.ptr(mask), self._ap.data_ptr(), self._id.data_ptr()))
         for t in (self._elapsed, self._success, self._reward, self._term, self._trunc):      # (the envs that keep their episode keep their last step's)
             t.masked_fill_(mask.bool(), 0) if mask is not None else t.zero_()
-        return self._obs(), {"episode_id": self._id, "elapsed_steps": self._elapsed, "is_success": self._success.view(self.torch.bool)}
+        return self._obs(), self._pc_info({"episode_id": self._id, "elapsed_steps": self._elapsed, "is_success": self._success.view(self.torch.bool)})
 
     def step(self, action):
         torch = self.torch
@@ -200,7 +268,7 @@ class VecEnv(DeviceImageOps):
         self.h.check(self.L.avsim_get_diag(self.h.h, self._diag.data_ptr()))
         obs = self._obs()
         diverged = ((self._diag[:, 3] & 1) != 0) & (self._elapsed > 0)       # (an env that starts an episode in this call has not diverged)
-        info = {"is_success": self._success.view(torch.bool), "episode_id": self._id, "elapsed_steps": self._elapsed, "diverged": diverged}
+        info = self._pc_info({"is_success": self._success.view(torch.bool), "episode_id": self._id, "elapsed_steps": self._elapsed, "diverged": diverged})
         return obs, self._reward, self._term.view(torch.bool), self._trunc.view(torch.bool), info
 
     # -- episode records -----------------------------------------------------------------------------
@@ -285,11 +353,11 @@ class VecEnv(DeviceImageOps):
 
 
 def make_vec(env_id, num_envs, max_episode_steps, device=None, cameras=None, depth_cameras=(), obs_format="lerobot", seed=0,
-             terminate_on_success=False, f64=False, options=None, observation_height=None, observation_width=None):
-    """A VecEnv of a registry id (env.ENVS); cameras default to the registry's, the image size to its 480 x 640."""
+             terminate_on_success=False, f64=False, options=None, observation_height=None, observation_width=None, pointcloud=None):
+    """A VecEnv of a registry id (env.ENVS); cameras default to the registry's, the image size to its 480 x 640.  pointcloud: VecEnv's."""
     spec = ENVS[env_id]
     return VecEnv(_TASK_OF_CLASS[spec["env"]], spec["num_arms"], num_envs, max_episode_steps, device=device,
                   cameras=spec["cameras"] if cameras is None else cameras, depth_cameras=depth_cameras, obs_format=obs_format, seed=seed,
                   terminate_on_success=terminate_on_success, f64=f64, options=options,
                   observation_height=spec["observation_height"] if observation_height is None else observation_height,
-                  observation_width=spec["observation_width"] if observation_width is None else observation_width)
+                  observation_width=spec["observation_width"] if observation_width is None else observation_width, pointcloud=pointcloud)

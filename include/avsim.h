@@ -217,6 +217,44 @@ int avsim_camera_count(const avsim_t* h);
  * avsim_render_depth; in device mode nothing synchronises once a call with the same cameras has run. */
 int avsim_render_rgb_f32(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, float* out);
 
+/* Point clouds from depth images on the device (csrc/avsim_pointcloud.hip); av_aloha_amd/pointcloud.py is the specification.
+ * avsim_camera_poses: out = float32[N][ncam][16], the world pose of camera cam_ids[c] in every env at the CURRENT state -- position pc[3],
+ * rotation Rc[9] (row major, camera frame to world; the camera looks along its -z, x to the right, y up), tan(fovy / 2) as the device's
+ * table holds it, three zeros.  From the body pose (pb, Rb) and the model's camera offset (cp, Rm) in float32, every product and sum rounded
+ * on its own, left to right: Rc[i][j] = (Rb[i][0] Rm[0][j] + Rb[i][1] Rm[1][j]) + Rb[i][2] Rm[2][j], pc[i] = ((pb[i] + Rb[i][0] cp[0]) +
+ * Rb[i][1] cp[1]) + Rb[i][2] cp[2].  The body poses are refreshed when they are another state's, as the render calls do.  `out` follows the
+ * handle's I/O mode, cam_ids is a host array.  AVSIM_EINVAL: ncam outside 1..16, a camera id out of range, a null pointer.
+ *
+ * avsim_point_cloud: one fixed-size cloud per env in the world frame, from ncam depth images [N][ncam][height][width] as avsim_render_depth
+ * writes them.  The caller supplies the depth -- normally the tensor just rendered for the same state and cameras --, THE POSES ARE THOSE OF
+ * THE CURRENT STATE (the records avsim_camera_poses returns, computed by the same kernel): a depth image of an earlier state is deprojected
+ * with the wrong extrinsics.  All arithmetic is float32, every operation rounded on its own, and the result equals the specification bit
+ * for bit given the pose records.
+ *   Deprojection: with t = tan(fovy / 2), scale = 2 t / (float)H; pixel (r, c) has x = ((c + 0.5) - 0.5 W) scale, y = -(((r + 0.5) - 0.5 H)
+ *     scale) -- the renderer's own rays --, the camera-frame point is (x d, y d, -d) and w[i] = ((pc[i] + Rc[i][0] X) + Rc[i][1] Y) +
+ *     Rc[i][2] Z.
+ *   Crop: a pixel is a candidate when d < max_depth and bounds lo[i] <= w[i] <= hi[i] on the three axes (inclusive; a NaN anywhere drops
+ *     the pixel).  The candidates of an env are ordered by (camera slot, row, column); M is their number.
+ *   Cap: AVSIM_PC_MAX_CANDIDATES = C.  With M > C the candidates at the positions (i M) / C (64-bit integers), i = 0 .. C - 1, are used and
+ *     M' = C; otherwise all, M' = M.
+ *   Farthest point sampling: selection 0 is candidate 0; every candidate's mind starts at +inf; after each selection s, mind[k] =
+ *     min(mind[k], (dx dx + dy dy) + dz dz) with dx = w[k] - w[s], ...; the next selection is the candidate with the largest mind, the
+ *     lowest position among equals.  npoints selections; with M' < npoints the rule returns candidate 0 for the rest (every mind is 0).
+ * xyz[n][p] is the selected point, index[n][p] its flat pixel slot H W + r W + c (a caller gathers colour or any per-pixel feature with it),
+ * count[n] = {M, min(M', npoints)}; with M = 0 the points are zeros and the indices -1.  depth, xyz, index and count follow the handle's I/O
+ * mode; cam_ids and bounds are HOST arrays in both modes, passed on by value: the caller may change them as soon as the call returns.  With
+ * AVSIM_IO_DEVICE a call synchronises nothing once a call of the same cameras, size and N has run (M stays on the device).  Scratch: the envs
+ * go through the kernels in chunks of at most 1024, and a chunk holds min(ncam H W, C) int32 and ncam x 16 floats per env -- at most one
+ * int32 per pixel of the chunk, 64 MiB + 1 MiB at the limits, whatever N is.
+ * AVSIM_EINVAL, with nothing launched and the outputs untouched: npoints outside 1..4096, height or width outside 1..65535, ncam outside
+ * 1..16, ncam H W > 2^24, a bound that is not finite or lo > hi, max_depth not finite or <= 0, a camera id out of range, a null pointer. */
+#define AVSIM_PC_MAX_CANDIDATES 16384
+int avsim_camera_poses(avsim_t* h, const int32_t* cam_ids, int ncam, float* out /* [N][ncam][16] */);
+int avsim_point_cloud(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width,
+                      const float* depth /* [N][ncam][H][W], as avsim_render_depth writes it */,
+                      const float bounds[6] /* host: xlo ylo zlo xhi yhi zhi, world */, float max_depth, int npoints,
+                      float* xyz /* [N][P][3] */, int32_t* index /* [N][P] */, int32_t* count /* [N][2] */);
+
 /* Baseline JPEG streams of rendered frames, encoded on the device (csrc/avsim_jpeg.hip.h): SOF0, 8 bit, JFIF, Y Cb Cr 4:2:0, the Annex K
  * Huffman tables in every frame, one restart interval per MCU row, integer arithmetic throughout -- byte for byte the stream of
  * av_aloha_amd/jpeg.py encode_reference, which is its specification (colour matrix, DCT, quantiser rounding: DESIGN 8.y).

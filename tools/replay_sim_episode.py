@@ -4,7 +4,11 @@
 registered for --env are rendered (T frames = T envs of one batched handle); the result goes to <dataset_dir>/<EnvName>/episode_<i>.hdf5
 with qpos / qvel / action cut to 14 columns for a 2-arm env.
 
-    python tools/replay_sim_episode.py --env gym_guided_vision/InsertPeg-2Arms-v0 --dataset_dir data/sim_insert_peg [--episode_idx 3]"""
+    python tools/replay_sim_episode.py --env gym_guided_vision/InsertPeg-2Arms-v0 --dataset_dir data/sim_insert_peg [--episode_idx 3]
+
+--pointcloud cams:h:w:P:xlo,ylo,zlo,xhi,yhi,zhi (cams: comma-separated camera names) also writes /observations/pointcloud float32 (T, P, 3):
+the world-frame cloud of those cameras' h x w depth images, cropped to the box and thinned to P points on the device (avsim_point_cloud),
+as VecEnv(pointcloud=...) gives it during evaluation."""
 import argparse
 import os
 import sys
@@ -20,7 +24,9 @@ if __name__ == "__main__":
     ap.add_argument("--dataset_dir", required=True)
     ap.add_argument("--episode_idx", type=int, default=None)
     ap.add_argument("--frames_per_batch", type=int, default=128)
+    ap.add_argument("--pointcloud", default=None, help="cams:h:w:P:xlo,ylo,zlo,xhi,yhi,zhi -- also write /observations/pointcloud")
     a = ap.parse_args()
-    written, fps = harness.rerender_dataset(a.dataset_dir, a.env, a.episode_idx, frames_per_batch=a.frames_per_batch)
+    written, fps = harness.rerender_dataset(a.dataset_dir, a.env, a.episode_idx, frames_per_batch=a.frames_per_batch,
+                                            pointcloud=harness.parse_pointcloud_option(a.pointcloud) if a.pointcloud else None)
     print(f"{len(written)} episodes re-rendered for {a.env} at {fps:.0f} frames/s (all registered cameras per frame, incl. HDF5 writing) -> "
           f"{os.path.join(a.dataset_dir, a.env.split('/')[-1])}")
