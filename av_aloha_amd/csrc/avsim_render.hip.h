@@ -582,7 +582,7 @@ __device__ __forceinline__ void render_tile(const int lane, const int tx0, const
                 float4 fl = make_float4(0.f, 0.f, 0.f, 0.f);      // this lane's face: the casting loops fetch the kept faces from here (v_readlane)
                 if (np <= 64) {
                     const bool on = lane < np;
-                    const float4 f = staged ? arena[aoff + (on ? lane : 0)] : P[on ? lane : 0];
+                    const float4 f = P[on ? lane : 0];      // (phase B stages inverse-depth faces of fast-path polyhedra only: a general-path entry is never staged)
                     fl = f;
                     const float n00 = f.x * xl + f.y * yb - f.z, n10 = f.x * xr + f.y * yb - f.z, n01 = f.x * xl + f.y * yt - f.z, n11 = f.x * xr + f.y * yt - f.z;
                     const bool front = on && f.w < 0;
@@ -839,9 +839,10 @@ __device__ __forceinline__ void render_tile(const int lane, const int tx0, const
 //      rectangle; ordered ballot compaction -> cand[].
 //   B  all four waves, a candidate each: the record's header (octagon, nearest depth, a packed word) into hA / hB / hC; a polyhedron's faces in
 //      camera-ray form, the faces' screen boxes and its silhouette edges (one per lane: at most 64 faces, 32 vertices) into a slice of `arena`
-//      (an LDS atomic hands out the slices; a polyhedron that does not fit stays in global memory and the tiles read it from there as before),
-//      and the bin-level rejection on the values just loaded: a silhouette edge with the bin's four corner rays outside (general path: a face seen
-//      from outside with the four corner rays on its outer side) drops the entry -- its header gets an empty box.
+//      (an LDS atomic hands out the slices; a polyhedron that does not fit stays in global memory and the tiles read it from there as before);
+//      a staged entry gets bit 5 and its arena offset in the packed word.  Only fast-path polyhedra (bit 4 clear, at most 64 faces and 64
+//      silhouette edges) are staged: general-path entries always stay in global memory.  B rejects nothing: the only bin-level rejections are
+//      A's octagon test and bin mask, and every tile repeats the silhouette-edge and outward-face tests on its own corner rays.
 //   C  the waves take the bin's tiles from an LDS counter (a tile under the arm costs several times an empty one) and cast each against the list.
 #ifndef AVSIM_RD_WAVES
 #define AVSIM_RD_WAVES 1
