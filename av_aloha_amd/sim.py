@@ -1,7 +1,13 @@
 """BatchedSim: numpy-facing wrapper of a libavsim handle (host-pointer I/O mode).
 
 This is the batched engine under the gym-style environments in env.py; every method is a direct call
-into the C-ABI (include/avsim.h).  There is no CPU fallback."""
+into the C-ABI (include/avsim.h).  There is no CPU fallback.
+
+compose, compose_label, image_stats, prep_images, jitter_images, augment_images, resize_images, camera_poses and
+point_cloud are images.ImageCalls's -- the one implementation that the torch front (images.DeviceImageOps, VecEnv)
+runs too -- through images.HostArrays: numpy arrays in and out, inputs converted with np.ascontiguousarray, a wrong
+`out` or canvas a ValueError, image_stats in uint64 with its index checked, and no stream to bind (the handle is in
+host I/O mode and synchronous).  The JPEG methods here speak lists of bytes and stay this class's own."""
 import ctypes as C
 import json
 import os
@@ -29,7 +35,9 @@ def load_blob(task, num_arms, variant="gym"):
     return blob, manifest
 
 
-class BatchedSim:
+class BatchedSim(images.ImageCalls):
+    _arrays = images.HostArrays       # compose ... point_cloud: images.ImageCalls's, on numpy arrays
+
     def __init__(self, task, num_arms=3, num_envs=1, device=0, f64=False, options=None, variant="gym", blob=None):
         assert task in TASK_KEYS, task
         file_blob, self.manifest = load_blob(task, num_arms, variant)
@@ -126,39 +134,6 @@ class BatchedSim:
         out = np.empty((self.N, len(ids), height, width), dtype=np.float32)
         self.h.check(self.h.L.avsim_render_depth(self.h.h, ids.ctypes.data, len(ids), height, width, out.ctypes.data))
         return out
-
-    def camera_poses(self, cameras):
-        """float32 [N, len(cameras), 16]: the world pose of the named cameras at the current state (avsim_camera_poses) -- position pc[3],
-        rotation Rc[9] (row major, camera frame to world, the camera looks along its -z), tan(fovy / 2), three zeros."""
-        ids = images.camera_ids(self.manifest, cameras)
-        out = np.empty((self.N, len(ids), 16), dtype=np.float32)
-        images.check_call(self.h, self.h.L.avsim_camera_poses(self.h.h, ids.ctypes.data, len(ids), out.ctypes.data))
-        return out
-
-    def point_cloud(self, cameras, height, width, bounds, npoints, max_depth=None, depth=None):
-        """(xyz float32 [N, P, 3], index int32 [N, P], count int32 [N, 2]): one cloud per env in the world frame from the depth images of the
-        named cameras, cropped to bounds (xlo ylo zlo xhi yhi zhi) and thinned by farthest point sampling (avsim_point_cloud): the bits of
-        av_aloha_amd.pointcloud.point_cloud_reference given camera_poses().  depth: float32 [N, len(cameras), height, width] of the CURRENT
-        state (None: rendered first); max_depth: None = the far plane, so that pixels that see nothing drop out.  index is the flat pixel
-        slot * H * W + r * W + c, count = (candidates, distinct points).  ValueError for what the library refuses."""
-        from . import pointcloud
-        ids = images.camera_ids(self.manifest, cameras)
-        if depth is None:
-            depth = self.render_depth(cameras, height, width)
-        d = np.ascontiguousarray(depth, dtype=np.float32)
-        if d.shape != (self.N, len(ids), height, width):
-            raise ValueError(f"point_cloud: depth is float32 {(self.N, len(ids), height, width)}, not {d.shape}")
-        b = np.ascontiguousarray(bounds, dtype=np.float32).reshape(-1)
-        if b.shape != (6,):
-            raise ValueError("point_cloud: bounds are xlo ylo zlo xhi yhi zhi")
-        P = int(npoints)
-        xyz = np.empty((self.N, max(P, 0), 3), dtype=np.float32)
-        index = np.empty((self.N, max(P, 0)), dtype=np.int32)
-        count = np.empty((self.N, 2), dtype=np.int32)
-        images.check_call(self.h, self.h.L.avsim_point_cloud(self.h.h, ids.ctypes.data, len(ids), height, width, d.ctypes.data, b.ctypes.data,
-                                                             pointcloud.FAR_PLANE if max_depth is None else float(max_depth), P, xyz.ctypes.data,
-                                                             index.ctypes.data, count.ctypes.data))
-        return xyz, index, count
 
     def load_visual(self, path=None):
         """The visual scene of render_rgb: the decimated mesh library models/visual_meshes.avv (compiler/vismesh.py) against the
@@ -284,143 +259,6 @@ class BatchedSim:
                 i = int(np.nonzero(status)[0][0])
                 raise jpeg.JpegError(int(status[i]), f"decode_jpeg: stream {i0 + i} is not a {H} x {W} stream of this encoder (status {int(status[i])}: "
                                                      "1 header, 2 marker structure or length, 4 entropy-coded data)")
-        return out
-
-    def compose(self, src, places, out=None, canvas_hw=None, nout=None, clear=None):
-        """Images resampled into rectangles of a canvas on the device (avsim_compose): the pixels of av_aloha_amd.compose.compose_reference.
-        src: u8 [n, H, W, 3] or float32 [n, 3, H, W] in [0, 1]; places: int rows (out image, src image, x0, y0, w, h).  out: the canvas to
-        draw on -- u8 [nout, CH, CW, 3] or float32 [nout, 3, CH, CW], written in place and returned --, or None: a u8 canvas of
-        canvas_hw = (CH, CW) and nout images is made.  clear: 0xRRGGBB to fill the canvas with first (a new canvas is cleared to 0 when
-        nothing is said).  ValueError for what the library refuses (a rectangle outside the canvas, overlaps, a shrink of more than 16)."""
-        src = np.ascontiguousarray(src)
-        p = np.ascontiguousarray(places, dtype=np.int32).reshape(-1, 6)
-        sf, n, H, W = images.layout(src)
-        if out is None:
-            if canvas_hw is None:
-                raise ValueError("compose: give a canvas (out=...) or its size (canvas_hw=...)")
-            nout = int(p[:, 0].max()) + 1 if nout is None and len(p) else int(nout or 1)
-            out = np.empty((nout, int(canvas_hw[0]), int(canvas_hw[1]), 3), dtype=np.uint8)
-            clear = 0 if clear is None else clear
-        df, no, CH, CW = self._canvas(out)
-        images.check_call(self.h, self.h.L.avsim_compose(self.h.h, src.ctypes.data, sf, n, H, W, out.ctypes.data, df, no, CH, CW, p.ctypes.data, len(p),
-                                                         0 if clear is None else 1, int(clear or 0) & 0xFFFFFF))
-        return out
-
-    @staticmethod
-    def _canvas(out):
-        if not (isinstance(out, np.ndarray) and out.flags.c_contiguous):
-            raise ValueError("compose: the canvas is a C-contiguous u8 [n, H, W, 3] or float32 [n, 3, H, W] array")
-        return images.layout(out)
-
-    def compose_label(self, canvas, where, prefix="", values=None, rgb=0xFFFFFF):
-        """prefix + str(values[i]) painted onto the canvas at where[i] = (out image, x, y, scale) in the colour rgb (avsim_compose_label):
-        the pixels of av_aloha_amd.compose.label_reference.  The canvas (compose's) is written in place and returned."""
-        df, no, CH, CW = self._canvas(canvas)
-        w = np.ascontiguousarray(where, dtype=np.int32).reshape(-1, 4)
-        v = None if values is None else np.ascontiguousarray(values, dtype=np.int64).reshape(len(w))
-        images.check_call(self.h, self.h.L.avsim_compose_label(self.h.h, canvas.ctypes.data, df, no, CH, CW, w.ctypes.data, len(w), prefix.encode("ascii", "replace"),
-                                                               _ffi.ptr(v), int(rgb) & 0xFFFFFF))
-        return canvas
-
-    def image_stats(self, img, index=None):
-        """uint64 [n, 3, 4]: (sum, sum of squares, min, max) of the u8 values per image and channel, reduced on the device
-        (avsim_image_stats): the integers of av_aloha_amd.imgprep.stats_reference.  img: u8 [n, H, W, 3] or float32 [n, 3, H, W]; index: the
-        images to reduce, in this order (None: all)."""
-        img = np.ascontiguousarray(img)
-        sf, n, H, W = self._canvas(img)
-        idx = None if index is None else np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
-        if idx is not None and len(idx) and (idx.min() < 0 or idx.max() >= n):
-            raise ValueError(f"image_stats: index outside [0, {n})")
-        m = n if idx is None else len(idx)
-        out = np.empty((m, 3, 4), dtype=np.uint64)
-        images.check_call(self.h, self.h.L.avsim_image_stats(self.h.h, img.ctypes.data, sf, _ffi.ptr(idx), m, H, W, out.ctypes.data))
-        return out
-
-    def prep_images(self, img, lut, box, out_hw, lut_index=None, src_index=None, out=None):
-        """float32 [nout, 3, oh, ow]: crops of img, mirrored where box says so, every channel through a table (avsim_image_prep): the bits of
-        av_aloha_amd.imgprep.prep_reference.  img: u8 [n, H, W, 3] or float32 [n, 3, H, W]; lut: float32 [nlut, 3, 256] (or [3, 256]); box:
-        int rows (x0, y0, flip), one per output; lut_index / src_index: the table / the source image of every output (None: table 0 /
-        image i).  ValueError for what the library refuses (a crop outside the source, an index out of range)."""
-        img = np.ascontiguousarray(img)
-        sf, n, H, W = self._canvas(img)
-        lut = np.ascontiguousarray(lut, dtype=np.float32).reshape(-1, 3, 256)
-        b = np.ascontiguousarray(box, dtype=np.int32).reshape(-1, 3)
-        li = None if lut_index is None else np.ascontiguousarray(lut_index, dtype=np.int32).reshape(len(b))
-        si = None if src_index is None else np.ascontiguousarray(src_index, dtype=np.int32).reshape(len(b))
-        oh, ow = int(out_hw[0]), int(out_hw[1])
-        if out is None:
-            out = np.empty((len(b), 3, max(oh, 0), max(ow, 0)), dtype=np.float32)
-        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (len(b), 3, oh, ow)):
-            raise ValueError("prep_images: out is a C-contiguous float32 [nout, 3, oh, ow] array")
-        images.check_call(self.h, self.h.L.avsim_image_prep(self.h.h, img.ctypes.data, sf, n, H, W, lut.ctypes.data, len(lut), _ffi.ptr(li), b.ctypes.data,
-                                                             len(b), _ffi.ptr(si), oh, ow, out.ctypes.data))
-        return out
-
-    def jitter_images(self, img, params, out_hw, mean=None, std=None, src_index=None, out=None):
-        """float32 [nout, 3, oh, ow]: brightness, contrast, saturation, hue and sharpness jitter of img, cropped, mirrored and normalised in one
-        pass (avsim_image_jitter): the bits of av_aloha_amd.imgaug.jitter_reference.  img: u8 [n, H, W, 3]; params: imgaug.PARAMS_DTYPE rows or
-        the pair (int32 [nout, 4] = (x0, y0, flip, mask), float32 [nout, 5] = the factors); mean / std: three values each, or None: the output
-        stays in [0, 1]; src_index: the source image of every output (None: image i).  ValueError for what the library refuses."""
-        from . import imgaug
-        img = np.ascontiguousarray(img)
-        if not (img.dtype == np.uint8 and img.ndim == 4 and img.shape[3] == 3):
-            raise ValueError("jitter_images: the images are a u8 [n, H, W, 3] array")
-        n, H, W = img.shape[:3]
-        bm, fac = imgaug.split_params(params)
-        si = None if src_index is None else np.ascontiguousarray(src_index, dtype=np.int32).reshape(len(bm))
-        ms = imgaug.mean_std(mean, std)
-        oh, ow = int(out_hw[0]), int(out_hw[1])
-        if out is None:
-            out = np.empty((len(bm), 3, max(oh, 0), max(ow, 0)), dtype=np.float32)
-        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (len(bm), 3, oh, ow)):
-            raise ValueError("jitter_images: out is a C-contiguous float32 [nout, 3, oh, ow] array")
-        images.check_call(self.h, self.h.L.avsim_image_jitter(self.h.h, img.ctypes.data, n, H, W, bm.ctypes.data, fac.ctypes.data, _ffi.ptr(si), len(bm), _ffi.ptr(ms), oh, ow,
-                                                               out.ctypes.data))
-        return out
-
-    def augment_images(self, img, params, matrix, out_hw, interp=0, mean=None, std=None, src_index=None, out=None):
-        """float32 [nout, 3, oh, ow]: jitter_images with the geometric op, mask bit 5 (avsim_image_augment): the bits of
-        av_aloha_amd.imgaug.jitter_affine_reference.  matrix: float32 [nout, 6], the inverse matrices (imgaug.affine_matrix) of the outputs that
-        have the bit, or None when none has; interp: 0 nearest, 1 bilinear.  ValueError for what the library refuses."""
-        from . import imgaug
-        img = np.ascontiguousarray(img)
-        if not (img.dtype == np.uint8 and img.ndim == 4 and img.shape[3] == 3):
-            raise ValueError("augment_images: the images are a u8 [n, H, W, 3] array")
-        n, H, W = img.shape[:3]
-        bm, fac = imgaug.split_params(params)
-        mat = None if matrix is None else np.ascontiguousarray(matrix, dtype=np.float32).reshape(len(bm), 6)
-        si = None if src_index is None else np.ascontiguousarray(src_index, dtype=np.int32).reshape(len(bm))
-        ms = imgaug.mean_std(mean, std)
-        oh, ow = int(out_hw[0]), int(out_hw[1])
-        if out is None:
-            out = np.empty((len(bm), 3, max(oh, 0), max(ow, 0)), dtype=np.float32)
-        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (len(bm), 3, oh, ow)):
-            raise ValueError("augment_images: out is a C-contiguous float32 [nout, 3, oh, ow] array")
-        images.check_call(self.h, self.h.L.avsim_image_augment(self.h.h, img.ctypes.data, n, H, W, bm.ctypes.data, fac.ctypes.data, _ffi.ptr(mat), int(interp), _ffi.ptr(si),
-                                                                len(bm), _ffi.ptr(ms), oh, ow, out.ctypes.data))
-        return out
-
-    def resize_images(self, img, src_box, dst, out_hw, antialias=True, fill=None, mean=None, std=None, src_index=None, out=None):
-        """float32 [nout, 3, oh, ow]: regions of img resized by the triangle filter of interpolate(mode="bilinear", antialias=...) into
-        rectangles of a padded output, mirrored and normalised (avsim_image_resize): the bits of av_aloha_amd.imgresize.resize_reference.  img:
-        u8 [n, H, W, 3] or float32 [n, 3, H, W] (read as floats); src_box: int rows (x0, y0, w, h, flip); dst: int rows (ox, oy, rw, rh); fill:
-        three values for the pixels outside dst (None: 0); mean / std: three values each, or None; src_index: the source image of every output
-        (None: image i).  ValueError for what the library refuses."""
-        from . import imgresize
-        img = np.ascontiguousarray(img)
-        sf, n, H, W = self._canvas(img)
-        b = np.ascontiguousarray(src_box, dtype=np.int32).reshape(-1, 5)
-        d = np.ascontiguousarray(dst, dtype=np.int32).reshape(len(b), 4)
-        si = None if src_index is None else np.ascontiguousarray(src_index, dtype=np.int32).reshape(len(b))
-        fl = None if fill is None else np.ascontiguousarray(fill, dtype=np.float32).reshape(3)
-        ms = imgresize.mean_std(mean, std)
-        oh, ow = int(out_hw[0]), int(out_hw[1])
-        if out is None:
-            out = np.empty((len(b), 3, max(oh, 0), max(ow, 0)), dtype=np.float32)
-        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (len(b), 3, oh, ow)):
-            raise ValueError("resize_images: out is a C-contiguous float32 [nout, 3, oh, ow] array")
-        images.check_call(self.h, self.h.L.avsim_image_resize(self.h.h, img.ctypes.data, sf, n, H, W, b.ctypes.data, d.ctypes.data, _ffi.ptr(si), len(b), int(antialias),
-                                                               _ffi.ptr(fl), _ffi.ptr(ms), oh, ow, out.ctypes.data))
         return out
 
     def jitter_gray_sums(self, nout):

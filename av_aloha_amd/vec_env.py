@@ -35,7 +35,7 @@ import numpy as np
 from . import _ffi
 from .constants import CAMERAS, MODEL_DIR, SIM_PHYSICS_ENV_STEP_RATIO
 from .env import ENVS
-from .images import DeviceImageOps, camera_ids, check_call, default_stride
+from .images import DeviceImageOps, camera_ids, default_stride
 from .sim import load_blob
 
 # Initial positions of the free objects in qpos order: (lo xyz, hi xyz) of the reference's uniform draws (env.py:474-501, 513-543,
@@ -87,7 +87,8 @@ def sample_poses(task, seed, episode_ids):
 
 class VecEnv(DeviceImageOps):
     """num_envs envs of one task on one GPU; see the module's docstring for the semantics.  The image calls on any tensor of the env's device
-    -- decode_jpeg, encode_images, compose, compose_label, image_stats, prep_images, jitter_images -- are images.DeviceImageOps's."""
+    -- decode_jpeg, encode_images, compose, compose_label, image_stats, prep_images, jitter_images, augment_images, resize_images -- and
+    camera_poses / point_cloud on demand are images.DeviceImageOps's (images.ImageCalls on tensors)."""
 
     metadata = {"autoreset_mode": "NextStep", "render_modes": []}
 
@@ -202,42 +203,6 @@ class VecEnv(DeviceImageOps):
         if self._pc is not None:
             info["pointcloud_count"], info["pointcloud_index"] = self._pc["count"], self._pc["index"]
         return info
-
-    # -- camera poses and point clouds on demand ---------------------------------------------------
-    def camera_poses(self, cameras):
-        """float32 [N, len(cameras), 16] on the env's device: the world pose of the named cameras at the current state (avsim_camera_poses) --
-        position pc[3], rotation Rc[9] (row major, camera frame to world, the camera looks along its -z), tan(fovy / 2), three zeros.  Does
-        not synchronise."""
-        self._bind_stream()
-        ids = camera_ids(self.manifest, cameras)
-        out = self.torch.empty((self.num_envs, len(ids), 16), dtype=self.torch.float32, device=self.device)
-        check_call(self.h, self.L.avsim_camera_poses(self.h.h, ids.ctypes.data, len(ids), out.data_ptr()))
-        return out
-
-    def point_cloud(self, cameras, height, width, bounds, npoints, max_depth=None, depth=None):
-        """(xyz float32 [N, P, 3], index int32 [N, P], count int32 [N, 2]) on the env's device: the world-frame cloud of the named cameras'
-        depth images at the current state, cropped to bounds (xlo ylo zlo xhi yhi zhi) and thinned by farthest point sampling
-        (avsim_point_cloud; av_aloha_amd/pointcloud.py is the specification).  depth: a float32 [N, len(cameras), height, width] tensor of the
-        CURRENT state (None: rendered here); max_depth None: the far plane.  Does not synchronise once the sizes have been seen."""
-        from . import pointcloud as pcspec
-        torch = self.torch
-        self._bind_stream()
-        ids = camera_ids(self.manifest, cameras)
-        N, P = self.num_envs, int(npoints)
-        if depth is None:
-            depth = torch.empty((N, len(ids), int(height), int(width)), dtype=torch.float32, device=self.device)
-            self.h.check(self.L.avsim_render_depth(self.h.h, ids.ctypes.data, len(ids), int(height), int(width), depth.data_ptr()))
-        assert isinstance(depth, torch.Tensor) and depth.dtype == torch.float32 and depth.device == self.device and depth.is_contiguous() and \
-            tuple(depth.shape) == (N, len(ids), int(height), int(width)), "point_cloud(depth=...): a contiguous float32 [N, cameras, height, width] tensor on the env's device"
-        b = np.ascontiguousarray(bounds, dtype=np.float32).reshape(-1)
-        if b.shape != (6,):
-            raise ValueError("point_cloud: bounds are xlo ylo zlo xhi yhi zhi")
-        xyz = torch.empty((N, max(P, 0), 3), dtype=torch.float32, device=self.device)
-        index = torch.empty((N, max(P, 0)), dtype=torch.int32, device=self.device)
-        count = torch.empty((N, 2), dtype=torch.int32, device=self.device)
-        check_call(self.h, self.L.avsim_point_cloud(self.h.h, ids.ctypes.data, len(ids), int(height), int(width), depth.data_ptr(), b.ctypes.data,
-                                                    float(pcspec.FAR_PLANE if max_depth is None else max_depth), P, xyz.data_ptr(), index.data_ptr(), count.data_ptr()))
-        return xyz, index, count
 
     # -- gym API -------------------------------------------------------------------------------------
     def reset(self, seed=None, options=None):

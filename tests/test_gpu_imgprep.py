@@ -261,6 +261,27 @@ def test_prep_refusals_leave_out_untouched(sim, dev):
     assert (t_out == 7.0).all().item()
 
 
+def test_prep_through_both_fronts(sim):
+    """BatchedSim.prep_images (numpy) and VecEnv.prep_images (torch) are one body behind two kinds of array: the same bytes from both, with
+    the table and source index arrays given, and those of the specification.  An output width of 6: rows that the 16-byte store cannot take."""
+    from av_aloha_amd.vec_env import make_vec
+    T = torch()
+    u8, lut, out_hw = noise((2, 9, 11, 3), 41), tables(), (4, 6)
+    box, lut_index, src_index = [(0, 0, 0), (5, 5, 1), (2, 3, 0)], [0, 2, 1], [1, 0, 1]
+    want = bits(imgprep.prep_reference(u8, lut, lut_index, box, out_hw, src_index))
+    env = make_vec("gym_guided_vision/InsertPeg-3Arms-v0", num_envs=2, max_episode_steps=5, cameras=[])
+    try:
+        t_lut = T.from_numpy(lut).to(env.device)
+        for arr in (u8, to_f32(u8)):
+            a = sim.prep_images(arr, lut, box, out_hw, lut_index, src_index)
+            t = env.prep_images(T.from_numpy(arr).to(env.device), t_lut, box, out_hw, lut_index, src_index)
+            assert isinstance(a, np.ndarray) and a.dtype == np.float32 and t.dtype == T.float32 and t.device == env.device
+            assert a.shape == tuple(t.shape) == (3, 3, 4, 6)
+            assert a.tobytes() == t.cpu().numpy().tobytes() == want.tobytes()
+    finally:
+        env.close()
+
+
 def test_prep_calls_in_a_row_keep_their_own_boxes(dev):
     """Six calls without a synchronisation between them, the caller's arrays overwritten as soon as a call returns: the library has copied
     them (more calls than it has staging slots, so slots are reused behind their events)."""

@@ -340,6 +340,57 @@ def test_rendered_clouds_against_the_oracle(moved):
     assert worst_px <= 0.01 and worst_share <= 0.005
 
 
+def test_camera_poses_through_both_fronts():
+    """BatchedSim.camera_poses (numpy) and VecEnv.camera_poses (torch) are one body behind two kinds of array: two envs of insert_peg with
+    different arm configurations, the same qpos in both handles -> the same bytes.  There is no numpy specification of the pose records (the
+    point-cloud specification takes them from the device), so the reference is the oracle's float64 kinematics, with the bounds and the
+    reasoning of test_poses_against_the_oracle: 1e-5 in the position and in every rotation entry -- the state is set, not simulated, so all
+    that differs is float32 rounding of metre-sized values along a chain of a dozen bodies, a few 1e-7 --, tan(fovy / 2) within 1e-6
+    relative."""
+    from av_aloha_amd.vec_env import make_vec
+    from orc_env import OrcEnv
+    T = torch()
+    obj = np.array([[0.15, 0.0, 0.01, 1, 0, 0, 0], [-0.15, 0.0, 0.021, 1, 0, 0, 0.0]])
+    md = model_dict("insert_peg")
+    sim = BatchedSim("insert_peg", 3, 2)
+    env = make_vec("gym_guided_vision/InsertPeg-3Arms-v0", num_envs=2, max_episode_steps=5, cameras=[])
+    e = OrcEnv("insert_peg")
+    try:
+        sim.reset(np.repeat(obj[None], 2, 0))
+        q = spread_qpos(sim.get_state()[0])
+        q[0, 2] += 0.11                                              # (spread_qpos leaves env 0 at home)
+        sim.set_qpos(q)
+        env.reset()
+        t_q = T.from_numpy(np.ascontiguousarray(q)).to(env.device)
+        env.h.check(env.L.avsim_set_qpos(env.h.h, t_q.data_ptr()))
+        a = sim.camera_poses(CAMS6)
+        t = env.camera_poses(CAMS6)
+        assert isinstance(a, np.ndarray) and a.dtype == np.float32 and a.shape == (2, 6, 16)
+        assert t.dtype == T.float32 and tuple(t.shape) == (2, 6, 16) and t.device == env.device
+        assert a.tobytes() == t.cpu().numpy().tobytes()
+        assert not np.array_equal(a[0], a[1]) and not a[:, :, 13:].any()
+        nb = md["nbody"]
+        dp = dr = dt = 0.0
+        for n in range(2):
+            e.reset(obj)
+            e.set_qpos(q[n])
+            e.L.orc_kinematics(e.dptr)
+            xpos, xmat = e.arr("xpos", 3 * nb).reshape(nb, 3), e.arr("xmat", 9 * nb).reshape(nb, 3, 3)
+            for ci, cam in enumerate(CAMS6):
+                c = e.man["camera_names"].index(cam)
+                b = int(md["cam_body"][c])
+                p, R = xpos[b] + xmat[b] @ md["cam_pos"].reshape(-1, 3)[c], xmat[b] @ quat2mat(md["cam_quat"].reshape(-1, 4)[c])
+                dp = max(dp, np.abs(a[n, ci, :3] - p).max())
+                dr = max(dr, np.abs(a[n, ci, 3:12].reshape(3, 3) - R).max())
+                dt = max(dt, abs(a[n, ci, 12] / np.tan(0.5 * np.deg2rad(md["cam_fovy"].reshape(-1)[c])) - 1))
+        print(f"camera poses of both fronts against the oracle: position {dp:.3g} m, rotation entries {dr:.3g}, tan(fovy / 2) {dt:.3g} relative")
+        assert dp <= 1e-5 and dr <= 1e-5 and dt <= 1e-6
+    finally:
+        env.close()
+        sim.close()
+        e.close()
+
+
 # ---- the layers above ---------------------------------------------------------------------------------------------------------------------
 
 SLOT = "gym_guided_vision/SlotInsertion-3Arms-v0"
