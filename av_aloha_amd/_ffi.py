@@ -77,6 +77,7 @@ def lib():
         L.avsim_image_resize.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp]
         L.avsim_camera_poses.argtypes = [vp, vp, i32, vp]
         L.avsim_point_cloud.argtypes = [vp, vp, i32, i32, i32, vp, vp, C.c_float, i32, vp, vp, vp]
+        L.avsim_voxel_grid.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, C.c_float, vp, vp]
         L.avsim_episode_setup.argtypes = [vp, vp, vp, C.c_uint64, i32, i32, C.c_int64]
         L.avsim_sample_poses.argtypes = [vp, C.c_uint64, i32, vp, vp]
         L.avsim_episode_reset.argtypes = [vp, vp, vp, vp]

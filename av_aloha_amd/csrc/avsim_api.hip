@@ -91,6 +91,7 @@ struct avsim {
     ChunkHost chunks;    // per-env execution of action chunks (avsim_chunks.hip.h), once avsim_chunk_setup has run
     ObsHistHost obshist; // per-env observation histories (avsim_obshist.hip.h), once avsim_obs_history_setup has run
     PcHost pointcloud;   // point clouds from depth images (avsim_pointcloud.hip.h): a chunk of envs' pose records and candidate lists
+    bool voxel_other_form = false;   // option "voxel_other_form": avsim_voxel_grid runs the accumulate form that AVSIM_VOXEL_MERGE did NOT pick (the same bits; there to be measured)
     bool jpegdec_events = false;   // option "jpeg_decode_events": avsim_jpeg_decode records ev[12..15] around its three kernels
     // the state's version: bumped by everything that writes qpos (reset, the steps, set_state); the image calls skip their pose pass and the shadow
     // map when they already hold this version's (a facade that fetches its cameras one call at a time repeats neither)
@@ -527,6 +528,7 @@ int avsim_set_option(avsim_t* h, const char* name, double value) {
     if (!std::strcmp(name, "render_shadow_size")) { if (value != 512 && value != 1024 && value != 2048) { h->set_error("render_shadow_size is 512, 1024 or 2048"); return AVSIM_EINVAL; } h->vis.shadow_size = (int)value; return AVSIM_OK; }
     if (!std::strcmp(name, "render_cam_major")) { h->vis.cam_major = value != 0; return AVSIM_OK; }
     if (!std::strcmp(name, "render_chunk")) { if (value < 1) { h->set_error("render_chunk is a number of envs >= 1"); return AVSIM_EINVAL; } h->render.env_chunk = (int)value; return AVSIM_OK; }
+    if (!std::strcmp(name, "voxel_other_form")) { h->voxel_other_form = value != 0; return AVSIM_OK; }
     if (!std::strcmp(name, "jpeg_decode_events")) { h->jpegdec_events = value != 0; return AVSIM_OK; }
     if (!std::strcmp(name, "jpeg_decode_budget")) { if (value < 1) { h->set_error("jpeg_decode_budget is a number of bytes >= 1"); return AVSIM_EINVAL; } h->jpegdec.coef_budget = (size_t)value; return AVSIM_OK; }
     if (!std::strcmp(name, "augment_scratch_bytes")) { if (!(value >= 1)) { h->set_error("augment_scratch_bytes is a number of bytes >= 1"); return AVSIM_EINVAL; } h->imgaug.scratch_limit = (size_t)value; return AVSIM_OK; }
@@ -1023,6 +1025,43 @@ int avsim_point_cloud(avsim_t* h, const int32_t* cam_ids, int ncam, int height, 
     if ((rc = h->out_end(PC_XYZ, xyz, bxyz))) return rc;
     if ((rc = h->out_end(PC_INDEX, index, bindex))) return rc;
     if ((rc = h->out_end(PC_COUNT, count, bcount))) return rc;
+    return h->finish();
+}
+
+// ---- voxel grids from depth (and colour) images (av_aloha_amd/voxel.py is the specification; the kernels: csrc/avsim_pointcloud.hip, below the cloud's)
+enum VoxSlot { VOX_DEPTH = 8, VOX_RGB = 9, VOX_OUT = 10 };
+int avsim_voxel_grid(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, const float* depth, const uint8_t* rgb, const float* bounds, float max_depth,
+                     const int32_t* grid, float* out) {
+    if (!h) return AVSIM_EINVAL;
+    if (!cam_ids || !depth || !bounds || !grid || !out) { h->set_error("avsim_voxel_grid: a null pointer"); return AVSIM_EINVAL; }
+    {   // the host arrays are checked before anything moves or is launched
+        std::string why;
+        if (voxel_validate(h->render.m.ncam, cam_ids, ncam, height, width, bounds, max_depth, grid, why)) { h->set_error("%s", why.c_str()); return AVSIM_EINVAL; }
+    }
+    if (h->io_device && ((uintptr_t)out & 15)) { h->set_error("avsim_voxel_grid: out is 16-byte aligned (the cells are cleared and finished with 16-byte accesses)"); return AVSIM_EINVAL; }
+    VoxCall c{};
+    for (int k = 0; k < ncam; k++) c.pc.cam[k] = cam_ids[k];
+    c.pc.ncam = ncam; c.pc.H = height; c.pc.W = width; c.pc.P = 0; c.pc.max_depth = max_depth;
+    for (int k = 0; k < 3; k++) { c.pc.lo[k] = bounds[k]; c.pc.hi[k] = bounds[3 + k]; c.g[k] = grid[k]; }
+    AVS_ON_DEVICE(h);
+    int rc;
+    const void *ddepth = nullptr, *drgb = nullptr;
+    void* dout = nullptr;
+    const size_t N = (size_t)h->N, q = (size_t)ncam * height * width, cell_floats = (size_t)grid[0] * grid[1] * grid[2] * VOX_CHANNELS, bout = sizeof(float) * N * cell_floats;
+    if ((rc = h->in(VOX_DEPTH, depth, sizeof(float) * N * q, &ddepth))) return rc;
+    if (rgb && (rc = h->in(VOX_RGB, rgb, 3 * N * q, &drgb))) return rc;
+    if ((rc = h->out_begin(VOX_OUT, out, bout, &dout))) return rc;
+    if ((rc = refresh_xpose(h))) return rc;
+    const int chunk = h->N < PC_ENV_CHUNK ? h->N : PC_ENV_CHUNK;
+    if (h->pointcloud.reserve_poses(chunk, ncam, h->err)) return AVSIM_EHIP;
+    for (int e0 = 0; e0 < h->N; e0 += chunk) {          // envs in chunks, as PcHost::run: the pose scratch is a chunk's
+        const int n = h->N - e0 < chunk ? h->N - e0 : chunk;
+        if (pointcloud_poses_launch(h->stream, pc_model(h), c.pc, e0, n, h->pointcloud.d_pose, h->err)) return AVSIM_EHIP;
+        if (voxel_launch(h->stream, c, n, (const float*)ddepth + (size_t)e0 * q, drgb ? (const uint8_t*)drgb + (size_t)e0 * q * 3 : nullptr, h->pointcloud.d_pose,
+                         (float*)dout + (size_t)e0 * cell_floats, (AVSIM_VOXEL_MERGE != 0) != h->voxel_other_form, h->err))
+            return AVSIM_EHIP;
+    }
+    if ((rc = h->out_end(VOX_OUT, out, bout))) return rc;
     return h->finish();
 }
 

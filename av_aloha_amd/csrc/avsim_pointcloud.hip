@@ -18,6 +18,7 @@
 //          coordinates (the winner's wave is a field of its position).  The LDS records alternate between two sets, which is what makes one
 //          barrier enough.  When the winning distance is 0 every distance is, and by the rule all further selections are candidate 0.
 //       3. The selected positions (LDS) become points and pixel indices, 1024 at a time.
+//   k_vox_clear, k_vox_accum, k_vox_finish   avsim_voxel_grid, below the cloud's: they call pc_world and read k_pc_poses's records.
 #include "avsim_pointcloud.hip.h"
 
 namespace avs {
@@ -224,6 +225,131 @@ int pointcloud_launch(hipStream_t stream, const PcCall& c, int n, const float* d
     hipLaunchKernelGGL(k_pc_cloud, dim3(n), dim3(PC_THREADS), 0, stream, c, depth, pose, list, (int)PcHost::list_len(c), xyz, index, count);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { err = std::string("point cloud kernel: ") + hipGetErrorString(e); return -3; }
+    return 0;
+}
+
+// ---- voxel grids (avsim_voxel_grid).  The caller's output [n][gx][gy][gz][8] is the accumulator: a cell's 32 bytes hold the u32
+// words count, sum qx, sum qy, sum qz, sum r, sum g, sum b and a zero until k_vox_finish turns them into the eight float32 channels in place.
+//   k_vox_clear    16-byte stores of zeros over the chunk's cells
+//   k_vox_accum    a lane per pixel (a workgroup of 256 pixels of one env): pc_world, the cell and the position inside it in 1/256 per axis,
+//       then no-return relaxed agent-scope integer adds into the cell's words -- 4 without a colour image, 7 with one.  MERGE: consecutive
+//       lanes of the wave that hit the same cell form a run (neighbouring pixels of a row mostly see one surface); the run's values are summed
+//       towards its first lane by a segmented shuffle scan -- three registers, two 16-bit sums each (a run's sum is at most 64 x 255), and
+//       only as many steps as the wave's longest run needs -- and the first lane alone adds.  Integer sums: the result does not depend on
+//       the form, nor on the order in which the adds arrive.
+//   k_vox_finish   a lane per cell: reads its 32 bytes and, where count > 0, writes the eight floats (an empty cell's zeros are +0.0 already)
+constexpr int VOX_THREADS = 256;
+
+__global__ void __launch_bounds__(256) k_vox_clear(float4* __restrict__ out, size_t n4) {
+    const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) out[i] = z;
+}
+
+__device__ __forceinline__ void vox_add(unsigned* p, unsigned v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+template <bool MERGE>
+__global__ void __launch_bounds__(VOX_THREADS) k_vox_accum(VoxCall vc, const float* __restrict__ depth, const uint8_t* __restrict__ rgb, const float* __restrict__ pose,
+                                                           unsigned* out) {
+    __shared__ float s_pose[PC_MAX_CAMS * PC_POSE_W];
+    __shared__ float s_scale[PC_MAX_CAMS];
+    const PcCall& c = vc.pc;
+    const int tid = threadIdx.x, lane = tid & 63, env = blockIdx.y;
+    const int Q = c.ncam * c.H * c.W, gx = vc.g[0], gy = vc.g[1], gz = vc.g[2];
+    depth += (size_t)env * Q;
+    pose += (size_t)env * c.ncam * PC_POSE_W;
+    out += (size_t)env * gx * gy * gz * VOX_CHANNELS;
+    PcView v;
+    v.HW = c.H * c.W; v.W = c.W; v.hh = 0.5f * (float)c.H; v.hw = 0.5f * (float)c.W; v.max_depth = c.max_depth;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { v.lo[k] = c.lo[k]; v.hi[k] = c.hi[k]; }
+    if (tid < c.ncam * PC_POSE_W) s_pose[tid] = pose[tid];
+    __syncthreads();
+    if (tid < c.ncam) s_scale[tid] = (2.0f * s_pose[tid * PC_POSE_W + 12]) / (float)c.H;
+    __syncthreads();
+
+    const int pix = blockIdx.x * VOX_THREADS + tid;
+    float w[3];
+    const bool ok = pix < Q && pc_world(v, s_pose, s_scale, depth, pix, w[0], w[1], w[2]);
+    int cell = -1;
+    unsigned q[3] = {0u, 0u, 0u}, col[3] = {0u, 0u, 0u};
+    if (ok) {
+        int ci[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const float g = (float)vc.g[k], inv = g / (c.hi[k] - c.lo[k]);
+            const float u = (w[k] - c.lo[k]) * inv;
+            const float fi = fminf(floorf(u), g - 1.0f);
+            const int qi = (int)((u - fi) * 256.0f);
+            const int i = (int)fi;
+            ci[k] = i < 0 ? 0 : i > vc.g[k] - 1 ? vc.g[k] - 1 : i;          // (0 <= fi <= g - 1 by the box; the clamp keeps the address inside whatever the floats)
+            q[k] = (unsigned)(qi < 0 ? 0 : qi > 255 ? 255 : qi);
+        }
+        cell = (ci[0] * gy + ci[1]) * gz + ci[2];
+        if (rgb) {
+            const uint8_t* p = rgb + ((size_t)env * Q + pix) * 3;
+            col[0] = p[0]; col[1] = p[1]; col[2] = p[2];
+        }
+    }
+    unsigned cnt = 1u;
+    bool add = ok;
+    if (MERGE) {
+        const int prev = __shfl_up(cell, 1);
+        const bool head = lane == 0 || prev != cell;
+        const unsigned long long heads = __ballot(head), rest = (heads >> lane) >> 1;
+        const int after = rest ? __builtin_ctzll(rest) : 63 - lane;          // the lanes after this one in its run
+        unsigned a = q[0] | (q[1] << 16), b = q[2] | (col[0] << 16), d = col[1] | (col[2] << 16);
+        for (int s = 1; s < 64; s <<= 1) {
+            if (__ballot(after >= s) == 0ull) break;          // (the same for the wave) no run reaches further
+            const unsigned ta = __shfl_down(a, s), tb = __shfl_down(b, s), td = __shfl_down(d, s);
+            if (after >= s) { a += ta; b += tb; d += td; }          // after step s a lane holds the sum of itself and the next 2 s - 1 lanes of its run
+        }
+        q[0] = a & 0xffffu; q[1] = a >> 16; q[2] = b & 0xffffu; col[0] = b >> 16; col[1] = d & 0xffffu; col[2] = d >> 16;
+        cnt = (unsigned)after + 1u;
+        add = ok && head;
+    }
+    if (add) {
+        unsigned* o = out + (size_t)cell * VOX_CHANNELS;
+        vox_add(o, cnt);
+        vox_add(o + 1, q[0]); vox_add(o + 2, q[1]); vox_add(o + 3, q[2]);
+        if (rgb) { vox_add(o + 4, col[0]); vox_add(o + 5, col[1]); vox_add(o + 6, col[2]); }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_vox_finish(VoxCall vc, size_t total, float* out) {
+    const PcCall& c = vc.pc;
+    const int gy = vc.g[1], gz = vc.g[2], cells = vc.g[0] * gy * gz;
+    float size[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) size[k] = (c.hi[k] - c.lo[k]) / (float)vc.g[k];
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const uint4 a = ((const uint4*)out)[2 * i], b = ((const uint4*)out)[2 * i + 1];
+        if (a.x == 0u) continue;
+        const int cell = (int)(i % (size_t)cells), iz = cell % gz, t = cell / gz, iy = t % gy, ix = t / gy;
+        const float n = (float)a.x;
+        float4 p, s;
+        p.x = c.lo[0] + ((float)ix + ((float)a.y / n + 0.5f) * 0.00390625f) * size[0];
+        p.y = c.lo[1] + ((float)iy + ((float)a.z / n + 0.5f) * 0.00390625f) * size[1];
+        p.z = c.lo[2] + ((float)iz + ((float)a.w / n + 0.5f) * 0.00390625f) * size[2];
+        p.w = ((float)b.x / n) * (1.0f / 255.0f);
+        s.x = ((float)b.y / n) * (1.0f / 255.0f);
+        s.y = ((float)b.z / n) * (1.0f / 255.0f);
+        s.z = n;
+        s.w = 1.0f;
+        ((float4*)out)[2 * i] = p;
+        ((float4*)out)[2 * i + 1] = s;
+    }
+}
+
+int voxel_launch(hipStream_t stream, const VoxCall& c, int n, const float* depth, const uint8_t* rgb, const float* pose, float* out, bool merge, std::string& err) {
+    const size_t total = (size_t)n * c.g[0] * c.g[1] * c.g[2], blocks = (total + 255) / 256;
+    const int Q = c.pc.ncam * c.pc.H * c.pc.W;
+    const dim3 sweep((unsigned)(blocks < 65536 ? blocks : 65536)), pixels((Q + VOX_THREADS - 1) / VOX_THREADS, n);
+    hipLaunchKernelGGL(k_vox_clear, sweep, dim3(256), 0, stream, (float4*)out, total * 2);
+    if (merge) hipLaunchKernelGGL(k_vox_accum<true>, pixels, dim3(VOX_THREADS), 0, stream, c, depth, rgb, pose, (unsigned*)out);
+    else hipLaunchKernelGGL(k_vox_accum<false>, pixels, dim3(VOX_THREADS), 0, stream, c, depth, rgb, pose, (unsigned*)out);
+    hipLaunchKernelGGL(k_vox_finish, sweep, dim3(256), 0, stream, c, total, out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { err = std::string("voxel grid kernels: ") + hipGetErrorString(e); return -3; }
     return 0;
 }
 

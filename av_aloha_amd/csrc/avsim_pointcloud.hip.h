@@ -1,4 +1,4 @@
-// avsim_pointcloud.hip.h -- point clouds on the device (avsim_camera_poses, avsim_point_cloud): what avsim_api.hip needs of the
+// avsim_pointcloud.hip.h -- point clouds and voxel grids on the device (avsim_camera_poses, avsim_point_cloud; avsim_voxel_grid; 8.ai): what avsim_api.hip needs of the
 // unit csrc/avsim_pointcloud.hip -- the limits, the checks on the caller's host arrays, the scratch of a chunk of envs and the launchers.
 //
 // av_aloha_amd/pointcloud.py is the specification, and the device equals it bit for bit given the camera poses.  Like the image calls that
@@ -80,18 +80,24 @@ struct PcHost {
         return q < (size_t)PC_MAX_CANDIDATES ? q : (size_t)PC_MAX_CANDIDATES;
     }
     int reserve(int chunk, const PcCall& c, std::string& err) {
-        const size_t np = (size_t)chunk * c.ncam * PC_POSE_W, nl = (size_t)chunk * list_len(c);
-        if (np > pose_cap) {
-            if (d_pose) (void)hipFree(d_pose);
-            d_pose = nullptr; pose_cap = 0;
-            if (hipMalloc((void**)&d_pose, np * sizeof(float)) != hipSuccess) { err = "hipMalloc(point cloud poses) failed"; return -3; }
-            pose_cap = np;
-        }
+        const size_t nl = (size_t)chunk * list_len(c);
+        if (const int rc = reserve_poses(chunk, c.ncam, err)) return rc;
         if (nl > list_cap) {
             if (d_list) (void)hipFree(d_list);
             d_list = nullptr; list_cap = 0;
             if (hipMalloc((void**)&d_list, nl * sizeof(int)) != hipSuccess) { err = "hipMalloc(point cloud candidates) failed"; return -3; }
             list_cap = nl;
+        }
+        return 0;
+    }
+    // the pose records alone (avsim_voxel_grid: its accumulator is the caller's output, no other scratch)
+    int reserve_poses(int chunk, int ncam, std::string& err) {
+        const size_t np = (size_t)chunk * ncam * PC_POSE_W;
+        if (np > pose_cap) {
+            if (d_pose) (void)hipFree(d_pose);
+            d_pose = nullptr; pose_cap = 0;
+            if (hipMalloc((void**)&d_pose, np * sizeof(float)) != hipSuccess) { err = "hipMalloc(point cloud poses) failed"; return -3; }
+            pose_cap = np;
         }
         return 0;
     }
@@ -114,5 +120,55 @@ struct PcHost {
         return 0;
     }
 };
+
+// ---- voxel grids (avsim_voxel_grid; av_aloha_amd/voxel.py is the specification): the same points and candidates scattered into a
+// dense grid of seven u32 sums per cell, in the caller's output buffer, and finished in place into eight float32 channels
+constexpr int VOX_MAX_DIM = 256;             // AVSIM_VOXEL_MAX_DIM
+constexpr int VOX_MAX_CELLS = 1 << 21;       // AVSIM_VOXEL_MAX_CELLS
+constexpr int VOX_CHANNELS = 8;
+// the accumulate form the library ships: 1 = runs of consecutive lanes in one cell are summed in the wave and the run's first lane adds,
+// 0 = every candidate lane adds.  Both are compiled; option "voxel_other_form" runs the one not picked here, for a measurement (tools/bench_voxel.py)
+#ifndef AVSIM_VOXEL_MERGE
+#define AVSIM_VOXEL_MERGE 1
+#endif
+
+struct VoxCall {
+    PcCall pc;                // cameras, image size, box, max_depth (P unused)
+    int g[3];
+};
+
+inline int voxel_validate(int ncam_model, const int32_t* cam_ids, int ncam, int H, int W, const float* bounds, float max_depth, const int32_t* grid, std::string& err) {
+    char buf[240];
+    const char* what = nullptr;
+    if (ncam < 1 || ncam > PC_MAX_CAMS) what = "1..16 cameras";
+    else if (H < 1 || H > 65535 || W < 1 || W > 65535) what = "an image size outside 1..65535";
+    else if ((long long)ncam * H * W > PC_MAX_PIXELS) what = "more than 2^24 pixels per env";
+    else if (grid[0] < 1 || grid[0] > VOX_MAX_DIM || grid[1] < 1 || grid[1] > VOX_MAX_DIM || grid[2] < 1 || grid[2] > VOX_MAX_DIM) what = "a grid dim outside 1..256";
+    else if ((long long)grid[0] * grid[1] * grid[2] > VOX_MAX_CELLS) what = "more than 2^21 cells";
+    else if (!std::isfinite(max_depth) || !(max_depth > 0.0f)) what = "max_depth is finite and > 0";
+    if (!what)
+        for (int k = 0; k < 6; k++)
+            if (!std::isfinite(bounds[k])) what = "a bound that is not finite";
+    if (!what)
+        for (int k = 0; k < 3; k++) {
+            if (!(bounds[k] < bounds[3 + k])) { what = "a lower bound that is not below its upper bound"; break; }
+            const volatile float ext = bounds[3 + k] - bounds[k];          // (volatile: rounded to float32 here, whatever the host's flags)
+            const volatile float inv = (float)grid[k] / ext, size = ext / (float)grid[k];
+            if (!std::isfinite(inv) || !std::isfinite(size)) what = "an extent whose cell size or its reciprocal is not a finite float32";
+        }
+    if (!what)
+        for (int c = 0; c < ncam; c++)
+            if (cam_ids[c] < 0 || cam_ids[c] >= ncam_model) what = "camera index out of range";
+    if (what) {
+        snprintf(buf, sizeof buf, "avsim_voxel_grid: %s (%d cameras, %d x %d, grid %d x %d x %d)", what, ncam, H, W, grid[0], grid[1], grid[2]);
+        err = buf;
+        return -1;
+    }
+    return 0;
+}
+
+// csrc/avsim_pointcloud.hip.  The three passes over a chunk of n envs: depth [n][ncam][H][W], rgb u8 [n][ncam][H][W][3] or null, pose
+// [n][ncam][16], out [n][gx][gy][gz][8] -- device pointers of the chunk's first env.  merge: the accumulate form.  -3: HIP
+int voxel_launch(hipStream_t stream, const VoxCall& c, int n, const float* depth, const uint8_t* rgb, const float* pose, float* out, bool merge, std::string& err);
 
 }  // namespace avs

@@ -1,9 +1,9 @@
 """The device image calls of libavsim (include/avsim.h) from Python.  ImageCalls implements compose and label, image statistics, prep, jitter,
-augment, resize, camera poses and point clouds once each, against one of two array adaptors: HostArrays (numpy; BatchedSim) and DeviceArrays
+augment, resize, camera poses, point clouds and voxel grids once each, against one of two array adaptors: HostArrays (numpy; BatchedSim) and DeviceArrays
 (torch tensors on a device; DeviceImageOps, which VecEnv inherits).  The adaptors hold all that differs between the fronts:
   * numpy converts what it is given (np.ascontiguousarray of the pixels, values= to int64, lut= to float32 [-1, 3, 256]); torch takes
     contiguous tensors of the right type on the owner's device and fails an assert for anything else;
-  * a wrong `out` or canvas, a jitter / augment img that is not u8 HWC, a depth of the wrong shape: ValueError in numpy, AssertionError in torch;
+  * a wrong `out` or canvas, a jitter / augment img that is not u8 HWC, a depth or rgb of the wrong shape: ValueError in numpy, AssertionError in torch;
   * image_stats returns uint64 and refuses an index outside [0, n) in numpy, returns int64 and clamps the index tensor in torch;
   * torch binds its current stream before a call and never synchronises; the numpy front's handle (host I/O mode) is synchronous by itself.
 DeviceImageOps adds the JPEG calls on buffers, and DeviceImages is DeviceImageOps for a caller that has no env (a data set, a video tool)."""
@@ -127,7 +127,7 @@ def _host(a, dtype, *shape):
 
 
 class ImageCalls:
-    """Compose and label, image statistics, prep, jitter, augment, resize, camera poses and point clouds: each call once, for the owner of a
+    """Compose and label, image statistics, prep, jitter, augment, resize, camera poses, point clouds and voxel grids: each call once, for the owner of a
     handle self.h (_ffi.Handle) -- and, for the camera calls, of a self.manifest -- whose self._arrays says what kind of array the pixels live
     in: HostArrays (numpy) or DeviceArrays (torch tensors on self.device).  The two kinds differ in what the adaptor holds and in nothing
     else: how an array is made, whether an input is converted or has to be right already, whether a wrong one is a ValueError or a failed
@@ -135,6 +135,8 @@ class ImageCalls:
     synchronous).  Arguments called HOST below are numpy arrays, lists or tuples on both fronts; the library checks them before it launches
     anything and copies them before the call returns.  AVSIM_EINVAL is a ValueError with the library's message, any other failure an
     AvsimError (check_call)."""
+
+    _cam_major = 0          # what the owner keeps option "render_cam_major" at between calls (voxel_grid's own colour render is env-major)
 
     def _canvas(self, a):
         """(fmt, n, H, W) of an image batch that is written in place, so has to be this front's kind of array already."""
@@ -328,6 +330,54 @@ class ImageCalls:
                                                       float(pointcloud.FAR_PLANE if max_depth is None else max_depth), P, A.ptr(xyz), A.ptr(index), A.ptr(count)))
         return xyz, index, count
 
+    def voxel_grid(self, cameras, height, width, bounds, grid, max_depth=None, depth=None, rgb=None, colour=False, out=None):
+        """float32 [N, gx, gy, gz, 8]: one dense grid per env over HOST bounds (xlo ylo zlo xhi yhi zhi, lo < hi) in the world frame, from the
+        depth images of the named cameras (avsim_voxel_grid): the bits of av_aloha_amd.voxel.voxel_grid_reference given camera_poses().  A
+        cell's channels: 0..2 the mean position of its points, 3..5 their mean colour in [0, 1] (0 without colour), 6 their number, 7
+        occupancy 1.0 / 0.0; an empty cell is zeros.  grid: an int or three ints.  depth: float32 [N, len(cameras), height, width] of the
+        CURRENT state (None: rendered first); rgb: uint8 [N, len(cameras), height, width, 3], the same pixels in avsim_render_rgb's env-major
+        layout (None and colour=True: rendered first; None and colour=False: no colour); max_depth: None = the far plane.  out: the array
+        to write.  The colour rendered here is what avsim_render_rgb draws for this owner -- the visual scene where one is loaded (a VecEnv
+        with `cameras`), the collision proxies otherwise -- and always env-major: "render_cam_major" is switched off for that render and
+        put back to self._cam_major, the value the owner keeps it at between calls (VecEnv: 1 with `cameras`; BatchedSim sets the option
+        in each of its own render methods, 0 here).  An rgb that is GIVEN has to be env-major.  ValueError for what the library refuses."""
+        from . import pointcloud, voxel
+        A = self._arrays
+        A.begin(self)
+        ids = camera_ids(self.manifest, cameras)
+        N, height, width = self.h.num_envs, int(height), int(width)
+        g = np.array(voxel.grid_dims(grid), dtype=np.int32)
+        if g.min() < 1 or g.max() > voxel.MAX_DIM or int(g[0]) * int(g[1]) * int(g[2]) > voxel.MAX_CELLS:      # (before an output of that size is made)
+            raise ValueError(f"voxel_grid: grid dims are 1..{voxel.MAX_DIM} with at most 2^21 cells, not {tuple(int(x) for x in g)}")
+        shape = (N, len(ids), height, width)
+        if depth is None:
+            depth = A.empty(self, shape, "float32")
+            self.h.check(self.h.L.avsim_render_depth(self.h.h, ids.ctypes.data, len(ids), height, width, A.ptr(depth)))
+        if rgb is None and colour:          # env-major whatever the owner keeps "render_cam_major" at: switched off for this render, then put back
+            rgb = A.empty(self, shape + (3,), "uint8")
+            self.h.check(self.h.L.avsim_set_option(self.h.h, b"render_cam_major", 0.0))
+            try:
+                self.h.check(self.h.L.avsim_render_rgb(self.h.h, ids.ctypes.data, len(ids), height, width, A.ptr(rgb)))
+            finally:
+                if self._cam_major:
+                    self.h.check(self.h.L.avsim_set_option(self.h.h, b"render_cam_major", 1.0))
+        text = "voxel_grid(depth=...): a contiguous float32 [N, cameras, height, width] tensor on the env's device"
+        depth = A.given(self, depth, "float32", None, text)
+        if tuple(depth.shape) != shape:
+            A.fail(f"voxel_grid: depth is float32 {shape}, not {tuple(depth.shape)}", text)
+        if rgb is not None:
+            text = "voxel_grid(rgb=...): a contiguous uint8 [N, cameras, height, width, 3] tensor on the env's device"
+            rgb = A.given(self, rgb, "uint8", None, text)
+            if tuple(rgb.shape) != shape + (3,):
+                A.fail(f"voxel_grid: rgb is uint8 {shape + (3,)}, not {tuple(rgb.shape)}", text)
+        b = np.ascontiguousarray(bounds, dtype=np.float32).reshape(-1)
+        if b.shape != (6,):
+            raise ValueError("voxel_grid: bounds are xlo ylo zlo xhi yhi zhi")
+        out = self._out("voxel_grid", out, (N, int(g[0]), int(g[1]), int(g[2]), 8), text="float32 [N, gx, gy, gz, 8]")
+        check_call(self.h, self.h.L.avsim_voxel_grid(self.h.h, ids.ctypes.data, len(ids), height, width, A.ptr(depth), _ffi.ptr(rgb), b.ctypes.data,
+                                                     float(pointcloud.FAR_PLANE if max_depth is None else max_depth), g.ctypes.data, A.ptr(out)))
+        return out
+
 
 class DeviceImageOps(ImageCalls):
     """The image calls on torch tensors, for the owner of a device-I/O handle: ImageCalls through DeviceArrays, and the JPEG calls, which
@@ -348,6 +398,12 @@ class DeviceImageOps(ImageCalls):
             self.h.check(self.L.avsim_sync(self.h.h))
             self.h.close()
             self.h = None
+
+    def voxel_grid(self, *args, channels_first=False, **kw):
+        """ImageCalls.voxel_grid; channels_first=True returns the [N, 8, gx, gy, gz] view of the same memory (out.permute(0, 4, 1, 2, 3):
+        channels_last_3d strides, which Conv3d takes as it is) -- no copy is made."""
+        out = ImageCalls.voxel_grid(self, *args, **kw)
+        return out.permute(0, 4, 1, 2, 3) if channels_first else out
 
     def decode_jpeg(self, buf, lengths, height=None, width=None, upsample="replicate", fmt=None, out=None, status=None):
         """The inverse of encode_jpeg on the device (avsim_jpeg_decode): buf uint8 [n, stride] and lengths int32 [n] as encode_jpeg

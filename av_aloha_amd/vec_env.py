@@ -13,6 +13,11 @@ per-env episodes and gymnasium's NEXT_STEP autoreset done by the library's kerne
   deprojected into the world frame, cropped and thinned by farthest point sampling (avsim_point_cloud); `info["pointcloud_count"]` int32
   [N, 2] = (candidates, distinct points) and `info["pointcloud_index"]` int32 [N, P], the flat pixels.  None (the default): no call, buffer
   or key changes.
+* voxels={"cameras": [...], "height": h, "width": w, "bounds": (xlo, ylo, zlo, xhi, yhi, zhi), "grid": g or (gx, gy, gz), "colour": False,
+  "max_depth": None} adds `observation.voxels` (gym format: `voxels`) float32 [N, 8, gx, gy, gz], a channels_last_3d view of the
+  [N, gx, gy, gz, 8] buffer that avsim_voxel_grid writes: per cell the mean position, the mean colour, the count and the occupancy.  The
+  depth, and with "colour" the u8 colour images, are rendered at the option's own size into its own buffers.  Refused together with the
+  "render_cam_major" option -- which `cameras` switch on --: the grid reads env-major images.  None (the default): no call, buffer or key changes.
 * Every tensor returned is a preallocated buffer that the next reset / step overwrites: clone what must outlive the call.
 * NEXT_STEP: an env whose episode ended (terminated or truncated) in call t starts its next episode in call t + 1, whose action does
   not reach it; that call reports reward 0, flags 0, elapsed 0, the new `info["episode_id"]` and the new episode's first observation.
@@ -88,15 +93,17 @@ def sample_poses(task, seed, episode_ids):
 class VecEnv(DeviceImageOps):
     """num_envs envs of one task on one GPU; see the module's docstring for the semantics.  The image calls on any tensor of the env's device
     -- decode_jpeg, encode_images, compose, compose_label, image_stats, prep_images, jitter_images, augment_images, resize_images -- and
-    camera_poses / point_cloud on demand are images.DeviceImageOps's (images.ImageCalls on tensors)."""
+    camera_poses / point_cloud / voxel_grid on demand are images.DeviceImageOps's (images.ImageCalls on tensors)."""
 
     metadata = {"autoreset_mode": "NextStep", "render_modes": []}
 
     def __init__(self, task, num_arms, num_envs, max_episode_steps, device=None, cameras=(), depth_cameras=(), obs_format="lerobot",
-                 seed=0, terminate_on_success=False, f64=False, options=None, observation_height=480, observation_width=640, pointcloud=None):
+                 seed=0, terminate_on_success=False, f64=False, options=None, observation_height=480, observation_width=640, pointcloud=None, voxels=None):
         import torch
         assert obs_format in ("lerobot", "gym"), obs_format
         assert all(c in CAMERAS for c in list(cameras) + list(depth_cameras)), "Invalid camera names"
+        if voxels is not None and (list(cameras) or float((options or {}).get("render_cam_major", 0)) != 0):      # (before there is a handle to give back)
+            raise ValueError("vec_env: voxels are refused together with the render_cam_major option (which `cameras` switch on): the grid reads env-major images")
         self.torch = torch
         self.task, self.num_arms, self.num_envs = task, num_arms, int(num_envs)
         self.max_episode_steps, self.terminate_on_success = int(max_episode_steps), bool(terminate_on_success)
@@ -107,6 +114,16 @@ class VecEnv(DeviceImageOps):
         d = torch.device("cuda", device) if isinstance(device, int) else torch.device(device if device is not None else "cuda")
         self.device = torch.device("cuda", d.index if d.index is not None else torch.cuda.current_device())
         blob, self.manifest = load_blob(task, num_arms)
+        vx = None
+        if voxels is not None:          # checked before there is a handle to give back
+            from . import pointcloud as pcspec, voxel as voxspec
+            vx = dict(voxels)
+            cams = list(vx["cameras"])
+            assert all(c in CAMERAS for c in cams), "Invalid camera names"
+            vx = {"cameras": cams, "ids": camera_ids(self.manifest, cams), "height": int(vx["height"]), "width": int(vx["width"]), "g": voxspec.grid_dims(vx["grid"]),
+                  "bounds": np.ascontiguousarray(vx["bounds"], dtype=np.float32).reshape(-1), "colour": bool(vx.get("colour")),
+                  "max_depth": float(pcspec.FAR_PLANE if vx.get("max_depth") is None else vx["max_depth"])}
+            voxspec.check_voxel_grid(len(self.manifest["camera_names"]), vx["ids"], vx["height"], vx["width"], vx["bounds"], vx["max_depth"], vx["g"])
         flags = _ffi.AVSIM_IO_DEVICE | (_ffi.AVSIM_F64_PHYSICS if f64 else 0)
         with torch.cuda.device(self.device):
             self.h = _ffi.Handle(blob, self.num_envs, self.device.index, flags)
@@ -116,6 +133,7 @@ class VecEnv(DeviceImageOps):
         options = {"render_shadows": 1, "render_samples": 4, "render_smooth": 1, **(options or {})}
         for k, v in options.items():
             self.h.check(self.L.avsim_set_option(self.h.h, k.encode(), float(v)))
+        self._cam_major = int(float(options.get("render_cam_major", 0)) != 0)      # what voxel_grid's own colour render puts the option back to
         self._cam_ids, self._depth_ids = camera_ids(self.manifest, self.cameras), camera_ids(self.manifest, self.depth_cameras)
         if self.cameras:
             with open(os.path.join(MODEL_DIR, "visual_meshes.avv"), "rb") as f:
@@ -123,6 +141,7 @@ class VecEnv(DeviceImageOps):
             self.h.check(self.L.avsim_load_visual(self.h.h, lib, len(lib)))
             self.h.check(self.L.avsim_set_option(self.h.h, b"render_proxies", 0.0))
             self.h.check(self.L.avsim_set_option(self.h.h, b"render_cam_major", 1.0))     # every camera's batch contiguous
+            self._cam_major = 1
         self._box = np.ascontiguousarray(OBJECT_BOXES[task][0], dtype=np.float64)
         self._share = np.ascontiguousarray(OBJECT_BOXES[task][1], dtype=np.int32)
         assert self._box.shape == (self.nobj, 6)
@@ -161,6 +180,13 @@ class VecEnv(DeviceImageOps):
                         "depth": torch.zeros((N, len(cams), ph, pw), dtype=torch.float32, device=dev),
                         "xyz": torch.zeros((N, P, 3), dtype=torch.float32, device=dev), "index": torch.zeros((N, P), dtype=torch.int32, device=dev),
                         "count": torch.zeros((N, 2), dtype=torch.int32, device=dev)}
+        self._vox = None
+        if vx is not None:          # a dense world-frame grid per env as an observation: its own cameras, size, depth and colour buffers
+            grid = torch.zeros((N,) + vx["g"] + (8,), dtype=torch.float32, device=dev)
+            nc = len(vx["cameras"])
+            self._vox = {**vx, "dims": np.array(vx["g"], dtype=np.int32), "depth": torch.zeros((N, nc, vx["height"], vx["width"]), dtype=torch.float32, device=dev),
+                         "rgb": torch.zeros((N, nc, vx["height"], vx["width"], 3), dtype=torch.uint8, device=dev) if vx["colour"] else None,
+                         "grid": grid, "view": grid.permute(0, 4, 1, 2, 3)}
         self._bind_stream()
         self._setup(self.seed, 0)
 
@@ -197,6 +223,15 @@ class VecEnv(DeviceImageOps):
             self.h.check(L.avsim_point_cloud(h, ids, nc, pc["height"], pc["width"], pc["depth"].data_ptr(), pc["bounds"].ctypes.data, pc["max_depth"], pc["points"],
                                              pc["xyz"].data_ptr(), pc["index"].data_ptr(), pc["count"].data_ptr()))
             obs["observation.pointcloud" if self.obs_format == "lerobot" else "pointcloud"] = pc["xyz"]
+        if self._vox is not None:
+            vx = self._vox
+            ids, nc = vx["ids"].ctypes.data, len(vx["cameras"])
+            self.h.check(L.avsim_render_depth(h, ids, nc, vx["height"], vx["width"], vx["depth"].data_ptr()))
+            if vx["rgb"] is not None:
+                self.h.check(L.avsim_render_rgb(h, ids, nc, vx["height"], vx["width"], vx["rgb"].data_ptr()))
+            self.h.check(L.avsim_voxel_grid(h, ids, nc, vx["height"], vx["width"], vx["depth"].data_ptr(), _ffi.ptr(vx["rgb"]), vx["bounds"].ctypes.data, vx["max_depth"],
+                                            vx["dims"].ctypes.data, vx["grid"].data_ptr()))
+            obs["observation.voxels" if self.obs_format == "lerobot" else "voxels"] = vx["view"]
         return obs
 
     def _pc_info(self, info):
@@ -318,11 +353,11 @@ class VecEnv(DeviceImageOps):
 
 
 def make_vec(env_id, num_envs, max_episode_steps, device=None, cameras=None, depth_cameras=(), obs_format="lerobot", seed=0,
-             terminate_on_success=False, f64=False, options=None, observation_height=None, observation_width=None, pointcloud=None):
-    """A VecEnv of a registry id (env.ENVS); cameras default to the registry's, the image size to its 480 x 640.  pointcloud: VecEnv's."""
+             terminate_on_success=False, f64=False, options=None, observation_height=None, observation_width=None, pointcloud=None, voxels=None):
+    """A VecEnv of a registry id (env.ENVS); cameras default to the registry's, the image size to its 480 x 640.  pointcloud, voxels: VecEnv's."""
     spec = ENVS[env_id]
     return VecEnv(_TASK_OF_CLASS[spec["env"]], spec["num_arms"], num_envs, max_episode_steps, device=device,
                   cameras=spec["cameras"] if cameras is None else cameras, depth_cameras=depth_cameras, obs_format=obs_format, seed=seed,
                   terminate_on_success=terminate_on_success, f64=f64, options=options,
                   observation_height=spec["observation_height"] if observation_height is None else observation_height,
-                  observation_width=spec["observation_width"] if observation_width is None else observation_width, pointcloud=pointcloud)
+                  observation_width=spec["observation_width"] if observation_width is None else observation_width, pointcloud=pointcloud, voxels=voxels)

@@ -255,6 +255,30 @@ int avsim_point_cloud(avsim_t* h, const int32_t* cam_ids, int ncam, int height, 
                       const float bounds[6] /* host: xlo ylo zlo xhi yhi zhi, world */, float max_depth, int npoints,
                       float* xyz /* [N][P][3] */, int32_t* index /* [N][P] */, int32_t* count /* [N][2] */);
 
+/* Voxel grids on the device (csrc/avsim_pointcloud.hip); av_aloha_amd/voxel.py is the specification, and the result equals it
+ * bit for bit given the pose records.  One dense grid per env over the box `bounds` in the world frame, from the same depth images, poses
+ * (THE CURRENT STATE'S), deprojection and candidate rule as avsim_point_cloud -- d < max_depth, the inclusive box, a NaN drops the pixel --
+ * without a cap: every candidate counts.  Per axis, float32, every operation rounded on its own: inv = (float)g / (hi - lo), size =
+ * (hi - lo) / (float)g, u = (w - lo) inv, i = min(floor(u), g - 1) (a point on hi goes to the last cell), frac = u - (float)i, q =
+ * clip((int)(frac 256), 0, 255).  A cell sums UNSIGNED 32-BIT INTEGERS -- count, q per axis and, with rgb, the pixel's three u8 values --,
+ * so the result does not depend on the order of the (atomic) adds and is the same for every call; 2^24 pixels x 255 < 2^32.  Eight float32
+ * channels per cell: 0..2 the mean position lo + ((float)i + ((float)sum_q / (float)count + 0.5) (1 / 256)) size, 3..5 the mean colour
+ * ((float)sum_c / (float)count) (1 / 255) (0 with rgb NULL), 6 (float)count, 7 occupancy 1.0 / 0.0; an empty cell is eight +0.0.
+ * depth, rgb (avsim_render_rgb's env-major u8 layout of the same pixels, or NULL) and out follow the handle's I/O mode; cam_ids, bounds and
+ * grid are HOST arrays in both modes, passed on by value.  `out` is the accumulator: no scratch grows with the grid (the pose records of a
+ * chunk of at most 1024 envs, shared with avsim_point_cloud, are all there is), and with AVSIM_IO_DEVICE it is 16-byte aligned.
+ * AVSIM_EINVAL, with nothing launched and out untouched: ncam outside 1..16, height or width outside 1..65535, ncam H W > 2^24, a grid dim
+ * outside 1..AVSIM_VOXEL_MAX_DIM, more than AVSIM_VOXEL_MAX_CELLS cells, a bound that is not finite, lo >= hi on an axis, an extent whose
+ * inv or size is not a finite float32, max_depth not finite or <= 0, a camera id out of range, a null cam_ids, depth, bounds, grid or out.
+ * The accumulate pass has two forms -- one add per candidate lane, or one per run of consecutive lanes in a cell -- and the build picks one
+ * (AVSIM_VOXEL_MERGE, csrc/avsim_pointcloud.hip.h; the merged one unless built otherwise).  Debug option "voxel_other_form" 1 runs the
+ * other: the same result, there so that tools/bench_voxel.py can time both in one process. */
+#define AVSIM_VOXEL_MAX_DIM 256
+#define AVSIM_VOXEL_MAX_CELLS (1 << 21)
+int avsim_voxel_grid(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width,
+                     const float* depth /* [N][ncam][H][W] */, const uint8_t* rgb /* [N][ncam][H][W][3], avsim_render_rgb's env-major layout, or NULL */,
+                     const float bounds[6] /* host */, float max_depth, const int32_t* grid /* host [3] */, float* out /* [N][gx][gy][gz][8] */);
+
 /* Baseline JPEG streams of rendered frames, encoded on the device (csrc/avsim_jpeg.hip.h): SOF0, 8 bit, JFIF, Y Cb Cr 4:2:0, the Annex K
  * Huffman tables in every frame, one restart interval per MCU row, integer arithmetic throughout -- byte for byte the stream of
  * av_aloha_amd/jpeg.py encode_reference, which is its specification (colour matrix, DCT, quantiser rounding: DESIGN 8.y).
