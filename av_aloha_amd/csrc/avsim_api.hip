@@ -9,7 +9,6 @@
 #include <cstring>
 #include <memory>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/avsim.h"
@@ -22,6 +21,7 @@
 #include "avsim_pointcloud.hip.h"
 #include "avsim_episode.hip.h"
 #include "avsim_ik.hip.h"
+#include "avsim_io.h"
 #include "avsim_jpeg.hip.h"
 #include "avsim_model.h"
 #include "avsim_phys.hip.h"
@@ -100,9 +100,7 @@ struct avsim {
     // device state (real = float, or double with AVSIM_F64_PHYSICS)
     void *d_qpos = nullptr, *d_qvel = nullptr, *d_ctrl = nullptr, *d_warm = nullptr;
     int* d_latch = nullptr;
-    // device scratch for host-pointer I/O
-    void* d_io[16] = {};
-    size_t d_io_sz[16] = {};
+    IoPool io;           // device copies of the arrays of a host caller, a call's scratch (avsim_io.h)
     // per-env episodes (avsim_episode_setup; avsim_episode.hip.h): parameters, per-env bookkeeping, records, outputs nobody asked for
     bool ep_ready = false;
     EpArgs ep{};
@@ -129,92 +127,15 @@ struct avsim {
         err = buf;
     }
     size_t rsz() const { return f64 ? 8 : 4; }
-    int io_buf(int slot, size_t bytes, void** out) {
-        if (d_io_sz[slot] < bytes) {
-            if (d_io[slot]) (void)hipFree(d_io[slot]);
-            d_io[slot] = nullptr;
-            d_io_sz[slot] = 0;
-            hipError_t e = hipMalloc(&d_io[slot], bytes);
-            if (e != hipSuccess) {
-                set_error("hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-                return AVSIM_EHIP;
-            }
-            d_io_sz[slot] = bytes;
-        }
-        *out = d_io[slot];
-        return 0;
-    }
-    // stage an input: returns device pointer holding `bytes` of `p` (host or device according to io mode)
-    int in(int slot, const void* p, size_t bytes, const void** out) {
-        if (io_device) { *out = p; return 0; }
-        void* d;
-        int rc = io_buf(slot, bytes, &d);
-        if (rc) return rc;
-        hipError_t e = hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, stream);
-        if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); return AVSIM_EHIP; }
-        *out = d;
-        return 0;
-    }
-    int out_begin(int slot, void* p, size_t bytes, void** dev) {
-        if (io_device) { *dev = p; return 0; }
-        return io_buf(slot, bytes, dev);
-    }
-    // Large results to pageable host memory (the images of avsim_render_*: 0.9 MB per 480 x 640 colour view).  hipMemcpy into pageable memory
-    // runs at ~5 GB/s here (measured: 354 MB of pixels in 66 of the 73 ms of a 64-env gym step).  Above 16 MB the copy is pipelined instead: the
-    // device buffer goes in 32 MB chunks by DMA into two pinned staging buffers while the previous chunk is copied on into the caller's memory by
-    // four threads.  Synchronous, like the plain path once finish() has run.
-    static constexpr size_t PIN_CHUNK = 32u << 20;
-    void* pin[2] = {nullptr, nullptr};
-    hipEvent_t pin_ev[2] = {nullptr, nullptr};
-    int out_end_pipelined(const char* src, char* dst, size_t bytes) {
-        for (int k = 0; k < 2; k++) {
-            if (!pin[k] && hipHostMalloc(&pin[k], PIN_CHUNK, hipHostMallocDefault) != hipSuccess) { pin[k] = nullptr; return 1; }      // (1: fall back to the plain copy)
-            if (!pin_ev[k] && hipEventCreateWithFlags(&pin_ev[k], hipEventDisableTiming) != hipSuccess) { pin_ev[k] = nullptr; return 1; }
-        }
-        const size_t nchunk = (bytes + PIN_CHUNK - 1) / PIN_CHUNK;
-        auto issue = [&](size_t c) -> hipError_t {
-            const size_t off = c * PIN_CHUNK, n = bytes - off < PIN_CHUNK ? bytes - off : PIN_CHUNK;
-            hipError_t e = hipMemcpyAsync(pin[c & 1], src + off, n, hipMemcpyDeviceToHost, stream);
-            return e != hipSuccess ? e : hipEventRecord(pin_ev[c & 1], stream);
-        };
-        hipError_t e = issue(0);
-        for (size_t c = 0; c < nchunk && e == hipSuccess; c++) {
-            if ((e = hipEventSynchronize(pin_ev[c & 1])) != hipSuccess) break;
-            if (c + 1 < nchunk && (e = issue(c + 1)) != hipSuccess) break;          // (the other buffer: its previous contents were copied out in the last round)
-            const size_t off = c * PIN_CHUNK, n = bytes - off < PIN_CHUNK ? bytes - off : PIN_CHUNK;
-            const char* from = (const char*)pin[c & 1];
-            constexpr int NT = 4;
-            const size_t part = ((n + NT - 1) / NT + 4095) & ~(size_t)4095;
-            std::thread th[NT - 1];
-            int started = 0;
-            for (int t = 1; t < NT; t++) {
-                const size_t a = (size_t)t * part;
-                if (a >= n) break;
-                const size_t m = n - a < part ? n - a : part;
-                th[started++] = std::thread([=] { std::memcpy(dst + off + a, from + a, m); });
-            }
-            std::memcpy(dst + off, from, n < part ? n : part);
-            for (int t = 0; t < started; t++) th[t].join();
-        }
-        if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); return AVSIM_EHIP; }
-        return 0;
-    }
-    int out_end(int slot, void* p, size_t bytes) {
-        if (io_device || !p) return 0;
-        if (bytes >= ((size_t)16 << 20)) {
-            const int rc = out_end_pipelined((const char*)d_io[slot], (char*)p, bytes);
-            if (rc != 1) return rc;
-        }
-        hipError_t e = hipMemcpyAsync(p, d_io[slot], bytes, hipMemcpyDeviceToHost, stream);
-        if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); return AVSIM_EHIP; }
-        return 0;
-    }
-    int finish() {  // host-pointer mode is synchronous
-        if (io_device) return 0;
-        hipError_t e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) { set_error("stream sync failed: %s", hipGetErrorString(e)); return AVSIM_EHIP; }
-        return 0;
-    }
+};
+
+// The arrays of one entry point (avsim_io.h), with the library's return codes: built after AVS_ON_DEVICE, asked once before the launch
+// (`if (io.failed()) return AVSIM_EHIP;`), and `return io.done();` last -- in host I/O mode that copies the outputs back and synchronises
+static_assert(IoPool::NBUF >= 4 + 2 * OBH_MAX_CAMS, "avsim_obs_history_push stages four arrays and two per camera");
+struct Call : IoCall {
+    explicit Call(avsim* h) : Call(h, h->io_device) {}
+    Call(avsim* h, bool device_mode) : IoCall(h->io, h->stream, device_mode, h->err) {}
+    int done() { return finish() == hipSuccess ? AVSIM_OK : AVSIM_EHIP; }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -362,6 +283,8 @@ __global__ void k_convert(size_t n, const A* __restrict__ a, B* __restrict__ b) 
 // ------------------------------------------------------------------------------------------------
 // C-ABI
 // ------------------------------------------------------------------------------------------------
+static int reset_from(avsim_t* h, bool device_mode, const uint8_t* mask, const double* obj_qpos);
+
 extern "C" {
 
 const char* avsim_last_error(const avsim_t* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
@@ -464,10 +387,7 @@ int avsim_create(const void* blob, size_t nbytes, int num_envs, int device, uint
     for (int i = 0; i < num_envs; i++)
         for (int o = 0; o < (*out)->nobj; o++)
             for (int k = 0; k < 7; k++) obj[((size_t)i * (*out)->nobj + o) * 7 + k] = (*out)->qpos_home[(*out)->obj_qadr[o] + k];
-    bool save = (*out)->io_device;
-    (*out)->io_device = false;
-    int rc = avsim_reset(*out, nullptr, obj.data());
-    (*out)->io_device = save;
+    int rc = reset_from(*out, /*device_mode=*/false, nullptr, obj.data());          // (a host array, whatever the handle's I/O mode)
     if (rc) {
         g_create_error = (*out)->err;
         avsim_destroy(*out);
@@ -494,13 +414,8 @@ void avsim_destroy(avsim_t* h) {
     h->pointcloud.destroy();
     for (void* p : {h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, (void*)h->d_latch})
         if (p) (void)hipFree(p);
-    for (void* p : h->d_io)
-        if (p) (void)hipFree(p);
+    h->io.destroy();
     for (void* p : h->ep_allocs) (void)hipFree(p);
-    for (int k = 0; k < 2; k++) {
-        if (h->pin[k]) (void)hipHostFree(h->pin[k]);
-        if (h->pin_ev[k]) (void)hipEventDestroy(h->pin_ev[k]);
-    }
     for (auto& ev : h->ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : h->kev) (void)hipEventDestroy(ev);
@@ -619,39 +534,33 @@ int avsim_observe(avsim_t* h, double* agent_pos, int32_t* reward, uint8_t* succe
     if (!h) return AVSIM_EINVAL;
     AVS_ON_DEVICE(h);
     AVS_PHYS_GATE(h);
-    int rc;
-    void *dap = nullptr, *drw = nullptr, *dsu = nullptr;
-    size_t N = h->N;
-    if (agent_pos && (rc = h->out_begin(4, agent_pos, sizeof(double) * N * h->nj, &dap))) return rc;
-    if (reward && (rc = h->out_begin(5, reward, sizeof(int32_t) * N, &drw))) return rc;
-    if (success && (rc = h->out_begin(6, success, N, &dsu))) return rc;
+    Call io(h);
+    const size_t N = h->N;
+    double* dap = io.out(agent_pos, sizeof(double) * N * h->nj);
+    int32_t* drw = io.out(reward, sizeof(int32_t) * N);
+    uint8_t* dsu = io.out(success, N);
+    if (io.failed()) return AVSIM_EHIP;
     h->phys.force_reward = 1;
-    rc = h->phys.launch(h->stream, h->N, 0, nullptr, h->nj, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, (double*)dap, (int32_t*)drw,
-                        (uint8_t*)dsu, h->err);
+    const int rc = h->phys.launch(h->stream, h->N, 0, nullptr, h->nj, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, dap, drw, dsu, h->err);
     h->phys.force_reward = 0;
     if (rc) return rc;
-    if ((rc = h->out_end(4, agent_pos, sizeof(double) * N * h->nj))) return rc;
-    if ((rc = h->out_end(5, reward, sizeof(int32_t) * N))) return rc;
-    if ((rc = h->out_end(6, success, N))) return rc;
-    return h->finish();
+    return io.done();
 }
 
 int avsim_fk_jac(avsim_t* h, int arm, int n, const double* q, double* T, double* J) {
     if (!h || arm < 0 || arm > 2 || n <= 0 || !q) { if (h) h->set_error("avsim_fk_jac: bad arguments"); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
-    int nj = h->ik.arm[arm].n, rc;
-    const void* dq;
-    void *dT = nullptr, *dJ = nullptr;
-    if ((rc = h->in(0, q, sizeof(double) * n * nj, &dq))) return rc;
-    if (T && (rc = h->out_begin(1, T, sizeof(double) * n * 16, &dT))) return rc;
-    if (J && (rc = h->out_begin(2, J, sizeof(double) * n * 6 * nj, &dJ))) return rc;
+    const int nj = h->ik.arm[arm].n;
+    Call io(h);
+    const double* dq = io.in(q, sizeof(double) * n * nj);
+    double* dT = io.out(T, sizeof(double) * n * 16);
+    double* dJ = io.out(J, sizeof(double) * n * 6 * nj);
+    if (io.failed()) return AVSIM_EHIP;
     dim3 grid((n + 63) / 64);
-    if (nj == 6) hipLaunchKernelGGL(k_fk_jac<6>, grid, dim3(64), 0, h->stream, h->ik, arm, n, (const double*)dq, (double*)dT, (double*)dJ);
-    else hipLaunchKernelGGL(k_fk_jac<7>, grid, dim3(64), 0, h->stream, h->ik, arm, n, (const double*)dq, (double*)dT, (double*)dJ);
+    if (nj == 6) hipLaunchKernelGGL(k_fk_jac<6>, grid, dim3(64), 0, h->stream, h->ik, arm, n, dq, dT, dJ);
+    else hipLaunchKernelGGL(k_fk_jac<7>, grid, dim3(64), 0, h->stream, h->ik, arm, n, dq, dT, dJ);
     HIPCHK(h, hipGetLastError());
-    if ((rc = h->out_end(1, T, sizeof(double) * n * 16))) return rc;
-    if ((rc = h->out_end(2, J, sizeof(double) * n * 6 * nj))) return rc;
-    return h->finish();
+    return io.done();
 }
 
 int avsim_ik(avsim_t* h, int arm, int controller, int max_iters, int n, const double* q, const double* pos,
@@ -662,63 +571,56 @@ int avsim_ik(avsim_t* h, int arm, int controller, int max_iters, int n, const do
     }
     if (controller == 1 && arm == 2) { h->set_error("avsim_ik: GradIK is defined for the 6-DoF manipulators only"); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
-    int nj = h->ik.arm[arm].n, rc;
+    const int nj = h->ik.arm[arm].n;
     int iters = max_iters > 0 ? max_iters : (controller == 0 ? h->ik.diff_iters : h->ik.grad_iters);
-    const void *dq, *dp, *dqt;
-    void* dout;
-    if ((rc = h->in(0, q, sizeof(double) * n * nj, &dq))) return rc;
-    if ((rc = h->in(1, pos, sizeof(double) * n * 3, &dp))) return rc;
-    if ((rc = h->in(2, quat, sizeof(double) * n * 4, &dqt))) return rc;
-    if ((rc = h->out_begin(3, qout, sizeof(double) * n * nj, &dout))) return rc;
+    Call io(h);
+    const double* dq = io.in(q, sizeof(double) * n * nj);
+    const double* dp = io.in(pos, sizeof(double) * n * 3);
+    const double* dqt = io.in(quat, sizeof(double) * n * 4);
+    double* dout = io.out(qout, sizeof(double) * n * nj);
+    if (io.failed()) return AVSIM_EHIP;
     dim3 grid(controller == 1 ? (n + 3) / 4 : (n + 63) / 64);
-    if (nj == 6)
-        hipLaunchKernelGGL(k_ik<6>, grid, dim3(64), 0, h->stream, h->ik, arm, controller, iters, n, (const double*)dq, (const double*)dp,
-                           (const double*)dqt, (double*)dout);
-    else
-        hipLaunchKernelGGL(k_ik<7>, grid, dim3(64), 0, h->stream, h->ik, arm, controller, iters, n, (const double*)dq, (const double*)dp,
-                           (const double*)dqt, (double*)dout);
+    if (nj == 6) hipLaunchKernelGGL(k_ik<6>, grid, dim3(64), 0, h->stream, h->ik, arm, controller, iters, n, dq, dp, dqt, dout);
+    else hipLaunchKernelGGL(k_ik<7>, grid, dim3(64), 0, h->stream, h->ik, arm, controller, iters, n, dq, dp, dqt, dout);
     HIPCHK(h, hipGetLastError());
-    if ((rc = h->out_end(3, qout, sizeof(double) * n * nj))) return rc;
-    return h->finish();
+    return io.done();
 }
 
 }  // extern "C"
 
 template <typename real>
-static int reset_impl(avsim_t* h, const uint8_t* mask, const double* obj) {
-    int rc;
-    const void *dm = nullptr, *dobj;
-    if (mask && (rc = h->in(0, mask, h->N, &dm))) return rc;
-    if ((rc = h->in(1, obj, sizeof(double) * h->N * h->nobj * 7, &dobj))) return rc;
-    hipLaunchKernelGGL(k_reset<real>, dim3((h->N + 63) / 64), dim3(64), 0, h->stream, h->N, h->nq, h->nv, h->nu, h->nobj,
-                       (const unsigned char*)dm, (const double*)dobj, h->phys.d_qpos_home, h->phys.d_ctrl_home, h->phys.d_obj_qadr,
-                       (real*)h->d_qpos, (real*)h->d_qvel, (real*)h->d_ctrl, (real*)h->d_warm, h->d_latch, h->phys.d_obj_reset);
+static int reset_impl(avsim_t* h, Call& io, const uint8_t* mask, const double* obj) {
+    const uint8_t* dm = io.in(mask, h->N);
+    const double* dobj = io.in(obj, sizeof(double) * h->N * h->nobj * 7);
+    if (io.failed()) return AVSIM_EHIP;
+    hipLaunchKernelGGL(k_reset<real>, dim3((h->N + 63) / 64), dim3(64), 0, h->stream, h->N, h->nq, h->nv, h->nu, h->nobj, dm, dobj, h->phys.d_qpos_home,
+                       h->phys.d_ctrl_home, h->phys.d_obj_qadr, (real*)h->d_qpos, (real*)h->d_qvel, (real*)h->d_ctrl, (real*)h->d_warm, h->d_latch,
+                       h->phys.d_obj_reset);
     HIPCHK(h, hipGetLastError());
     // mj_forward (env.py:244, 538): refresh kinematics + contacts of the new state, no time stepping
-    if ((rc = h->phys.launch(h->stream, h->N, 0, nullptr, h->nj, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, nullptr, nullptr,
-                             nullptr, h->err)))
+    if (int rc = h->phys.launch(h->stream, h->N, 0, nullptr, h->nj, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, nullptr, nullptr, nullptr, h->err))
         return rc;
-    return h->finish();
+    return io.done();
+}
+
+// avsim_reset; avsim_create brings the envs to the model's default pose through it, from a host array whatever the handle's I/O mode
+static int reset_from(avsim_t* h, bool device_mode, const uint8_t* mask, const double* obj_qpos) {
+    AVS_ON_DEVICE(h);
+    AVS_PHYS_GATE(h);
+    h->state_ver++;
+    Call io(h, device_mode);
+    return h->f64 ? reset_impl<double>(h, io, mask, obj_qpos) : reset_impl<float>(h, io, mask, obj_qpos);
 }
 
 extern "C" {
 
 int avsim_reset(avsim_t* h, const uint8_t* mask, const double* obj_qpos) {
     if (!h || !obj_qpos) { if (h) h->set_error("avsim_reset: obj_qpos is required"); return AVSIM_EINVAL; }
-    AVS_ON_DEVICE(h);
-    AVS_PHYS_GATE(h);
-    h->state_ver++;
-    return h->f64 ? reset_impl<double>(h, mask, obj_qpos) : reset_impl<float>(h, mask, obj_qpos);
+    return reset_from(h, h->io_device, mask, obj_qpos);
 }
 
-static int step_common(avsim_t* h, const float* d_action, int nsub, double* agent_pos, int32_t* reward, uint8_t* success) {
-    int rc;
-    h->state_ver++;
-    void *dap = nullptr, *drw = nullptr, *dsu = nullptr;
-    size_t N = h->N;
-    if (agent_pos && (rc = h->out_begin(4, agent_pos, sizeof(double) * N * h->nj, &dap))) return rc;
-    if (reward && (rc = h->out_begin(5, reward, sizeof(int32_t) * N, &drw))) return rc;
-    if (success && (rc = h->out_begin(6, success, N, &dsu))) return rc;
+// the physics launch of the steps, between its pair of timing events.  Device pointers all: the callers stage, and finish, round it
+static int step_common(avsim_t* h, const float* d_action, int nsub, double* dap, int32_t* drw, uint8_t* dsu) {
     if (h->ktiming) {
         if (h->kev_used >= 2 * EV_RING) {      // fold the recorded pairs into the running sum (waits for the newest of them: once per EV_RING launches)
             for (size_t i = 0; i + 1 < h->kev_used; i += 2) {
@@ -733,34 +635,41 @@ static int step_common(avsim_t* h, const float* d_action, int nsub, double* agen
         while (h->kev.size() < h->kev_used + 2) { hipEvent_t e; HIPCHK(h, hipEventCreate(&e)); h->kev.push_back(e); }
         HIPCHK(h, hipEventRecord(h->kev[h->kev_used], h->stream));
     }
-    if ((rc = h->phys.launch(h->stream, h->N, nsub, d_action, h->nj, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, (double*)dap,
-                             (int32_t*)drw, (uint8_t*)dsu, h->err)))
-        return rc;
+    if (int rc = h->phys.launch(h->stream, h->N, nsub, d_action, h->nj, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, dap, drw, dsu, h->err)) return rc;
     if (h->ktiming) {
         HIPCHK(h, hipEventRecord(h->kev[h->kev_used + 1], h->stream));
         h->kev_used += 2;
     }
-    if ((rc = h->out_end(4, agent_pos, sizeof(double) * N * h->nj))) return rc;
-    if ((rc = h->out_end(5, reward, sizeof(int32_t) * N))) return rc;
-    if ((rc = h->out_end(6, success, N))) return rc;
-    return h->finish();
+    return AVSIM_OK;
+}
+// ... with the three outputs every step has staged in front of it and brought back behind it
+static int step_staged(avsim_t* h, Call& io, const float* d_action, int nsub, double* agent_pos, int32_t* reward, uint8_t* success) {
+    h->state_ver++;
+    const size_t N = h->N;
+    double* dap = io.out(agent_pos, sizeof(double) * N * h->nj);
+    int32_t* drw = io.out(reward, sizeof(int32_t) * N);
+    uint8_t* dsu = io.out(success, N);
+    if (io.failed()) return AVSIM_EHIP;
+    if (int rc = step_common(h, d_action, nsub, dap, drw, dsu)) return rc;
+    return io.done();
 }
 
 int avsim_step(avsim_t* h, const float* action, int nsub, double* agent_pos, int32_t* reward, uint8_t* success) {
     if (!h || !action || nsub < 0) { if (h) h->set_error("avsim_step: bad arguments"); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
     AVS_PHYS_GATE(h);
-    const void* da;
-    int rc;
-    if ((rc = h->in(0, action, sizeof(float) * h->N * h->nj, &da))) return rc;
-    return step_common(h, (const float*)da, nsub, agent_pos, reward, success);
+    Call io(h);
+    const float* da = io.in(action, sizeof(float) * h->N * h->nj);
+    if (io.failed()) return AVSIM_EHIP;
+    return step_staged(h, io, da, nsub, agent_pos, reward, success);
 }
 
 int avsim_step_ctrl(avsim_t* h, int nsub, double* agent_pos, int32_t* reward, uint8_t* success) {
     if (!h || nsub < 0) { if (h) h->set_error("avsim_step_ctrl: bad arguments"); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
     AVS_PHYS_GATE(h);
-    return step_common(h, nullptr, nsub, agent_pos, reward, success);
+    Call io(h);
+    return step_staged(h, io, nullptr, nsub, agent_pos, reward, success);
 }
 
 int avsim_step_cartesian(avsim_t* h, const double* action23, int ik_mode, int nsub, double* agent_pos, int32_t* reward,
@@ -772,61 +681,58 @@ int avsim_step_cartesian(avsim_t* h, const double* action23, int ik_mode, int ns
     if (h->num_arms != 3) { h->set_error("avsim_step_cartesian: the 23-D Cartesian action drives three arms (sim_env.py:277-282)"); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
     AVS_PHYS_GATE(h);
-    const void* da;
-    int rc;
-    if ((rc = h->in(0, action23, sizeof(double) * h->N * 23, &da))) return rc;
+    Call io(h);
+    const double* da = io.in(action23, sizeof(double) * h->N * 23);
+    if (io.failed()) return AVSIM_EHIP;
     auto launch = [&](dim3 grid, int arm0) {
         if (h->f64)
-            hipLaunchKernelGGL(k_cart_ctrl<double>, grid, dim3(64), 0, h->stream, h->ik, ik_mode, arm0, h->N, h->nq, h->nu, (const double*)da,
+            hipLaunchKernelGGL(k_cart_ctrl<double>, grid, dim3(64), 0, h->stream, h->ik, ik_mode, arm0, h->N, h->nq, h->nu, da,
                                (const double*)h->d_qpos, (double*)h->d_ctrl);
         else
-            hipLaunchKernelGGL(k_cart_ctrl<float>, grid, dim3(64), 0, h->stream, h->ik, ik_mode, arm0, h->N, h->nq, h->nu, (const double*)da,
+            hipLaunchKernelGGL(k_cart_ctrl<float>, grid, dim3(64), 0, h->stream, h->ik, ik_mode, arm0, h->N, h->nq, h->nu, da,
                                (const float*)h->d_qpos, (float*)h->d_ctrl);
     };
     if (ik_mode == AVSIM_IK_DLS) launch(dim3((h->N + 63) / 64, 3), 0);
     else {
         // GradIK on the two manipulators: 16 lanes per env
-        if (h->f64) hipLaunchKernelGGL(k_gradik_ctrl<double>, dim3((h->N + 3) / 4, 2), dim3(64), 0, h->stream, h->ik, h->N, h->nq, h->nu, (const double*)da, (const double*)h->d_qpos, (double*)h->d_ctrl);
-        else hipLaunchKernelGGL(k_gradik_ctrl<float>, dim3((h->N + 3) / 4, 2), dim3(64), 0, h->stream, h->ik, h->N, h->nq, h->nu, (const double*)da, (const float*)h->d_qpos, (float*)h->d_ctrl);
+        if (h->f64) hipLaunchKernelGGL(k_gradik_ctrl<double>, dim3((h->N + 3) / 4, 2), dim3(64), 0, h->stream, h->ik, h->N, h->nq, h->nu, da, (const double*)h->d_qpos, (double*)h->d_ctrl);
+        else hipLaunchKernelGGL(k_gradik_ctrl<float>, dim3((h->N + 3) / 4, 2), dim3(64), 0, h->stream, h->ik, h->N, h->nq, h->nu, da, (const float*)h->d_qpos, (float*)h->d_ctrl);
         launch(dim3((h->N + 63) / 64, 1), 2);     // DiffIK on the camera arm: one env per lane
     }
     HIPCHK(h, hipGetLastError());
-    return step_common(h, nullptr, nsub, agent_pos, reward, success);
+    return step_staged(h, io, nullptr, nsub, agent_pos, reward, success);
 }
 
 // ---- state access --------------------------------------------------------------------------------
-static int put(avsim_t* h, int slot, const double* src, void* dst, size_t n) {
-    if (!src) return 0;
-    const void* d;
-    int rc;
-    if ((rc = h->in(slot, src, sizeof(double) * n, &d))) return rc;
+// one state array in / out, converted to / from the handle's real.  A null array is left out; so is everything after a failure, which the caller's
+// io.done() reports
+static void put(avsim_t* h, Call& io, const double* src, void* dst, size_t n) {
+    const double* d = io.in(src, sizeof(double) * n);
+    if (!d) return;
     unsigned g = (unsigned)((n + 255) / 256);
-    if (h->f64) hipLaunchKernelGGL((k_convert<double, double>), dim3(g), dim3(256), 0, h->stream, n, (const double*)d, (double*)dst);
-    else hipLaunchKernelGGL((k_convert<double, float>), dim3(g), dim3(256), 0, h->stream, n, (const double*)d, (float*)dst);
-    return 0;
+    if (h->f64) hipLaunchKernelGGL((k_convert<double, double>), dim3(g), dim3(256), 0, h->stream, n, d, (double*)dst);
+    else hipLaunchKernelGGL((k_convert<double, float>), dim3(g), dim3(256), 0, h->stream, n, d, (float*)dst);
 }
-static int get(avsim_t* h, int slot, double* dst, const void* src, size_t n) {
-    if (!dst) return 0;
-    void* d;
-    int rc;
-    if ((rc = h->out_begin(slot, dst, sizeof(double) * n, &d))) return rc;
+static void get(avsim_t* h, Call& io, double* dst, const void* src, size_t n) {
+    double* d = io.out(dst, sizeof(double) * n);
+    if (!d) return;
     unsigned g = (unsigned)((n + 255) / 256);
-    if (h->f64) hipLaunchKernelGGL((k_convert<double, double>), dim3(g), dim3(256), 0, h->stream, n, (const double*)src, (double*)d);
-    else hipLaunchKernelGGL((k_convert<float, double>), dim3(g), dim3(256), 0, h->stream, n, (const float*)src, (double*)d);
-    return h->out_end(slot, dst, sizeof(double) * n);
+    if (h->f64) hipLaunchKernelGGL((k_convert<double, double>), dim3(g), dim3(256), 0, h->stream, n, (const double*)src, d);
+    else hipLaunchKernelGGL((k_convert<float, double>), dim3(g), dim3(256), 0, h->stream, n, (const float*)src, d);
 }
 
 int avsim_get_state(avsim_t* h, double* qpos, double* qvel, double* ctrl, double* warm) {
     if (!h) return AVSIM_EINVAL;
     AVS_ON_DEVICE(h);
     size_t N = h->N;
-    int rc;
-    if ((rc = get(h, 0, qpos, h->d_qpos, N * h->nq))) return rc;
-    if ((rc = get(h, 1, qvel, h->d_qvel, N * h->nv))) return rc;
-    if ((rc = get(h, 2, ctrl, h->d_ctrl, N * h->nu))) return rc;
-    if ((rc = get(h, 3, warm, h->d_warm, N * h->nv))) return rc;
+    Call io(h);
+    get(h, io, qpos, h->d_qpos, N * h->nq);
+    get(h, io, qvel, h->d_qvel, N * h->nv);
+    get(h, io, ctrl, h->d_ctrl, N * h->nu);
+    get(h, io, warm, h->d_warm, N * h->nv);
+    if (io.failed()) return AVSIM_EHIP;
     HIPCHK(h, hipGetLastError());
-    return h->finish();
+    return io.done();
 }
 
 int avsim_set_state(avsim_t* h, const double* qpos, const double* qvel, const double* ctrl, const double* warm) {
@@ -835,30 +741,30 @@ int avsim_set_state(avsim_t* h, const double* qpos, const double* qvel, const do
     AVS_PHYS_GATE(h);
     h->state_ver++;
     size_t N = h->N;
-    int rc;
-    if ((rc = put(h, 0, qpos, h->d_qpos, N * h->nq))) return rc;
-    if ((rc = put(h, 1, qvel, h->d_qvel, N * h->nv))) return rc;
-    if ((rc = put(h, 2, ctrl, h->d_ctrl, N * h->nu))) return rc;
-    if ((rc = put(h, 3, warm, h->d_warm, N * h->nv))) return rc;
+    Call io(h);
+    put(h, io, qpos, h->d_qpos, N * h->nq);
+    put(h, io, qvel, h->d_qvel, N * h->nv);
+    put(h, io, ctrl, h->d_ctrl, N * h->nu);
+    put(h, io, warm, h->d_warm, N * h->nv);
+    if (io.failed()) return AVSIM_EHIP;
     HIPCHK(h, hipGetLastError());
-    if ((rc = h->phys.launch(h->stream, h->N, 0, nullptr, h->nj, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, nullptr, nullptr,
-                             nullptr, h->err)))
+    if (int rc = h->phys.launch(h->stream, h->N, 0, nullptr, h->nj, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, nullptr, nullptr, nullptr, h->err))
         return rc;
-    return h->finish();
+    return io.done();
 }
 
 int avsim_get_latch(avsim_t* h, int32_t* latch) {
     if (!h || !latch) return AVSIM_EINVAL;
     AVS_ON_DEVICE(h);
     HIPCHK(h, hipMemcpyAsync(latch, h->d_latch, sizeof(int32_t) * (size_t)h->N, h->io_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
-    return h->finish();
+    return Call(h).done();
 }
 
 int avsim_set_latch(avsim_t* h, const int32_t* latch) {
     if (!h || !latch) return AVSIM_EINVAL;
     AVS_ON_DEVICE(h);
     HIPCHK(h, hipMemcpyAsync(h->d_latch, latch, sizeof(int32_t) * (size_t)h->N, h->io_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-    return h->finish();
+    return Call(h).done();
 }
 
 // The object poses a diverged env falls back to (mj_checkPos-style reset): written by avsim_reset; state next to the
@@ -867,14 +773,14 @@ int avsim_get_reset_poses(avsim_t* h, double* obj_qpos) {
     if (!h || !obj_qpos) return AVSIM_EINVAL;
     AVS_ON_DEVICE(h);
     HIPCHK(h, hipMemcpyAsync(obj_qpos, h->phys.d_obj_reset, sizeof(double) * (size_t)h->N * h->nobj * 7, h->io_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
-    return h->finish();
+    return Call(h).done();
 }
 
 int avsim_set_reset_poses(avsim_t* h, const double* obj_qpos) {
     if (!h || !obj_qpos) return AVSIM_EINVAL;
     AVS_ON_DEVICE(h);
     HIPCHK(h, hipMemcpyAsync(h->phys.d_obj_reset, obj_qpos, sizeof(double) * (size_t)h->N * h->nobj * 7, h->io_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-    return h->finish();
+    return Call(h).done();
 }
 
 int avsim_set_qpos(avsim_t* h, const double* qpos) {
@@ -953,13 +859,11 @@ static int render_images(avsim_t* h, const int32_t* cam_ids, int ncam, int heigh
     if (!h || !cam_ids || !out) { if (h) h->set_error("%s: bad arguments", who); return AVSIM_EINVAL; }
     if (f32 && !(h->vis.loaded && !h->render_proxies)) { h->set_error("avsim_render_rgb_f32 draws the visual scene only (avsim_load_visual, render_proxies 0)"); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
-    int rc;
-    void* dout = nullptr;
-    const size_t bytes = (f32 ? 3 * sizeof(float) : rgb ? 3 : sizeof(float)) * (size_t)h->N * ncam * height * width;
-    if ((rc = h->out_begin(7, out, bytes, &dout))) return rc;
-    if ((rc = render_to(h, cam_ids, ncam, height, width, dout, rgb, f32))) return rc;
-    if ((rc = h->out_end(7, out, bytes))) return rc;
-    return h->finish();
+    Call io(h);
+    void* dout = io.out(out, (f32 ? 3 * sizeof(float) : rgb ? 3 : sizeof(float)) * (size_t)h->N * ncam * height * width);
+    if (io.failed()) return AVSIM_EHIP;
+    if (int rc = render_to(h, cam_ids, ncam, height, width, dout, rgb, f32)) return rc;
+    return io.done();
 }
 int avsim_render_depth(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, float* out) {
     return render_images(h, cam_ids, ncam, height, width, out, false);
@@ -974,7 +878,6 @@ int avsim_render_rgb_f32(avsim_t* h, const int32_t* cam_ids, int ncam, int heigh
 }
 
 // ---- point clouds from depth images (av_aloha_amd/pointcloud.py is the specification; the kernels: csrc/avsim_pointcloud.hip, a unit of its own flags)
-enum PcSlot { PC_DEPTH = 8, PC_XYZ = 10, PC_INDEX = 11, PC_COUNT = 12 };
 static PcModel pc_model(const avsim_t* h) {
     const RenderModel& m = h->render.m;
     return PcModel{h->render.d_xpose, m.cam_body, m.cam_pos, m.cam_mat, m.cam_fovy, m.nbody};
@@ -989,14 +892,12 @@ int avsim_camera_poses(avsim_t* h, const int32_t* cam_ids, int ncam, float* out)
     }
     c.ncam = ncam;
     AVS_ON_DEVICE(h);
-    int rc;
-    void* dout = nullptr;
-    const size_t bytes = sizeof(float) * PC_POSE_W * (size_t)h->N * ncam;
-    if ((rc = h->out_begin(PC_XYZ, out, bytes, &dout))) return rc;
-    if ((rc = refresh_xpose(h))) return rc;
-    if (pointcloud_poses_launch(h->stream, pc_model(h), c, 0, h->N, (float*)dout, h->err)) return AVSIM_EHIP;
-    if ((rc = h->out_end(PC_XYZ, out, bytes))) return rc;
-    return h->finish();
+    Call io(h);
+    float* dout = io.out(out, sizeof(float) * PC_POSE_W * (size_t)h->N * ncam);
+    if (io.failed()) return AVSIM_EHIP;
+    if (int rc = refresh_xpose(h)) return rc;
+    if (pointcloud_poses_launch(h->stream, pc_model(h), c, 0, h->N, dout, h->err)) return AVSIM_EHIP;
+    return io.done();
 }
 
 int avsim_point_cloud(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, const float* depth, const float* bounds, float max_depth, int npoints, float* xyz,
@@ -1012,24 +913,19 @@ int avsim_point_cloud(avsim_t* h, const int32_t* cam_ids, int ncam, int height, 
     c.ncam = ncam; c.H = height; c.W = width; c.P = npoints; c.max_depth = max_depth;
     for (int k = 0; k < 3; k++) { c.lo[k] = bounds[k]; c.hi[k] = bounds[3 + k]; }
     AVS_ON_DEVICE(h);
-    int rc;
-    const void* ddepth = nullptr;
-    void *dxyz = nullptr, *dindex = nullptr, *dcount = nullptr;
-    const size_t N = (size_t)h->N, bxyz = sizeof(float) * 3 * N * npoints, bindex = sizeof(int32_t) * N * npoints, bcount = sizeof(int32_t) * 2 * N;
-    if ((rc = h->in(PC_DEPTH, depth, sizeof(float) * N * ncam * height * width, &ddepth))) return rc;
-    if ((rc = h->out_begin(PC_XYZ, xyz, bxyz, &dxyz))) return rc;
-    if ((rc = h->out_begin(PC_INDEX, index, bindex, &dindex))) return rc;
-    if ((rc = h->out_begin(PC_COUNT, count, bcount, &dcount))) return rc;
-    if ((rc = refresh_xpose(h))) return rc;
-    if (h->pointcloud.run(h->stream, pc_model(h), c, h->N, (const float*)ddepth, (float*)dxyz, (int*)dindex, (int*)dcount, h->err)) return AVSIM_EHIP;
-    if ((rc = h->out_end(PC_XYZ, xyz, bxyz))) return rc;
-    if ((rc = h->out_end(PC_INDEX, index, bindex))) return rc;
-    if ((rc = h->out_end(PC_COUNT, count, bcount))) return rc;
-    return h->finish();
+    Call io(h);
+    const size_t N = (size_t)h->N;
+    const float* ddepth = io.in(depth, sizeof(float) * N * ncam * height * width);
+    float* dxyz = io.out(xyz, sizeof(float) * 3 * N * npoints);
+    int32_t* dindex = io.out(index, sizeof(int32_t) * N * npoints);
+    int32_t* dcount = io.out(count, sizeof(int32_t) * 2 * N);
+    if (io.failed()) return AVSIM_EHIP;
+    if (int rc = refresh_xpose(h)) return rc;
+    if (h->pointcloud.run(h->stream, pc_model(h), c, h->N, ddepth, dxyz, dindex, dcount, h->err)) return AVSIM_EHIP;
+    return io.done();
 }
 
 // ---- voxel grids from depth (and colour) images (av_aloha_amd/voxel.py is the specification; the kernels: csrc/avsim_pointcloud.hip, below the cloud's)
-enum VoxSlot { VOX_DEPTH = 8, VOX_RGB = 9, VOX_OUT = 10 };
 int avsim_voxel_grid(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, const float* depth, const uint8_t* rgb, const float* bounds, float max_depth,
                      const int32_t* grid, float* out) {
     if (!h) return AVSIM_EINVAL;
@@ -1044,30 +940,26 @@ int avsim_voxel_grid(avsim_t* h, const int32_t* cam_ids, int ncam, int height, i
     c.pc.ncam = ncam; c.pc.H = height; c.pc.W = width; c.pc.P = 0; c.pc.max_depth = max_depth;
     for (int k = 0; k < 3; k++) { c.pc.lo[k] = bounds[k]; c.pc.hi[k] = bounds[3 + k]; c.g[k] = grid[k]; }
     AVS_ON_DEVICE(h);
-    int rc;
-    const void *ddepth = nullptr, *drgb = nullptr;
-    void* dout = nullptr;
-    const size_t N = (size_t)h->N, q = (size_t)ncam * height * width, cell_floats = (size_t)grid[0] * grid[1] * grid[2] * VOX_CHANNELS, bout = sizeof(float) * N * cell_floats;
-    if ((rc = h->in(VOX_DEPTH, depth, sizeof(float) * N * q, &ddepth))) return rc;
-    if (rgb && (rc = h->in(VOX_RGB, rgb, 3 * N * q, &drgb))) return rc;
-    if ((rc = h->out_begin(VOX_OUT, out, bout, &dout))) return rc;
-    if ((rc = refresh_xpose(h))) return rc;
+    Call io(h);
+    const size_t N = (size_t)h->N, q = (size_t)ncam * height * width, cell_floats = (size_t)grid[0] * grid[1] * grid[2] * VOX_CHANNELS;
+    const float* ddepth = io.in(depth, sizeof(float) * N * q);
+    const uint8_t* drgb = io.in(rgb, 3 * N * q);
+    float* dout = io.out(out, sizeof(float) * N * cell_floats);
+    if (io.failed()) return AVSIM_EHIP;
+    if (int rc = refresh_xpose(h)) return rc;
     const int chunk = h->N < PC_ENV_CHUNK ? h->N : PC_ENV_CHUNK;
     if (h->pointcloud.reserve_poses(chunk, ncam, h->err)) return AVSIM_EHIP;
     for (int e0 = 0; e0 < h->N; e0 += chunk) {          // envs in chunks, as PcHost::run: the pose scratch is a chunk's
         const int n = h->N - e0 < chunk ? h->N - e0 : chunk;
         if (pointcloud_poses_launch(h->stream, pc_model(h), c.pc, e0, n, h->pointcloud.d_pose, h->err)) return AVSIM_EHIP;
-        if (voxel_launch(h->stream, c, n, (const float*)ddepth + (size_t)e0 * q, drgb ? (const uint8_t*)drgb + (size_t)e0 * q * 3 : nullptr, h->pointcloud.d_pose,
-                         (float*)dout + (size_t)e0 * cell_floats, (AVSIM_VOXEL_MERGE != 0) != h->voxel_other_form, h->err))
+        if (voxel_launch(h->stream, c, n, ddepth + (size_t)e0 * q, drgb ? drgb + (size_t)e0 * q * 3 : nullptr, h->pointcloud.d_pose, dout + (size_t)e0 * cell_floats,
+                         (AVSIM_VOXEL_MERGE != 0) != h->voxel_other_form, h->err))
             return AVSIM_EHIP;
     }
-    if ((rc = h->out_end(VOX_OUT, out, bout))) return rc;
-    return h->finish();
+    return io.done();
 }
 
-// ---- the image calls: what they share.  The staging slots (d_io) they use, by what a slot carries -- names that hold within the image calls
-// only: the episode calls further down use 8..11 for their own outputs
-enum ImgSlot { IMG_IN = 8, IMG_INDEX = 9, IMG_RESULT = 10, IMG_LEN_OUT = 11, IMG_LEN_IN = 12, IMG_TILE = 13 };
+// ---- the image calls: what they share
 // bytes per pixel of format 0 (u8 HWC) / 1 (float32 CHW)
 static size_t img_bpp(int fmt) { return fmt ? 12 : 3; }
 // refuses a format other than 0 / 1 and a size outside 1..65535, of the call's image and of its second one where it has two (a call whose
@@ -1110,16 +1002,14 @@ int avsim_jpeg_encode(avsim_t* h, const void* img, int fmt, const int32_t* index
     size_t rows;
     if ((rc = index_rows(h, "avsim_jpeg_encode", index, nimg, &rows))) return rc;
     AVS_ON_DEVICE(h);
-    const void *dimg = nullptr, *dindex = nullptr;
-    void *dout = nullptr, *dlen = nullptr;
-    if ((rc = h->in(IMG_IN, img, rows * (size_t)height * width * img_bpp(fmt), &dimg))) return rc;
-    if (index && (rc = h->in(IMG_INDEX, index, sizeof(int32_t) * (size_t)nimg, &dindex))) return rc;
-    if ((rc = h->out_begin(IMG_RESULT, out, (size_t)nimg * stride, &dout))) return rc;
-    if ((rc = h->out_begin(IMG_LEN_OUT, out_len, sizeof(int32_t) * (size_t)nimg, &dlen))) return rc;
-    if ((rc = h->jpeg.launch(h->stream, dimg, fmt, (const int*)dindex, nimg, height, width, quality, (uint8_t*)dout, stride, (int*)dlen, h->err))) return AVSIM_EHIP;
-    if ((rc = h->out_end(IMG_RESULT, out, (size_t)nimg * stride))) return rc;
-    if ((rc = h->out_end(IMG_LEN_OUT, out_len, sizeof(int32_t) * (size_t)nimg))) return rc;
-    return h->finish();
+    Call io(h);
+    const void* dimg = io.in(img, rows * (size_t)height * width * img_bpp(fmt));
+    const int32_t* dindex = io.in(index, sizeof(int32_t) * (size_t)nimg);
+    uint8_t* dout = io.out(out, (size_t)nimg * stride);
+    int32_t* dlen = io.out(out_len, sizeof(int32_t) * (size_t)nimg);
+    if (io.failed()) return AVSIM_EHIP;
+    if (h->jpeg.launch(h->stream, dimg, fmt, dindex, nimg, height, width, quality, dout, stride, dlen, h->err)) return AVSIM_EHIP;
+    return io.done();
 }
 
 // avsim_render_rgb's visual-scene images as JPEG streams: rendered into a buffer of the library's and encoded from there, so that no pixel
@@ -1137,17 +1027,21 @@ int avsim_render_jpeg(avsim_t* h, const int32_t* cam_ids, int ncam, int height, 
     AVS_ON_DEVICE(h);
     const int nstream = tile ? h->N : h->N * ncam;
     const size_t bytes = (size_t)3 * h->N * ncam * height * width;
-    void *dimg = nullptr, *dtile = nullptr, *dout = nullptr, *dlen = nullptr;
-    if ((rc = h->io_buf(7, bytes, &dimg))) return rc;
+    Call io(h);
+    void* dimg = io.scratch(bytes);
+    if (io.failed()) return AVSIM_EHIP;
     if ((rc = render_to(h, cam_ids, ncam, height, width, dimg, true, false))) return rc;
     if (tile && ncam > 1) {
-        if ((rc = h->io_buf(IMG_TILE, bytes, &dtile))) return rc;
+        void* dtile = io.scratch(bytes);
+        if (io.failed()) return AVSIM_EHIP;
         if (jpeg_tile(h->stream, dimg, dtile, h->N, ncam, height, width, h->err)) return AVSIM_EHIP;
         dimg = dtile;
     }
-    if ((rc = h->out_begin(IMG_RESULT, out, (size_t)nstream * stride, &dout))) return rc;
-    if ((rc = h->out_begin(IMG_LEN_OUT, out_len, sizeof(int32_t) * (size_t)nstream, &dlen))) return rc;
-    if (h->jpeg.launch(h->stream, dimg, 0, nullptr, nstream, height, (int)iw, quality, (uint8_t*)dout, stride, (int*)dlen, h->err)) return AVSIM_EHIP;
+    // a host caller's streams and lengths come back below, not through io.done(): device copies of the call's own
+    uint8_t* dout = h->io_device ? out : (uint8_t*)io.scratch((size_t)nstream * stride);
+    int32_t* dlen = h->io_device ? out_len : (int32_t*)io.scratch(sizeof(int32_t) * (size_t)nstream);
+    if (io.failed()) return AVSIM_EHIP;
+    if (h->jpeg.launch(h->stream, dimg, 0, nullptr, nstream, height, (int)iw, quality, dout, stride, dlen, h->err)) return AVSIM_EHIP;
     if (h->io_device) return AVSIM_OK;
     HIPCHK(h, hipMemcpyAsync(out_len, dlen, sizeof(int32_t) * (size_t)nstream, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1155,7 +1049,7 @@ int avsim_render_jpeg(avsim_t* h, const int32_t* cam_ids, int ncam, int height, 
     for (int i = 0; i < nstream; i++) w = out_len[i] > w ? out_len[i] : w;
     w = w < stride ? w : stride;
     if (w > 0) HIPCHK(h, hipMemcpy2DAsync(out, (size_t)stride, dout, (size_t)stride, (size_t)w, (size_t)nstream, hipMemcpyDeviceToHost, h->stream));
-    return h->finish();
+    return io.done();
 }
 
 // ... and back: the streams of avsim_jpeg_encode -> images (av_aloha_amd/jpeg.py decode_reference is the specification)
@@ -1170,18 +1064,15 @@ int avsim_jpeg_decode(avsim_t* h, const uint8_t* in, int64_t stride, const int32
     size_t rows;
     if ((rc = index_rows(h, "avsim_jpeg_decode", index, nimg, &rows))) return rc;
     AVS_ON_DEVICE(h);
-    const void *din = nullptr, *dlen = nullptr, *dindex = nullptr;
-    void *dout = nullptr, *dstatus = nullptr;
-    const size_t bytes = (size_t)nimg * height * width * img_bpp(fmt);
-    if ((rc = h->in(IMG_IN, in, rows * (size_t)stride, &din))) return rc;
-    if ((rc = h->in(IMG_LEN_IN, in_len, sizeof(int32_t) * rows, &dlen))) return rc;
-    if (index && (rc = h->in(IMG_INDEX, index, sizeof(int32_t) * (size_t)nimg, &dindex))) return rc;
-    if ((rc = h->out_begin(IMG_RESULT, out, bytes, &dout))) return rc;
-    if ((rc = h->out_begin(IMG_LEN_OUT, status, sizeof(int32_t) * (size_t)nimg, &dstatus))) return rc;
-    if ((rc = h->jpegdec.launch(h->stream, (const uint8_t*)din, stride, (const int*)dlen, (const int*)dindex, nimg, height, width, fmt, upsample, dout, (int*)dstatus, h->err, h->jpegdec_events ? h->ev + 12 : nullptr))) return AVSIM_EHIP;
-    if ((rc = h->out_end(IMG_RESULT, out, bytes))) return rc;
-    if ((rc = h->out_end(IMG_LEN_OUT, status, sizeof(int32_t) * (size_t)nimg))) return rc;
-    return h->finish();
+    Call io(h);
+    const uint8_t* din = io.in(in, rows * (size_t)stride);
+    const int32_t* dlen = io.in(in_len, sizeof(int32_t) * rows);
+    const int32_t* dindex = io.in(index, sizeof(int32_t) * (size_t)nimg);
+    void* dout = io.out(out, (size_t)nimg * height * width * img_bpp(fmt));
+    int32_t* dstatus = io.out(status, sizeof(int32_t) * (size_t)nimg);
+    if (io.failed()) return AVSIM_EHIP;
+    if (h->jpegdec.launch(h->stream, din, stride, dlen, dindex, nimg, height, width, fmt, upsample, dout, dstatus, h->err, h->jpegdec_events ? h->ev + 12 : nullptr)) return AVSIM_EHIP;
+    return io.done();
 }
 
 // Camera views resampled into rectangles of a canvas and labelled there (av_aloha_amd/compose.py is the specification; csrc/avsim_compose.hip.h)
@@ -1196,16 +1087,14 @@ int avsim_compose(avsim_t* h, const void* src, int src_fmt, int nsrc, int src_h,
         if (ComposeHost::validate(nsrc, src_h, src_w, nout, canvas_h, canvas_w, places, nplace, why)) { h->set_error("%s", why.c_str()); return AVSIM_EINVAL; }
     }
     AVS_ON_DEVICE(h);
-    const void* dsrc = nullptr;
-    void* dcanvas = nullptr;
-    const size_t sbytes = (size_t)nsrc * src_h * src_w * img_bpp(src_fmt), cbytes = (size_t)nout * canvas_h * canvas_w * img_bpp(canvas_fmt);
-    if ((rc = h->in(IMG_IN, src, sbytes, &dsrc))) return rc;
-    if ((rc = h->out_begin(IMG_RESULT, canvas, cbytes, &dcanvas))) return rc;
-    if (!h->io_device && !clear) HIPCHK(h, hipMemcpyAsync(dcanvas, canvas, cbytes, hipMemcpyHostToDevice, h->stream));
+    Call io(h);
+    const size_t cbytes = (size_t)nout * canvas_h * canvas_w * img_bpp(canvas_fmt);
+    const void* dsrc = io.in(src, (size_t)nsrc * src_h * src_w * img_bpp(src_fmt));
+    void* dcanvas = clear ? io.out(canvas, cbytes) : io.inout(canvas, cbytes);          // (a canvas that is cleared first need not go up)
+    if (io.failed()) return AVSIM_EHIP;
     if ((rc = h->compose.launch(h->stream, dsrc, src_fmt, nsrc, src_h, src_w, dcanvas, canvas_fmt, nout, canvas_h, canvas_w, places, nplace, clear, clear_rgb, h->err)))
         return rc == -1 ? AVSIM_EINVAL : AVSIM_EHIP;
-    if ((rc = h->out_end(IMG_RESULT, canvas, cbytes))) return rc;
-    return h->finish();
+    return io.done();
 }
 
 int avsim_compose_label(avsim_t* h, void* canvas, int canvas_fmt, int nout, int canvas_h, int canvas_w, const int32_t* where, int nlabel, const char* prefix,
@@ -1216,16 +1105,13 @@ int avsim_compose_label(avsim_t* h, void* canvas, int canvas_fmt, int nout, int 
     if ((rc = img_args(h, "avsim_compose_label", canvas_fmt, canvas_h, canvas_w))) return rc;
     if (nlabel == 0) return AVSIM_OK;
     AVS_ON_DEVICE(h);
-    void* dcanvas = nullptr;
-    const void* dvalue = nullptr;
-    const size_t cbytes = (size_t)nout * canvas_h * canvas_w * img_bpp(canvas_fmt);
-    if ((rc = h->out_begin(IMG_RESULT, canvas, cbytes, &dcanvas))) return rc;
-    if (!h->io_device) HIPCHK(h, hipMemcpyAsync(dcanvas, canvas, cbytes, hipMemcpyHostToDevice, h->stream));
-    if (value && (rc = h->in(IMG_INDEX, value, sizeof(int64_t) * (size_t)nlabel, &dvalue))) return rc;
+    Call io(h);
+    void* dcanvas = io.inout(canvas, (size_t)nout * canvas_h * canvas_w * img_bpp(canvas_fmt));
+    const int64_t* dvalue = io.in(value, sizeof(int64_t) * (size_t)nlabel);
+    if (io.failed()) return AVSIM_EHIP;
     if ((rc = h->compose.label(h->stream, dcanvas, canvas_fmt, nout, canvas_h, canvas_w, where, nlabel, prefix, (const long long*)dvalue, rgb, h->err)))
         return rc == -1 ? AVSIM_EINVAL : AVSIM_EHIP;
-    if ((rc = h->out_end(IMG_RESULT, canvas, cbytes))) return rc;
-    return h->finish();
+    return io.done();
 }
 
 void avsim_compose_font(uint8_t rows[128][7]) {
@@ -1245,15 +1131,13 @@ int avsim_image_stats(avsim_t* h, const void* img, int fmt, const int32_t* index
     size_t rows;
     if ((rc = index_rows(h, "avsim_image_stats", index, nimg, &rows))) return rc;
     AVS_ON_DEVICE(h);
-    const void *dimg = nullptr, *dindex = nullptr;
-    void* dout = nullptr;
-    const size_t obytes = sizeof(uint64_t) * 12 * (size_t)nimg;
-    if ((rc = h->in(IMG_IN, img, rows * (size_t)height * width * img_bpp(fmt), &dimg))) return rc;
-    if (index && (rc = h->in(IMG_INDEX, index, sizeof(int32_t) * (size_t)nimg, &dindex))) return rc;
-    if ((rc = h->out_begin(IMG_RESULT, out, obytes, &dout))) return rc;
-    if (ImgPrepHost::stats(h->stream, dimg, fmt, (const int*)dindex, nimg, height, width, (unsigned long long*)dout, h->err)) return AVSIM_EHIP;
-    if ((rc = h->out_end(IMG_RESULT, out, obytes))) return rc;
-    return h->finish();
+    Call io(h);
+    const void* dimg = io.in(img, rows * (size_t)height * width * img_bpp(fmt));
+    const int32_t* dindex = io.in(index, sizeof(int32_t) * (size_t)nimg);
+    uint64_t* dout = io.out(out, sizeof(uint64_t) * 12 * (size_t)nimg);
+    if (io.failed()) return AVSIM_EHIP;
+    if (ImgPrepHost::stats(h->stream, dimg, fmt, dindex, nimg, height, width, (unsigned long long*)dout, h->err)) return AVSIM_EHIP;
+    return io.done();
 }
 
 int avsim_image_prep(avsim_t* h, const void* img, int fmt, int nsrc, int height, int width, const float* lut, int nlut, const int32_t* lut_index,
@@ -1267,15 +1151,13 @@ int avsim_image_prep(avsim_t* h, const void* img, int fmt, int nsrc, int height,
         if (ImgPrepHost::validate(nsrc, height, width, nlut, lut_index, box, nout, src_index, out_h, out_w, why)) { h->set_error("%s", why.c_str()); return AVSIM_EINVAL; }
     }
     AVS_ON_DEVICE(h);
-    const void *dimg = nullptr, *dlut = nullptr;
-    void* dout = nullptr;
-    const size_t obytes = sizeof(float) * 3 * (size_t)nout * out_h * out_w;
-    if ((rc = h->in(IMG_IN, img, (size_t)nsrc * height * width * img_bpp(fmt), &dimg))) return rc;
-    if ((rc = h->in(IMG_INDEX, lut, sizeof(float) * 768 * (size_t)nlut, &dlut))) return rc;
-    if ((rc = h->out_begin(IMG_RESULT, out, obytes, &dout))) return rc;
-    if (ImgPrepHost::launch(h->stage, h->stream, dimg, fmt, height, width, (const float*)dlut, lut_index, box, nout, src_index, out_h, out_w, (float*)dout, h->err)) return AVSIM_EHIP;
-    if ((rc = h->out_end(IMG_RESULT, out, obytes))) return rc;
-    return h->finish();
+    Call io(h);
+    const void* dimg = io.in(img, (size_t)nsrc * height * width * img_bpp(fmt));
+    const float* dlut = io.in(lut, sizeof(float) * 768 * (size_t)nlut);
+    float* dout = io.out(out, sizeof(float) * 3 * (size_t)nout * out_h * out_w);
+    if (io.failed()) return AVSIM_EHIP;
+    if (ImgPrepHost::launch(h->stage, h->stream, dimg, fmt, height, width, dlut, lut_index, box, nout, src_index, out_h, out_w, dout, h->err)) return AVSIM_EHIP;
+    return io.done();
 }
 
 // Colour and sharpness augmentation (av_aloha_amd/imgaug.py is the specification; the kernels: csrc/avsim_imgaug.hip, a unit of its own flags)
@@ -1290,14 +1172,12 @@ int avsim_image_jitter(avsim_t* h, const void* img, int nsrc, int height, int wi
         if (imgaug_validate(nsrc, height, width, box_mask, factor, src_index, nout, mean_std, out_h, out_w, why)) { h->set_error("%s", why.c_str()); return AVSIM_EINVAL; }
     }
     AVS_ON_DEVICE(h);
-    const void* dimg = nullptr;
-    void* dout = nullptr;
-    const size_t obytes = sizeof(float) * 3 * (size_t)nout * out_h * out_w;
-    if ((rc = h->in(IMG_IN, img, (size_t)nsrc * height * width * img_bpp(0), &dimg))) return rc;
-    if ((rc = h->out_begin(IMG_RESULT, out, obytes, &dout))) return rc;
-    if (h->imgaug.launch(h->stage, h->stream, dimg, height, width, box_mask, factor, src_index, nout, mean_std, out_h, out_w, (float*)dout, h->err)) return AVSIM_EHIP;
-    if ((rc = h->out_end(IMG_RESULT, out, obytes))) return rc;
-    return h->finish();
+    Call io(h);
+    const void* dimg = io.in(img, (size_t)nsrc * height * width * img_bpp(0));
+    float* dout = io.out(out, sizeof(float) * 3 * (size_t)nout * out_h * out_w);
+    if (io.failed()) return AVSIM_EHIP;
+    if (h->imgaug.launch(h->stage, h->stream, dimg, height, width, box_mask, factor, src_index, nout, mean_std, out_h, out_w, dout, h->err)) return AVSIM_EHIP;
+    return io.done();
 }
 
 // avsim_image_jitter with the geometric op, bit 5.  Without the bit anywhere: avsim_image_jitter's launches
@@ -1314,16 +1194,14 @@ int avsim_image_augment(avsim_t* h, const void* img, int nsrc, int height, int w
     bool any = false;
     for (int i = 0; i < nout && !any; i++) any = box_mask[4 * (size_t)i + 3] & IAG_AFFINE;
     AVS_ON_DEVICE(h);
-    const void* dimg = nullptr;
-    void* dout = nullptr;
-    const size_t obytes = sizeof(float) * 3 * (size_t)nout * out_h * out_w;
-    if ((rc = h->in(IMG_IN, img, (size_t)nsrc * height * width * img_bpp(0), &dimg))) return rc;
-    if ((rc = h->out_begin(IMG_RESULT, out, obytes, &dout))) return rc;
-    if (any ? h->imgaug.launch_affine(h->stage, h->stream, dimg, height, width, box_mask, factor, affine, interp, src_index, nout, mean_std, out_h, out_w, (float*)dout, h->err)
-            : h->imgaug.launch(h->stage, h->stream, dimg, height, width, box_mask, factor, src_index, nout, mean_std, out_h, out_w, (float*)dout, h->err))
+    Call io(h);
+    const void* dimg = io.in(img, (size_t)nsrc * height * width * img_bpp(0));
+    float* dout = io.out(out, sizeof(float) * 3 * (size_t)nout * out_h * out_w);
+    if (io.failed()) return AVSIM_EHIP;
+    if (any ? h->imgaug.launch_affine(h->stage, h->stream, dimg, height, width, box_mask, factor, affine, interp, src_index, nout, mean_std, out_h, out_w, dout, h->err)
+            : h->imgaug.launch(h->stage, h->stream, dimg, height, width, box_mask, factor, src_index, nout, mean_std, out_h, out_w, dout, h->err))
         return AVSIM_EHIP;
-    if ((rc = h->out_end(IMG_RESULT, out, obytes))) return rc;
-    return h->finish();
+    return io.done();
 }
 
 // Resizing into a rectangle of a padded output (av_aloha_amd/imgresize.py is the specification; the kernels: csrc/avsim_imgresize.hip, a unit of its own flags)
@@ -1338,14 +1216,12 @@ int avsim_image_resize(avsim_t* h, const void* img, int fmt, int nsrc, int heigh
         if (imgresize_validate(nsrc, height, width, src_box, dst, src_index, nout, antialias, fill, mean_std, out_h, out_w, why)) { h->set_error("%s", why.c_str()); return AVSIM_EINVAL; }
     }
     AVS_ON_DEVICE(h);
-    const void* dimg = nullptr;
-    void* dout = nullptr;
-    const size_t obytes = sizeof(float) * 3 * (size_t)nout * out_h * out_w;
-    if ((rc = h->in(IMG_IN, img, (size_t)nsrc * height * width * img_bpp(fmt), &dimg))) return rc;
-    if ((rc = h->out_begin(IMG_RESULT, out, obytes, &dout))) return rc;
-    if (imgresize_run(h->stage, h->stream, dimg, fmt, height, width, src_box, dst, src_index, nout, antialias, fill, mean_std, out_h, out_w, (float*)dout, h->err)) return AVSIM_EHIP;
-    if ((rc = h->out_end(IMG_RESULT, out, obytes))) return rc;
-    return h->finish();
+    Call io(h);
+    const void* dimg = io.in(img, (size_t)nsrc * height * width * img_bpp(fmt));
+    float* dout = io.out(out, sizeof(float) * 3 * (size_t)nout * out_h * out_w);
+    if (io.failed()) return AVSIM_EHIP;
+    if (imgresize_run(h->stage, h->stream, dimg, fmt, height, width, src_box, dst, src_index, nout, antialias, fill, mean_std, out_h, out_w, dout, h->err)) return AVSIM_EHIP;
+    return io.done();
 }
 
 int avsim_image_jitter_sums(avsim_t* h, uint64_t* sums, int nout) {
@@ -1433,11 +1309,6 @@ static int ep_alloc(avsim_t* h, size_t bytes, void** p) {
     h->ep_allocs.push_back(*p);
     return 0;
 }
-// an output of the episode calls: the caller's pointer (staged in host-pointer mode), or the handle's own buffer when it is NULL
-static int ep_out(avsim_t* h, int slot, void* p, size_t bytes, void* own, void** dev) {
-    if (!p) { *dev = own; return 0; }
-    return h->out_begin(slot, p, bytes, dev);
-}
 
 template <typename real>
 static void ep_launch(avsim_t* h, int mode, const uint8_t* mask, double* ap, int* rw, uint8_t* su, uint8_t* te, uint8_t* tr, int64_t* id, int* el) {
@@ -1494,7 +1365,7 @@ int avsim_episode_setup(avsim_t* h, const double* box, const int32_t* share, uin
         HIPCHK(h, hipMemsetAsync(A.log_obj, 0, sizeof(double) * L * no * 7, h->stream));
     }
     h->ep_ready = true;
-    return h->finish();
+    return Call(h).done();
 }
 
 int avsim_sample_poses(avsim_t* h, uint64_t seed, int n, const int64_t* episode_id, double* obj_qpos) {
@@ -1502,16 +1373,13 @@ int avsim_sample_poses(avsim_t* h, uint64_t seed, int n, const int64_t* episode_
     if (!h->ep_ready) { h->set_error("avsim_sample_poses: call avsim_episode_setup first"); return AVSIM_EINVAL; }
     if (n == 0) return AVSIM_OK;
     AVS_ON_DEVICE(h);
-    int rc;
-    const void* did;
-    void* dout;
-    const size_t ob = sizeof(double) * (size_t)n * h->nobj * 7;
-    if ((rc = h->in(0, episode_id, sizeof(int64_t) * (size_t)n, &did))) return rc;
-    if ((rc = h->out_begin(1, obj_qpos, ob, &dout))) return rc;
-    hipLaunchKernelGGL(k_sample_poses, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->ep, seed, n, (const int64_t*)did, (double*)dout);
+    Call io(h);
+    const int64_t* did = io.in(episode_id, sizeof(int64_t) * (size_t)n);
+    double* dout = io.out(obj_qpos, sizeof(double) * (size_t)n * h->nobj * 7);
+    if (io.failed()) return AVSIM_EHIP;
+    hipLaunchKernelGGL(k_sample_poses, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->ep, seed, n, did, dout);
     HIPCHK(h, hipGetLastError());
-    if ((rc = h->out_end(1, obj_qpos, ob))) return rc;
-    return h->finish();
+    return io.done();
 }
 
 int avsim_episode_reset(avsim_t* h, const uint8_t* mask, double* agent_pos, int64_t* episode_id) {
@@ -1520,18 +1388,16 @@ int avsim_episode_reset(avsim_t* h, const uint8_t* mask, double* agent_pos, int6
     AVS_ON_DEVICE(h);
     h->state_ver++;
     const size_t N = h->N;
-    int rc;
-    const void* dm = nullptr;
-    void *dap, *did;
-    if (mask && (rc = h->in(0, mask, N, &dm))) return rc;
-    if ((rc = ep_out(h, 4, agent_pos, sizeof(double) * N * h->nj, h->ep_ap, &dap))) return rc;
-    if ((rc = ep_out(h, 8, episode_id, sizeof(int64_t) * N, h->ep_id, &did))) return rc;
-    if (h->f64) ep_launch<double>(h, 0, (const uint8_t*)dm, (double*)dap, nullptr, nullptr, nullptr, nullptr, (int64_t*)did, nullptr);
-    else ep_launch<float>(h, 0, (const uint8_t*)dm, (double*)dap, nullptr, nullptr, nullptr, nullptr, (int64_t*)did, nullptr);
+    Call io(h);
+    const uint8_t* dm = io.in(mask, N);
+    // (an output nobody asked for goes to the handle's own buffer: the kernel writes them all)
+    double* dap = io.out(agent_pos, sizeof(double) * N * h->nj, h->ep_ap);
+    int64_t* did = io.out(episode_id, sizeof(int64_t) * N, h->ep_id);
+    if (io.failed()) return AVSIM_EHIP;
+    if (h->f64) ep_launch<double>(h, 0, dm, dap, nullptr, nullptr, nullptr, nullptr, did, nullptr);
+    else ep_launch<float>(h, 0, dm, dap, nullptr, nullptr, nullptr, nullptr, did, nullptr);
     HIPCHK(h, hipGetLastError());
-    if ((rc = h->out_end(4, agent_pos, sizeof(double) * N * h->nj))) return rc;
-    if ((rc = h->out_end(8, episode_id, sizeof(int64_t) * N))) return rc;
-    return h->finish();
+    return io.done();
 }
 
 int avsim_episode_step(avsim_t* h, const float* action, int nsub, double* agent_pos, int32_t* reward, uint8_t* success, uint8_t* terminated,
@@ -1540,34 +1406,23 @@ int avsim_episode_step(avsim_t* h, const float* action, int nsub, double* agent_
     if (!h->ep_ready) { h->set_error("avsim_episode_step: call avsim_episode_setup first"); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
     const size_t N = h->N;
-    int rc;
-    const void* da;
-    void *dap, *drw, *dsu, *dte, *dtr, *did, *del;
-    if ((rc = h->in(0, action, sizeof(float) * N * h->nj, &da))) return rc;
-    if ((rc = ep_out(h, 4, agent_pos, sizeof(double) * N * h->nj, h->ep_ap, &dap))) return rc;
-    if ((rc = ep_out(h, 5, reward, sizeof(int32_t) * N, h->ep_rw, &drw))) return rc;
-    if ((rc = ep_out(h, 6, success, N, h->ep_su, &dsu))) return rc;
-    if ((rc = ep_out(h, 8, terminated, N, h->ep_te, &dte))) return rc;
-    if ((rc = ep_out(h, 9, truncated, N, h->ep_tr, &dtr))) return rc;
-    if ((rc = ep_out(h, 10, episode_id, sizeof(int64_t) * N, h->ep_id, &did))) return rc;
-    if ((rc = ep_out(h, 11, elapsed, sizeof(int32_t) * N, h->ep_el, &del))) return rc;
-    // the physics launch of avsim_step on device buffers (it also steps the envs that start an episode below; k_episode overwrites them)
-    const bool io = h->io_device;
-    h->io_device = true;
-    rc = step_common(h, (const float*)da, nsub, (double*)dap, (int32_t*)drw, (uint8_t*)dsu);
-    h->io_device = io;
-    if (rc) return rc;
-    if (h->f64) ep_launch<double>(h, 1, nullptr, (double*)dap, (int*)drw, (uint8_t*)dsu, (uint8_t*)dte, (uint8_t*)dtr, (int64_t*)did, (int*)del);
-    else ep_launch<float>(h, 1, nullptr, (double*)dap, (int*)drw, (uint8_t*)dsu, (uint8_t*)dte, (uint8_t*)dtr, (int64_t*)did, (int*)del);
+    Call io(h);
+    const float* da = io.in(action, sizeof(float) * N * h->nj);
+    double* dap = io.out(agent_pos, sizeof(double) * N * h->nj, h->ep_ap);
+    int32_t* drw = io.out(reward, sizeof(int32_t) * N, h->ep_rw);
+    uint8_t* dsu = io.out(success, N, h->ep_su);
+    uint8_t* dte = io.out(terminated, N, h->ep_te);
+    uint8_t* dtr = io.out(truncated, N, h->ep_tr);
+    int64_t* did = io.out(episode_id, sizeof(int64_t) * N, h->ep_id);
+    int32_t* del = io.out(elapsed, sizeof(int32_t) * N, h->ep_el);
+    if (io.failed()) return AVSIM_EHIP;
+    // the physics launch of avsim_step (it also steps the envs that start an episode below; k_episode overwrites them)
+    h->state_ver++;
+    if (int rc = step_common(h, da, nsub, dap, drw, dsu)) return rc;
+    if (h->f64) ep_launch<double>(h, 1, nullptr, dap, drw, dsu, dte, dtr, did, del);
+    else ep_launch<float>(h, 1, nullptr, dap, drw, dsu, dte, dtr, did, del);
     HIPCHK(h, hipGetLastError());
-    if ((rc = h->out_end(4, agent_pos, sizeof(double) * N * h->nj))) return rc;
-    if ((rc = h->out_end(5, reward, sizeof(int32_t) * N))) return rc;
-    if ((rc = h->out_end(6, success, N))) return rc;
-    if ((rc = h->out_end(8, terminated, N))) return rc;
-    if ((rc = h->out_end(9, truncated, N))) return rc;
-    if ((rc = h->out_end(10, episode_id, sizeof(int64_t) * N))) return rc;
-    if ((rc = h->out_end(11, elapsed, sizeof(int32_t) * N))) return rc;
-    return h->finish();
+    return io.done();
 }
 
 // Records and counters out: device pointers in device mode, or host pointers in either mode (a poll from the host); only a copy to host
@@ -1635,7 +1490,7 @@ int avsim_chunk_reset(avsim_t* h) {
     if (!h->chunks.ready) { h->set_error("avsim_chunk_reset: call avsim_chunk_setup first"); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
     HIPCHK(h, hipMemsetAsync(h->chunks.P.stepped, 0, sizeof(int) * (size_t)h->N, h->stream));
-    return h->finish();
+    return Call(h).done();
 }
 
 int avsim_chunk_need(avsim_t* h, const int64_t* episode_id, const int32_t* elapsed, uint8_t* need, int32_t* any) {
@@ -1644,18 +1499,15 @@ int avsim_chunk_need(avsim_t* h, const int64_t* episode_id, const int32_t* elaps
     if (!episode_id || !elapsed) { h->set_error("avsim_chunk_need: episode_id and elapsed are required"); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
     const size_t N = h->N;
-    int rc;
-    const void *did, *del;
-    void *dn = nullptr, *da = nullptr;
-    if ((rc = h->in(1, episode_id, sizeof(int64_t) * N, &did))) return rc;
-    if ((rc = h->in(2, elapsed, sizeof(int32_t) * N, &del))) return rc;
-    if (need && (rc = h->out_begin(5, need, N, &dn))) return rc;
-    if (any && (rc = h->out_begin(6, any, sizeof(int32_t), &da))) return rc;
-    chunk_launch_book(h->stream, h->chunks.P, 0, 0, (const int64_t*)did, (const int*)del, (uint8_t*)dn, (int*)da);
+    Call io(h);
+    const int64_t* did = io.in(episode_id, sizeof(int64_t) * N);
+    const int32_t* del = io.in(elapsed, sizeof(int32_t) * N);
+    uint8_t* dn = io.out(need, N);
+    int32_t* da = io.out(any, sizeof(int32_t));
+    if (io.failed()) return AVSIM_EHIP;
+    chunk_launch_book(h->stream, h->chunks.P, 0, 0, did, del, dn, da);
     HIPCHK(h, hipGetLastError());
-    if ((rc = h->out_end(5, need, N))) return rc;
-    if ((rc = h->out_end(6, any, sizeof(int32_t)))) return rc;
-    return h->finish();
+    return io.done();
 }
 
 int avsim_chunk_step(avsim_t* h, const float* chunks, const int64_t* episode_id, const int32_t* elapsed, float* action) {
@@ -1666,17 +1518,15 @@ int avsim_chunk_step(avsim_t* h, const float* chunks, const int64_t* episode_id,
     if (!chunks && P.mode == CHK_ENSEMBLE) { h->set_error("avsim_chunk_step: ensemble mode needs a chunk in every call"); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
     const size_t N = h->N;
-    int rc;
-    const void *dc = nullptr, *did, *del;
-    void* dact;
-    if (chunks && (rc = h->in(0, chunks, sizeof(float) * N * P.CA, &dc))) return rc;
-    if ((rc = h->in(1, episode_id, sizeof(int64_t) * N, &did))) return rc;
-    if ((rc = h->in(2, elapsed, sizeof(int32_t) * N, &del))) return rc;
-    if ((rc = h->out_begin(4, action, sizeof(float) * N * P.A, &dact))) return rc;
-    chunk_launch_step(h->stream, P, (const float*)dc, (const int64_t*)did, (const int*)del, (float*)dact);
+    Call io(h);
+    const float* dc = io.in(chunks, sizeof(float) * N * P.CA);
+    const int64_t* did = io.in(episode_id, sizeof(int64_t) * N);
+    const int32_t* del = io.in(elapsed, sizeof(int32_t) * N);
+    float* dact = io.out(action, sizeof(float) * N * P.A);
+    if (io.failed()) return AVSIM_EHIP;
+    chunk_launch_step(h->stream, P, dc, did, del, dact);
     HIPCHK(h, hipGetLastError());
-    if ((rc = h->out_end(4, action, sizeof(float) * N * P.A))) return rc;
-    return h->finish();
+    return io.done();
 }
 
 int avsim_chunk_starved(avsim_t* h, uint64_t* count) {
@@ -1702,7 +1552,7 @@ int avsim_obs_history_setup(avsim_t* h, int n_obs_steps, int state_dim, const fl
     }
     AVS_ON_DEVICE(h);
     HIPCHK(h, hipStreamSynchronize(h->stream));          // (buffers of an earlier set-up may still be in use)
-    if (h->obshist.setup(h->stream, h->N, n_obs_steps, state_dim, state_mean_std, ncam, fmt, height, width, lut, box, out_h, out_w, !h->io_device, h->err)) return AVSIM_EHIP;
+    if (h->obshist.setup(h->stream, h->N, n_obs_steps, state_dim, state_mean_std, ncam, fmt, height, width, lut, box, out_h, out_w, h->err)) return AVSIM_EHIP;
     HIPCHK(h, hipStreamSynchronize(h->stream));          // (the tables are on the device: the caller's arrays are free)
     return AVSIM_OK;
 }
@@ -1712,7 +1562,7 @@ int avsim_obs_history_reset(avsim_t* h) {
     if (!h->obshist.ready) { h->set_error("avsim_obs_history_reset: call avsim_obs_history_setup first"); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
     HIPCHK(h, hipMemsetAsync(h->obshist.P.pushed, 0, sizeof(int) * (size_t)h->N, h->stream));
-    return h->finish();
+    return Call(h).done();
 }
 
 int avsim_obs_history_push(avsim_t* h, const int64_t* episode_id, const int32_t* elapsed, const float* state, float* state_hist, const void* const* img,
@@ -1727,32 +1577,22 @@ int avsim_obs_history_push(avsim_t* h, const int64_t* episode_id, const int32_t*
     for (int c = 0; c < P.ncam; c++)
         if (!img[c] || !img_hist[c]) { h->set_error("avsim_obs_history_push: camera %d: a NULL pointer", c); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
-    const size_t N = h->N;
+    const size_t N = h->N, K = P.K;
+    // a host caller's histories cross twice per call (for tests and numpy callers)
+    Call io(h);
+    const int64_t* did = io.in(episode_id, sizeof(int64_t) * N);
+    const int32_t* del = io.in(elapsed, sizeof(int32_t) * N);
+    const float* dstate = P.D > 0 ? io.in(state, sizeof(float) * N * P.D) : nullptr;
+    float* dshist = P.D > 0 ? io.inout(state_hist, sizeof(float) * N * K * P.D) : nullptr;
     ObsPtrs Q{};
-    if (h->io_device) {
-        for (int c = 0; c < P.ncam; c++) { Q.img[c] = img[c]; Q.hist[c] = img_hist[c]; }
-        obs_launch_push(h->stream, P, Q, episode_id, elapsed, state, state_hist);
-        HIPCHK(h, hipGetLastError());
-        return AVSIM_OK;
-    }
-    // host I/O: every array in, the histories out again (for tests and numpy callers: the histories cross twice per call)
-    HIPCHK(h, hipMemcpyAsync(O.m_id, episode_id, sizeof(int64_t) * N, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(O.m_el, elapsed, sizeof(int32_t) * N, hipMemcpyHostToDevice, h->stream));
-    if (P.D > 0) {
-        HIPCHK(h, hipMemcpyAsync(O.m_state, state, sizeof(float) * N * P.D, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(O.m_shist, state_hist, O.shist_bytes(), hipMemcpyHostToDevice, h->stream));
-    }
     for (int c = 0; c < P.ncam; c++) {
-        HIPCHK(h, hipMemcpyAsync(O.m_img[c], img[c], O.src_bytes(), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(O.m_hist[c], img_hist[c], O.hist_bytes(), hipMemcpyHostToDevice, h->stream));
-        Q.img[c] = O.m_img[c];
-        Q.hist[c] = (float*)O.m_hist[c];
+        Q.img[c] = io.in(img[c], N * P.SH * P.SW * img_bpp(P.fmt));
+        Q.hist[c] = io.inout(img_hist[c], sizeof(float) * N * K * 3 * P.oh * P.ow);
     }
-    obs_launch_push(h->stream, P, Q, (const int64_t*)O.m_id, (const int*)O.m_el, (const float*)O.m_state, (float*)O.m_shist);
+    if (io.failed()) return AVSIM_EHIP;
+    obs_launch_push(h->stream, P, Q, did, del, dstate, dshist);
     HIPCHK(h, hipGetLastError());
-    if (P.D > 0) HIPCHK(h, hipMemcpyAsync(state_hist, O.m_shist, O.shist_bytes(), hipMemcpyDeviceToHost, h->stream));
-    for (int c = 0; c < P.ncam; c++) HIPCHK(h, hipMemcpyAsync(img_hist[c], O.m_hist[c], O.hist_bytes(), hipMemcpyDeviceToHost, h->stream));
-    return h->finish();
+    return io.done();
 }
 
 }  // extern "C"

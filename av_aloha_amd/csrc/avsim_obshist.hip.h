@@ -84,54 +84,37 @@ struct ObsHistHost {
     std::vector<void*> allocs;
     std::vector<float> host_f;        // what the set-up uploads (kept until the next set-up): mean, std, the tables
     std::vector<int> host_box;
-    // host I/O mode: the device copies of a push's arrays
-    void *m_id = nullptr, *m_el = nullptr, *m_state = nullptr, *m_shist = nullptr;
-    void* m_img[OBH_MAX_CAMS] = {};
-    void* m_hist[OBH_MAX_CAMS] = {};
-
-    size_t src_bytes() const { return (size_t)P.N * P.SH * P.SW * 3 * (P.fmt == 0 ? 1 : sizeof(float)); }
-    size_t hist_bytes() const { return sizeof(float) * (size_t)P.N * P.K * 3 * P.oh * P.ow; }
-    size_t shist_bytes() const { return sizeof(float) * (size_t)P.N * P.K * P.D; }
 
     void destroy() {
         for (void* p : allocs) (void)hipFree(p);
         allocs.clear();
         ready = false;
         P = ObsArgs{};
-        m_id = m_el = m_state = m_shist = nullptr;
-        for (int c = 0; c < OBH_MAX_CAMS; c++) m_img[c] = m_hist[c] = nullptr;
     }
 
-    // validated arguments; the stream is idle (the caller synchronised it).  mirrors: host I/O mode.  -3: HIP
+    // validated arguments; the stream is idle (the caller synchronised it).  -3: HIP
     int setup(hipStream_t stream, int N, int K, int D, const float* mean_std, int ncam, int fmt, int SH, int SW, const float* lut, const int32_t* box, int oh,
-              int ow, bool mirrors, std::string& err) {
+              int ow, std::string& err) {
         destroy();
         ObsArgs a{};
         a.N = N; a.K = K; a.D = D; a.has_ms = mean_std != nullptr && D > 0; a.ncam = ncam;
         if (ncam > 0) { a.fmt = fmt; a.SH = SH; a.SW = SW; a.oh = oh; a.ow = ow; }
-        P = a;                                                  // (the sizes below read it)
         const size_t n = (size_t)N;
         hipError_t e = hipSuccess;
-        auto get = [&](size_t bytes, bool zero) -> void* {
+        auto get = [&](size_t bytes) -> void* {
             void* p = nullptr;
             if (e != hipSuccess) return nullptr;
             if ((e = hipMalloc(&p, bytes ? bytes : 1)) != hipSuccess) return nullptr;
             allocs.push_back(p);
-            if (zero && (e = hipMemsetAsync(p, 0, bytes ? bytes : 1, stream)) != hipSuccess) return nullptr;
+            if ((e = hipMemsetAsync(p, 0, bytes ? bytes : 1, stream)) != hipSuccess) return nullptr;
             return p;
         };
-        a.last_id = (int64_t*)get(sizeof(int64_t) * n, true);
-        a.pushed = (int*)get(sizeof(int) * n, true);
-        a.cur_fresh = (int*)get(sizeof(int) * n, true);
+        a.last_id = (int64_t*)get(sizeof(int64_t) * n);
+        a.pushed = (int*)get(sizeof(int) * n);
+        a.cur_fresh = (int*)get(sizeof(int) * n);
         const size_t nf = 2 * (size_t)D + 768 * (size_t)ncam;
-        float* f = (float*)get(sizeof(float) * nf, true);
-        int* b = (int*)get(sizeof(int) * 3 * (size_t)(ncam ? ncam : 1), true);
-        if (mirrors) {
-            m_id = get(sizeof(int64_t) * n, false);
-            m_el = get(sizeof(int) * n, false);
-            if (D > 0) { m_state = get(sizeof(float) * n * D, false); m_shist = get(shist_bytes(), false); }
-            for (int c = 0; c < ncam; c++) { m_img[c] = get(src_bytes(), false); m_hist[c] = get(hist_bytes(), false); }
-        }
+        float* f = (float*)get(sizeof(float) * nf);
+        int* b = (int*)get(sizeof(int) * 3 * (size_t)(ncam ? ncam : 1));
         if (e == hipSuccess) {
             host_f.assign(nf ? nf : 1, 0.0f);
             if (a.has_ms) std::copy(mean_std, mean_std + 2 * D, host_f.begin());

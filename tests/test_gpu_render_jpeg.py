@@ -52,6 +52,15 @@ def test_streams_equal_those_of_the_rendered_frames(sim, H, W):
     assert jpeg.stream_size(tiled[0]) == (H, 2 * W)
 
 
+def test_small_tiled_streams_equal_those_of_the_tiled_frames(sim):
+    """8 x 12 views side by side: the rendered and the tiled images are scratch of the call, far smaller than the 120 x 160 ones the same buffers served."""
+    H, W = 8, 12
+    u8 = sim.render_rgb(CAMS, H, W)
+    tiled = sim.render_jpeg(CAMS, H, W, 90, tile=True)
+    assert tiled == sim.encode_jpeg(np.concatenate([u8[:, 0], u8[:, 1]], axis=2), 90)
+    assert len(tiled) == 3 and jpeg.stream_size(tiled[0]) == (H, 2 * W)
+
+
 def test_a_short_stride_reports_the_length_and_keeps_to_its_rows(sim):
     H, W = 120, 160
     full = [s for v in sim.render_jpeg(CAMS, H, W, 90) for s in v]

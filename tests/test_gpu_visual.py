@@ -166,7 +166,7 @@ def test_shadows_and_supersampling_match_the_oracle():
 
 
 def test_large_host_copies_take_the_pipelined_path_and_arrive_intact():
-    """Results of 16 MB and more go to host memory through two pinned staging buffers and four copy threads (avsim_api.hip out_end_pipelined)
+    """Results of 16 MB and more go to host memory through two pinned staging buffers and four copy threads (csrc/avsim_io.h copy_out_pipelined)
     instead of one pageable hipMemcpy: a 29 MB call (8 envs x 4 cameras x 480 x 640 x 3, not a multiple of the 32 MB chunk) and a 59 MB call
     (depth, f32: two chunks) against the same images fetched one camera at a time (7 / 9.8 MB each: the plain path)."""
     from av_aloha_amd.sim import BatchedSim
