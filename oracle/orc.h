@@ -145,6 +145,13 @@ int orc_vis_render_ex(const orc_data* d, int cam, int nvert, const double* vert,
 /* the same with per-corner lighting normals [ntri][9] (body frame): smooth shading; tnorm NULL = orc_vis_render_ex */
 int orc_vis_render_sm(const orc_data* d, int cam, int nvert, const double* vert, const int* vbody, int ntri, const int* tri, const double* rgb,
                       const double* uv, const int* tex, const int* texel, int texn, const double* tnorm, int H, int W, int ss, int shadows, unsigned char* out, int* tri_out, double* depth_out);
+/* f64 model of the device's depth-map shadow (DESIGN.md "The renderer's shadow contract"): the map of one state, and the image of
+ * orc_vis_render_sm with the sampling pattern moved by (dx, dy) pixel and the map's shadow; see orc_vis.c */
+int orc_vis_shadow_map(const orc_data* d, int nvert, const double* vert, const int* vbody, int ntri, const int* tri, int shn, double* map);
+int orc_vis_render_model(const orc_data* d, int cam, int nvert, const double* vert, const int* vbody, int ntri, const int* tri, const double* rgb,
+                         const double* uv, const int* tex, const int* texel, int texn, const double* tnorm, int H, int W, int ss, double dx, double dy,
+                         int shn, const double* map, double bias_scale, double eps_tex, double delta, unsigned char* out, unsigned char* out_lo,
+                         unsigned char* out_hi, double* dmin, double* dmax, unsigned char* flag, double* bias_out, int* samp_tri, unsigned char* samp_flag);
 
 /* env-level (env.py:203-249): reset to home pose with given object free-joint poses (nobj x 7) */
 void orc_reset(orc_data* d, const double* obj_qpos);

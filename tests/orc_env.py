@@ -111,11 +111,8 @@ class OrcEnv:
         assert hits >= 0
         return out, dep
 
-    def render_visual(self, cam, H, W, scene, ss=1, shadows=False, smooth=False):
-        """Colour image uint8 [H, W, 3] of the visual scene (scene = vismesh.expand_instances(library, model blob) + (texels,)), the index of the
-        triangle every pixel sees (-1: sky) and its depth: oracle/orc_vis.c, one ray per pixel against every triangle.  smooth (the device's
-        option render_smooth, on in the gym / Cartesian facades): the corners lit with their own normals (the scene's tnorm) and interpolated; False: one shade per triangle."""
-        ci = self.man["camera_names"].index(cam) if isinstance(cam, str) else int(cam)
+    @staticmethod
+    def _scene_arrays(scene, smooth):
         if len(scene) == 8:
             vert, vbody, tri, rgb, uv, tex, tnorm, texel = scene
         else:                                   # (a scene without corner normals: flat shading)
@@ -126,6 +123,14 @@ class OrcEnv:
         uv = np.ascontiguousarray(uv, dtype=np.float64); tex = np.ascontiguousarray(tex, dtype=np.int32)
         texel = np.ascontiguousarray(texel, dtype=np.int32)
         tn = np.ascontiguousarray(tnorm, dtype=np.float64) if (tnorm is not None and smooth) else None
+        return vert, vbody, tri, rgb, uv, tex, texel, tn
+
+    def render_visual(self, cam, H, W, scene, ss=1, shadows=False, smooth=False):
+        """Colour image uint8 [H, W, 3] of the visual scene (scene = vismesh.expand_instances(library, model blob) + (texels,)), the index of the
+        triangle every pixel sees (-1: sky) and its depth: oracle/orc_vis.c, one ray per pixel against every triangle.  smooth (the device's
+        option render_smooth, on in the gym / Cartesian facades): the corners lit with their own normals (the scene's tnorm) and interpolated; False: one shade per triangle."""
+        ci = self.man["camera_names"].index(cam) if isinstance(cam, str) else int(cam)
+        vert, vbody, tri, rgb, uv, tex, texel, tn = self._scene_arrays(scene, smooth)
         out = np.empty((H, W, 3), dtype=np.uint8)
         tid = np.empty((H, W), dtype=np.int32)
         dep = np.empty((H, W), dtype=np.float64)
@@ -136,6 +141,37 @@ class OrcEnv:
                                         int(round(len(texel) ** 0.5)), vp(tn), H, W, int(ss), int(bool(shadows)), vp(out), vp(tid), vp(dep))
         assert hits >= 0
         return out, tid, dep
+
+    def shadow_map(self, scene, shn):
+        """float64 [shn, shn]: the f64 model of the device's depth map from the light in the current state (orc_vis_shadow_map; -inf: empty)."""
+        vert, vbody, tri, *_ = self._scene_arrays(scene, False)
+        out = np.empty((shn, shn), dtype=np.float64)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        self.L.orc_vis_shadow_map.restype = C.c_int
+        assert self.L.orc_vis_shadow_map(self.dptr, len(vbody), vp(vert), vp(vbody), len(tri), vp(tri), int(shn), vp(out)) >= 0
+        return out
+
+    def render_model(self, cam, H, W, scene, smooth, shmap, dx=0.0, dy=0.0, ss=2, bias_scale=1.0, eps_tex=0.0, delta=0.0):
+        """The model of the device's default image (orc_vis_render_model): ss x ss samples moved by (dx, dy) pixel, the shadow looked up in
+        shmap (a shadow_map(); None: no shadows).  A dict: "rgb", "lo", "hi" uint8 [H, W, 3] (lo / hi: every fragile fragment at its darker /
+        lighter verdict); "dmin", "dmax", "bias" float64 [H, W]; "flag" uint8 [H, W] (1 shadowed, 2 fragile, 4 looked up: any fragment of
+        the pixel); "tri" int32 and "sflag" uint8 [H, W, ss ss], the same per sample."""
+        ci = self.man["camera_names"].index(cam) if isinstance(cam, str) else int(cam)
+        vert, vbody, tri, rgb, uv, tex, texel, tn = self._scene_arrays(scene, smooth)
+        ns = ss * ss
+        r = {"rgb": np.empty((H, W, 3), np.uint8), "lo": np.empty((H, W, 3), np.uint8), "hi": np.empty((H, W, 3), np.uint8),
+             "dmin": np.empty((H, W)), "dmax": np.empty((H, W)), "flag": np.empty((H, W), np.uint8), "bias": np.empty((H, W)),
+             "tri": np.empty((H, W, ns), np.int32), "sflag": np.empty((H, W, ns), np.uint8)}
+        vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        if shmap is not None:
+            assert shmap.dtype == np.float64 and shmap.flags["C_CONTIGUOUS"] and shmap.shape[0] == shmap.shape[1]
+        self.L.orc_vis_render_model.restype = C.c_int
+        hits = self.L.orc_vis_render_model(self.dptr, ci, len(vbody), vp(vert), vp(vbody), len(tex), vp(tri), vp(rgb), vp(uv), vp(tex), vp(texel),
+                                           int(round(len(texel) ** 0.5)), vp(tn), H, W, int(ss), C.c_double(dx), C.c_double(dy),
+                                           0 if shmap is None else shmap.shape[0], vp(shmap), C.c_double(bias_scale), C.c_double(eps_tex), C.c_double(delta),
+                                           *(vp(r[k]) for k in ("rgb", "lo", "hi", "dmin", "dmax", "flag", "bias", "tri", "sflag")))
+        assert hits >= 0
+        return r
 
     def close(self):
         self.L.orc_data_free(self.dptr)

@@ -385,3 +385,170 @@ def disturbed(md, q, sigma, rng):
     for a in md["objects_qposadr"]:
         q[int(a):int(a) + 3] += sigma * rng.standard_normal(3)
     return q
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the default image of the facades: shadows 1, samples 4 (DESIGN.md "The renderer's shadow contract"; the model: oracle/orc_vis.c
+# orc_vis_render_model)
+
+SHADOW_SIZE = 512                       # option "render_shadow_size": the default
+POSE_BOUND = 1e-5                       # metres: what tests/test_gpu_pointcloud.py bounds the device's pose error by (NOISE_DEVICE is its order)
+FRAGILE_MARGIN = 2.0
+SHIFTS = (-0.2, 0.0, 0.2)               # pixel: the 0.2-pixel rule of the one-ray images (K = 5 there: the rays 1 / 5 pixel off the centre)
+
+
+def light_box(md):
+    """(half extent in metres, texels per metre at `shn` = 1) of the light's shadow box."""
+    half = float(md["render_light"][3])
+    return half, 1.0 / (2.0 * half)
+
+
+def fragile_bounds(md, shn, margin=FRAGILE_MARGIN):
+    """(eps in texels, delta in metres) of the model's fragile verdicts.
+
+    A verdict compares the map's value at the texel that holds the sample's light-plane position with the sample's height.  The device's
+    poses are off the oracle's by at most POSE_BOUND = 1e-5 m (NOISE_DEVICE = 1e-6 is the order, tests/test_gpu_pointcloud.py holds the bound):
+    that moves the position by up to POSE_BOUND x itex texels (0.0043 texel at 512) and a height by up to POSE_BOUND.  Receiver and occluder
+    move independently, so eps and delta are FRAGILE_MARGIN = 2 times those figures: eps = 2e-5 m x itex (0.0085 texel at 512, 0.034 at
+    2048), delta = 2e-5 m.
+
+    Measured (test_render_envelope_host.py::test_non_fragile_verdicts_survive_pose_noise: visual_reference's noise scheme, NOISE_DEVICE, seed
+    0, every shadow state, the three cameras, smooth and flat): of 31 048 verdicts 18 are fragile at margin 2 and 0 of the others flipped (the flip
+    count the margin has to reach: 0); margins 0.5 and 1 flip none either, with 3 and 10 fragile: the noise of this seed is smaller than the
+    bound the margin is derived from."""
+    return margin * POSE_BOUND * shn * light_box(md)[1], margin * POSE_BOUND
+
+
+def model_renders(md, e, cam, H, W, scene, smooth, shn, shmap=None, shifts=SHIFTS, **kw):
+    """The model's renders of the oracle's current state over the shifted sampling patterns (shmap: another state's map for a counter-image)."""
+    eps, delta = fragile_bounds(md, shn)
+    if shmap is None:
+        shmap = e.shadow_map(scene, shn)
+    return [e.render_model(cam, H, W, scene, smooth, shmap, dx=dx, dy=dy, eps_tex=eps, delta=delta, **kw) for dy in shifts for dx in shifts]
+
+
+def production_envelope(e, cam, H, W, scene, smooth, shn=SHADOW_SIZE, md=None):
+    """Envelope of the image with shadows 1, samples 4: per channel the minimum and the maximum over the nine model renders with ss = 2 whose
+    sampling pattern is shifted by (dx, dy) in {-0.2, 0, +0.2}^2 pixel; a fragile sample enters with its shadowed and with its lit colour.
+    Edge pixels: the depth of the 36 samples (sky: the far plane) spreads by more than EDGE_SPREAD.  The envelope also carries .shadowed and
+    .fragile, bool images of the unshifted render (a fragment of the pixel is shadowed / has a fragile verdict)."""
+    md = md or model_dict()
+    rs = model_renders(md, e, cam, H, W, scene, smooth, shn)
+    lo = np.min([r["lo"] for r in rs], axis=0).astype(np.int32)
+    hi = np.max([r["hi"] for r in rs], axis=0).astype(np.int32)
+    far = lambda d: np.where(d > 0, d, FAR)
+    dlo = np.min([np.minimum(far(r["dmin"]), far(r["dmax"])) for r in rs], axis=0)
+    dhi = np.max([np.maximum(far(r["dmin"]), far(r["dmax"])) for r in rs], axis=0)
+    env = Envelope(lo, hi, (dhi - dlo) > EDGE_SPREAD, rs[4]["rgb"].astype(np.int32))
+    env.shadowed, env.fragile = (rs[4]["flag"] & 1).astype(bool), (rs[4]["flag"] & 2).astype(bool)
+    return env
+
+
+def production_reference(md, e, scene, q, cam, smooth, shn=SHADOW_SIZE, seed=0):
+    """visual_reference for the default image: (envelope of state q, the model's own image of q disturbed by NOISE_DEVICE, its (interior,
+    edge) counts outside the envelope)."""
+    H, W = VIS_HW
+    e.set_qpos(q)
+    env = production_envelope(e, cam, H, W, scene, smooth, shn, md)
+    e.set_qpos(disturbed(md, q, NOISE_DEVICE, np.random.default_rng(seed)))
+    img = e.render_model(cam, H, W, scene, smooth, e.shadow_map(scene, shn))["rgb"]
+    e.set_qpos(q)
+    bi, be = violations(img, env, TOL_VISUAL)
+    return env, img, (int(bi.sum()), int(be.sum()))
+
+
+def verdict_flips(md, e, scene, q, cam, smooth, shn=SHADOW_SIZE, margin=FRAGILE_MARGIN, seed=0):
+    """(verdicts compared, of them fragile, non-fragile ones flipped) between the model of state q and of q disturbed by NOISE_DEVICE: the
+    fragments that both images look up in the map at the same sample of the same triangle."""
+    H, W = VIS_HW
+    eps, delta = fragile_bounds(md, shn, margin)
+    e.set_qpos(q)
+    a = e.render_model(cam, H, W, scene, smooth, e.shadow_map(scene, shn), eps_tex=eps, delta=delta)
+    e.set_qpos(disturbed(md, q, NOISE_DEVICE, np.random.default_rng(seed)))
+    b = e.render_model(cam, H, W, scene, smooth, e.shadow_map(scene, shn))
+    e.set_qpos(q)
+    both = ((a["sflag"] & 4) != 0) & ((b["sflag"] & 4) != 0) & (a["tri"] == b["tri"])
+    fragile = both & ((a["sflag"] & 2) != 0)
+    flipped = both & ~fragile & ((a["sflag"] & 1) != (b["sflag"] & 1))
+    return int(both.sum()), int(fragile.sum()), int(flipped.sum())
+
+
+SHADOW_STATES = ["H0", "H1", "H2", "H3", "H4"]
+MIN_SHADOWED, MAX_FRAGILE = 0.02, 0.01       # of an image's pixels: the overhead image's shadowed ones, any image's fragile ones
+
+
+def shadow_states(e, scene=None):
+    """{name: qpos} of the states the default image is compared in (slot_insertion, three arms; the light shines straight down):
+    H0 the reset pose; H1 the stick 5 cm above the slot, turned against it: a detached shadow on the slot and the table; H2 the left gripper
+    low over the stick, the slot under the forearm: the arm's shadow across both; H3 the stick rolled by 45 deg about its long axis and
+    resting on one edge: under the overhang the gap to the table goes to zero, a contact shadow thinner than the bias; H4 the slot on the
+    table across the border x = +0.6 m of the light's box (the table ends at 0.61 m, overhead_cam sees 0.65 m) and the stick 5 cm above it
+    along the border: the shadow ends where the box does.  H1, H3 and H4 also turn the right arm (which carries wrist_cam_right) by a state's own
+    angle, so that no two envs of a batch share an arm pose.
+    With `scene`, every state's two conditions are asserted on the model and the figures returned too: (states, {name: (share of
+    overhead_cam's pixels shadowed, largest share of fragile pixels over VIS_CAMS)})."""
+    md = model_dict()
+    SLOT, STICK = 23, 30
+    S = {"H0": home_q(md, OBJ)}
+    e.set_qpos(S["H0"])
+    ng = len(e.man["geom_names"])
+    gx = lambda name: e.arr("geom_xpos", 3 * ng).reshape(-1, 3)[e.man["geom_names"].index(name)].copy()
+    gsz = lambda name: md["geom_size"].reshape(-1, 3)[e.man["geom_names"].index(name)]
+    table_top = gx("table")[2] + gsz("table")[2]
+    slot_top = gx("slot-1")[2] + gsz("slot-1")[2]
+    hs = gsz("stick")
+    # H1
+    q = S["H0"].copy()
+    q[8] += 0.15
+    q[STICK:STICK + 7] = body_pose_for_geom(md, e, "stick", np.array([0.02, 0.13, slot_top + 0.05 + hs[2]]), rot(2, 0.5))
+    S["H1"] = q
+    # H2: the left arm's shoulder and elbow lowered until the fingers are 3 .. 8 cm above the stick's top; stick and slot are as high as each
+    # other, so they lie 5 cm apart (two coplanar top faces would swap under any noise)
+    q = S["H0"].copy()
+    q[1] += 0.55
+    q[2] -= 0.25
+    e.set_qpos(q)
+    nb = md["nbody"]
+    bx = lambda name: e.arr("xpos", 3 * nb).reshape(-1, 3)[e.man["body_names"].index(name)].copy()
+    grip, fore = bx("left_gripper_base"), bx("left_lower_forearm_link")
+    gap = bx("left_left_finger_link")[2] - (table_top + 2 * hs[2])
+    assert 0.03 < gap < 0.08, f"the left fingers are {gap:.3f} m above the stick's top"
+    q[STICK:STICK + 7] = body_pose_for_geom(md, e, "stick", np.array([grip[0] + 0.12, grip[1], table_top + hs[2] + 1e-3]), rot(2, 0.3))
+    q[SLOT:SLOT + 7] = body_pose_for_geom(md, e, "slot-1", np.array([fore[0] - 0.03, fore[1], table_top + gsz("slot-1")[2] + 1e-3]), rot(2, 1.2))
+    S["H2"] = q
+    # H3
+    q = S["H0"].copy()
+    q[8] -= 0.2
+    drop = (hs[1] + hs[2]) / np.sqrt(2.0)
+    q[STICK:STICK + 7] = body_pose_for_geom(md, e, "stick", np.array([0.05, -0.08, table_top + drop]), rot(2, 0.35) @ rot(0, np.pi / 4))
+    S["H3"] = q
+    # H4
+    half = light_box(md)[0]
+    edge_x = float(md["render_light"][7]) + half
+    q = S["H0"].copy()
+    q[8:10] += (-0.1, 0.2)
+    q[SLOT:SLOT + 7] = body_pose_for_geom(md, e, "slot-1", np.array([edge_x, -0.15, table_top + gsz("slot-1")[2] + 1e-3]), rot(2, 0.0))
+    q[STICK:STICK + 7] = body_pose_for_geom(md, e, "stick", np.array([edge_x, -0.15, slot_top + 0.05 + hs[2]]), rot(2, np.pi / 2 + 0.15))
+    S["H4"] = q
+    e.set_qpos(q)
+    pc, Rc, th = cam_frame(md, e, "overhead_cam")
+    p = (np.array([edge_x, -0.15, table_top]) - pc) @ Rc
+    col, row = p[0] / -p[2] / (2 * th / VIS_HW[0]) + VIS_HW[1] / 2, -p[1] / -p[2] / (2 * th / VIS_HW[0]) + VIS_HW[0] / 2
+    assert 1 < col < VIS_HW[1] - 1 and 1 < row < VIS_HW[0] - 1, f"the border of the light's box is not in overhead_cam's image: pixel ({row:.1f}, {col:.1f})"
+    if scene is None:
+        return S
+    facts = {}
+    for name in SHADOW_STATES:
+        e.set_qpos(S[name])
+        shmap = e.shadow_map(scene, SHADOW_SIZE)
+        eps, delta = fragile_bounds(md, SHADOW_SIZE)
+        shadowed, fragile = 0.0, 0.0
+        for cam in VIS_CAMS:
+            r = e.render_model(cam, *VIS_HW, scene, True, shmap, eps_tex=eps, delta=delta)
+            if cam == "overhead_cam":
+                shadowed = float(((r["flag"] & 1) != 0).mean())
+            fragile = max(fragile, float(((r["flag"] & 2) != 0).mean()))
+        assert shadowed >= MIN_SHADOWED, f"{name}: the model shadows {100 * shadowed:.2f} % of overhead_cam's pixels"
+        assert fragile <= MAX_FRAGILE, f"{name}: {100 * fragile:.2f} % of an image's pixels hold a fragile sample"
+        facts[name] = (shadowed, fragile)
+    return S, facts

@@ -170,3 +170,147 @@ def test_visual_oracle_under_pose_noise(worlds, scene, state, cam, smooth):
         t = RE.Tally(interior_allowed=3 * ni + 2)
         t.add(gone, env, RE.TOL_VISUAL, "stick removed")
         assert not t.ok()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the default image: shadows 1, samples 4 (render_envelope.production_envelope over the oracle's model of the depth-map shadow)
+
+VH, VW = RE.VIS_HW
+
+
+@pytest.fixture(scope="module")
+def shadow_world(scene):
+    """(model, oracle, states, {state: (shadowed share of overhead_cam, largest fragile share)}, cache of production_reference results)."""
+    e = OrcEnv("slot_insertion", 3)
+    S, facts = RE.shadow_states(e, scene)
+    yield model_dict("slot_insertion"), e, S, facts, {}
+    e.close()
+
+
+def reference(shadow_world, scene, state, cam, smooth):
+    md, e, S, _, cache = shadow_world
+    if (state, cam, smooth) not in cache:
+        cache[state, cam, smooth] = RE.production_reference(md, e, scene, S[state], cam, smooth)
+    return cache[state, cam, smooth]
+
+
+def test_model_without_shadows_is_the_ray_caster(worlds, scene):
+    """orc_vis_render_model spares itself the triangles whose bounding box of ray directions a ray misses; with no map and no shift it must give
+    the bytes of orc_vis_render_sm, which tries every triangle.  With four samples where the near plane cuts no triangle that is seen
+    (overhead_cam; a cut triangle is two fragments to the model and one to orc_vis_render_sm), with one sample where it cuts the stick and
+    the slot (S2, S3)."""
+    md, e, S = worlds["slot_insertion"]
+    for state, cam, smooth, ss in (("S0", "overhead_cam", True, 2), ("S2", "wrist_cam_right", True, 1), ("S3", "wrist_cam_left", False, 1)):
+        e.set_qpos(S[state])
+        assert np.array_equal(e.render_model(cam, 30, 40, scene, smooth, None, ss=ss)["rgb"], e.render_visual(cam, 30, 40, scene, ss=ss, smooth=smooth)[0]), (state, cam)
+    e.set_qpos(S["S0"])
+
+
+def test_shadow_states_meet_their_conditions(shadow_world):
+    """Asserted in render_envelope.shadow_states on the model alone: >= 2 % of overhead_cam's pixels shadowed, <= 1 % of any image's pixels
+    with a fragile sample.  Measured: shadowed 12.8 / 13.1 / 11.8 / 12.9 / 12.1 % (H0 .. H4), fragile at most 0.13 % (3 pixels of 2240)."""
+    facts = shadow_world[3]
+    for name, (shadowed, fragile) in facts.items():
+        print(f"{name}: overhead_cam {100 * shadowed:.2f} % of the pixels shadowed; at most {100 * fragile:.2f} % of an image's pixels fragile")
+    assert list(facts) == RE.SHADOW_STATES and all(s >= RE.MIN_SHADOWED and f <= RE.MAX_FRAGILE for s, f in facts.values())
+
+
+def test_non_fragile_verdicts_survive_pose_noise(shadow_world, scene):
+    """The measurement behind render_envelope.fragile_bounds: the model of every shadow state against the model of the same state under
+    NOISE_DEVICE pose noise (seed 0), three cameras, per margin (eps = margin x 1e-5 m x itex texels, delta = margin x 1e-5 m).
+    Measured, of 31 048 verdicts compared: margin 0.5: 3 fragile, 0 flipped; 1: 10 fragile, 0 flipped; 2: 18 fragile, 0 flipped."""
+    md, e, S, _, _ = shadow_world
+    for margin in (0.5, 1.0, RE.FRAGILE_MARGIN):
+        tot = np.zeros(3, dtype=np.int64)
+        for state in RE.SHADOW_STATES:
+            for cam in RE.VIS_CAMS:
+                tot += RE.verdict_flips(md, e, scene, S[state], cam, True, margin=margin)
+        print(f"margin {margin:g}: {tot[0]} verdicts compared, {tot[1]} fragile, {tot[2]} non-fragile ones flipped")
+        if margin == RE.FRAGILE_MARGIN:
+            assert tot[0] > 10000 and tot[2] == 0
+
+
+@pytest.mark.parametrize("smooth", [True, False])
+@pytest.mark.parametrize("cam", RE.VIS_CAMS)
+@pytest.mark.parametrize("state", RE.SHADOW_STATES)
+def test_production_model_under_pose_noise_stays_inside_its_envelope(shadow_world, scene, state, cam, smooth):
+    """Sound: the model's image of the state under NOISE_DEVICE pose noise against the state's envelope, within the fixed part of the allowance
+    the device gets (2 interior pixels) and one edge pixel an image.  Measured: 0 interior pixels in all thirty images; 0 edge pixels in 27, one
+    in three (wrist_cam_right: H0 and H2 flat, H1 smooth -- where one of them was looked at, a sample lay so near the edge between two
+    triangles of the frame, of unlike shade, that the noise moved it across: nine renders 0.2 pixel apart do not span that)."""
+    env, img, (ni, ne) = reference(shadow_world, scene, state, cam, smooth)
+    print(f"{state} {cam} {'smooth' if smooth else 'flat'}: edge pixels {100 * env.edge.mean():.1f} %, shadowed {100 * env.shadowed.mean():.1f} %, "
+          f"model under 1e-6 noise: {ni} interior, {ne} edge pixels outside")
+    assert ni <= 2 and ne <= 1
+
+
+def outside(img, env):
+    bi, be = RE.violations(img, env, RE.TOL_VISUAL)
+    return int(bi.sum()), int(be.sum())
+
+
+@pytest.mark.parametrize("state,other", [("H0", "H2"), ("H1", "H0"), ("H2", "H0"), ("H3", "H2"), ("H4", "H0")])
+def test_production_counter_images_fail_by_a_wide_margin(shadow_world, scene, state, other):
+    """Sharp: five wrong images of the state in overhead_cam, each outside the envelope in at least ten times the pixels the device is allowed
+    (3 x the model's own count under noise + 2 = 2): no shadows; the shadows of another state (its bodies in the shadow pass only); zero
+    bias; one sample instead of four; the image shifted by one pixel.
+    Measured (interior + edge pixels outside, of 2240; the smallest and the largest over H0 .. H4): no shadows 93 .. 101; another state's
+    shadows 23 (H1 with H0's) .. 61; zero bias 394 .. 411; one sample 221 .. 233; shifted 463 .. 505.  Ten times the allowance is 20."""
+    md, e, S, _, _ = shadow_world
+    cam, smooth = "overhead_cam", True
+    env, _, (ri, _) = reference(shadow_world, scene, state, cam, smooth)
+    allowed = 3 * ri + 2
+    e.set_qpos(S[other])
+    other_map = e.shadow_map(scene, RE.SHADOW_SIZE)
+    e.set_qpos(S[state])
+    own_map = e.shadow_map(scene, RE.SHADOW_SIZE)
+    true = e.render_model(cam, VH, VW, scene, smooth, own_map)["rgb"]
+    assert outside(true, env) == (0, 0)
+    counter = {
+        "no shadows": e.render_model(cam, VH, VW, scene, smooth, None)["rgb"],
+        f"the shadows of {other}": e.render_model(cam, VH, VW, scene, smooth, other_map)["rgb"],
+        "zero bias": e.render_model(cam, VH, VW, scene, smooth, own_map, bias_scale=0.0)["rgb"],
+        "one sample": e.render_model(cam, VH, VW, scene, smooth, own_map, ss=1)["rgb"],
+        "shifted by one pixel": np.roll(true, 1, axis=1),
+    }
+    for what, img in counter.items():
+        ni, ne = outside(img, env)
+        print(f"{state} {cam}: {what}: {ni} interior + {ne} edge pixels outside the envelope (allowed {allowed})")
+        assert ni + ne >= 10 * allowed, what
+
+
+def exact_shadow_boundary(lit, exact):
+    """Pixels of the exact-ray image at a shadow boundary: the exact shadow darkens them and not one of their eight neighbours, or the reverse."""
+    dark = (exact.astype(np.int32) < lit.astype(np.int32) - 2).any(-1)
+    p = np.pad(dark, 1, mode="edge")
+    near = np.zeros_like(dark)
+    for di in (0, 1, 2):
+        for dj in (0, 1, 2):
+            near |= p[di:di + VH, dj:dj + VW] != dark
+    return near
+
+
+@pytest.mark.parametrize("state", RE.SHADOW_STATES)
+def test_model_agrees_with_the_exact_rays_away_from_shadow_boundaries(shadow_world, scene, state):
+    """Consistent: the model (depth map of 512 texels, bias) and the exact shadow ray (render_visual ss = 2, shadows) in overhead_cam differ by
+    more than 2 levels only within r pixels of a shadow boundary of the exact image, r = 1 (the boundary's own width) + (a texel's diagonal +
+    the pixel's bias) projected at the pixel's nearest depth.  Measured, H0 .. H4: 1.12 / 1.07 / 1.12 / 1.43 / 1.16 % of the pixels differ
+    (24 .. 32 of 2240), none of them away from a boundary; the share of the image that lies that near a boundary is printed too."""
+    md, e, S, _, _ = shadow_world
+    cam, smooth = "overhead_cam", True
+    e.set_qpos(S[state])
+    m = e.render_model(cam, VH, VW, scene, smooth, e.shadow_map(scene, RE.SHADOW_SIZE))
+    lit = e.render_model(cam, VH, VW, scene, smooth, None)["rgb"]
+    exact = e.render_visual(cam, VH, VW, scene, ss=2, shadows=True, smooth=smooth)[0]
+    differ = (np.abs(m["rgb"].astype(np.int32) - exact) > 2).any(-1)
+    boundary = np.argwhere(exact_shadow_boundary(lit, exact))
+    _, _, th = RE.cam_frame(md, e, cam)
+    texel = 2 * RE.light_box(md)[0] / RE.SHADOW_SIZE
+    assert len(boundary) > 0
+    depth = np.where(m["dmin"] > 0, m["dmin"], np.where(m["dmax"] > 0, m["dmax"], RE.FAR))
+    r = 1 + (np.sqrt(2.0) * texel + np.maximum(m["bias"], 1e-3)) / (depth * 2 * th / VH)
+    dist = np.array([[np.abs(boundary - (i, j)).max(1).min() for j in range(VW)] for i in range(VH)])
+    far = int((differ & (dist > r)).sum())
+    print(f"{state} {cam}: model and exact rays differ in {100 * differ.mean():.2f} % of the pixels ({int(differ.sum())}), {far} of them away from an exact "
+          f"shadow boundary; {100 * (dist <= r).mean():.1f} % of the image lies that near one")
+    assert far == 0
