@@ -172,32 +172,25 @@ __global__ void __launch_bounds__(64) k_fk_jac(IkParams P, int arm, int n, const
     }
 }
 
-template <int NJ>
-__global__ void __launch_bounds__(64) k_ik(IkParams P, int arm, int controller, int iters, int n, const double* __restrict__ q,
+// avsim_ik's GradIK: one problem per 16-lane row (gradik spreads its cost evaluations over the row), four per block.  (Its DiffIK: k_cart_ctrl.)
+__global__ void __launch_bounds__(64) k_ik(IkParams P, int arm, int iters, int n, const double* __restrict__ q,
                                            const double* __restrict__ pos, const double* __restrict__ quat,
                                            double* __restrict__ qout) {
-    // DiffIK: one problem per lane.  GradIK: one problem per 16-lane row (gradik spreads its cost evaluations over the row)
-    const int gt = blockIdx.x * blockDim.x + threadIdx.x;
-    const int i = controller == 1 ? gt >> 4 : gt;
+    const int i = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const bool live = i < n;
     const int ii = live ? i : n - 1;          // idle rows of the last block shadow the last problem (wave-wide shuffles inside gradik)
-    double th[NJ], out[NJ], tp[3], qx[4], Rt[9];
+    double th[6], out[6], tp[3], qx[4], Rt[9];
 #pragma unroll
-    for (int k = 0; k < NJ; k++) th[k] = q[(size_t)ii * NJ + k];
+    for (int k = 0; k < 6; k++) th[k] = q[(size_t)ii * 6 + k];
 #pragma unroll
     for (int k = 0; k < 3; k++) tp[k] = pos[(size_t)ii * 3 + k];
     qx[0] = quat[(size_t)ii * 4 + 1]; qx[1] = quat[(size_t)ii * 4 + 2]; qx[2] = quat[(size_t)ii * 4 + 3];
     qx[3] = quat[(size_t)ii * 4 + 0];  // wxyz_to_xyzw (diff_ik.py:59)
     quat2mat_xyzw(qx, Rt);
-    if (controller == 0) {
-        if (!live) return;
-        diffik<double, NJ>(P, arm, th, tp, Rt, iters, out);
-    } else {
-        if constexpr (NJ == 6) gradik<double>(P, arm, th, tp, Rt, iters, out);
-        if (!live || (threadIdx.x & 15) != 0) return;
-    }
+    gradik<double>(P, arm, th, tp, Rt, iters, out);
+    if (!live || (threadIdx.x & 15) != 0) return;
 #pragma unroll
-    for (int k = 0; k < NJ; k++) qout[(size_t)i * NJ + k] = out[k];
+    for (int k = 0; k < 6; k++) qout[(size_t)i * 6 + k] = out[k];
 }
 
 // sim_env.py:277-301: Cartesian action -> ctrl, IK seeded with the MEASURED qpos
@@ -228,36 +221,56 @@ __global__ void __launch_bounds__(64) k_gradik_ctrl(IkParams P, int N, int nq, i
     c[6] = (real)((1.0 - trig) * (P.grip_hi - P.grip_lo) + P.grip_lo);
 }
 
-template <typename real>
-__global__ void __launch_bounds__(64) k_cart_ctrl(IkParams P, int mode, int arm0, int N, int nq, int nu, const double* __restrict__ act,
-                                                  const real* __restrict__ qpos, real* __restrict__ ctrl) {
-    // blockIdx.y + arm0 = arm.  One env per lane, except the GradIK arms of the reference mode: one env per 16-lane row
+// DiffIK, one problem per lane, blockIdx.y + arm0 = arm: THE kernel behind avsim_step_cartesian (the DLS mode's three arms, the reference
+// mode's camera arm) and behind avsim_ik's DiffIK.  One compiled body, so that the control path and the stand-alone call answer a problem
+// with the same bits: this unit fuses multiply-adds where the compiler sees fit, and it chose differently in two kernels' inlined copies of
+// diffik<double, 7> (tests/test_gpu_ik_batch.py measured up to 4.5e-11 between ctrl and avsim_ik).  So the addressing and the two real
+// types are arguments here, not template parameters.
+struct DiffIkIo {
+    const void* q;            // joints: a row per problem, float (q_f32) or double, q_stride entries long; q_adr: the arm's joints
+    int q_f32, q_stride, q_adr;          // stand at IkArm::qadr in it (a qpos row), else the row is the joint vector
+    const double *pos, *quat, *trig;     // targets: pos[3], quat wxyz[4], trigger (null: no gripper) of problem i, arm y at
+    int pos_stride, quat_stride, arm_stride;        // i * stride + y * arm_stride (y = blockIdx.y)
+    void* out;                // answers: float (out_f32) or double, problem i, arm y at i * out_stride + y * out_arm_stride
+    int out_f32, out_stride, out_arm_stride;
+};
+__global__ void __launch_bounds__(64) k_cart_ctrl(IkParams P, int arm0, int iters, int N, DiffIkIo io) {
     const int arm = blockIdx.y + arm0;
-    (void)mode;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
-    const double* a = act + (size_t)i * 23 + (arm == 0 ? 0 : (arm == 1 ? 8 : 16));
-    double tp[3] = {a[0], a[1], a[2]}, qx[4] = {a[4], a[5], a[6], a[3]}, Rt[9];
+    const size_t ay = (size_t)blockIdx.y * io.arm_stride;
+    const double* ap = io.pos + (size_t)i * io.pos_stride + ay;
+    const double* aq = io.quat + (size_t)i * io.quat_stride + ay;
+    double tp[3] = {ap[0], ap[1], ap[2]}, qx[4] = {aq[1], aq[2], aq[3], aq[0]}, Rt[9];      // wxyz_to_xyzw (diff_ik.py:59)
     quat2mat_xyzw(qx, Rt);
-    const real* qp = qpos + (size_t)i * nq;
-    real* c = ctrl + (size_t)i * nu + (arm == 0 ? 0 : (arm == 1 ? 7 : 14));
     const IkArm& A = P.arm[arm];
+    const size_t qo = (size_t)i * io.q_stride, oo = (size_t)i * io.out_stride + (size_t)blockIdx.y * io.out_arm_stride;
+    auto load = [&](int k) -> double {
+        const size_t j = qo + (io.q_adr ? A.qadr[k] : k);
+        return io.q_f32 ? (double)((const float*)io.q)[j] : ((const double*)io.q)[j];
+    };
+    auto store = [&](int k, double v) {
+        if (io.out_f32) ((float*)io.out)[oo + k] = (float)v;
+        else ((double*)io.out)[oo + k] = v;
+    };
     if (arm == 2) {
         double th[7], out[7];
 #pragma unroll
-        for (int k = 0; k < 7; k++) th[k] = (double)qp[A.qadr[k]];
-        diffik<double, 7>(P, 2, th, tp, Rt, P.diff_iters, out);
+        for (int k = 0; k < 7; k++) th[k] = load(k);
+        diffik<double, 7>(P, 2, th, tp, Rt, iters, out);
 #pragma unroll
-        for (int k = 0; k < 7; k++) c[k] = (real)out[k];
+        for (int k = 0; k < 7; k++) store(k, out[k]);
     } else {
         double th[6], out[6];
 #pragma unroll
-        for (int k = 0; k < 6; k++) th[k] = (double)qp[A.qadr[k]];
-        diffik<double, 6>(P, arm, th, tp, Rt, P.diff_iters, out);       // (the GradIK arms of the reference mode: k_gradik_ctrl)
+        for (int k = 0; k < 6; k++) th[k] = load(k);
+        diffik<double, 6>(P, arm, th, tp, Rt, iters, out);       // (the GradIK arms of the reference mode: k_gradik_ctrl)
 #pragma unroll
-        for (int k = 0; k < 6; k++) c[k] = (real)out[k];
-        double trig = a[7];  // sim_env.py:300-301: unnorm(1 - trigger)
-        c[6] = (real)((1.0 - trig) * (P.grip_hi - P.grip_lo) + P.grip_lo);
+        for (int k = 0; k < 6; k++) store(k, out[k]);
+        if (io.trig) {
+            const double trig = io.trig[(size_t)i * io.pos_stride + ay];  // sim_env.py:300-301: unnorm(1 - trigger)
+            store(6, (1.0 - trig) * (P.grip_hi - P.grip_lo) + P.grip_lo);
+        }
     }
 }
 
@@ -579,9 +592,11 @@ int avsim_ik(avsim_t* h, int arm, int controller, int max_iters, int n, const do
     const double* dqt = io.in(quat, sizeof(double) * n * 4);
     double* dout = io.out(qout, sizeof(double) * n * nj);
     if (io.failed()) return AVSIM_EHIP;
-    dim3 grid(controller == 1 ? (n + 3) / 4 : (n + 63) / 64);
-    if (nj == 6) hipLaunchKernelGGL(k_ik<6>, grid, dim3(64), 0, h->stream, h->ik, arm, controller, iters, n, dq, dp, dqt, dout);
-    else hipLaunchKernelGGL(k_ik<7>, grid, dim3(64), 0, h->stream, h->ik, arm, controller, iters, n, dq, dp, dqt, dout);
+    if (controller == 1) hipLaunchKernelGGL(k_ik, dim3((n + 3) / 4), dim3(64), 0, h->stream, h->ik, arm, iters, n, dq, dp, dqt, dout);
+    else {
+        const DiffIkIo dio = {dq, 0, nj, 0, dp, dqt, nullptr, 3, 4, 0, dout, 0, nj, 0};
+        hipLaunchKernelGGL(k_cart_ctrl, dim3((n + 63) / 64), dim3(64), 0, h->stream, h->ik, arm, iters, n, dio);
+    }
     HIPCHK(h, hipGetLastError());
     return io.done();
 }
@@ -684,13 +699,11 @@ int avsim_step_cartesian(avsim_t* h, const double* action23, int ik_mode, int ns
     Call io(h);
     const double* da = io.in(action23, sizeof(double) * h->N * 23);
     if (io.failed()) return AVSIM_EHIP;
-    auto launch = [&](dim3 grid, int arm0) {
-        if (h->f64)
-            hipLaunchKernelGGL(k_cart_ctrl<double>, grid, dim3(64), 0, h->stream, h->ik, ik_mode, arm0, h->N, h->nq, h->nu, da,
-                               (const double*)h->d_qpos, (double*)h->d_ctrl);
-        else
-            hipLaunchKernelGGL(k_cart_ctrl<float>, grid, dim3(64), 0, h->stream, h->ik, ik_mode, arm0, h->N, h->nq, h->nu, da,
-                               (const float*)h->d_qpos, (float*)h->d_ctrl);
+    auto launch = [&](dim3 grid, int arm0) {      // arms arm0 .. arm0 + grid.y - 1: their slices of the action (8 entries an arm) and of ctrl (7)
+        const size_t real = h->f64 ? sizeof(double) : sizeof(float);
+        const DiffIkIo dio = {h->d_qpos, !h->f64, h->nq, 1, da + 8 * arm0, da + 8 * arm0 + 3, da + 8 * arm0 + 7, 23, 23, 8,
+                              (char*)h->d_ctrl + real * 7 * arm0, !h->f64, h->nu, 7};
+        hipLaunchKernelGGL(k_cart_ctrl, grid, dim3(64), 0, h->stream, h->ik, arm0, h->ik.diff_iters, h->N, dio);
     };
     if (ik_mode == AVSIM_IK_DLS) launch(dim3((h->N + 63) / 64, 3), 0);
     else {

@@ -210,6 +210,7 @@ void orc_diffik_R(const orc_model* m, int arm, const double* q, const double pos
                   double k_ori, double damping, const double* k_null, const double* q0, double max_angvel, double dt,
                   int iterations, double* q_out);
 void orc_gradik_R(const orc_model* m, int arm, const double* q, const double pos[3], const double Rt[9], double* q_out);
+extern int orc_gradik_last_it; /* iterations the last orc_gradik / orc_gradik_R call ran */
 /* sim_env.py:277-301 mapping: 23-D Cartesian action -> 21 ctrl (mode 0: GradIK,GradIK,DiffIK as the reference;
    mode 1: DiffIK on all three arms as north_star) */
 void orc_cart_to_ctrl(const orc_data* d, const double* action23, int mode, double* action21);

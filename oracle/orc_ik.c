@@ -376,6 +376,9 @@ static double gik_cost(const gik* g, const double* q, const double* qs, const do
 }
 
 int orc_gradik_max_it = 50; /* sim_env.py:95 max_iterations (exported so tests can truncate the descent) */
+/* iterations the last call ran: below orc_gradik_max_it where the loop was left at one of its two breaks.  (Laddering orc_gradik_max_it
+ * does not show this: a truncated run answers like the full one as soon as the best iterate stops improving, loop left or not.) */
+int orc_gradik_last_it = 0;
 
 /* grad_ik.py:8-99 */
 void orc_gradik(const orc_model* m, int arm, const double* qs, const double pos[3], const double quat_wxyz[4],
@@ -411,6 +414,7 @@ void orc_gradik_R(const orc_model* m, int arm, const double* qs, const double po
     double grad[6] = {0}, work[6], local[6], best[6];
     for (int i = 0; i < n; i++) work[i] = local[i] = best[i] = qs[i];
     double local_cost = init, best_cost = init, prev = 0.0;
+    orc_gradik_last_it = max_it;
     for (int it = 0; it < max_it; it++) {
         for (int i = 0; i < n; i++) {
             work[i] = local[i] - step;
@@ -450,8 +454,10 @@ void orc_gradik_R(const orc_model* m, int arm, const double* qs, const double po
             for (int j = 0; j < 3; j++) Rl[3 * i + j] = Tl[4 * i + j];
         double d[3] = {tp[0] - Tl[3], tp[1] - Tl[7], tp[2] - Tl[11]};
         orc_angular_error(tR, Rl, e);
-        if (norm3(d) < pthr && norm3(e) < rthr) break;
-        if (fabs(local_cost - prev) <= min_delta) break;
+        if ((norm3(d) < pthr && norm3(e) < rthr) || fabs(local_cost - prev) <= min_delta) {
+            orc_gradik_last_it = it + 1;
+            break;
+        }
         prev = local_cost;
     }
     for (int i = 0; i < n; i++) qout[i] = qs[i] + joint_p * (best[i] - qs[i]);
