@@ -65,7 +65,8 @@ struct DevGuard {
         return AVSIM_EHIP;                                                                                  \
     }
 
-constexpr size_t EV_RING = 1024;      // HIP event pairs kept per timing list before they are folded into a running sum
+// Device memory belongs to members that release it themselves (avsim_dev.h).  avsim_destroy synchronises the stream, deletes the handle -- which
+// frees all of it -- and destroys the stream last
 struct avsim {
     int device = 0;
     uint32_t flags = 0;
@@ -98,25 +99,22 @@ struct avsim {
     unsigned long long state_ver = 1, xpose_ver = 0;
     bool render_proxies = false;   // option "render_proxies": avsim_render_rgb draws the collision proxies even with a visual scene loaded
     // device state (real = float, or double with AVSIM_F64_PHYSICS)
+    DevArena state;
     void *d_qpos = nullptr, *d_qvel = nullptr, *d_ctrl = nullptr, *d_warm = nullptr;
     int* d_latch = nullptr;
     IoPool io;           // device copies of the arrays of a host caller, a call's scratch (avsim_io.h)
     // per-env episodes (avsim_episode_setup; avsim_episode.hip.h): parameters, per-env bookkeeping, records, outputs nobody asked for
     bool ep_ready = false;
     EpArgs ep{};
-    std::vector<void*> ep_allocs;
+    DevArena ep_arena;
     double* ep_ap = nullptr;
     int *ep_rw = nullptr, *ep_el = nullptr;
     uint8_t *ep_su = nullptr, *ep_te = nullptr, *ep_tr = nullptr;
     int64_t* ep_id = nullptr;
-    // kernel timing
     // kernel timing: pairs of HIP events recorded around every physics launch on the launch stream, read
     // back (and only then synchronised) by avsim_kernel_time
     bool ktiming = false;
-    std::vector<hipEvent_t> kev;
-    size_t kev_used = 0;
-    double kev_ms = 0;            // launches folded out of the event list (it holds at most EV_RING pairs: a long run with kernel_timing on
-    int64_t kev_n = 0;            // and nobody asking does not grow it)
+    EventTimer ktimer;
 
     void set_error(const char* fmt, ...) {
         char buf[1024];
@@ -387,9 +385,10 @@ int avsim_create(const void* blob, size_t nbytes, int num_envs, int device, uint
     h->own_stream = true;
     for (auto& ev : h->ev) (void)hipEventCreate(&ev);
     size_t N = num_envs, r = h->rsz();
-    if (hipMalloc(&h->d_qpos, N * h->nq * r) != hipSuccess || hipMalloc(&h->d_qvel, N * h->nv * r) != hipSuccess ||
-        hipMalloc(&h->d_ctrl, N * h->nu * r) != hipSuccess || hipMalloc(&h->d_warm, N * h->nv * r) != hipSuccess ||
-        hipMalloc((void**)&h->d_latch, N * sizeof(int)) != hipSuccess) {
+    h->d_qpos = h->state.get(N * h->nq * r); h->d_qvel = h->state.get(N * h->nv * r);
+    h->d_ctrl = h->state.get(N * h->nu * r); h->d_warm = h->state.get(N * h->nv * r);
+    h->d_latch = (int*)h->state.get(N * sizeof(int));
+    if (h->state.error() != hipSuccess) {
         g_create_error = "avsim_create: hipMalloc of the state arrays failed";
         avsim_destroy(h.release());
         return AVSIM_EHIP;
@@ -414,26 +413,13 @@ void avsim_destroy(avsim_t* h) {
     if (!h) return;
     DevGuard dev_guard_(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->phys.destroy();
-    h->render.destroy();
-    h->vis.destroy();
-    h->jpeg.destroy();
-    h->jpegdec.destroy();
-    h->compose.destroy();
-    h->stage.destroy();
-    h->imgaug.destroy();
-    h->chunks.destroy();
-    h->obshist.destroy();
-    h->pointcloud.destroy();
-    for (void* p : {h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, (void*)h->d_latch})
-        if (p) (void)hipFree(p);
+    h->stage.destroy();          // (pinned memory and events next to the device buffers: these two keep a destroy())
     h->io.destroy();
-    for (void* p : h->ep_allocs) (void)hipFree(p);
     for (auto& ev : h->ev)
         if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : h->kev) (void)hipEventDestroy(ev);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    const hipStream_t own = h->own_stream ? h->stream : nullptr;
+    delete h;                    // every member's device memory and timing events
+    if (own) (void)hipStreamDestroy(own);
 }
 
 int avsim_dims(const avsim_t* h, int32_t d[AVSIM_NDIMS]) {
@@ -510,32 +496,18 @@ int avsim_event_elapsed_ms(avsim_t* h, int a, int b, float* ms) {
 int avsim_kernel_time(avsim_t* h, int reset, double* total_ms, int64_t* launches) {
     if (!h) return AVSIM_EINVAL;
     AVS_ON_DEVICE(h);
-    double tot = 0;
-    for (size_t i = 0; i + 1 < h->kev_used; i += 2) {
-        float ms = 0;
-        HIPCHK(h, hipEventSynchronize(h->kev[i + 1]));
-        HIPCHK(h, hipEventElapsedTime(&ms, h->kev[i], h->kev[i + 1]));
-        tot += ms;
-    }
-    if (total_ms) *total_ms = tot + h->kev_ms;
-    if (launches) *launches = (int64_t)(h->kev_used / 2) + h->kev_n;
-    if (reset) { h->kev_used = 0; h->kev_ms = 0; h->kev_n = 0; }
+    long long n = 0;
+    HIPCHK(h, h->ktimer.read(reset != 0, total_ms, &n));
+    if (launches) *launches = n;
     return AVSIM_OK;
 }
 
 int avsim_render_kernel_time(avsim_t* h, int reset, double* total_ms, int64_t* launches) {
     if (!h) return AVSIM_EINVAL;
     AVS_ON_DEVICE(h);
-    double tot = 0;
-    for (size_t i = 0; i + 1 < h->render.tev_used; i += 2) {
-        float ms = 0;
-        HIPCHK(h, hipEventSynchronize(h->render.tev[i + 1]));
-        HIPCHK(h, hipEventElapsedTime(&ms, h->render.tev[i], h->render.tev[i + 1]));
-        tot += ms;
-    }
-    if (total_ms) *total_ms = tot + h->render.tev_ms;
-    if (launches) *launches = (int64_t)(h->render.tev_used / 2) + h->render.tev_n;
-    if (reset) { h->render.tev_used = 0; h->render.tev_ms = 0; h->render.tev_n = 0; }
+    long long n = 0;
+    HIPCHK(h, h->render.timer.read(reset != 0, total_ms, &n));
+    if (launches) *launches = n;
     return AVSIM_OK;
 }
 
@@ -636,25 +608,9 @@ int avsim_reset(avsim_t* h, const uint8_t* mask, const double* obj_qpos) {
 
 // the physics launch of the steps, between its pair of timing events.  Device pointers all: the callers stage, and finish, round it
 static int step_common(avsim_t* h, const float* d_action, int nsub, double* dap, int32_t* drw, uint8_t* dsu) {
-    if (h->ktiming) {
-        if (h->kev_used >= 2 * EV_RING) {      // fold the recorded pairs into the running sum (waits for the newest of them: once per EV_RING launches)
-            for (size_t i = 0; i + 1 < h->kev_used; i += 2) {
-                float ms = 0;
-                HIPCHK(h, hipEventSynchronize(h->kev[i + 1]));
-                HIPCHK(h, hipEventElapsedTime(&ms, h->kev[i], h->kev[i + 1]));
-                h->kev_ms += ms;
-            }
-            h->kev_n += (int64_t)(h->kev_used / 2);
-            h->kev_used = 0;
-        }
-        while (h->kev.size() < h->kev_used + 2) { hipEvent_t e; HIPCHK(h, hipEventCreate(&e)); h->kev.push_back(e); }
-        HIPCHK(h, hipEventRecord(h->kev[h->kev_used], h->stream));
-    }
+    if (h->ktiming) HIPCHK(h, h->ktimer.begin(h->stream));      // (once per EV_RING launches this waits for the pairs held and folds them into the sum)
     if (int rc = h->phys.launch(h->stream, h->N, nsub, d_action, h->nj, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, dap, drw, dsu, h->err)) return rc;
-    if (h->ktiming) {
-        HIPCHK(h, hipEventRecord(h->kev[h->kev_used + 1], h->stream));
-        h->kev_used += 2;
-    }
+    if (h->ktiming) HIPCHK(h, h->ktimer.end(h->stream));
     return AVSIM_OK;
 }
 // ... with the three outputs every step has staged in front of it and brought back behind it
@@ -807,14 +763,14 @@ int avsim_get_contacts(avsim_t* h, int32_t* ncon, int32_t* pairs, double* dist) 
     size_t N = h->N, cap = h->phys.maxcon;
     if (h->io_device) {
         if (ncon) HIPCHK(h, hipMemcpyAsync(ncon, h->phys.d_ncon, N * 4, hipMemcpyDeviceToDevice, h->stream));
-        if (pairs) HIPCHK(h, hipMemcpyAsync(pairs, h->phys.d_cpairs, N * cap * 8, hipMemcpyDeviceToDevice, h->stream));
-        if (dist) HIPCHK(h, hipMemcpyAsync(dist, h->phys.d_cdist, N * cap * 8, hipMemcpyDeviceToDevice, h->stream));
+        if (pairs) HIPCHK(h, hipMemcpyAsync(pairs, h->phys.cpairs.ptr(), N * cap * 8, hipMemcpyDeviceToDevice, h->stream));
+        if (dist) HIPCHK(h, hipMemcpyAsync(dist, h->phys.cdist.ptr(), N * cap * 8, hipMemcpyDeviceToDevice, h->stream));
         return AVSIM_OK;
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (ncon) HIPCHK(h, hipMemcpy(ncon, h->phys.d_ncon, N * 4, hipMemcpyDeviceToHost));
-    if (pairs) HIPCHK(h, hipMemcpy(pairs, h->phys.d_cpairs, N * cap * 8, hipMemcpyDeviceToHost));
-    if (dist) HIPCHK(h, hipMemcpy(dist, h->phys.d_cdist, N * cap * 8, hipMemcpyDeviceToHost));
+    if (pairs) HIPCHK(h, hipMemcpy(pairs, h->phys.cpairs.ptr(), N * cap * 8, hipMemcpyDeviceToHost));
+    if (dist) HIPCHK(h, hipMemcpy(dist, h->phys.cdist.ptr(), N * cap * 8, hipMemcpyDeviceToHost));
     return AVSIM_OK;
 }
 
@@ -964,8 +920,8 @@ int avsim_voxel_grid(avsim_t* h, const int32_t* cam_ids, int ncam, int height, i
     if (h->pointcloud.reserve_poses(chunk, ncam, h->err)) return AVSIM_EHIP;
     for (int e0 = 0; e0 < h->N; e0 += chunk) {          // envs in chunks, as PcHost::run: the pose scratch is a chunk's
         const int n = h->N - e0 < chunk ? h->N - e0 : chunk;
-        if (pointcloud_poses_launch(h->stream, pc_model(h), c.pc, e0, n, h->pointcloud.d_pose, h->err)) return AVSIM_EHIP;
-        if (voxel_launch(h->stream, c, n, ddepth + (size_t)e0 * q, drgb ? drgb + (size_t)e0 * q * 3 : nullptr, h->pointcloud.d_pose, dout + (size_t)e0 * cell_floats,
+        if (pointcloud_poses_launch(h->stream, pc_model(h), c.pc, e0, n, h->pointcloud.pose.as<float>(), h->err)) return AVSIM_EHIP;
+        if (voxel_launch(h->stream, c, n, ddepth + (size_t)e0 * q, drgb ? drgb + (size_t)e0 * q * 3 : nullptr, h->pointcloud.pose.as<float>(), dout + (size_t)e0 * cell_floats,
                          (AVSIM_VOXEL_MERGE != 0) != h->voxel_other_form, h->err))
             return AVSIM_EHIP;
     }
@@ -1241,7 +1197,7 @@ int avsim_image_jitter_sums(avsim_t* h, uint64_t* sums, int nout) {
     if (!h) return AVSIM_EINVAL;
     if (!sums || nout < 1 || nout > h->imgaug.nout) { h->set_error("avsim_image_jitter_sums: %d sums asked for, the last avsim_image_jitter made %d outputs", nout, h->imgaug.nout); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
-    HIPCHK(h, hipMemcpyAsync(sums, h->imgaug.gsum, sizeof(uint64_t) * (size_t)nout, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(sums, h->imgaug.gsum.ptr(), sizeof(uint64_t) * (size_t)nout, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return AVSIM_OK;
 }
@@ -1293,10 +1249,10 @@ int avsim_reward_from_pairs(avsim_t* h, const int32_t* geom_pairs, int nsets, in
     if (!h || (!geom_pairs && cap > 0) || !reward || nsets < 0 || cap < 0) { if (h) h->set_error("avsim_reward_from_pairs: bad arguments"); return AVSIM_EINVAL; }
     if (nsets == 0) return AVSIM_OK;
     AVS_ON_DEVICE(h);
-    int *dp = nullptr, *dl = nullptr, *dr = nullptr;
+    DevBuf buf;
     const size_t pb = sizeof(int) * (size_t)nsets * (cap ? cap : 1) * 2, nb = sizeof(int) * (size_t)nsets;
-    HIPCHK(h, hipMalloc(&dp, pb + 2 * nb));
-    dl = dp + (pb / sizeof(int)); dr = dl + nsets;
+    HIPCHK(h, buf.alloc(pb + 2 * nb));
+    int *const dp = buf.as<int>(), *const dl = dp + (pb / sizeof(int)), *const dr = dl + nsets;
     hipError_t e = hipSuccess;
     if (cap) e = hipMemcpyAsync(dp, geom_pairs, sizeof(int) * (size_t)nsets * cap * 2, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = latch ? hipMemcpyAsync(dl, latch, nb, hipMemcpyHostToDevice, h->stream) : hipMemsetAsync(dl, 0, nb, h->stream);
@@ -1309,7 +1265,6 @@ int avsim_reward_from_pairs(avsim_t* h, const int32_t* geom_pairs, int nsets, in
     if (e == hipSuccess) e = hipMemcpyAsync(reward, dr, nb, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess && latch) e = hipMemcpyAsync(latch, dl, nb, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(dp);
     if (e != hipSuccess) { h->set_error("avsim_reward_from_pairs: %s", hipGetErrorString(e)); return AVSIM_EHIP; }
     return AVSIM_OK;
 }
@@ -1317,12 +1272,6 @@ int avsim_reward_from_pairs(avsim_t* h, const int32_t* geom_pairs, int nsets, in
 }  // extern "C"
 
 // ---- per-env episodes (avsim_episode.hip.h) ----------------------------------------------------------------------------------------
-static int ep_alloc(avsim_t* h, size_t bytes, void** p) {
-    if (hipMalloc(p, bytes ? bytes : 1) != hipSuccess) { *p = nullptr; h->set_error("avsim_episode_setup: hipMalloc(%zu) failed", bytes); return AVSIM_EHIP; }
-    h->ep_allocs.push_back(*p);
-    return 0;
-}
-
 template <typename real>
 static void ep_launch(avsim_t* h, int mode, const uint8_t* mask, double* ap, int* rw, uint8_t* su, uint8_t* te, uint8_t* tr, int64_t* id, int* el) {
     EpArgs A = h->ep;
@@ -1341,8 +1290,7 @@ int avsim_episode_setup(avsim_t* h, const double* box, const int32_t* share, uin
     if (h->nobj > EP_MAXOBJ) { h->set_error("avsim_episode_setup: at most %d free objects", EP_MAXOBJ); return AVSIM_EINVAL; }
     AVS_ON_DEVICE(h);
     HIPCHK(h, hipStreamSynchronize(h->stream));          // (buffers of an earlier set-up may still be in use)
-    for (void* p : h->ep_allocs) (void)hipFree(p);
-    h->ep_allocs.clear();
+    h->ep_arena.clear();
     h->ep_ready = false;
     const size_t N = h->N, no = h->nobj, L = (size_t)log_capacity;
     EpArgs& A = h->ep;
@@ -1350,9 +1298,7 @@ int avsim_episode_setup(avsim_t* h, const double* box, const int32_t* share, uin
     A.N = h->N; A.nq = h->nq; A.nv = h->nv; A.nu = h->nu; A.nj = h->nj; A.nobj = h->nobj;
     A.max_steps = max_episode_steps; A.term_on_success = terminate_on_success != 0; A.seed = seed; A.log_cap = log_capacity;
     A.qhome = h->phys.d_qpos_home; A.chome = h->phys.d_ctrl_home; A.objadr = h->phys.d_obj_qadr; A.obj_reset = h->phys.d_obj_reset;
-    void* p;
-    int rc;
-#define EPA(field, T, n) do { if ((rc = ep_alloc(h, sizeof(T) * (n), &p))) return rc; field = (T*)p; } while (0)
+#define EPA(field, T, n) do { if (!(field = (T*)h->ep_arena.get(sizeof(T) * (n)))) { h->set_error("avsim_episode_setup: hipMalloc(%zu) failed", sizeof(T) * (n)); return AVSIM_EHIP; } } while (0)
     EPA(A.id, int64_t, N); EPA(A.elapsed, int, N); EPA(A.maxr, int, N); EPA(A.ret, double, N); EPA(A.succ, uint8_t, N); EPA(A.pending, uint8_t, N);
     EPA(A.log_ret, double, L); EPA(A.log_obj, double, L * no * 7); EPA(A.log_len, int, L); EPA(A.log_maxr, int, L); EPA(A.log_succ, uint8_t, L);
     EPA(A.count, int64_t, 2);

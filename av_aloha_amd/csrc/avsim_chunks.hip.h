@@ -14,6 +14,8 @@
 #include <string>
 #include <vector>
 
+#include "avsim_dev.h"
+
 namespace avs {
 
 constexpr int CHK_MAX_C = 1024, CHK_MAX_A = 64;
@@ -73,12 +75,11 @@ void chunk_launch_step(hipStream_t stream, const ChunkArgs& P, const float* chun
 struct ChunkHost {
     bool ready = false;
     ChunkArgs P{};
-    std::vector<void*> allocs;
+    DevArena arena;
     std::vector<float> host_tab;      // what the set-up uploads: w, cum, mean, std (kept until the next set-up)
 
     void destroy() {
-        for (void* p : allocs) (void)hipFree(p);
-        allocs.clear();
+        arena.clear();
         ready = false;
         P = ChunkArgs{};
     }
@@ -91,15 +92,7 @@ struct ChunkHost {
         a.has_ms = mean_std != nullptr;
         a.magic = A >= 2 ? (unsigned)(0x100000000ull / (unsigned)A) + 1u : 0u;
         const size_t n = (size_t)N, rows = mode == CHK_QUEUE ? (size_t)k : (size_t)C;
-        hipError_t e = hipSuccess;
-        auto get = [&](size_t bytes) -> void* {
-            void* p = nullptr;
-            if (e != hipSuccess) return nullptr;
-            if ((e = hipMalloc(&p, bytes ? bytes : 1)) != hipSuccess) return nullptr;
-            allocs.push_back(p);
-            if ((e = hipMemsetAsync(p, 0, bytes ? bytes : 1, stream)) != hipSuccess) return nullptr;
-            return p;
-        };
+        auto get = [&](size_t bytes) { return arena.zeroed(bytes, stream); };
         a.last_id = (int64_t*)get(sizeof(int64_t) * n);
         a.stepped = (int*)get(sizeof(int) * n); a.sa = (int*)get(sizeof(int) * n); a.sb = (int*)get(sizeof(int) * n);
         a.cur_a = (int*)get(sizeof(int) * n); a.cur_b = (int*)get(sizeof(int) * n);
@@ -107,6 +100,7 @@ struct ChunkHost {
         a.prev = (float*)get(sizeof(float) * n * A);
         a.starved = (unsigned long long*)get(sizeof(unsigned long long));
         float* tab = (float*)get(sizeof(float) * (2 * (size_t)C + 2 * (size_t)A));
+        hipError_t e = arena.error();
         if (e == hipSuccess) {
             host_tab.assign(2 * (size_t)C + 2 * (size_t)A, 0.0f);
             if (tables) std::copy(tables, tables + 2 * C, host_tab.begin());

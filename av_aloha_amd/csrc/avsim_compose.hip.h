@@ -257,43 +257,30 @@ inline void compose_axis_table(int n_in, int n_out, std::vector<int>& tab, int& 
 struct ComposeHost {
     struct Table {
         int n_in, n_out, ks;
-        int* dev;
+        DevBuf dev;
         std::unique_ptr<std::vector<int>> host;      // the upload's source: never written again
     };
     struct Call {                                    // the validated host arrays of a call and their device form
         std::vector<int32_t> key;
-        void* dev;
+        DevBuf dev;
         std::unique_ptr<std::vector<uint8_t>> host;
         int gx, gy;
     };
     std::vector<Table> tables;
     std::vector<Call> calls;
-    float* d_unit = nullptr;
+    DevBuf d_unit;
     std::unique_ptr<std::vector<float>> unit_host;
 
     void drop(hipStream_t stream) {
         (void)hipStreamSynchronize(stream);
-        for (auto& t : tables) (void)hipFree(t.dev);
-        for (auto& c : calls) (void)hipFree(c.dev);
         tables.clear();
         calls.clear();
     }
-    void destroy() {
-        for (auto& t : tables) (void)hipFree(t.dev);
-        for (auto& c : calls) (void)hipFree(c.dev);
-        tables.clear();
-        calls.clear();
-        if (d_unit) (void)hipFree(d_unit);
-        d_unit = nullptr;
-        unit_host.reset();
-    }
-    int upload(hipStream_t stream, const void* host, size_t bytes, void** dev, std::string& err) {
-        *dev = nullptr;
-        hipError_t rc = hipMalloc(dev, bytes ? bytes : 4);
-        if (rc == hipSuccess && bytes) rc = hipMemcpyAsync(*dev, host, bytes, hipMemcpyHostToDevice, stream);
+    int upload(hipStream_t stream, const void* host, size_t bytes, DevBuf& dev, std::string& err) {
+        hipError_t rc = dev.alloc(bytes ? bytes : 4);
+        if (rc == hipSuccess && bytes) rc = hipMemcpyAsync(dev.ptr(), host, bytes, hipMemcpyHostToDevice, stream);
         if (rc != hipSuccess) {
-            if (*dev) (void)hipFree(*dev);
-            *dev = nullptr;
+            dev.free();
             err = std::string("compose tables: ") + hipGetErrorString(rc);
             return -3;
         }
@@ -303,7 +290,7 @@ struct ComposeHost {
         if (d_unit) return 0;
         unit_host = std::make_unique<std::vector<float>>(256);
         for (int k = 0; k < 256; k++) (*unit_host)[k] = (float)k / 255.0f;      // divided on the host, as the renderer's and the decoder's table
-        return upload(stream, unit_host->data(), 256 * sizeof(float), (void**)&d_unit, err);
+        return upload(stream, unit_host->data(), 256 * sizeof(float), d_unit, err);
     }
     // the table of an axis (nullptr for equal sizes); -1: some tile would need more rows than the kernel's LDS holds
     int table(hipStream_t stream, int n_in, int n_out, bool vertical, const int** dev, int* ks, std::string& err) {
@@ -311,13 +298,13 @@ struct ComposeHost {
         *ks = 0;
         if (n_in == n_out) return 0;
         for (auto& t : tables)
-            if (t.n_in == n_in && t.n_out == n_out) { *dev = t.dev; *ks = t.ks; return vertical ? rows_fit(*t.host, n_out, err) : 0; }
-        Table t{n_in, n_out, 0, nullptr, std::make_unique<std::vector<int>>()};
+            if (t.n_in == n_in && t.n_out == n_out) { *dev = t.dev.as<int>(); *ks = t.ks; return vertical ? rows_fit(*t.host, n_out, err) : 0; }
+        Table t{n_in, n_out, 0, DevBuf{}, std::make_unique<std::vector<int>>()};
         compose_axis_table(n_in, n_out, *t.host, t.ks);
         if (vertical && rows_fit(*t.host, n_out, err)) return -1;
-        int rc = upload(stream, t.host->data(), t.host->size() * sizeof(int), (void**)&t.dev, err);
+        int rc = upload(stream, t.host->data(), t.host->size() * sizeof(int), t.dev, err);
         if (rc) return rc;
-        *dev = t.dev;
+        *dev = t.dev.as<int>();
         *ks = t.ks;
         tables.push_back(std::move(t));
         return 0;
@@ -358,21 +345,21 @@ struct ComposeHost {
                 gx = std::max(gx, (q.w + CMP_TW - 1) / CMP_TW);
                 gy = std::max(gy, (q.h + CMP_TH - 1) / CMP_TH);
             }
-            Call c{std::move(key), nullptr, std::move(host), gx, gy};
-            if ((rc = upload(stream, c.host->data(), c.host->size(), &c.dev, err))) return rc;
+            Call c{std::move(key), DevBuf{}, std::move(host), gx, gy};
+            if ((rc = upload(stream, c.host->data(), c.host->size(), c.dev, err))) return rc;
             calls.push_back(std::move(c));
             call = &calls.back();
         }
         if (clear) {
             const size_t plane = (size_t)CH * CW, total = (size_t)nout * plane * 3;
             const unsigned blocks = (unsigned)std::min<size_t>((total / (df ? 1 : 4) + 255) / 256 + 1, 16384);
-            if (df == 0) hipLaunchKernelGGL(k_compose_fill<0>, dim3(blocks), dim3(256), 0, stream, canvas, total, plane, clear_rgb, d_unit);
-            else hipLaunchKernelGGL(k_compose_fill<1>, dim3(blocks), dim3(256), 0, stream, canvas, total, plane, clear_rgb, d_unit);
+            if (df == 0) hipLaunchKernelGGL(k_compose_fill<0>, dim3(blocks), dim3(256), 0, stream, canvas, total, plane, clear_rgb, d_unit.as<float>());
+            else hipLaunchKernelGGL(k_compose_fill<1>, dim3(blocks), dim3(256), 0, stream, canvas, total, plane, clear_rgb, d_unit.as<float>());
         }
-        const ComposePlace* dp = (const ComposePlace*)call->dev;
+        const ComposePlace* dp = call->dev.as<const ComposePlace>();
         for (int p0 = 0; p0 < nplace; p0 += 65535) {
             const dim3 grid(call->gx, call->gy, std::min(65535, nplace - p0));
-#define CMP_LAUNCH(S, D) hipLaunchKernelGGL((k_compose<S, D>), grid, dim3(CMP_THREADS), 0, stream, dp, p0, src, SH, SW, canvas, CH, CW, d_unit)
+#define CMP_LAUNCH(S, D) hipLaunchKernelGGL((k_compose<S, D>), grid, dim3(CMP_THREADS), 0, stream, dp, p0, src, SH, SW, canvas, CH, CW, d_unit.as<float>())
             if (sf == 0 && df == 0) CMP_LAUNCH(0, 0);
             else if (sf == 0) CMP_LAUNCH(0, 1);
             else if (df == 0) CMP_LAUNCH(1, 0);
@@ -446,15 +433,15 @@ struct ComposeHost {
             if (calls.size() >= 64) drop(stream);
             auto host = std::make_unique<std::vector<uint8_t>>((size_t)nlabel * 4 * sizeof(int32_t));
             std::memcpy(host->data(), where, host->size());
-            Call c{std::move(key), nullptr, std::move(host), 0, 0};
-            if ((rc = upload(stream, c.host->data(), c.host->size(), &c.dev, err))) return rc;
+            Call c{std::move(key), DevBuf{}, std::move(host), 0, 0};
+            if ((rc = upload(stream, c.host->data(), c.host->size(), c.dev, err))) return rc;
             calls.push_back(std::move(c));
             call = &calls.back();
         }
         ComposeText text{};
         if (np) std::memcpy(text.c, prefix, np);
-        if (df == 0) hipLaunchKernelGGL(k_compose_label<0>, dim3(nlabel), dim3(256), 0, stream, (const int*)call->dev, text, (int)np, value, canvas, CH, CW, rgb, d_unit);
-        else hipLaunchKernelGGL(k_compose_label<1>, dim3(nlabel), dim3(256), 0, stream, (const int*)call->dev, text, (int)np, value, canvas, CH, CW, rgb, d_unit);
+        if (df == 0) hipLaunchKernelGGL(k_compose_label<0>, dim3(nlabel), dim3(256), 0, stream, call->dev.as<const int>(), text, (int)np, value, canvas, CH, CW, rgb, d_unit.as<float>());
+        else hipLaunchKernelGGL(k_compose_label<1>, dim3(nlabel), dim3(256), 0, stream, call->dev.as<const int>(), text, (int)np, value, canvas, CH, CW, rgb, d_unit.as<float>());
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) { err = std::string("compose label kernel: ") + hipGetErrorString(e); return -3; }
         return 0;

@@ -151,31 +151,16 @@ int imgaug_launch_affine(hipStream_t stream, const void* src, int SH, int SW, co
 // The host side of avsim_image_jitter: the gray sums behind contrast, one 64-bit slot per output, grown on demand and kept for
 // avsim_image_jitter_sums; the per-call arrays go through the library's pinned staging like avsim_image_prep's
 struct ImgAugHost {
-    unsigned long long* gsum = nullptr;
-    size_t gsum_cap = 0;
+    DevBuf gsum;       // unsigned long long [outputs, rounded up to 512]
     int nout = 0;      // the outputs of the last call
     // avsim_image_augment: the float images of the outputs that have sharpness and bit 5, a group at a time; grown on demand, at most
     // scratch_limit bytes (option "augment_scratch_bytes") unless one image alone is larger
-    float* scratch = nullptr;
-    size_t scratch_cap = 0, scratch_limit = IAG_SCRATCH_BYTES;
-
-    void destroy() {
-        if (gsum) (void)hipFree(gsum);
-        if (scratch) (void)hipFree(scratch);
-        const size_t limit = scratch_limit;
-        *this = ImgAugHost{};
-        scratch_limit = limit;
-    }
+    DevBuf scratch;
+    size_t scratch_limit = IAG_SCRATCH_BYTES;
 
     int grow_sums(int n, std::string& err) {
-        if (gsum_cap >= (size_t)n) return 0;
-        if (gsum) (void)hipFree(gsum);
-        gsum = nullptr;
-        gsum_cap = 0;
-        const size_t cap = ((size_t)n + 511) & ~(size_t)511;
-        const hipError_t e = hipMalloc((void**)&gsum, sizeof(unsigned long long) * cap);
-        if (e != hipSuccess) { gsum = nullptr; err = std::string("image jitter sums: ") + hipGetErrorString(e); return -3; }
-        gsum_cap = cap;
+        const hipError_t e = gsum.reserve(sizeof(unsigned long long) * (((size_t)n + 511) & ~(size_t)511));
+        if (e != hipSuccess) { err = std::string("image jitter sums: ") + hipGetErrorString(e); return -3; }
         return 0;
     }
 
@@ -192,18 +177,12 @@ struct ImgAugHost {
         if (count[2] > 0) {
             const size_t one = sizeof(float) * 3 * (size_t)SH * SW;
             group = (int)std::min<size_t>(std::min<size_t>((size_t)count[2], 65535), std::max<size_t>(1, scratch_limit / one));
-            if (scratch_cap < one * group) {      // (hipFree waits for the kernels that still read the old one)
-                if (scratch) (void)hipFree(scratch);
-                scratch = nullptr;
-                scratch_cap = 0;
-                const hipError_t e = hipMalloc((void**)&scratch, one * group);
-                if (e != hipSuccess) { scratch = nullptr; err = std::string("image augment scratch: ") + hipGetErrorString(e); return -3; }
-                scratch_cap = one * group;
-            }
+            const hipError_t e = scratch.reserve(one * group);      // (growing frees the old one, which waits for the kernels that still read it)
+            if (e != hipSuccess) { err = std::string("image augment scratch: ") + hipGetErrorString(e); return -3; }
         }
         if (ring.upload(*s, bytes, stream, err)) return -3;
         std::string lerr;
-        const int lrc = imgaug_launch_affine(stream, src, SH, SW, s->dev, n, ncon, count, interp, mean_std != nullptr, oh, ow, gsum, scratch, group, out, lerr);
+        const int lrc = imgaug_launch_affine(stream, src, SH, SW, s->dev.ptr(), n, ncon, count, interp, mean_std != nullptr, oh, ow, gsum.as<unsigned long long>(), scratch.as<float>(), group, out, lerr);
         const int rc = ring.release(*s, stream, err);
         if (lrc) { err = lerr; return lrc; }
         if (rc == 0) nout = n;
@@ -220,7 +199,7 @@ struct ImgAugHost {
         const int ncon = imgaug_pack(s->pin, box_mask, factor, src_index, n, mean_std);
         if (ring.upload(*s, bytes, stream, err)) return -3;
         std::string lerr;
-        const int lrc = imgaug_launch(stream, src, SH, SW, s->dev, n, ncon, mean_std != nullptr, oh, ow, gsum, out, lerr);
+        const int lrc = imgaug_launch(stream, src, SH, SW, s->dev.ptr(), n, ncon, mean_std != nullptr, oh, ow, gsum.as<unsigned long long>(), out, lerr);
         const int rc = ring.release(*s, stream, err);
         if (lrc) { err = lerr; return lrc; }
         if (rc == 0) nout = n;

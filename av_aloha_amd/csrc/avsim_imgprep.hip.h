@@ -273,8 +273,8 @@ struct ImgPrepHost {
         const int bands = (oh + rb - 1) / rb;
         for (int i0 = 0; i0 < nout; i0 += 65535) {
             const dim3 grid(bands, std::min(65535, nout - i0));
-            if (sf == 0) hipLaunchKernelGGL(k_image_prep<0>, grid, dim3(IPR_THREADS), 0, stream, src, SH, SW, lut, (const PrepItem*)s.dev, i0, oh, ow, rb, out);
-            else hipLaunchKernelGGL(k_image_prep<1>, grid, dim3(IPR_THREADS), 0, stream, src, SH, SW, lut, (const PrepItem*)s.dev, i0, oh, ow, rb, out);
+            if (sf == 0) hipLaunchKernelGGL(k_image_prep<0>, grid, dim3(IPR_THREADS), 0, stream, src, SH, SW, lut, s.dev.as<const PrepItem>(), i0, oh, ow, rb, out);
+            else hipLaunchKernelGGL(k_image_prep<1>, grid, dim3(IPR_THREADS), 0, stream, src, SH, SW, lut, s.dev.as<const PrepItem>(), i0, oh, ow, rb, out);
         }
         const hipError_t e = hipGetLastError();
         const int rc = ring.release(s, stream, err);

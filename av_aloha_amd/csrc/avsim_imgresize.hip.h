@@ -111,7 +111,7 @@ inline int imgresize_run(StageRing& ring, hipStream_t stream, const void* src, i
     imgresize_pack(s->pin, src_box, dst, src_index, n, fill, mean_std, count);
     if (ring.upload(*s, bytes, stream, err)) return -3;
     std::string lerr;
-    const int lrc = imgresize_launch(stream, src, fmt, SH, SW, s->dev, n, count, antialias, mean_std != nullptr, oh, ow, out, lerr);
+    const int lrc = imgresize_launch(stream, src, fmt, SH, SW, s->dev.ptr(), n, count, antialias, mean_std != nullptr, oh, ow, out, lerr);
     const int rc = ring.release(*s, stream, err);
     if (lrc) { err = lerr; return lrc; }
     return rc;

@@ -12,6 +12,8 @@
 #include <string>
 #include <thread>
 
+#include "avsim_devbuf.h"
+
 namespace avs {
 
 struct IoPool {
@@ -24,14 +26,15 @@ struct IoPool {
     static constexpr size_t PIPELINE_FROM = (size_t)16 << 20, PIN_CHUNK = (size_t)32 << 20;
     static constexpr int COPY_THREADS = 4;
 
-    void* buf[NBUF] = {};      // grow-only, each as large as the largest array it has served
+    DevBuf own[NBUF];          // grow-only, each as large as the largest array it has served
+    void* buf[NBUF] = {};      // own[k]'s pointer and capacity as grow() and destroy() left them: what the calls (and tests/hostshim_io) read
     size_t cap[NBUF] = {};
     void* pin[2] = {};
     hipEvent_t pin_ev[2] = {};
 
     void destroy() {
         for (int k = 0; k < NBUF; k++) {
-            if (buf[k]) (void)hipFree(buf[k]);
+            own[k].free();
             buf[k] = nullptr;
             cap[k] = 0;
         }
@@ -41,6 +44,14 @@ struct IoPool {
             pin[k] = nullptr;
             pin_ev[k] = nullptr;
         }
+    }
+
+    // buffer k, at least `bytes` large; empty after a failure
+    hipError_t grow(int k, size_t bytes) {
+        const hipError_t e = own[k].reserve(bytes);
+        buf[k] = own[k].ptr();
+        cap[k] = own[k].cap();
+        return e;
     }
 
     // the two pinned chunks and their events, made at the first large result; false: there is no pinned memory to have (the plain copy serves)
@@ -165,15 +176,8 @@ private:
             return nullptr;
         }
         const int k = used_++;
-        if (pool_.cap[k] < bytes) {
-            if (pool_.buf[k]) (void)hipFree(pool_.buf[k]);
-            pool_.buf[k] = nullptr;
-            pool_.cap[k] = 0;
-            check(hipMalloc(&pool_.buf[k], bytes), "hipMalloc", bytes);
-            if (e_ != hipSuccess) return pool_.buf[k] = nullptr;
-            pool_.cap[k] = bytes;
-        }
-        return pool_.buf[k];
+        if (pool_.cap[k] < bytes) check(pool_.grow(k, bytes), "hipMalloc", bytes);
+        return e_ == hipSuccess ? pool_.buf[k] : nullptr;
     }
     void* upload(void* d, const void* p, size_t bytes) {
         if (e_ != hipSuccess) return nullptr;

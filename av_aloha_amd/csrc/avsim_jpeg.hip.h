@@ -19,6 +19,8 @@
 #include <string>
 #include <vector>
 
+#include "avsim_dev.h"
+
 namespace avs {
 
 constexpr int JPG_HDR = 629;                 // SOI APP0 DQT DQT SOF0 DHT x 4 DRI SOS
@@ -746,37 +748,27 @@ inline void jpeg_build_tables(int H, int W, int quality, JpegTables& t) {
 struct JpegHost {
     struct Entry {
         int H, W, quality;
-        JpegTables* dev;
+        DevBuf dev;                              // a JpegTables
         std::unique_ptr<JpegTables> host;        // the upload's source: never written again
     };
     std::vector<Entry> cache;                    // tables of the shapes / qualities seen
-    uint8_t* d_stage = nullptr;                  // [images of a launch][interval][cap]: the intervals' bytes before they are packed
-    size_t stage_sz = 0;
-    int* d_ivlen = nullptr;
-    size_t ivlen_n = 0;
+    DevBuf stage;                                // [images of a launch][interval][cap]: the intervals' bytes before they are packed
+    DevBuf ivlen;
     size_t stage_budget = (size_t)512 << 20;     // a call whose staging would be larger goes through the kernels in groups of images
 
-    void destroy() {
-        for (auto& e : cache) (void)hipFree(e.dev);
-        cache.clear();
-        if (d_stage) (void)hipFree(d_stage);
-        if (d_ivlen) (void)hipFree(d_ivlen);
-        d_stage = nullptr; d_ivlen = nullptr; stage_sz = 0; ivlen_n = 0;
-    }
     int tables(hipStream_t stream, int H, int W, int quality, const JpegTables** out, std::string& err) {
         for (auto& e : cache)
-            if (e.H == H && e.W == W && e.quality == quality) { *out = e.dev; return 0; }
+            if (e.H == H && e.W == W && e.quality == quality) { *out = e.dev.as<JpegTables>(); return 0; }
         if (cache.size() >= 64) {                // (a caller that walks through shapes: start over once nothing reads the old ones)
             (void)hipStreamSynchronize(stream);
-            for (auto& e : cache) (void)hipFree(e.dev);
             cache.clear();
         }
-        Entry e{H, W, quality, nullptr, std::make_unique<JpegTables>()};
+        Entry e{H, W, quality, DevBuf{}, std::make_unique<JpegTables>()};
         jpeg_build_tables(H, W, quality, *e.host);
-        hipError_t rc = hipMalloc(&e.dev, sizeof(JpegTables));
-        if (rc == hipSuccess) rc = hipMemcpyAsync(e.dev, e.host.get(), sizeof(JpegTables), hipMemcpyHostToDevice, stream);
-        if (rc != hipSuccess) { if (e.dev) (void)hipFree(e.dev); err = std::string("jpeg tables: ") + hipGetErrorString(rc); return -3; }
-        *out = e.dev;
+        hipError_t rc = e.dev.reserve(sizeof(JpegTables));
+        if (rc == hipSuccess) rc = hipMemcpyAsync(e.dev.ptr(), e.host.get(), sizeof(JpegTables), hipMemcpyHostToDevice, stream);
+        if (rc != hipSuccess) { err = std::string("jpeg tables: ") + hipGetErrorString(rc); return -3; }
+        *out = e.dev.as<JpegTables>();
         cache.push_back(std::move(e));
         return 0;
     }
@@ -795,18 +787,9 @@ struct JpegHost {
         size_t group = stage_budget / per_img;
         group = group < 1 ? 1 : group > (size_t)nimg ? (size_t)nimg : group;
         if (group * mh > 0x3fffffffULL) group = 0x3fffffffULL / mh;
-        if (stage_sz < group * per_img) {
-            if (d_stage) (void)hipFree(d_stage);
-            d_stage = nullptr; stage_sz = 0;
-            if (hipMalloc(&d_stage, group * per_img) != hipSuccess) { err = "jpeg staging: hipMalloc failed"; return -3; }
-            stage_sz = group * per_img;
-        }
-        if (ivlen_n < group * mh) {
-            if (d_ivlen) (void)hipFree(d_ivlen);
-            d_ivlen = nullptr; ivlen_n = 0;
-            if (hipMalloc(&d_ivlen, group * mh * sizeof(int)) != hipSuccess) { err = "jpeg staging: hipMalloc failed"; return -3; }
-            ivlen_n = group * mh;
-        }
+        if (stage.reserve(group * per_img) != hipSuccess || ivlen.reserve(group * mh * sizeof(int)) != hipSuccess) { err = "jpeg staging: hipMalloc failed"; return -3; }
+        uint8_t* const d_stage = stage.as<uint8_t>();
+        int* const d_ivlen = ivlen.as<int>();
         for (int i0 = 0; i0 < nimg; i0 += (int)group) {
             const int n = nimg - i0 < (int)group ? nimg - i0 : (int)group;
             if (fmt == 0) hipLaunchKernelGGL(k_jpeg_interval<0>, dim3(n * mh), dim3(64), 0, stream, T, img, index, i0, H, W, mw, mh, d_stage, (int)cap, d_ivlen);
@@ -854,51 +837,36 @@ inline int jpeg_build_dec_tables(JpegDecTables& t) {
 }
 
 struct JpegDecHost {
-    JpegDecTables* d_tab = nullptr;
+    DevBuf tab;                                  // a JpegDecTables
     std::unique_ptr<JpegDecTables> host;         // the upload's source: never written again
-    int16_t* d_coef = nullptr;                   // [images of a launch][MCU row][MCU][6][64]: zeroed, then the entropy decoder's coefficients
-    size_t coef_sz = 0;
-    int* d_ivoff = nullptr;                      // [image][mh + 1]
-    size_t ivoff_n = 0;
-    uint8_t* d_qtab = nullptr;                   // [image][2][64], natural order
-    size_t qtab_n = 0;
+    DevBuf coef;                                 // int16 [images of a launch][MCU row][MCU][6][64]: zeroed, then the entropy decoder's coefficients
+    DevBuf ivoff;                                // int [image][mh + 1]
+    DevBuf qtab;                                 // u8 [image][2][64], natural order
     size_t coef_budget = (size_t)512 << 20;      // a call whose staging would be larger goes through the kernels in groups of images
 
-    void destroy() {
-        for (void* p : {(void*)d_tab, (void*)d_coef, (void*)d_ivoff, (void*)d_qtab})
-            if (p) (void)hipFree(p);
-        d_tab = nullptr; d_coef = nullptr; d_ivoff = nullptr; d_qtab = nullptr;
-        coef_sz = ivoff_n = qtab_n = 0;
-        host.reset();
-    }
-    template <typename P>
-    static bool grow(P*& p, size_t& have, size_t want) {
-        if (have >= want) return true;
-        if (p) (void)hipFree(p);
-        p = nullptr; have = 0;
-        if (hipMalloc(&p, want * sizeof(P)) != hipSuccess) return false;
-        have = want;
-        return true;
-    }
     // in, in_len, index, out, status: device pointers
     int launch(hipStream_t stream, const uint8_t* in, long long stride, const int* in_len, const int* index, int nimg, int H, int W, int fmt, int upsample,
                void* out, int* status, std::string& err, hipEvent_t* ev = nullptr) {          // ev: four events recorded around the three kernels (of the last group)
-        if (!d_tab) {
+        if (!tab) {
             host = std::make_unique<JpegDecTables>();
             if (jpeg_build_dec_tables(*host)) { err = "jpeg decode tables: more long-code prefixes than JPD_NSUB"; host.reset(); return -3; }
-            hipError_t rc = hipMalloc(&d_tab, sizeof(JpegDecTables));
-            if (rc == hipSuccess) rc = hipMemcpyAsync(d_tab, host.get(), sizeof(JpegDecTables), hipMemcpyHostToDevice, stream);
-            if (rc != hipSuccess) { if (d_tab) (void)hipFree(d_tab); d_tab = nullptr; err = std::string("jpeg decode tables: ") + hipGetErrorString(rc); return -3; }
+            hipError_t rc = tab.reserve(sizeof(JpegDecTables));
+            if (rc == hipSuccess) rc = hipMemcpyAsync(tab.ptr(), host.get(), sizeof(JpegDecTables), hipMemcpyHostToDevice, stream);
+            if (rc != hipSuccess) { tab.free(); err = std::string("jpeg decode tables: ") + hipGetErrorString(rc); return -3; }
         }
         const int mh = (H + 15) / 16, mw = (W + 15) / 16;
         const size_t per_img = (size_t)mh * mw * 384;                 // coefficients
         size_t group = coef_budget / (per_img * sizeof(int16_t));
         group = group < 1 ? 1 : group > (size_t)nimg ? (size_t)nimg : group;
         if (group > 65535) group = 65535;                             // (gridDim.z)
-        if (!grow(d_coef, coef_sz, group * per_img) || !grow(d_ivoff, ivoff_n, group * (mh + 1)) || !grow(d_qtab, qtab_n, group * 128)) {
+        if (coef.reserve(group * per_img * sizeof(int16_t)) != hipSuccess || ivoff.reserve(group * (mh + 1) * sizeof(int)) != hipSuccess || qtab.reserve(group * 128) != hipSuccess) {
             err = "jpeg decode staging: hipMalloc failed";
             return -3;
         }
+        const JpegDecTables* const d_tab = tab.as<JpegDecTables>();
+        int16_t* const d_coef = coef.as<int16_t>();
+        int* const d_ivoff = ivoff.as<int>();
+        uint8_t* const d_qtab = qtab.as<uint8_t>();
         const int nchunk = (mw + JPD_K - 1) / JPD_K;
         for (int i0 = 0; i0 < nimg; i0 += (int)group) {
             const int n = nimg - i0 < (int)group ? nimg - i0 : (int)group;

@@ -15,6 +15,8 @@
 #include <string>
 #include <vector>
 
+#include "avsim_dev.h"
+
 namespace avs {
 
 constexpr int OBH_MAX_K = 16, OBH_MAX_D = 256, OBH_MAX_CAMS = 8;
@@ -81,13 +83,12 @@ void obs_launch_push(hipStream_t stream, const ObsArgs& P, const ObsPtrs& Q, con
 struct ObsHistHost {
     bool ready = false;
     ObsArgs P{};
-    std::vector<void*> allocs;
+    DevArena arena;
     std::vector<float> host_f;        // what the set-up uploads (kept until the next set-up): mean, std, the tables
     std::vector<int> host_box;
 
     void destroy() {
-        for (void* p : allocs) (void)hipFree(p);
-        allocs.clear();
+        arena.clear();
         ready = false;
         P = ObsArgs{};
     }
@@ -100,21 +101,14 @@ struct ObsHistHost {
         a.N = N; a.K = K; a.D = D; a.has_ms = mean_std != nullptr && D > 0; a.ncam = ncam;
         if (ncam > 0) { a.fmt = fmt; a.SH = SH; a.SW = SW; a.oh = oh; a.ow = ow; }
         const size_t n = (size_t)N;
-        hipError_t e = hipSuccess;
-        auto get = [&](size_t bytes) -> void* {
-            void* p = nullptr;
-            if (e != hipSuccess) return nullptr;
-            if ((e = hipMalloc(&p, bytes ? bytes : 1)) != hipSuccess) return nullptr;
-            allocs.push_back(p);
-            if ((e = hipMemsetAsync(p, 0, bytes ? bytes : 1, stream)) != hipSuccess) return nullptr;
-            return p;
-        };
+        auto get = [&](size_t bytes) { return arena.zeroed(bytes, stream); };
         a.last_id = (int64_t*)get(sizeof(int64_t) * n);
         a.pushed = (int*)get(sizeof(int) * n);
         a.cur_fresh = (int*)get(sizeof(int) * n);
         const size_t nf = 2 * (size_t)D + 768 * (size_t)ncam;
         float* f = (float*)get(sizeof(float) * nf);
         int* b = (int*)get(sizeof(int) * 3 * (size_t)(ncam ? ncam : 1));
+        hipError_t e = arena.error();
         if (e == hipSuccess) {
             host_f.assign(nf ? nf : 1, 0.0f);
             if (a.has_ms) std::copy(mean_std, mean_std + 2 * D, host_f.begin());

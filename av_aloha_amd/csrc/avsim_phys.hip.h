@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "avsim_collide.hip.h"
+#include "avsim_dev.h"
 #include "avsim_math.hip.h"
 #include "avsim_model.h"
 #include "avsim_phys_layout.h"
@@ -3588,36 +3589,36 @@ struct PhysHost {
     int specialised = 1;            // option "phys_specialised": 0 never, 1 the kernel compiled for the model when one matches, 2 require one
     bool host_only = false;         // init() assembles the table image, the offsets and the layouts without a device (tools/gen_phys_specs)
     int N = 0, max_reward = 0;
-    std::vector<void*> allocs;
+    DevArena arena;                 // everything allocated once: the model's tables, the per-env counters
     DevModel<float> mf;
     DevModel<double> md;
     Layout lay, lay2;               // first pass / second pass (lay2 == lay with one tier)
     bool two_pass() const { return maxcon1 < maxcon || maxefc1 < maxefc; }
     int pair_waves = 1;             // option "pair_waves": 0 = every env that needs the full capacities waits for the second pass
-    int* d_retry = nullptr;         // two counters (used alternately, like d_head) + the list of envs for the second pass
+    int* d_retry = nullptr;         // two counters (used alternately, like head) + the list of envs for the second pass
     unsigned long long retry_parity = 0;
-    void* d_kargs2 = nullptr;       // KArgs of the second pass
+    DevBuf kargs2;                  // KArgs of the second pass
     double *d_qpos_home = nullptr, *d_ctrl_home = nullptr, *d_obj_reset = nullptr;
     int* d_obj_qadr = nullptr;
-    int *d_ncon = nullptr, *d_cpairs = nullptr, *d_diag = nullptr;
+    int *d_ncon = nullptr, *d_diag = nullptr;
     int *d_cost = nullptr, *d_order = nullptr;     // per-env cost of the last step and the launch order made from it (k_env_order)
     int order_envs = 1;                            // option "order_envs"
     bool have_cost = false;
     long long* d_prof = nullptr;   // optional per-env phase cycle counters (option "profile_phases")
     float* d_xpose = nullptr;      // when set, the launch also exports body poses float[N][nbody][12] (render path)
-    double* d_cdist = nullptr;
+    DevBuf cpairs, cdist;          // the contact export: int[N][maxcon][2], double[N][maxcon] (alloc_contacts)
 
     std::vector<int> img_int;
     std::vector<double> img_real;
     MOff moff;
     void* d_img_real = nullptr;
     int* d_img_int = nullptr;
-    void* d_kargs = nullptr;        // KArgs<float|double> in device memory
+    DevBuf kargs;                   // KArgs<float|double> in device memory
     bool kargs_dirty = true;
     unsigned attr_done = 0;         // the kernel's LDS-size attribute, the CU count and the work counters are set up (once per handle)
     int num_cu = 256;               // CUs of the handle's device (persistent blocks: one per CU's LDS share)
     int persist_over = 1;           // option "persist_blocks": blocks launched per resident slot (1 = exactly what the CUs hold)
-    int* d_head = nullptr;          // two work counters, used alternately: a launch takes envs from one and zeroes the other
+    DevBuf head;                    // two work counters, used alternately: a launch takes envs from one and zeroes the other
     unsigned long long launch_count = 0;
     // device pointer that converts to the plain and to the global-address-space pointer types
     template <typename T>
@@ -3629,13 +3630,10 @@ struct PhysHost {
     };
     template <typename T>
     DevPtr<T> up(const std::vector<T>& v) {
-        void* p = nullptr;
-        size_t n = (v.size() ? v.size() : 1) * sizeof(T);
         if (host_only) return DevPtr<T>{nullptr};
-        if (hipMalloc(&p, n) != hipSuccess) throw std::runtime_error("hipMalloc failed while uploading the model");
-        if (v.size() && hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("hipMemcpy failed while uploading the model");
-        allocs.push_back(p);
-        return DevPtr<T>{(T*)p};
+        T* p = arena.upload(v);
+        if (!p) throw std::runtime_error(arena.error() == hipErrorOutOfMemory ? "hipMalloc failed while uploading the model" : "hipMemcpy failed while uploading the model");
+        return DevPtr<T>{p};
     }
     template <typename real>
     DevPtr<real> upr(const std::vector<double>& v) {
@@ -3895,35 +3893,25 @@ struct PhysHost {
 
     int dims[7] = {0, 0, 0, 0, 0, 0, 0};
     size_t lds_bytes() const { return (size_t)lay.bytes_per_env + (size_t)moff.nreal * (f64 ? 8 : 4) + (size_t)moff.nint * 4; }   // WPB = 1 figure (first pass)
-    void* d_rows = nullptr;
-    void* d_coup = nullptr;
-    int* d_near = nullptr;
-    void* d_gref = nullptr;
+    DevBuf rows, coup, near, gref;
+    // sized by maxcon / maxefc exactly, which an option may raise and lower: always reallocated
     void alloc_contacts() {
         if (host_only) return;
-        if (d_rows) (void)hipFree(d_rows);
-        d_rows = nullptr;
-        if (hipMalloc(&d_rows, (size_t)N * maxefc * ROW_S * (f64 ? 8 : 4) * 2) != hipSuccess) throw std::runtime_error("hipMalloc of the constraint row buffers failed");
-        mf.rJ_glob = (float*)d_rows; md.rJ_glob = (double*)d_rows;
+        if (rows.alloc((size_t)N * maxefc * ROW_S * (f64 ? 8 : 4) * 2) != hipSuccess) throw std::runtime_error("hipMalloc of the constraint row buffers failed");
+        mf.rJ_glob = rows.as<float>(); md.rJ_glob = rows.as<double>();
         mf.rB_glob = mf.rJ_glob + (size_t)N * maxefc * ROW_S; md.rB_glob = md.rJ_glob + (size_t)N * maxefc * ROW_S;
-        if (d_coup) (void)hipFree(d_coup);
-        if (d_near) (void)hipFree(d_near);
-        if (d_gref) (void)hipFree(d_gref);
-        d_coup = nullptr; d_near = nullptr; d_gref = nullptr;
-        if (hipMalloc(&d_gref, ((size_t)N * dims[4] * 3 + (size_t)N * 64 * BOX_OVF_W) * (f64 ? 8 : 4)) != hipSuccess) throw std::runtime_error("hipMalloc of the Verlet reference buffer failed");
-        mf.gref_glob = (float*)d_gref; md.gref_glob = (double*)d_gref;
+        if (gref.alloc(((size_t)N * dims[4] * 3 + (size_t)N * 64 * BOX_OVF_W) * (f64 ? 8 : 4)) != hipSuccess) throw std::runtime_error("hipMalloc of the Verlet reference buffer failed");
+        mf.gref_glob = gref.as<float>(); md.gref_glob = gref.as<double>();
         mf.bxo_glob = mf.gref_glob + (size_t)N * dims[4] * 3; md.bxo_glob = md.gref_glob + (size_t)N * dims[4] * 3;      // box-box overflow records behind the reference centres
-        if (hipMalloc(&d_coup, (size_t)N * lay2.maxgrp * GA_W * (f64 ? 8 : 4)) != hipSuccess || hipMalloc((void**)&d_near, (size_t)N * (NEAR_MAX + CAND_MAX) * 4) != hipSuccess)
+        if (coup.alloc((size_t)N * lay2.maxgrp * GA_W * (f64 ? 8 : 4)) != hipSuccess || near.alloc((size_t)N * (NEAR_MAX + CAND_MAX) * 4) != hipSuccess)
             throw std::runtime_error("hipMalloc of the coupling / neighbour buffers failed");
-        mf.gA_glob = (float*)d_coup; md.gA_glob = (double*)d_coup; mf.near_glob = d_near; md.near_glob = d_near; mf.cand_glob = md.cand_glob = d_near + (size_t)N * NEAR_MAX;
+        int* const d_near = near.as<int>();
+        mf.gA_glob = coup.as<float>(); md.gA_glob = coup.as<double>(); mf.near_glob = d_near; md.near_glob = d_near; mf.cand_glob = md.cand_glob = d_near + (size_t)N * NEAR_MAX;
         kargs_dirty = true;
-        if (d_cpairs) (void)hipFree(d_cpairs);
-        if (d_cdist) (void)hipFree(d_cdist);
-        d_cpairs = nullptr; d_cdist = nullptr;
-        if (hipMalloc((void**)&d_cpairs, (size_t)N * maxcon * 8) != hipSuccess || hipMalloc((void**)&d_cdist, (size_t)N * maxcon * 8) != hipSuccess)
+        if (cpairs.alloc((size_t)N * maxcon * 8) != hipSuccess || cdist.alloc((size_t)N * maxcon * 8) != hipSuccess)
             throw std::runtime_error("hipMalloc of the contact export buffers failed");
-        (void)hipMemset(d_cpairs, 0xff, (size_t)N * maxcon * 8);
-        (void)hipMemset(d_cdist, 0, (size_t)N * maxcon * 8);
+        (void)hipMemset(cpairs.ptr(), 0xff, (size_t)N * maxcon * 8);
+        (void)hipMemset(cdist.ptr(), 0, (size_t)N * maxcon * 8);
     }
     bool init(const Blob& b, int N_, bool f64_, std::string& err) {
         N = N_;
@@ -3955,17 +3943,6 @@ struct PhysHost {
             return false;
         }
         return true;
-    }
-    void destroy() {
-        for (void* p : allocs) (void)hipFree(p);
-        allocs.clear();
-        if (d_cpairs) (void)hipFree(d_cpairs);
-        if (d_cdist) (void)hipFree(d_cdist);
-        if (d_rows) (void)hipFree(d_rows);
-        if (d_coup) (void)hipFree(d_coup);
-        if (d_near) (void)hipFree(d_near);
-        if (d_gref) (void)hipFree(d_gref);
-        d_cpairs = nullptr; d_cdist = nullptr; d_rows = nullptr; d_coup = nullptr; d_near = nullptr; d_gref = nullptr;
     }
     bool set_option(const char* name, double v) {
         std::string n(name);
@@ -4041,10 +4018,9 @@ struct PhysHost {
             int dev = 0;
             hipDeviceProp_t prop;
             if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) num_cu = prop.multiProcessorCount;
-            if (!d_head) {
-                if (hipMalloc((void**)&d_head, 2 * sizeof(int)) != hipSuccess) { err = "hipMalloc(work counters) failed"; return -3; }
-                allocs.push_back(d_head);
-                (void)hipMemset(d_head, 0, 2 * sizeof(int));
+            if (!head) {
+                if (head.reserve(2 * sizeof(int)) != hipSuccess) { err = "hipMalloc(work counters) failed"; return -3; }
+                (void)hipMemset(head.ptr(), 0, 2 * sizeof(int));
             }
             attr_done = 1;
         }
@@ -4076,10 +4052,9 @@ struct PhysHost {
         if (nblk > (N + wpb - 1) / wpb) nblk = (N + wpb - 1) / wpb;
         if (kargs_dirty) {
             KArgs<real> ka{m, lay, moff}, ka2{m, lay2, moff};
-            if (!d_kargs) { if (hipMalloc(&d_kargs, sizeof(KArgs<double>)) != hipSuccess) { err = "hipMalloc(kernel arguments) failed"; return -3; } allocs.push_back(d_kargs); }
-            if (!d_kargs2) { if (hipMalloc(&d_kargs2, sizeof(KArgs<double>)) != hipSuccess) { err = "hipMalloc(kernel arguments) failed"; return -3; } allocs.push_back(d_kargs2); }
+            if (kargs.reserve(sizeof(KArgs<double>)) != hipSuccess || kargs2.reserve(sizeof(KArgs<double>)) != hipSuccess) { err = "hipMalloc(kernel arguments) failed"; return -3; }
             (void)hipStreamSynchronize(st);
-            if (hipMemcpy(d_kargs, &ka, sizeof(ka), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_kargs2, &ka2, sizeof(ka2), hipMemcpyHostToDevice) != hipSuccess) { err = "hipMemcpy(kernel arguments) failed"; return -3; }
+            if (hipMemcpy(kargs.ptr(), &ka, sizeof(ka), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(kargs2.ptr(), &ka2, sizeof(ka2), hipMemcpyHostToDevice) != hipSuccess) { err = "hipMemcpy(kernel arguments) failed"; return -3; }
             kargs_dirty = false;
         }
         // (checked BEFORE anything is enqueued: set_option admits 16 .. 1000, so this cannot fire through the API)
@@ -4096,27 +4071,27 @@ struct PhysHost {
         const int par = (int)(retry_parity & 1);      // which of the two list counters this step uses (its second pass zeroes the other)
         int* const rlist = d_retry + 2;
         {
-            int* head = d_head + (launch_count & 1);
-            int* next = d_head + ((launch_count + 1) & 1);
+            int* head = this->head.as<int>() + (launch_count & 1);
+            int* next = this->head.as<int>() + ((launch_count + 1) & 1);
             launch_count++;
-            hipLaunchKernelGGL(two ? kern2 : kern1, dim3(nblk), dim3(64 * wpb), shmem, st, (KPtr<real>)d_kargs, (const real*)d_img_real, (const int*)d_img_int, N, nsub, pgs_iters, action, want_reward,
+            hipLaunchKernelGGL(two ? kern2 : kern1, dim3(nblk), dim3(64 * wpb), shmem, st, (KPtr<real>)kargs.ptr(), (const real*)d_img_real, (const int*)d_img_int, N, nsub, pgs_iters, action, want_reward,
                                (real*)qpos, (real*)qvel, (real*)ctrl, (real*)warm, latch, agent, (int*)reward, (unsigned char*)success, d_ncon,
-                               d_cpairs, d_cdist, d_diag, max_reward, export_contacts, d_prof, d_xpose, order, order_envs ? d_cost : (int*)nullptr, head, next,
-                               d_retry, two ? (1 + 2 * par) | pairing : 0, (KPtr<real>)d_kargs2);
+                               cpairs.as<int>(), cdist.as<double>(), d_diag, max_reward, export_contacts, d_prof, d_xpose, order, order_envs ? d_cost : (int*)nullptr, head, next,
+                               d_retry, two ? (1 + 2 * par) | pairing : 0, (KPtr<real>)kargs2.ptr());
         }
         if (two) {
             // second pass: the envs the first one gave up on, with the full capacities; one workgroup per CU is plenty for the few there
             // are (the workgroups loop over the list), and a launch that finds the list empty returns at once
-            int* head = d_head + (launch_count & 1);
-            int* next = d_head + ((launch_count + 1) & 1);
+            int* head = this->head.as<int>() + (launch_count & 1);
+            int* next = this->head.as<int>() + ((launch_count + 1) & 1);
             launch_count++;
             retry_parity++;
             int nblk2 = num_cu;
             if (nblk2 > (N + wpb2 - 1) / wpb2) nblk2 = (N + wpb2 - 1) / wpb2;
-            hipLaunchKernelGGL(kern2, dim3(nblk2), dim3(64 * wpb2), shmem2, st, (KPtr<real>)d_kargs2, (const real*)d_img_real, (const int*)d_img_int, N, nsub, pgs_iters, action, want_reward,
+            hipLaunchKernelGGL(kern2, dim3(nblk2), dim3(64 * wpb2), shmem2, st, (KPtr<real>)kargs2.ptr(), (const real*)d_img_real, (const int*)d_img_int, N, nsub, pgs_iters, action, want_reward,
                                (real*)qpos, (real*)qvel, (real*)ctrl, (real*)warm, latch, agent, (int*)reward, (unsigned char*)success, d_ncon,
-                               d_cpairs, d_cdist, d_diag, max_reward, export_contacts, d_prof, d_xpose, (const int*)rlist, order_envs ? d_cost : (int*)nullptr, head, next,
-                               d_retry, (2 + 2 * par) | (maxcon1 << 8) | (maxefc1 << 18), (KPtr<real>)d_kargs2);      // (+ the FIRST tier's capacities: what "needed the full record" is measured against)
+                               cpairs.as<int>(), cdist.as<double>(), d_diag, max_reward, export_contacts, d_prof, d_xpose, (const int*)rlist, order_envs ? d_cost : (int*)nullptr, head, next,
+                               d_retry, (2 + 2 * par) | (maxcon1 << 8) | (maxefc1 << 18), (KPtr<real>)kargs2.ptr());      // (+ the FIRST tier's capacities: what "needed the full record" is measured against)
         }
         if (nsub > 0) have_cost = true;
         hipError_t e = hipGetLastError();

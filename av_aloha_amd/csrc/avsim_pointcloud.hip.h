@@ -12,6 +12,8 @@
 #include <cstdio>
 #include <string>
 
+#include "avsim_dev.h"
+
 namespace avs {
 
 constexpr int PC_THREADS = 1024;             // one workgroup per env: 16 waves
@@ -71,9 +73,7 @@ int pointcloud_launch(hipStream_t stream, const PcCall& c, int n, const float* d
 
 // The scratch of a chunk of envs: pose records and candidate lists.  Grows, never shrinks; allocating synchronises (the first use of a size)
 struct PcHost {
-    float* d_pose = nullptr;
-    int* d_list = nullptr;
-    size_t pose_cap = 0, list_cap = 0;
+    DevBuf pose, list;
 
     static size_t list_len(const PcCall& c) {
         const size_t q = (size_t)c.ncam * c.H * c.W;
@@ -82,29 +82,14 @@ struct PcHost {
     int reserve(int chunk, const PcCall& c, std::string& err) {
         const size_t nl = (size_t)chunk * list_len(c);
         if (const int rc = reserve_poses(chunk, c.ncam, err)) return rc;
-        if (nl > list_cap) {
-            if (d_list) (void)hipFree(d_list);
-            d_list = nullptr; list_cap = 0;
-            if (hipMalloc((void**)&d_list, nl * sizeof(int)) != hipSuccess) { err = "hipMalloc(point cloud candidates) failed"; return -3; }
-            list_cap = nl;
-        }
+        if (list.reserve(nl * sizeof(int)) != hipSuccess) { err = "hipMalloc(point cloud candidates) failed"; return -3; }
         return 0;
     }
     // the pose records alone (avsim_voxel_grid: its accumulator is the caller's output, no other scratch)
     int reserve_poses(int chunk, int ncam, std::string& err) {
         const size_t np = (size_t)chunk * ncam * PC_POSE_W;
-        if (np > pose_cap) {
-            if (d_pose) (void)hipFree(d_pose);
-            d_pose = nullptr; pose_cap = 0;
-            if (hipMalloc((void**)&d_pose, np * sizeof(float)) != hipSuccess) { err = "hipMalloc(point cloud poses) failed"; return -3; }
-            pose_cap = np;
-        }
+        if (pose.reserve(np * sizeof(float)) != hipSuccess) { err = "hipMalloc(point cloud poses) failed"; return -3; }
         return 0;
-    }
-    void destroy() {
-        if (d_pose) (void)hipFree(d_pose);
-        if (d_list) (void)hipFree(d_list);
-        d_pose = nullptr; d_list = nullptr; pose_cap = 0; list_cap = 0;
     }
     // poses of the current body poses, then the cloud, a chunk of envs at a time.  All pointers: device, of env 0
     int run(hipStream_t stream, const PcModel& m, const PcCall& c, int N, const float* depth, float* xyz, int* index, int* count, std::string& err) {
@@ -114,8 +99,8 @@ struct PcHost {
         const size_t q = (size_t)c.ncam * c.H * c.W;
         for (int e0 = 0; e0 < N; e0 += chunk) {
             const int n = N - e0 < chunk ? N - e0 : chunk;
-            if ((rc = pointcloud_poses_launch(stream, m, c, e0, n, d_pose, err))) return rc;
-            if ((rc = pointcloud_launch(stream, c, n, depth + (size_t)e0 * q, d_pose, d_list, xyz + (size_t)e0 * c.P * 3, index + (size_t)e0 * c.P, count + (size_t)e0 * 2, err))) return rc;
+            if ((rc = pointcloud_poses_launch(stream, m, c, e0, n, pose.as<float>(), err))) return rc;
+            if ((rc = pointcloud_launch(stream, c, n, depth + (size_t)e0 * q, pose.as<float>(), list.as<int>(), xyz + (size_t)e0 * c.P * 3, index + (size_t)e0 * c.P, count + (size_t)e0 * 2, err))) return rc;
         }
         return 0;
     }

@@ -29,6 +29,7 @@
 #include <tuple>
 #include <vector>
 
+#include "avsim_dev.h"
 #include "avsim_model.h"
 
 namespace avs {
@@ -971,34 +972,29 @@ __global__ void __launch_bounds__(256, RGB ? 1 : AVSIM_RD_WAVES) k_render_depth(
 // host side: float image of the geoms / cameras, scratch buffers, launches
 struct RenderHost {
     RenderModel m{};
-    std::vector<void*> allocs;
+    DevArena arena;                 // the model's tables, d_xpose, d_camaux
     float* d_xpose = nullptr;       // [N][nbody][12] body poses written by the physics kernel's forward pass
-    float* d_recs = nullptr;
-    int* d_counts = nullptr;
-    int* d_order = nullptr;
-    float* d_tplanes = nullptr;     // [N][ncam][nplane][4] faces of the polyhedra in camera-ray form
-    float* d_fbox = nullptr;        // [N][ncam][nplane][4] screen boxes of the faces seen from outside
-    float* d_sedge = nullptr;       // [N][ncam][nedge][4] silhouette edges (lines in the image, positive inside), compacted per polyhedron
-    float* d_heads = nullptr;       // [N][ncam][ngeom][16] the kept records' list headers in front-to-back order (octagon, nearest depth, packed word, record, offsets, bin mask)
+    // scratch of one chunk of envs, each grown to what the largest call so far has needed of it
+    DevBuf recs;
+    DevBuf counts;                  // [chunk][16] (by the chunk alone: 16 camera slots per env)
+    DevBuf order;
+    DevBuf tplanes;                 // [chunk][ncam][nplane][4] faces of the polyhedra in camera-ray form
+    DevBuf fbox;                    // [chunk][ncam][nplane][4] screen boxes of the faces seen from outside
+    DevBuf sedge;                   // [chunk][ncam][nedge][4] silhouette edges (lines in the image, positive inside), compacted per polyhedron
+    DevBuf heads;                   // [chunk][ncam][ngeom][16] the kept records' list headers in front-to-back order (octagon, nearest depth, packed word, record, offsets, bin mask)
     float* d_camaux = nullptr;      // [N][16][8] light direction and world up axis in the camera frame
-    int* d_cam_ids = nullptr;
-    size_t recs_cap = 0, counts_cap = 0;
+    DevBuf cam_ids;
     int N = 0;
     // option "kernel_timing": HIP events around every k_render_depth launch on the launch stream (avsim_render_kernel_time)
     bool timing = false;
     int env_chunk = 4096;           // option "render_chunk": envs per pass of the two kernels (launch()): bounds the scratch of a bigger batch
-    std::vector<hipEvent_t> tev;
-    size_t tev_used = 0;
-    double tev_ms = 0;             // launches folded out of the event list (at most 1024 pairs are kept: a long run that renders every step with
-    long long tev_n = 0;           // "kernel_timing" on does not grow it)
+    EventTimer timer;
 
     template <typename T>
     T* up(const std::vector<T>& v) {
-        void* p = nullptr;
-        if (hipMalloc(&p, (v.size() ? v.size() : 1) * sizeof(T)) != hipSuccess) throw std::runtime_error("hipMalloc failed while uploading the render model");
-        if (v.size() && hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("hipMemcpy failed while uploading the render model");
-        allocs.push_back(p);
-        return (T*)p;
+        T* p = arena.upload(v);
+        if (!p) throw std::runtime_error(arena.error() == hipErrorOutOfMemory ? "hipMalloc failed while uploading the render model" : "hipMemcpy failed while uploading the render model");
+        return p;
     }
     static std::vector<float> tofloat(const std::vector<double>& v) { return std::vector<float>(v.begin(), v.end()); }
     static void quat2mat(const double* q, double* R) {
@@ -1100,21 +1096,6 @@ struct RenderHost {
         m.znear = (float)clip[0]; m.zfar = (float)clip[1];
         d_xpose = up(std::vector<float>((size_t)N * m.nbody * 12, 0.0f));
     }
-    void destroy() {
-        for (void* p : allocs) (void)hipFree(p);
-        allocs.clear();
-        for (auto& ev : tev) (void)hipEventDestroy(ev);
-        tev.clear(); tev_used = 0;
-        if (d_recs) (void)hipFree(d_recs);
-        if (d_counts) (void)hipFree(d_counts);
-        if (d_order) (void)hipFree(d_order);
-        if (d_tplanes) (void)hipFree(d_tplanes);
-        if (d_fbox) (void)hipFree(d_fbox);
-        if (d_sedge) (void)hipFree(d_sedge);
-        if (d_heads) (void)hipFree(d_heads);
-        if (d_cam_ids) (void)hipFree(d_cam_ids);
-        d_heads = nullptr; d_recs = nullptr; d_counts = nullptr; d_order = nullptr; d_tplanes = nullptr; d_fbox = nullptr; d_sedge = nullptr; d_cam_ids = nullptr; recs_cap = 0; counts_cap = 0;
-    }
     // d_out: device float[N][ncam_sel][H][W], or (rgb) u8[N][ncam_sel][H][W][3]; body poses must already be in d_xpose (same stream)
     int launch(hipStream_t st, const int* cam_ids_host, int ncam_sel, int H, int W, void* d_out, bool rgb, std::string& err) {
         if (ncam_sel < 1 || ncam_sel > 16 || H < 1 || W < 1 || H > 4096 || W > 4096) { err = "avsim_render_depth: bad camera count or image size"; return -1; }
@@ -1127,45 +1108,20 @@ struct RenderHost {
         // 17.1 in sixteen -- k_render_depth is not waiting for those reads, and every pass has a tail.)
         const int chunk = N < env_chunk ? N : env_chunk;
         const size_t need = (size_t)chunk * ncam_sel * m.ngeom * REC_W;
-        // d_counts is sized by the chunk alone (16 camera slots per env), the other buffers by chunk x cameras: a larger chunk with fewer cameras can
-        // leave `need` where it was, so the chunk size that was allocated for is tracked on its own
-        if (need > recs_cap || (size_t)chunk > counts_cap) {
-            if (d_recs) (void)hipFree(d_recs);
-            if (d_counts) (void)hipFree(d_counts);
-            if (d_order) (void)hipFree(d_order);
-            if (d_tplanes) (void)hipFree(d_tplanes);
-            if (d_fbox) (void)hipFree(d_fbox);
-            if (d_sedge) (void)hipFree(d_sedge);
-            if (d_heads) (void)hipFree(d_heads);
-            d_heads = nullptr; d_recs = nullptr; d_counts = nullptr; d_order = nullptr; d_tplanes = nullptr; d_fbox = nullptr; d_sedge = nullptr; recs_cap = 0; counts_cap = 0;
-            if (hipMalloc((void**)&d_recs, need * sizeof(float)) != hipSuccess || hipMalloc((void**)&d_counts, (size_t)chunk * 16 * sizeof(int)) != hipSuccess ||
-                hipMalloc((void**)&d_order, (size_t)chunk * ncam_sel * m.ngeom * sizeof(int)) != hipSuccess ||
-                hipMalloc((void**)&d_tplanes, (size_t)chunk * ncam_sel * (m.nplane + 1) * 4 * sizeof(float)) != hipSuccess ||
-                hipMalloc((void**)&d_fbox, (size_t)chunk * ncam_sel * (m.nplane + 1) * 4 * sizeof(float)) != hipSuccess ||
-                hipMalloc((void**)&d_sedge, (size_t)chunk * ncam_sel * (m.nedge + 1) * 4 * sizeof(float)) != hipSuccess ||
-                hipMalloc((void**)&d_heads, (size_t)chunk * ncam_sel * m.ngeom * 16 * sizeof(float)) != hipSuccess) {
-                err = "hipMalloc(render records) failed";
-                return -3;
-            }
-            recs_cap = need;
-            counts_cap = (size_t)chunk;
+        const size_t views = (size_t)chunk * ncam_sel;
+        if (recs.reserve(need * sizeof(float)) != hipSuccess || counts.reserve((size_t)chunk * 16 * sizeof(int)) != hipSuccess ||
+            order.reserve(views * m.ngeom * sizeof(int)) != hipSuccess || tplanes.reserve(views * (m.nplane + 1) * 4 * sizeof(float)) != hipSuccess ||
+            fbox.reserve(views * (m.nplane + 1) * 4 * sizeof(float)) != hipSuccess || sedge.reserve(views * (m.nedge + 1) * 4 * sizeof(float)) != hipSuccess ||
+            heads.reserve(views * m.ngeom * 16 * sizeof(float)) != hipSuccess) {
+            err = "hipMalloc(render records) failed";
+            return -3;
         }
-        if (!d_cam_ids && hipMalloc((void**)&d_cam_ids, 16 * sizeof(int)) != hipSuccess) { err = "hipMalloc(camera ids) failed"; return -3; }
+        if (cam_ids.reserve(16 * sizeof(int)) != hipSuccess) { err = "hipMalloc(camera ids) failed"; return -3; }
+        float *const d_recs = recs.as<float>(), *const d_tplanes = tplanes.as<float>(), *const d_fbox = fbox.as<float>(), *const d_sedge = sedge.as<float>(), *const d_heads = heads.as<float>();
+        int *const d_counts = counts.as<int>(), *const d_order = order.as<int>(), *const d_cam_ids = cam_ids.as<int>();
         if (hipMemcpyAsync(d_cam_ids, cam_ids_host, ncam_sel * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) { err = "camera id copy failed"; return -3; }
         const int bin_tx = bin_width((W + TILE_W - 1) / TILE_W);
         const int tiles = (((W + TILE_W - 1) / TILE_W + bin_tx - 1) / bin_tx) * (((H + TILE_H - 1) / TILE_H + BIN_TY - 1) / BIN_TY);     // bins
-        if (timing) {
-            if (tev_used >= 2 * 1024) {
-                for (size_t i = 0; i + 1 < tev_used; i += 2) {
-                    float ms = 0;
-                    (void)hipEventSynchronize(tev[i + 1]);
-                    if (hipEventElapsedTime(&ms, tev[i], tev[i + 1]) == hipSuccess) tev_ms += ms;
-                }
-                tev_n += (long long)(tev_used / 2);
-                tev_used = 0;
-            }
-            while (tev.size() < tev_used + 2) { hipEvent_t ev; if (hipEventCreate(&ev) != hipSuccess) { err = "hipEventCreate failed"; return -3; } tev.push_back(ev); }
-        }
         for (int e0 = 0; e0 < N; e0 += chunk) {
             const int n = N - e0 < chunk ? N - e0 : chunk;
             const long long total_ll = (long long)tiles * ncam_sel * n;
@@ -1176,7 +1132,7 @@ struct RenderHost {
             hipLaunchKernelGGL(k_render_geoms, dim3(ncam_sel, n), dim3(64), 0, st, m, xp, (const int*)d_cam_ids, ncam_sel, H, W, d_recs, d_counts, d_order, d_tplanes, aux, d_fbox, d_sedge);
             hipLaunchKernelGGL(k_render_heads, dim3(ncam_sel * n), dim3(256), 0, st, (const float*)d_recs, (const int*)d_counts, (const int*)d_order, (const float4*)d_sedge, m.nedge, m.cam_fovy,
                                (const int*)d_cam_ids, ncam_sel, m.ngeom, H, W, (float4*)d_heads, bin_tx);
-            if (timing && e0 == 0) (void)hipEventRecord(tev[tev_used], st);       // (the image kernel's time; with more than one chunk the later chunks' set-up kernels are inside)
+            if (timing && e0 == 0 && timer.begin(st) != hipSuccess) { err = "hipEventCreate failed"; return -3; }       // (the image kernel's time; with more than one chunk the later chunks' set-up kernels are inside)
             const size_t px = (size_t)e0 * ncam_sel * H * W;
             if (rgb)
                 hipLaunchKernelGGL(k_render_depth<true>, dim3(nblk), dim3(256), 0, st, (const float*)d_recs, (const int*)d_counts, (const float4*)d_heads, (const float4*)d_tplanes, (const float4*)d_fbox, (const float4*)d_sedge, m.nplane, m.nedge,
@@ -1187,7 +1143,7 @@ struct RenderHost {
         }
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) { err = std::string("render kernel launch: ") + hipGetErrorString(e); return -3; }
-        if (timing) { (void)hipEventRecord(tev[tev_used + 1], st); tev_used += 2; }
+        if (timing) (void)timer.end(st);
 #ifdef AVSIM_RENDER_STATS
         {
             unsigned long long hst[8];

@@ -5,14 +5,16 @@
 
 #include <string>
 
+#include "avsim_devbuf.h"
+
 namespace avs {
 
 struct StageRing {
     static constexpr int NSLOT = 4;
     struct Slot {
         void* pin = nullptr;
-        void* dev = nullptr;
-        size_t cap = 0;
+        DevBuf dev;
+        size_t cap = 0;      // of either
         hipEvent_t done = nullptr;
         bool busy = false;
     };
@@ -23,7 +25,6 @@ struct StageRing {
         for (auto& s : slot) {
             if (s.busy) (void)hipEventSynchronize(s.done);
             if (s.pin) (void)hipHostFree(s.pin);
-            if (s.dev) (void)hipFree(s.dev);
             if (s.done) (void)hipEventDestroy(s.done);
             s = Slot{};
         }
@@ -38,12 +39,11 @@ struct StageRing {
         s.busy = false;
         if (e == hipSuccess && s.cap < bytes) {
             if (s.pin) (void)hipHostFree(s.pin);
-            if (s.dev) (void)hipFree(s.dev);
-            s.pin = s.dev = nullptr;
+            s.pin = nullptr;
             s.cap = 0;
             const size_t cap = (bytes + 4095) & ~(size_t)4095;
             e = hipHostMalloc(&s.pin, cap, hipHostMallocDefault);
-            if (e == hipSuccess) e = hipMalloc(&s.dev, cap);
+            if (e == hipSuccess) e = s.dev.reserve(cap);
             if (e == hipSuccess) s.cap = cap;
         }
         if (e == hipSuccess && !s.done) e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming);
@@ -53,7 +53,7 @@ struct StageRing {
 
     // the slot's pinned bytes to its device copy, on `stream`.  -3: HIP (nothing is in flight, the slot stays idle)
     int upload(Slot& s, size_t bytes, hipStream_t stream, std::string& err) {
-        const hipError_t e = hipMemcpyAsync(s.dev, s.pin, bytes, hipMemcpyHostToDevice, stream);
+        const hipError_t e = hipMemcpyAsync(s.dev.ptr(), s.pin, bytes, hipMemcpyHostToDevice, stream);
         if (e != hipSuccess) err = std::string("image staging ring: ") + hipGetErrorString(e);
         return e == hipSuccess ? 0 : -3;
     }

@@ -27,6 +27,7 @@
 #include <string>
 #include <vector>
 
+#include "avsim_dev.h"
 #include "avsim_model.h"
 
 namespace avs {
@@ -753,29 +754,29 @@ struct VisHost {
     std::vector<double> inst_pos, inst_mat, inst_scale, inst_rgba;
     bool have_inst = false, loaded = false;
     VisScene S{};
-    VisScratch X{};
-    std::vector<void*> allocs;
+    VisScratch X{};                  // what the kernels get: views of the scratch buffers below
+    DevArena arena;                  // the scene
+    DevBuf vcam, rec, bbox, list, trec, grec, bigq;      // per-slot scratch, X's pointers
+    DevBuf flags;                    // X.flags
     int slots = 0, max_slots = 0, nviews_cap = 0, last_nviews = 0;     // scratch slots allocated / the most a launch uses (VIS_WG_PER_CU x CUs); flag rows allocated / written by the last launch
     bool attr_done = false;
-    int* d_cam_ids = nullptr;
-    int cam_ids_last[16] = {}, ncam_last = -1;     // what d_cam_ids holds: a call with the same cameras copies nothing (no host-to-device copy per step)
+    DevBuf cam_ids;
+    int cam_ids_last[16] = {}, ncam_last = -1;     // what cam_ids holds: a call with the same cameras copies nothing (no host-to-device copy per step)
     int samples = 1;                 // option "render_samples": 1, or 4 = 2 x 2 supersampling
     bool cam_major = false;          // option "render_cam_major": the images as [cam][N][H][W][3] (every camera's batch contiguous) instead of [N][cam][H][W][3]
     int shadow_size = VIS_SM;        // option "render_shadow_size": 512 | 1024 | 2048 texels per side (MuJoCo's own map is 8192 wide, scene.xml:12; 2.3 mm texels at 512)
     bool smooth_opt = false;         // option "render_smooth": corners lit with their own normals and interpolated (needs a library with lib_tnorm); on in the gym / Cartesian facades, off in a bare handle (like shadows and multisampling: the raw kernel timings stay comparable)
     bool shadows = false;            // option "render_shadows": the directional light casts shadows (depth map from the light, one per env)
-    unsigned* d_shmap = nullptr;
+    DevBuf shmap;
     int shmap_envs = 0;
     unsigned long long shmap_ver = 0;   // the state version (avsim_api.hip) the shadow maps were rendered for
     double light_host[20] = {0};     // the model's render_light (lights, sky, shadow box, specular term)
 
     template <typename T>
     T* up(const std::vector<T>& v) {
-        void* p = nullptr;
-        if (hipMalloc(&p, (v.size() ? v.size() : 1) * sizeof(T)) != hipSuccess) throw std::runtime_error("hipMalloc failed while uploading the visual scene");
-        if (v.size() && hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("hipMemcpy failed while uploading the visual scene");
-        allocs.push_back(p);
-        return (T*)p;
+        T* p = arena.upload(v);
+        if (!p) throw std::runtime_error(arena.error() == hipErrorOutOfMemory ? "hipMalloc failed while uploading the visual scene" : "hipMemcpy failed while uploading the visual scene");
+        return p;
     }
     void keep_instances(const Blob& b) {
         try {
@@ -862,12 +863,6 @@ struct VisHost {
         }
         loaded = true;
     }
-    void destroy() {
-        for (void* p : allocs) (void)hipFree(p);
-        allocs.clear();
-        for (void* p : {(void*)X.vcam, (void*)X.rec, (void*)X.bbox, (void*)X.list, (void*)X.trec, (void*)X.grec, (void*)X.bigq, (void*)X.flags, (void*)d_cam_ids, (void*)d_shmap}) if (p) (void)hipFree(p);
-        X = VisScratch{}; d_cam_ids = nullptr; ncam_last = -1; d_shmap = nullptr; shmap_envs = 0; shmap_ver = 0; loaded = false; slots = 0; max_slots = 0; nviews_cap = 0; last_nviews = 0;
-    }
     // overflow flags of the last launch, OR over the views (bit 0: triangle records, bit 1: tile lists); synchronises the stream
     // f32: planar float32 [3][H][W] views in [0, 1], (float)u8 / 255 of the u8 image bit for bit (k_vis_render<..., float>)
     int launch(hipStream_t st, int N, const float* d_xpose, const int* cam_ids_host, int ncam_sel, int ncam_model, int H, int W, void* d_out, std::string& err, unsigned long long state_ver = 0,
@@ -886,7 +881,7 @@ struct VisHost {
             max_slots = VIS_WG_PER_CU * cus;
             X.reccap = S.ntri + 2048;                  // near-plane clipping can split a triangle in two
             X.listcap = 8 * S.ntri + 4 * VIS_MAXTILES;
-            if (hipMalloc((void**)&d_cam_ids, 16 * sizeof(int)) != hipSuccess) { err = "hipMalloc(visual render camera ids) failed"; max_slots = 0; return -3; }
+            if (cam_ids.reserve(16 * sizeof(int)) != hipSuccess) { err = "hipMalloc(visual render camera ids) failed"; max_slots = 0; return -3; }
         }
         // per-slot scratch (camera-frame vertices, triangle records, their boxes, tile lists: ~2.8 MB a slot for the 20 k-triangle
         // scenes) for as many workgroups as this call can use -- a single env with one camera holds one slot, not one per CU
@@ -894,26 +889,24 @@ struct VisHost {
         const int want = nviews < max_slots ? nviews : max_slots;
         if (want > slots) {
             if (hipStreamSynchronize(st) != hipSuccess) { err = "visual render: stream synchronisation failed"; return -3; }
-            for (void* p : {(void*)X.vcam, (void*)X.rec, (void*)X.bbox, (void*)X.list, (void*)X.trec, (void*)X.grec, (void*)X.bigq}) if (p) (void)hipFree(p);
-            X.vcam = nullptr; X.rec = nullptr; X.bbox = nullptr; X.list = nullptr; X.trec = nullptr; X.grec = nullptr; X.bigq = nullptr; slots = 0;
-            if (hipMalloc((void**)&X.vcam, (size_t)want * S.nvert * sizeof(float4)) != hipSuccess || hipMalloc((void**)&X.rec, (size_t)want * X.reccap * 4 * sizeof(float4)) != hipSuccess ||
-                hipMalloc((void**)&X.bbox, (size_t)want * X.reccap * 4 * sizeof(int)) != hipSuccess || hipMalloc((void**)&X.list, ((size_t)want * X.listcap + 16) * sizeof(int)) != hipSuccess ||      // (+ 16: the tile stage reads its list four entries at a time)
-                hipMalloc((void**)&X.trec, (size_t)want * VIS_TEXCAP * 3 * sizeof(float4)) != hipSuccess || hipMalloc((void**)&X.grec, (size_t)want * X.reccap * 3 * sizeof(float4)) != hipSuccess || hipMalloc((void**)&X.bigq, (size_t)want * X.reccap * sizeof(int)) != hipSuccess) {
-                for (void* p : {(void*)X.vcam, (void*)X.rec, (void*)X.bbox, (void*)X.list, (void*)X.trec, (void*)X.grec, (void*)X.bigq}) if (p) (void)hipFree(p);
-                X.vcam = nullptr; X.rec = nullptr; X.bbox = nullptr; X.list = nullptr; X.trec = nullptr; X.grec = nullptr; X.bigq = nullptr;
-                err = "hipMalloc(visual render scratch) failed"; return -3;
-            }
+            slots = 0;
+            const bool ok = vcam.reserve((size_t)want * S.nvert * sizeof(float4)) == hipSuccess && rec.reserve((size_t)want * X.reccap * 4 * sizeof(float4)) == hipSuccess &&
+                            bbox.reserve((size_t)want * X.reccap * 4 * sizeof(int)) == hipSuccess && list.reserve(((size_t)want * X.listcap + 16) * sizeof(int)) == hipSuccess &&      // (+ 16: the tile stage reads its list four entries at a time)
+                            trec.reserve((size_t)want * VIS_TEXCAP * 3 * sizeof(float4)) == hipSuccess && grec.reserve((size_t)want * X.reccap * 3 * sizeof(float4)) == hipSuccess &&
+                            bigq.reserve((size_t)want * X.reccap * sizeof(int)) == hipSuccess;
+            X.vcam = vcam.as<float4>(); X.rec = rec.as<float4>(); X.bbox = bbox.as<int>(); X.list = list.as<int>(); X.trec = trec.as<float4>(); X.grec = grec.as<float4>(); X.bigq = bigq.as<int>();
+            if (!ok) { err = "hipMalloc(visual render scratch) failed"; return -3; }
             slots = want;
         }
         if (nviews > nviews_cap) {
-            if (X.flags) (void)hipFree(X.flags);
-            X.flags = nullptr;
-            if (hipMalloc((void**)&X.flags, (size_t)nviews * 8 * sizeof(int)) != hipSuccess) { err = "hipMalloc(visual render flags) failed"; nviews_cap = 0; return -3; }
+            const hipError_t e = flags.reserve((size_t)nviews * 8 * sizeof(int));
+            X.flags = flags.as<int>();
+            if (e != hipSuccess) { err = "hipMalloc(visual render flags) failed"; nviews_cap = 0; return -3; }
             nviews_cap = nviews;
         }
         last_nviews = nviews;
         const bool same_cams = ncam_last == ncam_sel && !std::memcmp(cam_ids_last, cam_ids_host, ncam_sel * sizeof(int));
-        if (hipMemsetAsync(X.flags, 0, (size_t)nviews * 8 * sizeof(int), st) != hipSuccess || (!same_cams && hipMemcpyAsync(d_cam_ids, cam_ids_host, ncam_sel * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess)) { ncam_last = -1; err = "visual render set-up copy failed"; return -3; }
+        if (hipMemsetAsync(X.flags, 0, (size_t)nviews * 8 * sizeof(int), st) != hipSuccess || (!same_cams && hipMemcpyAsync(cam_ids.ptr(), cam_ids_host, ncam_sel * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess)) { ncam_last = -1; err = "visual render set-up copy failed"; return -3; }
         std::memcpy(cam_ids_last, cam_ids_host, ncam_sel * sizeof(int));
         ncam_last = ncam_sel;
         const int grid = nviews < slots ? nviews : slots;
@@ -938,27 +931,26 @@ struct VisHost {
             }
             if (N > shmap_envs) {
                 if (hipStreamSynchronize(st) != hipSuccess) { err = "visual render: stream synchronisation failed"; return -3; }
-                if (d_shmap) (void)hipFree(d_shmap);
-                d_shmap = nullptr; shmap_envs = 0;
-                if (hipMalloc((void**)&d_shmap, (size_t)N * shadow_size * shadow_size * sizeof(unsigned)) != hipSuccess) { err = "hipMalloc(shadow maps) failed"; return -3; }
+                shmap_envs = 0;
+                if (shmap.alloc((size_t)N * shadow_size * shadow_size * sizeof(unsigned)) != hipSuccess) { err = "hipMalloc(shadow maps) failed"; return -3; }
                 shmap_envs = N;
                 shmap_ver = 0;
             }
-            S.shmap = d_shmap;
+            S.shmap = shmap.as<unsigned>();
             if (state_ver == 0 || shmap_ver != state_ver) {      // (the maps of this state may be there already: an earlier call for other cameras)
                 // few envs: the maps in bands of rows (a workgroup each), so that one env's map is not one workgroup's work (16 bands for one env)
                 int bands = 1;
                 while (bands < 16 && N * bands < 256) bands *= 2;
-                hipLaunchKernelGGL(k_vis_shadow, dim3(N, bands), dim3(VIS_SHADOW_THREADS), 0, st, S, d_xpose, d_shmap, N);
+                hipLaunchKernelGGL(k_vis_shadow, dim3(N, bands), dim3(VIS_SHADOW_THREADS), 0, st, S, d_xpose, shmap.as<unsigned>(), N);
                 shmap_ver = state_ver;
             }
         }
         const bool sh = S.shmap != nullptr;
         const bool sm = S.smooth != 0 && S.tnorm != nullptr;
-#define VIS_LAUNCH(SS_, SH_) do { if (f32) { if (sm) hipLaunchKernelGGL((k_vis_render<SS_, SH_, true, float>), dim3(grid), dim3(VIS_THREADS), shmem, st, S, X, d_xpose, (const int*)d_cam_ids, ncam_sel, N, H, W, (float*)d_out, cam_major ? 1 : 0); \
-                                            else hipLaunchKernelGGL((k_vis_render<SS_, SH_, false, float>), dim3(grid), dim3(VIS_THREADS), shmem, st, S, X, d_xpose, (const int*)d_cam_ids, ncam_sel, N, H, W, (float*)d_out, cam_major ? 1 : 0); break; } \
-                                  if (sm) hipLaunchKernelGGL((k_vis_render<SS_, SH_, true>), dim3(grid), dim3(VIS_THREADS), shmem, st, S, X, d_xpose, (const int*)d_cam_ids, ncam_sel, N, H, W, (unsigned char*)d_out, cam_major ? 1 : 0); \
-                                  else hipLaunchKernelGGL((k_vis_render<SS_, SH_, false>), dim3(grid), dim3(VIS_THREADS), shmem, st, S, X, d_xpose, (const int*)d_cam_ids, ncam_sel, N, H, W, (unsigned char*)d_out, cam_major ? 1 : 0); } while (0)
+#define VIS_LAUNCH(SS_, SH_) do { if (f32) { if (sm) hipLaunchKernelGGL((k_vis_render<SS_, SH_, true, float>), dim3(grid), dim3(VIS_THREADS), shmem, st, S, X, d_xpose, cam_ids.as<const int>(), ncam_sel, N, H, W, (float*)d_out, cam_major ? 1 : 0); \
+                                            else hipLaunchKernelGGL((k_vis_render<SS_, SH_, false, float>), dim3(grid), dim3(VIS_THREADS), shmem, st, S, X, d_xpose, cam_ids.as<const int>(), ncam_sel, N, H, W, (float*)d_out, cam_major ? 1 : 0); break; } \
+                                  if (sm) hipLaunchKernelGGL((k_vis_render<SS_, SH_, true>), dim3(grid), dim3(VIS_THREADS), shmem, st, S, X, d_xpose, cam_ids.as<const int>(), ncam_sel, N, H, W, (unsigned char*)d_out, cam_major ? 1 : 0); \
+                                  else hipLaunchKernelGGL((k_vis_render<SS_, SH_, false>), dim3(grid), dim3(VIS_THREADS), shmem, st, S, X, d_xpose, cam_ids.as<const int>(), ncam_sel, N, H, W, (unsigned char*)d_out, cam_major ? 1 : 0); } while (0)
         if (samples > 1) { if (sh) VIS_LAUNCH(2, true); else VIS_LAUNCH(2, false); }
         else { if (sh) VIS_LAUNCH(1, true); else VIS_LAUNCH(1, false); }
 #undef VIS_LAUNCH

@@ -1,5 +1,6 @@
-// Host stand-in for <hip/hip_runtime.h>, for csrc/avsim_io.h alone (tests/hostshim_io/io_main.cpp, tests/test_io_host.py): the runtime calls that
-// header makes, over malloc and memcpy.  Copies execute at once, every call is counted, and the n-th hipMalloc / hipHostMalloc / copy can be told to fail.
+// Host stand-in for <hip/hip_runtime.h>, for csrc/avsim_io.h, avsim_stage.h, avsim_devbuf.h and avsim_dev.h alone (tests/hostshim_io/io_main.cpp and dev_main.cpp,
+// tests/test_io_host.py and test_dev_host.py): the runtime calls those headers make, over malloc and memcpy.  Copies execute at once, every call is
+// counted, and the n-th hipMalloc / hipHostMalloc / copy / event creation / elapsed-time read can be told to fail.
 #pragma once
 #include <cstddef>
 #include <cstdlib>
@@ -13,12 +14,12 @@ constexpr unsigned hipHostMallocDefault = 0, hipEventDisableTiming = 2;
 
 struct FakeHip {
     // calls made so far
-    int mallocs = 0, frees = 0, host_mallocs = 0, host_frees = 0, copies = 0, h2d = 0, d2h = 0, events = 0, event_destroys = 0, records = 0, event_syncs = 0, stream_syncs = 0;
-    size_t d2h_bytes = 0, last_d2h_bytes = 0;
+    int mallocs = 0, frees = 0, host_mallocs = 0, host_frees = 0, copies = 0, h2d = 0, d2h = 0, events = 0, event_destroys = 0, records = 0, event_syncs = 0, stream_syncs = 0, memsets = 0, elapsed = 0;
+    size_t d2h_bytes = 0, last_d2h_bytes = 0, last_malloc_bytes = 0;
     const void* last_d2h_dst = nullptr;
     // the k-th call from now fails (1: the next one); 0: none
-    int fail_malloc = 0, fail_host_malloc = 0, fail_copy = 0, fail_sync = 0;
-    int total() const { return mallocs + frees + host_mallocs + host_frees + copies + events + event_destroys + records + event_syncs + stream_syncs; }
+    int fail_malloc = 0, fail_host_malloc = 0, fail_copy = 0, fail_sync = 0, fail_event = 0, fail_elapsed = 0;
+    int total() const { return mallocs + frees + host_mallocs + host_frees + copies + events + event_destroys + records + event_syncs + stream_syncs + memsets + elapsed; }
 };
 inline FakeHip g_hip;
 inline bool fake_hits(int& countdown) { return countdown > 0 && --countdown == 0; }
@@ -28,6 +29,7 @@ inline const char* hipGetErrorString(hipError_t e) {
 }
 inline hipError_t hipMalloc(void** p, size_t bytes) {
     g_hip.mallocs++;
+    g_hip.last_malloc_bytes = bytes;
     if (fake_hits(g_hip.fail_malloc)) { *p = nullptr; return hipErrorOutOfMemory; }
     *p = std::malloc(bytes ? bytes : 1);          // (exactly `bytes`: AddressSanitizer sees a copy that runs past a buffer)
     return *p ? hipSuccess : hipErrorOutOfMemory;
@@ -46,6 +48,21 @@ inline hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMe
     if (kind == hipMemcpyHostToDevice) g_hip.h2d++;
     else { g_hip.d2h++; g_hip.d2h_bytes += bytes; g_hip.last_d2h_bytes = bytes; g_hip.last_d2h_dst = dst; }
     if (bytes) std::memcpy(dst, src, bytes);
+    return hipSuccess;
+}
+inline hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) { return hipMemcpyAsync(dst, src, bytes, kind, nullptr); }
+inline hipError_t hipMemsetAsync(void* p, int v, size_t bytes, hipStream_t) { g_hip.memsets++; std::memset(p, v, bytes); return hipSuccess; }
+inline hipError_t hipEventCreate(hipEvent_t* e) {
+    g_hip.events++;
+    if (fake_hits(g_hip.fail_event)) { *e = nullptr; return hipErrorOutOfMemory; }
+    *e = (hipEvent_t)std::malloc(1);
+    return hipSuccess;
+}
+// every pair took a quarter of a millisecond: sums of them are exact in binary
+inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) {
+    g_hip.elapsed++;
+    if (fake_hits(g_hip.fail_elapsed)) return hipErrorInvalidValue;
+    *ms = 0.25f;
     return hipSuccess;
 }
 inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { g_hip.events++; *e = (hipEvent_t)std::malloc(1); return hipSuccess; }
