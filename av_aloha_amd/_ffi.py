@@ -78,6 +78,7 @@ def lib():
         L.avsim_camera_poses.argtypes = [vp, vp, i32, vp]
         L.avsim_point_cloud.argtypes = [vp, vp, i32, i32, i32, vp, vp, C.c_float, i32, vp, vp, vp]
         L.avsim_voxel_grid.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, C.c_float, vp, vp]
+        L.avsim_virtual_views.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, C.c_float, vp, i32, vp, i32, vp, vp]
         L.avsim_episode_setup.argtypes = [vp, vp, vp, C.c_uint64, i32, i32, C.c_int64]
         L.avsim_sample_poses.argtypes = [vp, C.c_uint64, i32, vp, vp]
         L.avsim_episode_reset.argtypes = [vp, vp, vp, vp]

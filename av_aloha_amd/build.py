@@ -20,7 +20,7 @@ def build_hip(force=False, verbose=False):
     """hipcc --offload-arch=gfx950: avsim_api.hip (C-ABI, f32 product kernels, IK, render), avsim_phys_spec.hip (the f32 physics
     kernel specialised per model), avsim_phys_f64.hip (the f64 parity kernel, -ffp-contract=off so that it rounds like the oracle) ,
     avsim_imgaug.hip (the image augmentation, which rounds like its numpy specification) avsim_chunks.hip (the execution of action
-    chunks, likewise), avsim_obshist.hip (the observation histories, likewise) avsim_imgresize.hip (the image resize, likewise) and avsim_pointcloud.hip (the point clouds and the voxel grids, likewise) compiled side by side, linked into libavsim.so."""
+    chunks, likewise), avsim_obshist.hip (the observation histories, likewise) avsim_imgresize.hip (the image resize, likewise) and avsim_pointcloud.hip (the point clouds, the voxel grids and the virtual views, likewise) compiled side by side, linked into libavsim.so."""
     srcs = [os.path.join(SRC, f) for f in sorted(os.listdir(SRC)) if not f.endswith(".o") and not f.startswith(".")] + [os.path.join(ROOT, "include", "avsim.h"), os.path.abspath(__file__)]       # (this file holds the flags: a library built with other flags is stale too)
     if not force and not _stale(LIB, srcs):
         return LIB

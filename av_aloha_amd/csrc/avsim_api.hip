@@ -92,6 +92,7 @@ struct avsim {
     ChunkHost chunks;    // per-env execution of action chunks (avsim_chunks.hip.h), once avsim_chunk_setup has run
     ObsHistHost obshist; // per-env observation histories (avsim_obshist.hip.h), once avsim_obs_history_setup has run
     PcHost pointcloud;   // point clouds from depth images (avsim_pointcloud.hip.h): a chunk of envs' pose records and candidate lists
+    int virtviews_form = 0;          // option "virtviews_form": 0 = avsim_virtual_views runs the scatter form AVSIM_VV_FORM, f + 1 = form f (the same bits; there to be measured)
     bool voxel_other_form = false;   // option "voxel_other_form": avsim_voxel_grid runs the accumulate form that AVSIM_VOXEL_MERGE did NOT pick (the same bits; there to be measured)
     bool jpegdec_events = false;   // option "jpeg_decode_events": avsim_jpeg_decode records ev[12..15] around its three kernels
     // the state's version: bumped by everything that writes qpos (reset, the steps, set_state); the image calls skip their pose pass and the shadow
@@ -443,6 +444,7 @@ int avsim_set_option(avsim_t* h, const char* name, double value) {
     if (!std::strcmp(name, "render_cam_major")) { h->vis.cam_major = value != 0; return AVSIM_OK; }
     if (!std::strcmp(name, "render_chunk")) { if (value < 1) { h->set_error("render_chunk is a number of envs >= 1"); return AVSIM_EINVAL; } h->render.env_chunk = (int)value; return AVSIM_OK; }
     if (!std::strcmp(name, "voxel_other_form")) { h->voxel_other_form = value != 0; return AVSIM_OK; }
+    if (!std::strcmp(name, "virtviews_form")) { if (!(value >= 0 && value <= 5 && value == (int)value)) { h->set_error("virtviews_form is 0 (the form the build ships) or 1 + a form 0..4"); return AVSIM_EINVAL; } h->virtviews_form = (int)value; return AVSIM_OK; }
     if (!std::strcmp(name, "jpeg_decode_events")) { h->jpegdec_events = value != 0; return AVSIM_OK; }
     if (!std::strcmp(name, "jpeg_decode_budget")) { if (value < 1) { h->set_error("jpeg_decode_budget is a number of bytes >= 1"); return AVSIM_EINVAL; } h->jpegdec.coef_budget = (size_t)value; return AVSIM_OK; }
     if (!std::strcmp(name, "augment_scratch_bytes")) { if (!(value >= 1)) { h->set_error("augment_scratch_bytes is a number of bytes >= 1"); return AVSIM_EINVAL; } h->imgaug.scratch_limit = (size_t)value; return AVSIM_OK; }
@@ -923,6 +925,44 @@ int avsim_voxel_grid(avsim_t* h, const int32_t* cam_ids, int ncam, int height, i
         if (pointcloud_poses_launch(h->stream, pc_model(h), c.pc, e0, n, h->pointcloud.pose.as<float>(), h->err)) return AVSIM_EHIP;
         if (voxel_launch(h->stream, c, n, ddepth + (size_t)e0 * q, drgb ? drgb + (size_t)e0 * q * 3 : nullptr, h->pointcloud.pose.as<float>(), dout + (size_t)e0 * cell_floats,
                          (AVSIM_VOXEL_MERGE != 0) != h->voxel_other_form, h->err))
+            return AVSIM_EHIP;
+    }
+    return io.done();
+}
+
+// ---- virtual orthographic views from depth (and colour) images (av_aloha_amd/virtviews.py is the specification; the kernels: csrc/avsim_pointcloud.hip, below the grid's)
+int avsim_virtual_views(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, const float* depth, const uint8_t* rgb, const float* bounds, float max_depth,
+                        const int32_t* views, int nviews, const int32_t* size, int radius, float* out, int32_t* index) {
+    if (!h) return AVSIM_EINVAL;
+    if (!cam_ids || !depth || !bounds || !views || !size || !out || !index) { h->set_error("avsim_virtual_views: a null pointer"); return AVSIM_EINVAL; }
+    {   // the host arrays are checked before anything moves or is launched
+        std::string why;
+        if (virtviews_validate(h->render.m.ncam, cam_ids, ncam, height, width, bounds, max_depth, views, nviews, size, radius, why)) { h->set_error("%s", why.c_str()); return AVSIM_EINVAL; }
+    }
+    if (h->io_device && ((uintptr_t)out & 15)) { h->set_error("avsim_virtual_views: out is 16-byte aligned (the pixels are cleared and finished with 16-byte accesses)"); return AVSIM_EINVAL; }
+    VvCall c{};
+    for (int k = 0; k < ncam; k++) c.pc.cam[k] = cam_ids[k];
+    c.pc.ncam = ncam; c.pc.H = height; c.pc.W = width; c.pc.P = 0; c.pc.max_depth = max_depth;
+    for (int k = 0; k < 3; k++) { c.pc.lo[k] = bounds[k]; c.pc.hi[k] = bounds[3 + k]; }
+    for (int k = 0; k < nviews; k++) c.view[k] = views[k];
+    c.nviews = nviews; c.VH = size[0]; c.VW = size[1]; c.radius = radius;
+    AVS_ON_DEVICE(h);
+    Call io(h);
+    const size_t N = (size_t)h->N, q = (size_t)ncam * height * width, vp = (size_t)nviews * size[0] * size[1];
+    const float* ddepth = io.in(depth, sizeof(float) * N * q);
+    const uint8_t* drgb = io.in(rgb, 3 * N * q);
+    float* dout = io.out(out, sizeof(float) * N * vp * VV_CHANNELS);
+    int32_t* dindex = io.out(index, sizeof(int32_t) * N * vp);
+    if (io.failed()) return AVSIM_EHIP;
+    if (int rc = refresh_xpose(h)) return rc;
+    const int chunk = h->N < PC_ENV_CHUNK ? h->N : PC_ENV_CHUNK;
+    if (h->pointcloud.reserve_poses(chunk, ncam, h->err)) return AVSIM_EHIP;
+    const int form = h->virtviews_form ? h->virtviews_form - 1 : AVSIM_VV_FORM;
+    for (int e0 = 0; e0 < h->N; e0 += chunk) {          // envs in chunks, as avsim_voxel_grid: the pose scratch is a chunk's
+        const int n = h->N - e0 < chunk ? h->N - e0 : chunk;
+        if (pointcloud_poses_launch(h->stream, pc_model(h), c.pc, e0, n, h->pointcloud.pose.as<float>(), h->err)) return AVSIM_EHIP;
+        if (virtviews_launch(h->stream, c, n, ddepth + (size_t)e0 * q, drgb ? drgb + (size_t)e0 * q * 3 : nullptr, h->pointcloud.pose.as<float>(), dout + (size_t)e0 * vp * VV_CHANNELS,
+                             dindex + (size_t)e0 * vp, form, h->err))
             return AVSIM_EHIP;
     }
     return io.done();

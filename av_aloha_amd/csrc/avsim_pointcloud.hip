@@ -19,6 +19,7 @@
 //          barrier enough.  When the winning distance is 0 every distance is, and by the rule all further selections are candidate 0.
 //       3. The selected positions (LDS) become points and pixel indices, 1024 at a time.
 //   k_vox_clear, k_vox_accum, k_vox_finish   avsim_voxel_grid, below the cloud's: they call pc_world and read k_pc_poses's records.
+//   k_vv_clear, k_vv_scatter, k_vv_finish   avsim_virtual_views, below the grid's: likewise.
 #include "avsim_pointcloud.hip.h"
 
 namespace avs {
@@ -350,6 +351,215 @@ int voxel_launch(hipStream_t stream, const VoxCall& c, int n, const float* depth
     hipLaunchKernelGGL(k_vox_finish, sweep, dim3(256), 0, stream, c, total, out);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { err = std::string("voxel grid kernels: ") + hipGetErrorString(e); return -3; }
+    return 0;
+}
+
+// ---- virtual orthographic views (avsim_virtual_views).  The caller's output [n][V][VH][VW][8] is the z-buffer: the first 8 of a
+// virtual pixel's 32 bytes hold its key, (bits of dist << 32) | source slot, until k_vv_finish turns the pixel into its eight float32 channels.
+//   k_vv_clear     one 16-byte store of ones per virtual pixel: the key of a pixel nothing covers (no candidate has it: a dist is no NaN)
+//   k_vv_scatter   a lane per source pixel (a workgroup of 256 pixels of one env): pc_world once, the four pixel coordinates the six views choose
+//       from (x and y along VW, y and z along VH), then per view the key and a relaxed agent-scope 64-bit atomic MINIMUM into every pixel of the
+//       footprint that lies inside the image -- one global_atomic_umin_x2 without return each, no compare-and-swap loop.  CHECK: a relaxed load
+//       of the pixel's key first, and no atomic when the lane's own is not smaller; keys only decrease, so a stale read is safe.  The loads go
+//       out in batches -- with radius 0 those of all views, BEFORE the runs merge, otherwise three pixels of a footprint row -- so that a lane waits once per batch.  MERGE:
+//       consecutive lanes of the wave on the same virtual pixel form a run, a segmented shuffle scan takes the run's minimum towards its first
+//       lane, and that lane alone issues the footprint.  A minimum depends neither on the form nor on the order of arrival.
+//   k_vv_finish    a lane per virtual pixel (a workgroup of 256 of one env): reads the key, recomputes the winner's world point from its slot
+//       with pc_world (the same function, the same bits), reads its colour and writes the eight floats and the index
+constexpr int VV_THREADS = 256;
+
+__global__ void __launch_bounds__(256) k_vv_clear(uint4* __restrict__ out, size_t npix) {
+    const uint4 ones = make_uint4(~0u, ~0u, ~0u, ~0u);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (size_t)gridDim.x * 256) out[2 * i] = ones;
+}
+
+// the pixel of coordinate w on an image axis of n pixels over [lo, hi]: the voxel grid's cell formula (the clamp keeps the address inside whatever the floats)
+__device__ __forceinline__ int vv_pixel(float w, float lo, float hi, int n) {
+    const float g = (float)n, inv = g / (hi - lo);
+    const float u = (w - lo) * inv;
+    const int i = (int)fminf(floorf(u), g - 1.0f);
+    return i < 0 ? 0 : i > n - 1 ? n - 1 : i;
+}
+
+// what a lane brings to every view
+struct VvLane {
+    float w[3];
+    int cx, cy, ry, rz;          // x, y as columns (of VW), y, z as rows (of VH), ascending
+    int pix, lane;
+    bool ok;
+};
+
+// the lane's key and virtual pixel in view iv, whether it is a candidate or not
+__device__ __forceinline__ void vv_place(const VvCall& vc, const VvLane& l, int iv, unsigned long long& key, int& pr, int& pc) {
+    const PcCall& c = vc.pc;
+    const int VH = vc.VH, VW = vc.VW;
+    float dist;
+    switch (vc.view[iv]) {          // (the same for the whole grid)
+        case 0: dist = c.hi[0] - l.w[0]; pc = l.cy; pr = VH - 1 - l.rz; break;
+        case 1: dist = l.w[0] - c.lo[0]; pc = VW - 1 - l.cy; pr = VH - 1 - l.rz; break;
+        case 2: dist = c.hi[1] - l.w[1]; pc = VW - 1 - l.cx; pr = VH - 1 - l.rz; break;
+        case 3: dist = l.w[1] - c.lo[1]; pc = l.cx; pr = VH - 1 - l.rz; break;
+        case 4: dist = c.hi[2] - l.w[2]; pc = l.cx; pr = VH - 1 - l.ry; break;
+        default: dist = l.w[2] - c.lo[2]; pc = l.cx; pr = l.ry; break;
+    }
+    key = ((unsigned long long)__float_as_uint(dist) << 32) | (unsigned)l.pix;
+}
+
+// whether the lane issues.  MERGE: the run of consecutive lanes on the lane's virtual pixel takes its minimum towards its first lane, which alone issues
+template <bool MERGE>
+__device__ __forceinline__ bool vv_issues(const VvCall& vc, const VvLane& l, unsigned long long& key, int pr, int pc) {
+    if (!MERGE) return l.ok;
+    const int target = l.ok ? pr * vc.VW + pc : -1;
+    const int prev = __shfl_up(target, 1);
+    const bool head = l.lane == 0 || prev != target;
+    const unsigned long long heads = __ballot(head), rest = (heads >> l.lane) >> 1;
+    const int after = rest ? __builtin_ctzll(rest) : 63 - l.lane;          // the lanes after this one in its run
+    for (int s = 1; s < 64; s <<= 1) {
+        if (__ballot(after >= s) == 0ull) break;          // (the same for the wave) no run reaches further
+        const unsigned long long t = __shfl_down(key, s);
+        if (after >= s && t < key) key = t;          // after step s a lane holds the minimum of itself and the next 2 s - 1 lanes of its run
+    }
+    return l.ok && head;
+}
+
+__device__ __forceinline__ unsigned long long vv_load(const unsigned long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void vv_min(unsigned long long* p, unsigned long long key) { (void)__hip_atomic_fetch_min(p, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+template <bool CHECK, bool MERGE>
+__global__ void __launch_bounds__(VV_THREADS) k_vv_scatter(VvCall vc, const float* __restrict__ depth, const float* __restrict__ pose, unsigned long long* out) {
+    __shared__ float s_pose[PC_MAX_CAMS * PC_POSE_W];
+    __shared__ float s_scale[PC_MAX_CAMS];
+    const PcCall& c = vc.pc;
+    const int tid = threadIdx.x, env = blockIdx.y;
+    const int Q = c.ncam * c.H * c.W, VH = vc.VH, VW = vc.VW, R = vc.radius;
+    depth += (size_t)env * Q;
+    pose += (size_t)env * c.ncam * PC_POSE_W;
+    out += (size_t)env * vc.nviews * VH * VW * 4;
+    PcView v;
+    v.HW = c.H * c.W; v.W = c.W; v.hh = 0.5f * (float)c.H; v.hw = 0.5f * (float)c.W; v.max_depth = c.max_depth;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { v.lo[k] = c.lo[k]; v.hi[k] = c.hi[k]; }
+    if (tid < c.ncam * PC_POSE_W) s_pose[tid] = pose[tid];
+    __syncthreads();
+    if (tid < c.ncam) s_scale[tid] = (2.0f * s_pose[tid * PC_POSE_W + 12]) / (float)c.H;
+    __syncthreads();
+
+    VvLane l;
+    l.pix = blockIdx.x * VV_THREADS + tid;
+    l.lane = tid & 63;
+    l.w[0] = l.w[1] = l.w[2] = 0.0f;
+    l.ok = l.pix < Q && pc_world(v, s_pose, s_scale, depth, l.pix, l.w[0], l.w[1], l.w[2]);
+    if (!MERGE && !l.ok) return;
+    l.cx = l.cy = l.ry = l.rz = 0;
+    if (l.ok) {
+        l.cx = vv_pixel(l.w[0], c.lo[0], c.hi[0], VW);
+        l.cy = vv_pixel(l.w[1], c.lo[1], c.hi[1], VW);
+        l.ry = vv_pixel(l.w[1], c.lo[1], c.hi[1], VH);
+        l.rz = vv_pixel(l.w[2], c.lo[2], c.hi[2], VH);
+    }
+    const size_t view_words = (size_t)VH * VW * 4;
+    if (CHECK && R == 0) {          // one pixel per view: the loads of all views go out together and travel while the runs merge; then the atomics that are left
+        unsigned long long key[VV_MAX_VIEWS], cur[VV_MAX_VIEWS];
+        size_t at[VV_MAX_VIEWS];          // (offsets, not pointers: the accesses stay global ones)
+        int pr[VV_MAX_VIEWS], pc[VV_MAX_VIEWS];
+#pragma unroll
+        for (int iv = 0; iv < VV_MAX_VIEWS; iv++) {
+            key[iv] = 0ull;
+            at[iv] = 0;          // (a lane that is no candidate loads a word of the buffer all the same: no branch round the load)
+            pr[iv] = pc[iv] = 0;
+            if (iv < vc.nviews) {
+                vv_place(vc, l, iv, key[iv], pr[iv], pc[iv]);
+                if (l.ok) at[iv] = iv * view_words + (size_t)(pr[iv] * VW + pc[iv]) * 4;
+            }
+        }
+#pragma unroll
+        for (int iv = 0; iv < VV_MAX_VIEWS; iv++) cur[iv] = iv < vc.nviews ? vv_load(out + at[iv]) : 0ull;
+#pragma unroll
+        for (int iv = 0; iv < VV_MAX_VIEWS; iv++)
+            if (iv < vc.nviews) {
+                const bool go = vv_issues<MERGE>(vc, l, key[iv], pr[iv], pc[iv]);
+                if (go && key[iv] < cur[iv]) vv_min(out + at[iv], key[iv]);
+            }
+        return;
+    }
+    for (int iv = 0; iv < vc.nviews; iv++, out += view_words) {
+        unsigned long long key;
+        int pr, pc;
+        vv_place(vc, l, iv, key, pr, pc);
+        if (!vv_issues<MERGE>(vc, l, key, pr, pc)) continue;
+        const int r0 = pr - R < 0 ? 0 : pr - R, r1 = pr + R > VH - 1 ? VH - 1 : pr + R;
+        const int c0 = pc - R < 0 ? 0 : pc - R, c1 = pc + R > VW - 1 ? VW - 1 : pc + R;
+        for (int r = r0; r <= r1; r++) {
+            unsigned long long* row = out + (size_t)r * VW * 4;
+            if (CHECK) {          // three pixels of the row at a time: their loads together, then the atomics that are left
+                for (int q = c0; q <= c1; q += 3) {
+                    const int q1 = q + 1 <= c1 ? q + 1 : q, q2 = q + 2 <= c1 ? q + 2 : q;
+                    const unsigned long long a0 = vv_load(row + (size_t)q * 4), a1 = vv_load(row + (size_t)q1 * 4), a2 = vv_load(row + (size_t)q2 * 4);
+                    if (key < a0) vv_min(row + (size_t)q * 4, key);
+                    if (q1 != q && key < a1) vv_min(row + (size_t)q1 * 4, key);
+                    if (q2 != q && key < a2) vv_min(row + (size_t)q2 * 4, key);
+                }
+            } else {
+                for (int q = c0; q <= c1; q++) vv_min(row + (size_t)q * 4, key);
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(VV_THREADS) k_vv_finish(VvCall vc, const float* __restrict__ depth, const uint8_t* __restrict__ rgb, const float* __restrict__ pose, float* out,
+                                                          int32_t* __restrict__ index) {
+    __shared__ float s_pose[PC_MAX_CAMS * PC_POSE_W];
+    __shared__ float s_scale[PC_MAX_CAMS];
+    const PcCall& c = vc.pc;
+    const int tid = threadIdx.x, env = blockIdx.y;
+    const int Q = c.ncam * c.H * c.W, VP = vc.nviews * vc.VH * vc.VW;
+    depth += (size_t)env * Q;
+    pose += (size_t)env * c.ncam * PC_POSE_W;
+    PcView v;
+    v.HW = c.H * c.W; v.W = c.W; v.hh = 0.5f * (float)c.H; v.hw = 0.5f * (float)c.W; v.max_depth = c.max_depth;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { v.lo[k] = c.lo[k]; v.hi[k] = c.hi[k]; }
+    if (tid < c.ncam * PC_POSE_W) s_pose[tid] = pose[tid];
+    __syncthreads();
+    if (tid < c.ncam) s_scale[tid] = (2.0f * s_pose[tid * PC_POSE_W + 12]) / (float)c.H;
+    __syncthreads();
+
+    const int i = blockIdx.x * VV_THREADS + tid;
+    if (i >= VP) return;
+    const size_t at = (size_t)env * VP + i;
+    const uint2 key = ((const uint2*)out)[4 * at];          // x: the slot, y: the bits of dist
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
+    int slot = -1;
+    if (key.x < (unsigned)Q && key.y != ~0u) {          // (a written key's slot is below Q: the test keeps the reads inside whatever the buffer held)
+        slot = (int)key.x;
+        pc_world(v, s_pose, s_scale, depth, slot, b.x, b.y, b.z);
+        if (rgb) {
+            const uint8_t* p = rgb + ((size_t)env * Q + slot) * 3;
+            a.x = (float)p[0] * (1.0f / 255.0f); a.y = (float)p[1] * (1.0f / 255.0f); a.z = (float)p[2] * (1.0f / 255.0f);
+        }
+        a.w = __uint_as_float(key.y);
+        b.w = 1.0f;
+    }
+    ((float4*)out)[2 * at] = a;
+    ((float4*)out)[2 * at + 1] = b;
+    index[at] = slot;
+}
+
+int virtviews_launch(hipStream_t stream, const VvCall& c, int n, const float* depth, const uint8_t* rgb, const float* pose, float* out, int32_t* index, int form, std::string& err) {
+    const int VP = c.nviews * c.VH * c.VW, Q = c.pc.ncam * c.pc.H * c.pc.W;
+    const size_t total = (size_t)n * VP, blocks = (total + 255) / 256;
+    const dim3 sweep((unsigned)(blocks < 65536 ? blocks : 65536)), pixels((Q + VV_THREADS - 1) / VV_THREADS, n), vpixels((VP + VV_THREADS - 1) / VV_THREADS, n);
+    unsigned long long* keys = (unsigned long long*)out;
+    hipLaunchKernelGGL(k_vv_clear, sweep, dim3(256), 0, stream, (uint4*)out, total);
+    switch (vv_form(form, c)) {
+        case 0: hipLaunchKernelGGL((k_vv_scatter<false, false>), pixels, dim3(VV_THREADS), 0, stream, c, depth, pose, keys); break;
+        case 1: hipLaunchKernelGGL((k_vv_scatter<true, false>), pixels, dim3(VV_THREADS), 0, stream, c, depth, pose, keys); break;
+        case 2: hipLaunchKernelGGL((k_vv_scatter<false, true>), pixels, dim3(VV_THREADS), 0, stream, c, depth, pose, keys); break;
+        default: hipLaunchKernelGGL((k_vv_scatter<true, true>), pixels, dim3(VV_THREADS), 0, stream, c, depth, pose, keys); break;
+    }
+    hipLaunchKernelGGL(k_vv_finish, vpixels, dim3(VV_THREADS), 0, stream, c, depth, rgb, pose, out, index);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { err = std::string("virtual view kernels: ") + hipGetErrorString(e); return -3; }
     return 0;
 }
 

@@ -1,5 +1,5 @@
 """The device image calls of libavsim (include/avsim.h) from Python.  ImageCalls implements compose and label, image statistics, prep, jitter,
-augment, resize, camera poses, point clouds and voxel grids once each, against one of two array adaptors: HostArrays (numpy; BatchedSim) and DeviceArrays
+augment, resize, camera poses, point clouds, voxel grids and virtual views once each, against one of two array adaptors: HostArrays (numpy; BatchedSim) and DeviceArrays
 (torch tensors on a device; DeviceImageOps, which VecEnv inherits).  The adaptors hold all that differs between the fronts:
   * numpy converts what it is given (np.ascontiguousarray of the pixels, values= to int64, lut= to float32 [-1, 3, 256]); torch takes
     contiguous tensors of the right type on the owner's device and fails an assert for anything else;
@@ -127,7 +127,7 @@ def _host(a, dtype, *shape):
 
 
 class ImageCalls:
-    """Compose and label, image statistics, prep, jitter, augment, resize, camera poses, point clouds and voxel grids: each call once, for the owner of a
+    """Compose and label, image statistics, prep, jitter, augment, resize, camera poses, point clouds, voxel grids and virtual views: each call once, for the owner of a
     handle self.h (_ffi.Handle) -- and, for the camera calls, of a self.manifest -- whose self._arrays says what kind of array the pixels live
     in: HostArrays (numpy) or DeviceArrays (torch tensors on self.device).  The two kinds differ in what the adaptor holds and in nothing
     else: how an array is made, whether an input is converted or has to be right already, whether a wrong one is a ValueError or a failed
@@ -378,6 +378,60 @@ class ImageCalls:
                                                      float(pointcloud.FAR_PLANE if max_depth is None else max_depth), g.ctypes.data, A.ptr(out)))
         return out
 
+    def virtual_views(self, cameras, height, width, bounds, views, size, radius=1, max_depth=None, depth=None, rgb=None, colour=False, out=None, index=None):
+        """(out float32 [N, V, VH, VW, 8], index int32 [N, V, VH, VW]): V orthographic virtual images per env of the box HOST bounds (xlo ylo
+        zlo xhi yhi zhi, lo < hi) in the world frame, z-buffered from the depth images of the named cameras (avsim_virtual_views): the bits of
+        av_aloha_amd.virtviews.virtual_views_reference given camera_poses().  views: names ("+x" "-x" "+y" "-y" "+z" "-z": the face the box is
+        seen from) or codes 0..5, 1 to 6 of them; size: an int or (VH, VW), 1..1024; radius: a point covers (2 radius + 1)^2 pixels, 0..4.  A
+        pixel's channels: 0..2 the colour in [0, 1] of the nearest point that covers it (0 without colour), 3 its distance from the view's
+        face, 4..6 its world position, 7 1.0; a pixel nothing covers is zeros.  index is the winner's flat source pixel slot * H * W + r * W + c
+        (-1: none).  depth: float32 [N, len(cameras), height, width] of the CURRENT state (None: rendered first); rgb: uint8 [N, len(cameras),
+        height, width, 3], the same pixels in avsim_render_rgb's env-major layout (None and colour=True: rendered first, env-major whatever
+        the owner keeps "render_cam_major" at, as voxel_grid does; None and colour=False: no colour); max_depth: None = the far plane.  out,
+        index: the arrays to write.  ValueError for what the library refuses."""
+        from . import pointcloud, virtviews
+        A = self._arrays
+        A.begin(self)
+        ids = camera_ids(self.manifest, cameras)
+        N, height, width = self.h.num_envs, int(height), int(width)
+        v = np.array(virtviews.view_codes(views), dtype=np.int32)
+        sz = np.array(virtviews.view_size(size), dtype=np.int32)
+        if not 1 <= len(v) <= virtviews.MAX_VIEWS or sz.min() < 1 or sz.max() > virtviews.MAX_SIZE:      # (before outputs of that size are made)
+            raise ValueError(f"virtual_views: 1..{virtviews.MAX_VIEWS} views of 1..{virtviews.MAX_SIZE} pixels a side, not {len(v)} of {tuple(int(x) for x in sz)}")
+        shape = (N, len(ids), height, width)
+        if depth is None:
+            depth = A.empty(self, shape, "float32")
+            self.h.check(self.h.L.avsim_render_depth(self.h.h, ids.ctypes.data, len(ids), height, width, A.ptr(depth)))
+        if rgb is None and colour:          # env-major whatever the owner keeps "render_cam_major" at: switched off for this render, then put back
+            rgb = A.empty(self, shape + (3,), "uint8")
+            self.h.check(self.h.L.avsim_set_option(self.h.h, b"render_cam_major", 0.0))
+            try:
+                self.h.check(self.h.L.avsim_render_rgb(self.h.h, ids.ctypes.data, len(ids), height, width, A.ptr(rgb)))
+            finally:
+                if self._cam_major:
+                    self.h.check(self.h.L.avsim_set_option(self.h.h, b"render_cam_major", 1.0))
+        text = "virtual_views(depth=...): a contiguous float32 [N, cameras, height, width] tensor on the env's device"
+        depth = A.given(self, depth, "float32", None, text)
+        if tuple(depth.shape) != shape:
+            A.fail(f"virtual_views: depth is float32 {shape}, not {tuple(depth.shape)}", text)
+        if rgb is not None:
+            text = "virtual_views(rgb=...): a contiguous uint8 [N, cameras, height, width, 3] tensor on the env's device"
+            rgb = A.given(self, rgb, "uint8", None, text)
+            if tuple(rgb.shape) != shape + (3,):
+                A.fail(f"virtual_views: rgb is uint8 {shape + (3,)}, not {tuple(rgb.shape)}", text)
+        b = np.ascontiguousarray(bounds, dtype=np.float32).reshape(-1)
+        if b.shape != (6,):
+            raise ValueError("virtual_views: bounds are xlo ylo zlo xhi yhi zhi")
+        vshape = (N, len(v), int(sz[0]), int(sz[1]))
+        out = self._out("virtual_views", out, vshape + (8,), text="float32 [N, V, VH, VW, 8]")
+        if index is not None and not A.ok(self, index, "int32", vshape):
+            A.fail("virtual_views: index is a C-contiguous int32 [N, V, VH, VW] array")
+        index = A.empty(self, vshape, "int32") if index is None else index
+        check_call(self.h, self.h.L.avsim_virtual_views(self.h.h, ids.ctypes.data, len(ids), height, width, A.ptr(depth), _ffi.ptr(rgb), b.ctypes.data,
+                                                        float(pointcloud.FAR_PLANE if max_depth is None else max_depth), v.ctypes.data, len(v), sz.ctypes.data, int(radius),
+                                                        A.ptr(out), A.ptr(index)))
+        return out, index
+
 
 class DeviceImageOps(ImageCalls):
     """The image calls on torch tensors, for the owner of a device-I/O handle: ImageCalls through DeviceArrays, and the JPEG calls, which
@@ -404,6 +458,12 @@ class DeviceImageOps(ImageCalls):
         channels_last_3d strides, which Conv3d takes as it is) -- no copy is made."""
         out = ImageCalls.voxel_grid(self, *args, **kw)
         return out.permute(0, 4, 1, 2, 3) if channels_first else out
+
+    def virtual_views(self, *args, channels_first=False, **kw):
+        """ImageCalls.virtual_views; channels_first=True returns out as the [N, V, 8, VH, VW] view of the same memory (out.permute(0, 1, 4,
+        2, 3); its flatten(0, 1) is a channels_last [N V, 8, VH, VW] batch, which Conv2d takes as it is) -- no copy is made."""
+        out, index = ImageCalls.virtual_views(self, *args, **kw)
+        return (out.permute(0, 1, 4, 2, 3) if channels_first else out), index
 
     def decode_jpeg(self, buf, lengths, height=None, width=None, upsample="replicate", fmt=None, out=None, status=None):
         """The inverse of encode_jpeg on the device (avsim_jpeg_decode): buf uint8 [n, stride] and lengths int32 [n] as encode_jpeg

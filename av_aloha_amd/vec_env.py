@@ -18,6 +18,13 @@ per-env episodes and gymnasium's NEXT_STEP autoreset done by the library's kerne
   [N, gx, gy, gz, 8] buffer that avsim_voxel_grid writes: per cell the mean position, the mean colour, the count and the occupancy.  The
   depth, and with "colour" the u8 colour images, are rendered at the option's own size into its own buffers.  Refused together with the
   "render_cam_major" option -- which `cameras` switch on --: the grid reads env-major images.  None (the default): no call, buffer or key changes.
+* views={"cameras": [...], "height": h, "width": w, "bounds": (xlo, ylo, zlo, xhi, yhi, zhi), "views": ["+z", "+x", "-x", "+y", "-y"], "size": 220 or
+  (vh, vw), "radius": 1, "colour": True, "max_depth": None} adds `observation.virtual_views` (gym format: `virtual_views`) float32
+  [N, V, 8, VH, VW], a view of the [N, V, VH, VW, 8] buffer that avsim_virtual_views writes: RVT's orthographic images of the box, per pixel
+  the nearest point's colour, its distance from the view's face, its world position and a hit flag; `info["virtual_views_index"]` int32
+  [N, V, VH, VW] is the winning source pixel (-1: none).  The depth, and with "colour" the u8 colour images, are rendered at the option's own
+  size into its own buffers.  Refused together with "render_cam_major" / `cameras`, as voxels are; allowed next to pointcloud and voxels.
+  None (the default): no call, buffer or key changes.
 * Every tensor returned is a preallocated buffer that the next reset / step overwrites: clone what must outlive the call.
 * NEXT_STEP: an env whose episode ended (terminated or truncated) in call t starts its next episode in call t + 1, whose action does
   not reach it; that call reports reward 0, flags 0, elapsed 0, the new `info["episode_id"]` and the new episode's first observation.
@@ -93,17 +100,19 @@ def sample_poses(task, seed, episode_ids):
 class VecEnv(DeviceImageOps):
     """num_envs envs of one task on one GPU; see the module's docstring for the semantics.  The image calls on any tensor of the env's device
     -- decode_jpeg, encode_images, compose, compose_label, image_stats, prep_images, jitter_images, augment_images, resize_images -- and
-    camera_poses / point_cloud / voxel_grid on demand are images.DeviceImageOps's (images.ImageCalls on tensors)."""
+    camera_poses / point_cloud / voxel_grid / virtual_views on demand are images.DeviceImageOps's (images.ImageCalls on tensors)."""
 
     metadata = {"autoreset_mode": "NextStep", "render_modes": []}
 
     def __init__(self, task, num_arms, num_envs, max_episode_steps, device=None, cameras=(), depth_cameras=(), obs_format="lerobot",
-                 seed=0, terminate_on_success=False, f64=False, options=None, observation_height=480, observation_width=640, pointcloud=None, voxels=None):
+                 seed=0, terminate_on_success=False, f64=False, options=None, observation_height=480, observation_width=640, pointcloud=None, voxels=None, views=None):
         import torch
         assert obs_format in ("lerobot", "gym"), obs_format
         assert all(c in CAMERAS for c in list(cameras) + list(depth_cameras)), "Invalid camera names"
         if voxels is not None and (list(cameras) or float((options or {}).get("render_cam_major", 0)) != 0):      # (before there is a handle to give back)
             raise ValueError("vec_env: voxels are refused together with the render_cam_major option (which `cameras` switch on): the grid reads env-major images")
+        if views is not None and (list(cameras) or float((options or {}).get("render_cam_major", 0)) != 0):
+            raise ValueError("vec_env: views are refused together with the render_cam_major option (which `cameras` switch on): the virtual views read env-major images")
         self.torch = torch
         self.task, self.num_arms, self.num_envs = task, num_arms, int(num_envs)
         self.max_episode_steps, self.terminate_on_success = int(max_episode_steps), bool(terminate_on_success)
@@ -124,6 +133,17 @@ class VecEnv(DeviceImageOps):
                   "bounds": np.ascontiguousarray(vx["bounds"], dtype=np.float32).reshape(-1), "colour": bool(vx.get("colour")),
                   "max_depth": float(pcspec.FAR_PLANE if vx.get("max_depth") is None else vx["max_depth"])}
             voxspec.check_voxel_grid(len(self.manifest["camera_names"]), vx["ids"], vx["height"], vx["width"], vx["bounds"], vx["max_depth"], vx["g"])
+        vv = None
+        if views is not None:           # likewise
+            from . import pointcloud as pcspec, virtviews as vvspec
+            vv = dict(views)
+            cams = list(vv["cameras"])
+            assert all(c in CAMERAS for c in cams), "Invalid camera names"
+            vv = {"cameras": cams, "ids": camera_ids(self.manifest, cams), "height": int(vv["height"]), "width": int(vv["width"]),
+                  "codes": np.array(vvspec.view_codes(vv.get("views", ["+z", "+x", "-x", "+y", "-y"])), dtype=np.int32), "size": np.array(vvspec.view_size(vv.get("size", 220)), dtype=np.int32),
+                  "radius": int(vv.get("radius", 1)), "bounds": np.ascontiguousarray(vv["bounds"], dtype=np.float32).reshape(-1), "colour": bool(vv.get("colour", True)),
+                  "max_depth": float(pcspec.FAR_PLANE if vv.get("max_depth") is None else vv["max_depth"])}
+            vvspec.check_virtual_views(len(self.manifest["camera_names"]), vv["ids"], vv["height"], vv["width"], vv["bounds"], vv["max_depth"], vv["codes"], vv["size"], vv["radius"])
         flags = _ffi.AVSIM_IO_DEVICE | (_ffi.AVSIM_F64_PHYSICS if f64 else 0)
         with torch.cuda.device(self.device):
             self.h = _ffi.Handle(blob, self.num_envs, self.device.index, flags)
@@ -187,6 +207,13 @@ class VecEnv(DeviceImageOps):
             self._vox = {**vx, "dims": np.array(vx["g"], dtype=np.int32), "depth": torch.zeros((N, nc, vx["height"], vx["width"]), dtype=torch.float32, device=dev),
                          "rgb": torch.zeros((N, nc, vx["height"], vx["width"], 3), dtype=torch.uint8, device=dev) if vx["colour"] else None,
                          "grid": grid, "view": grid.permute(0, 4, 1, 2, 3)}
+        self._vv = None
+        if vv is not None:          # RVT's orthographic images of the box per env as an observation: their own cameras, size, depth and colour buffers
+            nc, vshape = len(vv["cameras"]), (N, len(vv["codes"]), int(vv["size"][0]), int(vv["size"][1]))
+            out = torch.zeros(vshape + (8,), dtype=torch.float32, device=dev)
+            self._vv = {**vv, "depth": torch.zeros((N, nc, vv["height"], vv["width"]), dtype=torch.float32, device=dev),
+                        "rgb": torch.zeros((N, nc, vv["height"], vv["width"], 3), dtype=torch.uint8, device=dev) if vv["colour"] else None,
+                        "out": out, "view": out.permute(0, 1, 4, 2, 3), "index": torch.zeros(vshape, dtype=torch.int32, device=dev)}
         self._bind_stream()
         self._setup(self.seed, 0)
 
@@ -232,11 +259,22 @@ class VecEnv(DeviceImageOps):
             self.h.check(L.avsim_voxel_grid(h, ids, nc, vx["height"], vx["width"], vx["depth"].data_ptr(), _ffi.ptr(vx["rgb"]), vx["bounds"].ctypes.data, vx["max_depth"],
                                             vx["dims"].ctypes.data, vx["grid"].data_ptr()))
             obs["observation.voxels" if self.obs_format == "lerobot" else "voxels"] = vx["view"]
+        if self._vv is not None:
+            vv = self._vv
+            ids, nc = vv["ids"].ctypes.data, len(vv["cameras"])
+            self.h.check(L.avsim_render_depth(h, ids, nc, vv["height"], vv["width"], vv["depth"].data_ptr()))
+            if vv["rgb"] is not None:
+                self.h.check(L.avsim_render_rgb(h, ids, nc, vv["height"], vv["width"], vv["rgb"].data_ptr()))
+            self.h.check(L.avsim_virtual_views(h, ids, nc, vv["height"], vv["width"], vv["depth"].data_ptr(), _ffi.ptr(vv["rgb"]), vv["bounds"].ctypes.data, vv["max_depth"],
+                                               vv["codes"].ctypes.data, len(vv["codes"]), vv["size"].ctypes.data, vv["radius"], vv["out"].data_ptr(), vv["index"].data_ptr()))
+            obs["observation.virtual_views" if self.obs_format == "lerobot" else "virtual_views"] = vv["view"]
         return obs
 
     def _pc_info(self, info):
         if self._pc is not None:
             info["pointcloud_count"], info["pointcloud_index"] = self._pc["count"], self._pc["index"]
+        if self._vv is not None:
+            info["virtual_views_index"] = self._vv["index"]
         return info
 
     # -- gym API -------------------------------------------------------------------------------------
@@ -353,11 +391,11 @@ class VecEnv(DeviceImageOps):
 
 
 def make_vec(env_id, num_envs, max_episode_steps, device=None, cameras=None, depth_cameras=(), obs_format="lerobot", seed=0,
-             terminate_on_success=False, f64=False, options=None, observation_height=None, observation_width=None, pointcloud=None, voxels=None):
-    """A VecEnv of a registry id (env.ENVS); cameras default to the registry's, the image size to its 480 x 640.  pointcloud, voxels: VecEnv's."""
+             terminate_on_success=False, f64=False, options=None, observation_height=None, observation_width=None, pointcloud=None, voxels=None, views=None):
+    """A VecEnv of a registry id (env.ENVS); cameras default to the registry's, the image size to its 480 x 640.  pointcloud, voxels, views: VecEnv's."""
     spec = ENVS[env_id]
     return VecEnv(_TASK_OF_CLASS[spec["env"]], spec["num_arms"], num_envs, max_episode_steps, device=device,
                   cameras=spec["cameras"] if cameras is None else cameras, depth_cameras=depth_cameras, obs_format=obs_format, seed=seed,
                   terminate_on_success=terminate_on_success, f64=f64, options=options,
                   observation_height=spec["observation_height"] if observation_height is None else observation_height,
-                  observation_width=spec["observation_width"] if observation_width is None else observation_width, pointcloud=pointcloud, voxels=voxels)
+                  observation_width=spec["observation_width"] if observation_width is None else observation_width, pointcloud=pointcloud, voxels=voxels, views=views)

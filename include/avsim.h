@@ -279,6 +279,54 @@ int avsim_voxel_grid(avsim_t* h, const int32_t* cam_ids, int ncam, int height, i
                      const float* depth /* [N][ncam][H][W] */, const uint8_t* rgb /* [N][ncam][H][W][3], avsim_render_rgb's env-major layout, or NULL */,
                      const float bounds[6] /* host */, float max_depth, const int32_t* grid /* host [3] */, float* out /* [N][gx][gy][gz][8] */);
 
+/* Virtual orthographic views on the device (csrc/avsim_pointcloud.hip); av_aloha_amd/virtviews.py is the specification, and the
+ * result equals it bit for bit given the pose records.  What RVT and RVT-2 feed their 2-D transformer: the fused cloud of an env's depth
+ * cameras re-rendered into nviews (1..6, repeats allowed) axis-aligned orthographic images of the box `bounds` in the world frame, every one
+ * VH x VW (size[0] x size[1], each 1..AVSIM_VV_MAX_SIZE).  Depth images, poses (THE CURRENT STATE'S), deprojection and candidate rule are
+ * avsim_point_cloud's -- d < max_depth, the inclusive box, a NaN drops the pixel -- without a cap.  A view is a code 0..5, a proper,
+ * unmirrored look at the box from outside (row 0 is the top of the image):
+ *   code  name  seen from       column runs along  row runs along   dist
+ *   0     +x    the hi-x face   y ascending        z descending     hi_x - w_x
+ *   1     -x    the lo-x face   y descending       z descending     w_x - lo_x
+ *   2     +y    the hi-y face   x descending       z descending     hi_y - w_y
+ *   3     -y    the lo-y face   x ascending        z descending     w_y - lo_y
+ *   4     +z    above           x ascending        y descending     hi_z - w_z
+ *   5     -z    below           x ascending        y ascending      w_z - lo_z
+ * Pixel coordinate, float32 with every operation rounded on its own, for an image axis of n pixels (VW for a column, VH for a row) along
+ * world axis k: inv = (float)n / (hi_k - lo_k), u = (w_k - lo_k) inv, i = min(floor(u), n - 1) -- avsim_voxel_grid's cell formula; a point
+ * on hi goes to the last pixel --; ascending the pixel is i, descending n - 1 - i.  Footprint: with `radius` r (0..AVSIM_VV_MAX_RADIUS) a
+ * candidate at (pr, pc) covers the pixels (pr + dr, pc + dc), |dr|, |dc| <= r, that lie inside the image.  Key: a candidate's key in a view
+ * is the UNSIGNED 64-BIT value (bits(dist) << 32) | slot -- the float32 bit pattern of its dist, which is >= 0 inside the box (a point on
+ * the face gives +0), above its flat pixel slot H W + r W + c < 2^24.  The winner of a virtual pixel is the SMALLEST key among the
+ * candidates that cover it: the nearest point and, among equals, the lowest slot.  A minimum does not depend on the order it is taken in,
+ * so the (atomic) scatter gives the same result on every call.
+ * out[n][v][r][c] = eight float32: 0..2 the winner's colour (float)u8 * (1.0f / 255.0f) (0 with rgb NULL), 3 its dist in metres, 4..6 its
+ * world point -- the deprojection's values for the winning slot, not the pixel's centre --, 7 1.0.  index[n][v][r][c] = the winning slot (a
+ * caller gathers any per-pixel feature with it, as with avsim_point_cloud's index).  A pixel nothing covers is eight +0.0 and index -1.
+ * depth, rgb (avsim_render_rgb's env-major u8 layout of the same pixels, or NULL), out and index follow the handle's I/O mode; cam_ids,
+ * bounds, views and size are HOST arrays in both modes, passed on by value: the caller may change them as soon as the call returns.  `out`
+ * is the z-buffer (a pixel's first 8 of its 32 bytes hold the key until the last pass): no scratch beyond the pose records of a chunk of at
+ * most 1024 envs, shared with avsim_point_cloud, and with AVSIM_IO_DEVICE nothing synchronises once a call of the same number of cameras
+ * has run; there `out` is 16-byte aligned.
+ * AVSIM_EINVAL, with nothing launched and both outputs untouched: ncam outside 1..16, height or width outside 1..65535, ncam H W > 2^24,
+ * nviews outside 1..6, a view code outside 0..5, a size outside 1..1024, radius outside 0..4, a bound that is not finite, lo >= hi on an
+ * axis, an extent whose inv or pixel size (hi_k - lo_k) / (float)n is not a finite float32 -- every axis against both VH and VW, whichever
+ * views are named --, max_depth not finite or <= 0, a camera id out of range, out not 16-byte aligned in device mode, a null pointer other
+ * than rgb.
+ * The scatter pass has two independent cuts, each of which keeps the bits -- a plain load of the pixel's key that skips the atomic when the
+ * lane's key is not smaller (keys only decrease: a stale read is safe), and merging runs of consecutive lanes on one virtual pixel in the
+ * wave --; all four forms are compiled and the build picks (AVSIM_VV_FORM, csrc/avsim_pointcloud.hip.h: bit 0 the load, bit 1 the merge,
+ * 4 the merge always and the load where it was measured to pay: with radius > 0, and with radius 0 when a view has more pixels than the env
+ * has source pixels).  4 SHIPS.  Debug option "virtviews_form" f + 1 runs form f (0: the build's) so that tools/bench_virtviews.py can
+ * time them in one process. */
+#define AVSIM_VV_MAX_VIEWS 6
+#define AVSIM_VV_MAX_SIZE 1024
+#define AVSIM_VV_MAX_RADIUS 4
+int avsim_virtual_views(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width,
+                        const float* depth /* [N][ncam][H][W] */, const uint8_t* rgb /* [N][ncam][H][W][3], avsim_render_rgb's env-major layout, or NULL */,
+                        const float bounds[6] /* host */, float max_depth, const int32_t* views /* host [nviews] */, int nviews,
+                        const int32_t* size /* host [2]: VH, VW */, int radius, float* out /* [N][nviews][VH][VW][8] */, int32_t* index /* [N][nviews][VH][VW] */);
+
 /* Baseline JPEG streams of rendered frames, encoded on the device (csrc/avsim_jpeg.hip.h): SOF0, 8 bit, JFIF, Y Cb Cr 4:2:0, the Annex K
  * Huffman tables in every frame, one restart interval per MCU row, integer arithmetic throughout -- byte for byte the stream of
  * av_aloha_amd/jpeg.py encode_reference, which is its specification (colour matrix, DCT, quantiser rounding: DESIGN 8.y).
