@@ -9,6 +9,14 @@ LIB = os.path.join(HERE, "libavsim.so")
 SRC = os.path.join(HERE, "csrc")
 
 
+# The flag lists of the physics units (why each flag: the comments in _build_hip_locked).  Module level so that tools/asm_addr_counts.py
+# compiles the device assembly with the very flags of the build.
+COMMON_FLAGS = ["--offload-arch=gfx950", "-std=c++17", "-fPIC", "-fno-gpu-rdc"]
+F32_FLAGS = ["-O2", "-fno-hip-fp32-correctly-rounded-divide-sqrt", "-fgpu-flush-denormals-to-zero", "-fno-slp-vectorize", "-fno-vectorize",
+             "-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]
+F64_FLAGS = ["-O3", "-ffp-contract=off", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]
+
+
 def _stale(target, sources):
     if not os.path.exists(target):
         return True
@@ -35,9 +43,7 @@ def build_hip(force=False, verbose=False):
 
 def _build_hip_locked(verbose):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    common = [hipcc, "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-c"]
-    F32_FLAGS = ["-O2", "-fno-hip-fp32-correctly-rounded-divide-sqrt", "-fgpu-flush-denormals-to-zero", "-fno-slp-vectorize", "-fno-vectorize",
-                 "-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]
+    common = [hipcc] + COMMON_FLAGS + ["-c"]
     units = [
         # f32 divide / sqrt through v_rcp / v_rsq (~1 ulp) instead of the correctly rounded 10-instruction sequences; the f64
         # parity mode is unaffected and the f32 tolerances of tests/test_gpu_physics.py are stated against the f64 oracle
@@ -57,7 +63,7 @@ def _build_hip_locked(verbose):
         # unchanged -- but the scripted closed-loop episodes become other trajectories (GradIK amplifies a rounding), and on the new SlotInsertion episodes the
         # device's contact counts differ from the FULL-hull oracle's in 1.8 % of the env-steps where tests/test_gpu_fidelity.py asserts <= 1 % (0.29 % on the unfused
         # build's episodes): not adopted (profiles/r06_experiments.txt 5)
-        ("avsim_phys_f64", ["-O3", "-ffp-contract=off", "-mllvm", "-amdgpu-sched-strategy=max-ilp"] + os.environ.get("AVSIM_EXTRA_FLAGS_F64", "").split()),
+        ("avsim_phys_f64", F64_FLAGS + os.environ.get("AVSIM_EXTRA_FLAGS_F64", "").split()),
         # the image augmentation equals its numpy specification (av_aloha_amd/imgaug.py) bit for bit, which F32_FLAGS cannot give: -ffp-contract=off keeps
         # a * f + b * g two multiplications and an addition; -fhip-fp32-correctly-rounded-divide-sqrt (the compiler's default, named so that it stays) makes
         # x / y the IEEE sequence v_div_scale / v_rcp / v_fma x 4 / v_div_fmas / v_div_fixup; -fno-gpu-flush-denormals-to-zero (also the default for

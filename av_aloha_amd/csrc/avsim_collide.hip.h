@@ -85,7 +85,10 @@ AVS_DEV void support(const Shape<T>& s, const T* d, T* out) {
             int iu = (int)((u + T(1)) * T(0.5) * T(R)), iv = (int)((v + T(1)) * T(0.5) * T(R));
             iu = iu > 0 ? (iu < R - 1 ? iu : R - 1) : 0;
             iv = iv > 0 ? (iv < R - 1 ? iv : R - 1) : 0;
-            GLB_PTR(const T) C = s.hull + 32 * (size_t)(s.hbase + ((2 * a + (lm < T(0) ? 1 : 0)) * R + iu) * R + iv);
+            // (the one table of the model, the same pointer in every lane; it travels in the per-lane Shape, so it is made scalar again here.
+            // Offsets in 32 bits: the host refuses a table of 4 GiB or more, PhysHost::build)
+            const GArr<const T> H(glb_uniform(s.hull));
+            const GArr<const T> C = H + 32 * (s.hbase + ((2 * a + (lm < T(0) ? 1 : 0)) * R + iu) * R + iv);
             const T tie = TieTol<T>::rel * T(0.1) * (ax + ay + az);
             T vx[8], vy[8], vz[8], pr[8], w0, w1;
 #pragma unroll
@@ -97,7 +100,7 @@ AVS_DEV void support(const Shape<T>& s, const T* d, T* out) {
             T bd = T(-1e30);
 #pragma unroll
             for (int k = 0; k < 8; k++) { pr[k] = vx[k] * l[0] + vy[k] * l[1] + vz[k] * l[2]; bd = pr[k] > bd ? pr[k] : bd; }
-            GLB_PTR(const T) O = s.hull + 4 * ((size_t)s.hovf + (size_t)(cnt > 8 ? (int)w1 : 0));
+            const GArr<const T> O = H + 4 * (s.hovf + (cnt > 8 ? (int)w1 : 0));
             const int more = cnt - 8, lastm = more - 1;
             for (int i = 0; i < more; i += 8) {     // (cells at the normal of a face with many vertices: the further candidates)
 #pragma unroll
@@ -182,8 +185,10 @@ template <> struct MprTol<double> { static constexpr double tol = 1e-6, tiny2 = 
 template <> struct MprTol<float> { static constexpr float tol = 1e-6f, tiny2 = 1e-16f, eps = 1e-9f; };
 
 // MPR on A - B: returns 1 with depth>0, dir (unit, A -> B) and pos when the shapes overlap
+// (always inlined into its two callers, narrow and mpr_perturbed: as a function of its own the two Shapes travel through the wave's private
+// segment.  The inliner used to decide so by itself; it is sensitive to the size of `support`, so the decision is now written down.)
 template <typename T>
-__device__ int mpr_penetration(const Shape<T>& A, const Shape<T>& B, T* depth, T* dir, T* pos) {
+__device__ __attribute__((always_inline)) int mpr_penetration(const Shape<T>& A, const Shape<T>& B, T* depth, T* dir, T* pos) {
     const T tol = MprTol<T>::tol;
     const int maxit = 50;
     MPt<T> v0, v1, v2, v3, v4;
@@ -595,8 +600,8 @@ __device__ int box_box(const Shape<T>& a, const Shape<T>& b, AVS_LDS(T) scr, AVS
             for (int c = 0; c < 3; c++) scr[SLOT_P + 3 * x + c] = wv[c] + rpos[c];
             scr[x] = -dq_;
         } else {
-            ovf[4 * (x - BOX_SLOTC)] = -dq_;
-            for (int c = 0; c < 3; c++) ovf[4 * (x - BOX_SLOTC) + 1 + c] = wv[c] + rpos[c];
+            (ovf + 4 * (x - BOX_SLOTC))[0] = -dq_;
+            for (int c = 0; c < 3; c++) (ovf + 4 * (x - BOX_SLOTC))[1 + c] = wv[c] + rpos[c];
         }
     }
     for (int c = 0; c < 3; c++) scr[SLOT_N + c] = n[c];
@@ -614,7 +619,7 @@ template <typename T> AVS_DEV T sel33(const T (*M)[3], int i, int j) { return se
 template <typename T> AVS_DEV T row_get(T x, int g16, int l) { return __shfl(x, g16 | l, 64); }
 
 template <typename T, typename OVF>
-__device__ int box_box16(const Shape<T>& a, const Shape<T>& b, AVS_LDS(T) scr, AVS_LDS(T) work, OVF ovf, int lane, bool on) {
+__device__ __attribute__((always_inline)) int box_box16(const Shape<T>& a, const Shape<T>& b, AVS_LDS(T) scr, AVS_LDS(T) work, OVF ovf, int lane, bool on) {      // (one caller; inlined there as before, see mpr_penetration)
     const int t = lane & 15, g16 = lane & ~15;
     const unsigned rowmask_sh = g16;
     const T *Ra = a.mat, *Rb = b.mat;
@@ -817,8 +822,8 @@ __device__ int box_box16(const Shape<T>& a, const Shape<T>& b, AVS_LDS(T) scr, A
             for (int c = 0; c < 3; c++) scr[SLOT_P + 3 * t + c] = wv[c] + rpos[c];
             scr[t] = -dq_;
         } else {
-            ovf[4 * (t - BOX_SLOTC)] = -dq_;
-            for (int c = 0; c < 3; c++) ovf[4 * (t - BOX_SLOTC) + 1 + c] = wv[c] + rpos[c];
+            (ovf + 4 * (t - BOX_SLOTC))[0] = -dq_;
+            for (int c = 0; c < 3; c++) (ovf + 4 * (t - BOX_SLOTC))[1 + c] = wv[c] + rpos[c];
         }
     }
     if (on && t == 0) { for (int c = 0; c < 3; c++) scr[SLOT_N + c] = n[c]; }
@@ -850,7 +855,7 @@ AVS_DEV bool boxes_separated(const Shape<T>& a, const Shape<T>& b) {
 // dispatch for every pair that is not box-box (those go through box_box with their own work area); at most one contact,
 // written to the lane's result slot: dist [0], pos [SLOT_P, +3), normal [SLOT_N, +3)
 template <typename T>
-__device__ int narrow(const Shape<T>& a, const Shape<T>& b, AVS_LDS(T) scr) {
+__device__ __attribute__((always_inline)) int narrow(const Shape<T>& a, const Shape<T>& b, AVS_LDS(T) scr) {      // (one caller; inlined there as before, see mpr_penetration)
     int ta = a.type, tb = b.type;
     if (boxes_separated(a, b)) return 0;
     T dist[1], pos[3], nrm[3];

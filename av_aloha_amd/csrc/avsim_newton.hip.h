@@ -37,15 +37,15 @@ namespace avs {
 // without it the compiler sinks each element's load into the branch that consumes it (load - wait - use, sixteen times)
 typedef float nv4f __attribute__((ext_vector_type(4)));
 typedef double nv2d __attribute__((ext_vector_type(2)));
-AVS_DEV void load_row16(GLB_PTR(const float) src, float* v) {
-    GLB_PTR(const nv4f) p = (GLB_PTR(const nv4f))src;
+AVS_DEV void load_row16(GArr<const float> src, float* v) {
+    const GArr<const nv4f> p = src.as<const nv4f>();
     nv4f a = p[0], b = p[1], c = p[2], d = p[3];
     asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
     v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
     v[8] = c.x; v[9] = c.y; v[10] = c.z; v[11] = c.w; v[12] = d.x; v[13] = d.y; v[14] = d.z; v[15] = d.w;
 }
-AVS_DEV void load_row16(GLB_PTR(const double) src, double* v) {
-    GLB_PTR(const nv2d) p = (GLB_PTR(const nv2d))src;
+AVS_DEV void load_row16(GArr<const double> src, double* v) {
+    const GArr<const nv2d> p = src.as<const nv2d>();
     nv2d t[8];
 #pragma unroll
     for (int q = 0; q < 8; q++) t[q] = p[q];
@@ -60,7 +60,7 @@ struct NewtonArgs {
     LDS_PTR(real) rowS;          // 8 reals per row: aref, R, [Newton: J a - aref], 1/diag|0, lo, hi, force, 1/friction
     LDS_PTR(const int) rowI;     // dof windows of the row: (adr 6 | n 4 | tree 3) x 2
     LDS_PTR(const int) rmeta;    // type 2 | id 10 | sub 8 | tree ids
-    GLB_PTR(const real) rJ;      // 16 reals per row, global memory (L2-resident scratch of this env)
+    GArr<const real> rJ;         // 16 reals per row, global memory (L2-resident scratch of this env): uniform base, GArr
     LDS_PTR(const real) M;       // per-tree dense blocks
     LDS_PTR(real) a;             // qacc (in: start point, out: solution)
     LDS_PTR(const real) as;      // qacc_smooth
@@ -90,7 +90,7 @@ template <typename real>
 AVS_DEV real nrow_dot(const NewtonArgs<real>& A, int i, LDS_PTR(const real) v) {
     const int ra = A.rowI[i];
     const int a0 = ra & 63, nA = (ra >> 6) & 15, b0 = (ra >> 13) & 63, nB = (ra >> 19) & 15;
-    GLB_PTR(const real) J = A.rJ + ROW_S * i;
+    const GArr<const real> J = A.rJ + ROW_S * i;
     real s = 0;
 #pragma unroll
     for (int k = 0; k < TREE_W; k++) {
@@ -232,7 +232,7 @@ template <typename real> AVS_DEV real lead_v1(int ra) { return ((ra >> 13) & 1) 
 // sums the contact's <= 6 rows in registers (coalesced 64-byte row reads) and adds once: an atomic instruction then carries 16
 // distinct addresses per contact instead of one address per tree from every row (the rows of a tree all share their slots).
 template <typename real>
-AVS_DEV void rows_jt_force(LDS_PTR(const real) rowS, LDS_PTR(const int) rowI, LDS_PTR(const int) cefc, GLB_PTR(const real) rJ, LDS_PTR(real) out,
+AVS_DEV void rows_jt_force(LDS_PTR(const real) rowS, LDS_PTR(const int) rowI, LDS_PTR(const int) cefc, GArr<const real> rJ, LDS_PTR(real) out,
                            int nlead, int ncon, int lane, real sgn) {
     for (int i = lane; i < nlead; i += 64) {
         const real f = rowS[RS_S * i + 6];
@@ -270,7 +270,7 @@ AVS_DEV void rows_jt_force(LDS_PTR(const real) rowS, LDS_PTR(const int) rowI, LD
 template <typename real>
 AVS_DEV void nblock4_load(const NewtonArgs<real>& A, int lane, int r0, int dim, bool on, real* Jraw) {
     const int t = lane & 15;
-    GLB_PTR(const real) J = A.rJ + ROW_S * (on ? r0 : 0);
+    const GArr<const real> J = A.rJ + ROW_S * (on ? r0 : 0);
 #pragma unroll
     for (int p = 0; p < 6; p++) Jraw[p] = J[ROW_S * (p < dim ? p : 0) + t];
 }
@@ -291,11 +291,11 @@ AVS_DEV void nblock4(const NewtonArgs<real>& A, int lane, int r0, int dim, bool 
             // The entries of the other columns come straight from the rows in memory (the look-ahead read has just brought the
             // lines in): 30 four-byte reads in flight together instead of 30 ds_bpermute round trips of 50 - 75 cycles each.
             const int tc = lane & 7, s0 = (lane & 8) >> 1, gqc = on ? nslot_dof(ra, tc) : -1;
-            GLB_PTR(const real) J = A.rJ + ROW_S * (on ? r0 : 0);
+            const GArr<const real> J = A.rJ + ROW_S * (on ? r0 : 0);
             real Jc[6], Js[4][6];
 #pragma unroll
             for (int p = 0; p < 6; p++) {
-                GLB_PTR(const real) Jp = J + ROW_S * (p < dim ? p : 0);
+                const GArr<const real> Jp = J + ROW_S * (p < dim ? p : 0);
                 Jc[p] = Jp[tc];
 #pragma unroll
                 for (int u = 0; u < 4; u++) Js[u][p] = Jp[s0 + u];
@@ -707,10 +707,7 @@ __device__ __attribute__((always_inline)) int newton_solve(KA ka, GLB_PTR(const 
         LDS_PTR(const int) li = (LDS_PTR(const int))(unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)li_);
         tol = lane_get(tol, 0); scale = lane_get(scale, 0);
         A.rowS = r + ka->lay.rowS; A.rowI = ii + ka->lay.rowI; A.rmeta = ii + ka->lay.rmeta;
-        {   // the row pointer is wave-uniform: back to SGPRs
-            const unsigned long long p_ = (unsigned long long)rows;
-            A.rJ = (GLB_PTR(const real))(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(p_ >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)p_));
-        }
+        A.rJ = GArr<const real>(glb_uniform(rows));      // the row pointer is wave-uniform: back to SGPRs
         A.M = r + ka->lay.M; A.a = r + ka->lay.qacc; A.as = r + ka->lay.asm_;
         A.H = r + ka->lay.nH; A.g = r + ka->lay.ng; A.dl = r + ka->lay.ndl; A.jv = r + ka->lay.njv;
         A.cefc = ii + ka->lay.cefc;
@@ -1044,6 +1041,7 @@ __device__ __attribute__((always_inline)) int newton_solve(KA ka, GLB_PTR(const 
 template <typename real, int NCH, typename KA>
 __device__ AVS_OUTLINE_5 int newton_solve_coupled(KA ka, GLB_PTR(const real) rows, LDS_PTR(real) r_, LDS_PTR(int) ii_, LDS_PTR(const int) li_, int nefc, int ncon, int nlead,
                                                               int iters, real tol, real scale, int profiling) {
+    PHASE_LAUNDER();      // `ka` arrives in VGPRs: back to SGPRs, so that what is read through it is a scalar load, not a load through a VGPR address
     return newton_solve<real, NCH, true>(ka, rows, r_, ii_, li_, nefc, ncon, nlead, iters, tol, scale, profiling);
 }
 

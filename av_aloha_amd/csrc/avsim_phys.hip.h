@@ -441,10 +441,12 @@ template <typename real> AVS_DEV NoslipLead<real> nl_unpack(nl_v4 a, nl_v4 b, nl
 template <typename T> AVS_DEV LDS_PTR(T) uni_lds(LDS_PTR(T) p) {
     return (LDS_PTR(T))(unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)p);
 }
-template <typename T> AVS_DEV GLB_PTR(T) uni_glb(GLB_PTR(T) p) {
-    const unsigned long long v = (unsigned long long)p;
-    return (GLB_PTR(T))(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v));
-}
+// (the Gauss-Seidel and noslip functions below keep plain global pointers, 64-bit per-lane addresses: with their bases held in SGPR pairs they moved more
+// SGPRs through VGPR lanes and their phase got slower)
+template <typename T> AVS_DEV GLB_PTR(T) uni_glb(GLB_PTR(T) p) { return glb_uniform(p); }
+template <typename T> AVS_DEV GArr<T> garr(GLB_PTR(T) p) { return GArr<T>(p); }      // (a base the compiler already has in SGPRs)
+// a model table in global memory: a pointer member of ka->m, scalar-loaded through the (laundered) ka
+#define TAB(name) garr(ka->m.name)
 
 // Step of the multiplier iteration of a sliding contact's QCQP, |y(la)| = r with y = -(A + la I)^-1 b.  MuJoCo's mju_QCQP takes
 // Newton steps on |y|^2 - r^2 from la = 0 (val / (2 y.w), w = (A + la I)^-1 y); that function is strongly convex in la and the
@@ -1646,13 +1648,13 @@ namespace avs {
 // one 16-word row record to global memory in 16-byte pieces (rows are 64- / 128-byte aligned)
 typedef float avs_v4f __attribute__((ext_vector_type(4)));
 typedef double avs_v2d __attribute__((ext_vector_type(2)));
-AVS_DEV void store_row16(GLB_PTR(float) dst, const float* v) {
+AVS_DEV void store_row16(GArr<float> dst, const float* v) {
 #pragma unroll
-    for (int q = 0; q < 4; q++) { avs_v4f t = {v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]}; ((GLB_PTR(avs_v4f))dst)[q] = t; }
+    for (int q = 0; q < 4; q++) { avs_v4f t = {v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]}; dst.as<avs_v4f>()[q] = t; }
 }
-AVS_DEV void store_row16(GLB_PTR(double) dst, const double* v) {
+AVS_DEV void store_row16(GArr<double> dst, const double* v) {
 #pragma unroll
-    for (int q = 0; q < 8; q++) { avs_v2d t = {v[2 * q], v[2 * q + 1]}; ((GLB_PTR(avs_v2d))dst)[q] = t; }
+    for (int q = 0; q < 8; q++) { avs_v2d t = {v[2 * q], v[2 * q + 1]}; dst.as<avs_v2d>()[q] = t; }
 }
 
 // eight consecutive LDS reals whose address is a multiple of 16 bytes, as two (four) vector reads
@@ -1690,7 +1692,7 @@ struct SInert {
 template <typename real, typename KA>
 AVS_DEV void body_inertia(KA ka, const real* xmat, const real* xipos, int b, SInert<real>& s) {
     const real* R = xmat + 9 * b;
-    GLB_PTR(const real) Ib = ka->m.body_inertia + 6 * b;
+    const GArr<const real> Ib = TAB(body_inertia) + 6 * b;
     real I3[9] = {Ib[0], Ib[3], Ib[4], Ib[3], Ib[1], Ib[5], Ib[4], Ib[5], Ib[2]}, T[9], Ic[9];
 #pragma unroll
     for (int i = 0; i < 3; i++)
@@ -1700,7 +1702,7 @@ AVS_DEV void body_inertia(KA ka, const real* xmat, const real* xipos, int b, SIn
     for (int i = 0; i < 3; i++)
 #pragma unroll
         for (int j = 0; j < 3; j++) Ic[3 * i + j] = T[3 * i] * R[3 * j] + T[3 * i + 1] * R[3 * j + 1] + T[3 * i + 2] * R[3 * j + 2];
-    real ms = ka->m.body_mass[b];
+    real ms = TAB(body_mass)[b];
     real c[3] = {xipos[3 * b], xipos[3 * b + 1], xipos[3 * b + 2]};
     real cc = dot3(c, c);
     s.m = ms;
@@ -1896,13 +1898,15 @@ struct Env {
     // (the model's two integers outside its head: the spec's constants in a per-model kernel)
     AVS_DEV int nobj_() const { if constexpr (spec_fixed<SPEC>) return SPEC::nobj; else return ka->m.nobj; }
     AVS_DEV int hull_ovf_() const { if constexpr (spec_fixed<SPEC>) return SPEC::hull_ovf; else return ka->m.hull_ovf; }
-    AVS_DEV GLB_PTR(real) rows_() const { return (GLB_PTR(real))ka->m.rJ_glob + (size_t)env * ka->lay.gefc * ROW_S; }
-    AVS_DEV GLB_PTR(real) rowsB_() const { return (GLB_PTR(real))ka->m.rB_glob + (size_t)env * ka->lay.gefc * ROW_S; }
-    AVS_DEV GLB_PTR(real) coup_() const { return (GLB_PTR(real))ka->m.gA_glob + (size_t)env * ka->lay.ggrp * GA_W; }
-    AVS_DEV GLB_PTR(int) near_() const { return (GLB_PTR(int))ka->m.near_glob + (size_t)env * NEAR_MAX; }
-    AVS_DEV GLB_PTR(int) cand_() const { return (GLB_PTR(int))ka->m.cand_glob + (size_t)env * CAND_MAX; }
-    AVS_DEV GLB_PTR(real) bxo_() const { return (GLB_PTR(real))ka->m.bxo_glob + (size_t)env * 64 * BOX_OVF_W; }
-    AVS_DEV GLB_PTR(real) gref_() const { return (GLB_PTR(real))ka->m.gref_glob + (size_t)env * ka->m.ngeom * 3; }
+    // the env's blocks of the global scratch: base + env * stride as a 64-bit SCALAR sum, once per phase (the env is wave-uniform; the phases
+    // reach it through an object in memory, hence the readfirstlane inside glb_block); the lanes' offsets inside the block fit 32 bits for any N
+    AVS_DEV GArr<real> rows_() const { return glb_block((GLB_PTR(real))ka->m.rJ_glob, env, (unsigned)(ka->lay.gefc * ROW_S)); }
+    AVS_DEV GArr<real> rowsB_() const { return glb_block((GLB_PTR(real))ka->m.rB_glob, env, (unsigned)(ka->lay.gefc * ROW_S)); }
+    AVS_DEV GArr<real> coup_() const { return glb_block((GLB_PTR(real))ka->m.gA_glob, env, (unsigned)(ka->lay.ggrp * GA_W)); }
+    AVS_DEV GArr<int> near_() const { return glb_block((GLB_PTR(int))ka->m.near_glob, env, (unsigned)NEAR_MAX); }
+    AVS_DEV GArr<int> cand_() const { return glb_block((GLB_PTR(int))ka->m.cand_glob, env, (unsigned)CAND_MAX); }
+    AVS_DEV GArr<real> bxo_() const { return glb_block((GLB_PTR(real))ka->m.bxo_glob, env, (unsigned)(64 * BOX_OVF_W)); }
+    AVS_DEV GArr<real> gref_() const { return glb_block((GLB_PTR(real))ka->m.gref_glob, env, (unsigned)(ka->m.ngeom * 3)); }
     AVS_DEV const int* body_parent_() const { return LI() + ka->mo.body_parent; }
     AVS_DEV const int* body_jntadr_() const { return LI() + ka->mo.body_jntadr; }
     AVS_DEV const int* body_jntnum_() const { return LI() + ka->mo.body_jntnum; }
@@ -2025,8 +2029,8 @@ struct Env {
             real R[9], pos[3];
             int a = -1;
             if (body_tree_()[b] < 0) {
-                for (int k = 0; k < 3; k++) pos[k] = ka->m.static_xpos[3 * b + k];
-                for (int k = 0; k < 9; k++) R[k] = ka->m.static_xmat[9 * b + k];
+                for (int k = 0; k < 3; k++) pos[k] = (TAB(static_xpos) + 3 * b)[k];
+                for (int k = 0; k < 9; k++) R[k] = (TAB(static_xmat) + 9 * b)[k];
             } else {
                 const int p = body_parent_()[b], ja = body_jntadr_()[b], jn = body_jntnum_()[b];
                 const int jt = jn > 0 ? jnt_type_()[ja] : -1;
@@ -2065,12 +2069,12 @@ struct Env {
                         for (int k = 0; k < 3; k++) pos[k] += t0[k] * q;
                     }
                     if (body_tree_()[p] < 0) {      // parent welded to the world: fold its constant pose in right away
-                        GLB_PTR(const real) Rp = ka->m.static_xmat + 9 * p;
+                        const GArr<const real> Rp = TAB(static_xmat) + 9 * p;
                         real Rn[9], t0[3];
                         for (int i = 0; i < 3; i++)
                             for (int j = 0; j < 3; j++) Rn[3 * i + j] = Rp[3 * i] * R[j] + Rp[3 * i + 1] * R[3 + j] + Rp[3 * i + 2] * R[6 + j];
                         mulmat(Rp, pos, t0);
-                        for (int k = 0; k < 3; k++) pos[k] = ka->m.static_xpos[3 * p + k] + t0[k];
+                        for (int k = 0; k < 3; k++) pos[k] = (TAB(static_xpos) + 3 * p)[k] + t0[k];
                         for (int k = 0; k < 9; k++) R[k] = Rn[k];
                     } else a = p;
                 }
@@ -2358,27 +2362,28 @@ struct Env {
         GSYNC();
     }
 
-    __device__ void load_shape(int g, Shape<real>& s) {
+    // (always inlined, as the inliner used to decide by itself: out of line the Shape goes through memory and `ka` arrives in VGPRs)
+    __device__ __attribute__((always_inline)) void load_shape(int g, Shape<real>& s) {
         LDS_BASES();
         real *xpos = r + ka->lay.xpos, *xmat = r + ka->lay.xmat, *gcen = r + ka->lay.gcen;
         s.type = geom_type_()[g];
-        for (int k = 0; k < 3; k++) s.size[k] = ka->m.geom_size[3 * g + k];
+        for (int k = 0; k < 3; k++) s.size[k] = (TAB(geom_size) + 3 * g)[k];
         s.hull = ka->m.hull_vert;
-        s.hbase = ka->m.geom_hull[2 * g];
-        s.hR = ka->m.geom_hull[2 * g + 1];
+        s.hbase = (TAB(geom_hull) + 2 * g)[0];
+        s.hR = (TAB(geom_hull) + 2 * g)[1];
         s.hovf = hull_ovf_();
         s.nh = 0;
-        for (int k = 0; k < 3; k++) { s.lc[k] = ka->m.geom_lbox[6 * g + k]; s.lh[k] = ka->m.geom_lbox[6 * g + 3 + k]; }
+        for (int k = 0; k < 3; k++) { s.lc[k] = (TAB(geom_lbox) + 6 * g)[k]; s.lh[k] = (TAB(geom_lbox) + 6 * g)[3 + k]; }
         if (geom_static_()[g]) {
-            for (int k = 0; k < 3; k++) { s.pos[k] = ka->m.geom_xpos0[3 * g + k]; s.center[k] = ka->m.geom_cen0[3 * g + k]; }
-            for (int k = 0; k < 9; k++) s.mat[k] = ka->m.geom_xmat0[9 * g + k];
+            for (int k = 0; k < 3; k++) { s.pos[k] = (TAB(geom_xpos0) + 3 * g)[k]; s.center[k] = (TAB(geom_cen0) + 3 * g)[k]; }
+            for (int k = 0; k < 9; k++) s.mat[k] = (TAB(geom_xmat0) + 9 * g)[k];
         } else {
             int b = geom_body_()[g];
-            real gp[3] = {ka->m.geom_pos[3 * g], ka->m.geom_pos[3 * g + 1], ka->m.geom_pos[3 * g + 2]}, t3[3];
+            real gp[3] = {(TAB(geom_pos) + 3 * g)[0], (TAB(geom_pos) + 3 * g)[1], (TAB(geom_pos) + 3 * g)[2]}, t3[3];
             mulmat(xmat + 9 * b, gp, t3);
             for (int k = 0; k < 3; k++) { s.pos[k] = xpos[3 * b + k] + t3[k]; s.center[k] = gcen[3 * g + k]; }
             const real* Rb = xmat + 9 * b;
-            GLB_PTR(const real) Rg = ka->m.geom_mat + 9 * g;
+            const GArr<const real> Rg = TAB(geom_mat) + 9 * g;
             for (int i = 0; i < 3; i++)
                 for (int j = 0; j < 3; j++) s.mat[3 * i + j] = Rb[3 * i] * Rg[j] + Rb[3 * i + 1] * Rg[3 + j] + Rb[3 * i + 2] * Rg[6 + j];
         }
@@ -2393,6 +2398,8 @@ struct Env {
     // 20 KB written and read back per narrow-phase pass, most of the kernel's spill traffic (profiles/r05_experiments.txt section 7).
     __device__ AVS_OUTLINE_0 static void multi_perturb(KRef<real, SPEC> ka_, real* r_, int* i_, int lane_, int grp_, const real* lr_, const int* li_, int env_,
                                                                    int pga, int pgb, int src, int pert) {
+        // (`ka_` arrives in VGPRs and stays there: laundered back to SGPRs, the table pointers became scalar loads, the function waited on lgkmcnt(0) 18 times
+        // instead of 5 and the narrow phase was no faster -- DESIGN.md section 9.  The pointers read through it are per-lane values for the compiler: `off` form.)
         Env e(ka_, r_, i_, lane_, grp_, lr_, li_);       // (an Env by value is an aggregate of 22 dwords: passed in memory)
         e.env = env_;
         LDS_PTR(real) os = (LDS_PTR(real))(e.r + e.ka->lay.scr + SLOT_W * src);
@@ -2416,23 +2423,23 @@ struct Env {
         PHASE_BEGIN();
         real* gcen = r + ka->lay.gcen;
         int* misc = ii + ka->lay.misc;
-        GLB_PTR(int) cand = cand_();
+        const GArr<int> cand = cand_();
         int ncand = 0;
         long long tb0 = __builtin_readcyclecounter();
         const real skin = real(0.03);
-        GLB_PTR(real) gref = gref_();
-        GLB_PTR(int) nearl = near_();
+        const GArr<real> gref = gref_();
+        const GArr<int> nearl = near_();
         // pair test with extra reach `pad` (0 = exact broad phase)
         auto pair_hit = [&](int p, real pad) -> bool {
-            int g1 = ka->m.pair_geom[2 * p], g2 = ka->m.pair_geom[2 * p + 1];
+            int g1 = (TAB(pair_geom) + 2 * p)[0], g2 = (TAB(pair_geom) + 2 * p)[1];
             bool s1 = geom_static_()[g1], s2 = geom_static_()[g2];
-            real mg = ka->m.pair_margin[p] + pad;
+            real mg = TAB(pair_margin)[p] + pad;
             if (s1 || s2) {
                 // dynamic bounding sphere against the world AABB of the static geom
                 int gs = s1 ? g1 : g2, gd = s1 ? g2 : g1;
                 real rd = geom_rbound_()[gd] + mg, d2 = 0;
                 for (int k = 0; k < 3; k++) {
-                    real c = gcen[3 * gd + k], lo = ka->m.geom_aabb0[6 * gs + k], hi = ka->m.geom_aabb0[6 * gs + 3 + k];
+                    real c = gcen[3 * gd + k], lo = (TAB(geom_aabb0) + 6 * gs)[k], hi = (TAB(geom_aabb0) + 6 * gs)[3 + k];
                     real e = c < lo ? lo - c : (c > hi ? c - hi : real(0));
                     d2 += e * e;
                 }
@@ -2447,7 +2454,7 @@ struct Env {
         if (misc[7]) {
             for (int g = lane; g < ka->m.ngeom; g += G)
                 if (!geom_static_()[g]) {
-                    const real d[3] = {gcen[3 * g] - gref[3 * g], gcen[3 * g + 1] - gref[3 * g + 1], gcen[3 * g + 2] - gref[3 * g + 2]};
+                    const real d[3] = {gcen[3 * g] - (gref + 3 * g)[0], gcen[3 * g + 1] - (gref + 3 * g)[1], gcen[3 * g + 2] - (gref + 3 * g)[2]};
                     moved |= dot3(d, d) > real(0.25) * skin * skin;
                 }
         }
@@ -2502,14 +2509,14 @@ struct Env {
         // else, then the multiccd perturbations of the convex pairs found in contact: the wave executes the clipping code and the
         // MPR code once each instead of both in every pass.
         int* mlist = ii + ka->lay.cand;      // lanes of the pairs that get the multiccd treatment (the kinematics' table is idle here)
-        GLB_PTR(real) bxo = bxo_();          // points 4..7 of the box-box manifolds of this pass, one record per lane
+        const GArr<real> bxo = bxo_();        // points 4..7 of the box-box manifolds of this pass, one record per lane
         for (int base = 0; base < ncand; base += G) {
             const int ci = base + lane;
             int n = 0, p = 0, nn = 0;
             LDS_PTR(real) scr = (LDS_PTR(real))(r + ka->lay.scr + SLOT_W * lane);
             const bool valid = ci < ncand;
             if (valid) p = cand[ci];
-            const int ga = ka->m.pair_geom[2 * p], gb = ka->m.pair_geom[2 * p + 1];
+            const int ga = (TAB(pair_geom) + 2 * p)[0], gb = (TAB(pair_geom) + 2 * p)[1];
             const int tya = geom_type_()[ga], tyb = geom_type_()[gb];
             const bool isbox = valid && tya == G_BOX && tyb == G_BOX;
             const long long tn0_ = profiling ? __builtin_readcyclecounter() : 0;
@@ -2592,10 +2599,10 @@ struct Env {
                 }
             }
             int keepmask = 0;
-            GLB_PTR(const real) ov = bxo + BOX_OVF_W * lane;
+            const GArr<const real> ov = bxo + BOX_OVF_W * lane;
             if (valid) {
                 // drop separated points (margin = 0 here) while keeping order; a box pair's points 4..7 sit in its overflow record
-                real mg = ka->m.pair_margin[p];
+                real mg = TAB(pair_margin)[p];
                 for (int k = 0; k < nn; k++)
                     if ((isbox && k >= BOX_SLOTC ? ov[4 * (k - BOX_SLOTC)] : scr[k]) < mg) { keepmask |= 1 << k; n++; }
             }
@@ -2613,9 +2620,9 @@ struct Env {
                     w++;
                     if (c < ka->lay.maxcon) {
                         const bool o = isbox && k >= BOX_SLOTC;
-                        cdist[c] = o ? ov[4 * (k - BOX_SLOTC)] : scr[k];
+                        cdist[c] = o ? (ov + 4 * (k - BOX_SLOTC))[0] : scr[k];
                         cpair[c] = p;
-                        for (int q = 0; q < 3; q++) { cpos[3 * c + q] = o ? ov[4 * (k - BOX_SLOTC) + 1 + q] : scr[SLOT_P + 3 * k + q]; cnrm[3 * c + q] = scr[SLOT_N + q]; }
+                        for (int q = 0; q < 3; q++) { cpos[3 * c + q] = o ? (ov + 4 * (k - BOX_SLOTC))[1 + q] : scr[SLOT_P + 3 * k + q]; cnrm[3 * c + q] = scr[SLOT_N + q]; }
                     }
                 }
             if (ncon + tot > ka->lay.maxcon) ovf = 1;
@@ -2687,7 +2694,7 @@ struct Env {
             int c = base + lane, dim = 0;
             if (c < ncon) {
                 int p = cpair[c];
-                if (cdist[c] < ka->m.pair_margin[p] - ka->m.pair_gap[p]) dim = ka->m.pair_condim[p];
+                if (cdist[c] < TAB(pair_margin)[p] - TAB(pair_gap)[p]) dim = TAB(pair_condim)[p];
             }
             int off = 0, tot = 0;
             for (int j = 1; j <= 6; j++) {
@@ -2716,7 +2723,7 @@ struct Env {
         GSYNC();
         ROWPROBE(0);
         // --- fill rows (one row per lane) ---
-        GLB_PTR(real) rJ = rows_();
+        const GArr<real> rJ = rows_();
         real *rowS = r + ka->lay.rowS, *warm = r + ka->lay.warm, *Minv = r + ka->lay.Minv, *asm_ = r + ka->lay.asm_;
         const bool newton = ka->m.solver == 1;
         // Newton + noslip with the dry-friction rows relaxed per tree (pgs_groups): nothing reads the J M^-1 rows or the
@@ -2743,26 +2750,26 @@ struct Env {
             real solref[2], solimp[5];
             bool valid = true;
             if (LEAD && type == R_EQ) {
-                GLB_PTR(const real) c = ka->m.eq_polycoef + 5 * id;
-                real q1 = qpos[ka->m.eq_qpos1[id]] - ka->m.qpos0[ka->m.eq_qpos1[id]], q2 = qpos[ka->m.eq_qpos2[id]] - ka->m.qpos0[ka->m.eq_qpos2[id]];
+                const GArr<const real> c = TAB(eq_polycoef) + 5 * id;
+                real q1 = qpos[TAB(eq_qpos1)[id]] - TAB(qpos0)[TAB(eq_qpos1)[id]], q2 = qpos[TAB(eq_qpos2)[id]] - TAB(qpos0)[TAB(eq_qpos2)[id]];
                 real poly = c[0] + q2 * (c[1] + q2 * (c[2] + q2 * (c[3] + q2 * c[4])));
                 real dpoly = c[1] + q2 * (2 * c[2] + q2 * (3 * c[3] + q2 * 4 * c[4]));
-                int d1 = ka->m.eq_dof1[id], d2 = ka->m.eq_dof2[id];
+                int d1 = TAB(eq_dof1)[id], d2 = TAB(eq_dof2)[id];
                 tA = dof_tree_()[d1];
                 pos = q1 - poly;
                 diag0 = dof_invweight0_()[d1] + dof_invweight0_()[d2];
                 j1 = d1 - tree_dofadr_()[tA]; v1 = 1;
                 j2 = d2 - tree_dofadr_()[tA]; v2 = -dpoly;   // both joints of a gripper live in the same tree
-                for (int k = 0; k < 2; k++) solref[k] = ka->m.eq_solref[2 * id + k];
-                for (int k = 0; k < 5; k++) solimp[k] = ka->m.eq_solimp[5 * id + k];
+                for (int k = 0; k < 2; k++) solref[k] = (TAB(eq_solref) + 2 * id)[k];
+                for (int k = 0; k < 5; k++) solimp[k] = (TAB(eq_solimp) + 5 * id)[k];
             } else if (LEAD && type == R_FLOSS) {
                 int d = floss_dof_()[id];
                 tA = dof_tree_()[d];
                 diag0 = dof_invweight0_()[d];
                 floss = dof_frictionloss_()[d];
                 j1 = d - tree_dofadr_()[tA]; v1 = 1;
-                for (int k = 0; k < 2; k++) solref[k] = ka->m.dof_solref[2 * d + k];
-                for (int k = 0; k < 5; k++) solimp[k] = ka->m.dof_solimp[5 * d + k];
+                for (int k = 0; k < 2; k++) solref[k] = (TAB(dof_solref) + 2 * d)[k];
+                for (int k = 0; k < 5; k++) solimp[k] = (TAB(dof_solimp) + 5 * d)[k];
             } else if (LEAD && type == R_LIMIT) {
                 int j = id, d = jnt_dofadr_()[j];
                 real q = qpos[jnt_qposadr_()[j]];
@@ -2771,11 +2778,11 @@ struct Env {
                 margin = jnt_margin_()[j];
                 diag0 = dof_invweight0_()[d];
                 j1 = d - tree_dofadr_()[tA]; v1 = sub == 0 ? real(1) : real(-1);
-                for (int k = 0; k < 2; k++) solref[k] = ka->m.jnt_solref[2 * j + k];
-                for (int k = 0; k < 5; k++) solimp[k] = ka->m.jnt_solimp[5 * j + k];
+                for (int k = 0; k < 2; k++) solref[k] = (TAB(jnt_solref) + 2 * j)[k];
+                for (int k = 0; k < 5; k++) solimp[k] = (TAB(jnt_solimp) + 5 * j)[k];
             } else if (!LEAD) {
                 int c = id, p = cpair[c];
-                int g1 = ka->m.pair_geom[2 * p], g2 = ka->m.pair_geom[2 * p + 1], b1 = geom_body_()[g1], b2 = geom_body_()[g2];
+                int g1 = (TAB(pair_geom) + 2 * p)[0], g2 = (TAB(pair_geom) + 2 * p)[1], b1 = geom_body_()[g1], b2 = geom_body_()[g2];
                 int t1 = body_tree_()[b1], t2 = body_tree_()[b2];
                 tA = t1 >= 0 ? t1 : t2;
                 tB = (t1 >= 0 && t2 >= 0 && t2 != t1) ? t2 : -1;
@@ -2811,10 +2818,10 @@ struct Env {
                     }
                 }
                 pos = sub == 0 ? cdist[c] : real(0);
-                margin = ka->m.pair_margin[p] - ka->m.pair_gap[p];
+                margin = TAB(pair_margin)[p] - TAB(pair_gap)[p];
                 diag0 = body_invweight0_()[2 * b1] + body_invweight0_()[2 * b2];
-                for (int k = 0; k < 2; k++) solref[k] = ka->m.pair_solref[2 * p + k];
-                for (int k = 0; k < 5; k++) solimp[k] = ka->m.pair_solimp[5 * p + k];
+                for (int k = 0; k < 2; k++) solref[k] = (TAB(pair_solref) + 2 * p)[k];
+                for (int k = 0; k < 5; k++) solimp[k] = (TAB(pair_solimp) + 5 * p)[k];
             }
             (void)valid;
             const int j2c = j2 >= 0 ? j2 : (j1 >= 0 ? j1 : 0), j1c = j1 >= 0 ? j1 : 0;      // leading rows: the two entries (the second
@@ -2835,7 +2842,7 @@ struct Env {
                 real imp0 = imp_row;
                 real R0 = tmax(real(1e-15), (1 - imp0) * diag0 / imp0);
                 real R1 = R0 / tmax(real(1e-15), ka->m.impratio);
-                real mu0 = ka->m.pair_friction[5 * p], mur = ka->m.pair_friction[5 * p + sub - 1];
+                real mu0 = (TAB(pair_friction) + 5 * p)[0], mur = (TAB(pair_friction) + 5 * p)[sub - 1];
                 R = sub == 1 ? R1 : R1 * mu0 * mu0 / tmax(real(1e-15), mur * mur);
                 imp = imp0;
                 K = 0;
@@ -2958,7 +2965,7 @@ struct Env {
         ROWPROBE(2);
         // --- Gauss-Seidel groups: the leading non-contact rows in packs of GRP_MAX, then one group per contact ---
         int* gI = ii + ka->lay.gI;
-        GLB_PTR(real) gA = coup_();
+        const GArr<real> gA = coup_();
         const int nlead = misc[4];   // number of equality / dry-friction / limit rows (they precede the contacts)
         int ngrp = 0;
         for (int base = 0; base < nefc; base += G) {
@@ -2967,7 +2974,7 @@ struct Env {
             int cnt = 0, isc = 0;
             if (i < nefc) {
                 if (i < nlead) { head = (i % GRP_MAX) == 0; cnt = nlead - i < GRP_MAX ? nlead - i : GRP_MAX; }
-                else { int meta = rmeta[i]; head = ((meta >> 12) & 255) == 0; cnt = ka->m.pair_condim[cpair[(meta >> 2) & 1023]]; isc = 1; }
+                else { int meta = rmeta[i]; head = ((meta >> 12) & 255) == 0; cnt = TAB(pair_condim)[cpair[(meta >> 2) & 1023]]; isc = 1; }
             }
             int tot, rk = group_rank<G>(head, grp, lane, &tot);
             if (head && ngrp + rk < ka->lay.maxgrp) gI[ngrp + rk] = i | (cnt << 16) | (isc << 24);
@@ -3003,9 +3010,10 @@ struct Env {
                 int ir = start + rr, is = start + ss, ra = rowI[ir], rs = rowI[is];
                 // J_r . (J_s M^-1) over the tree windows the two rows share: the stored rows of J M^-1 are zero-padded, and a
                 // window of row r matches a window of row s iff it is the same kinematic tree
-                GLB_PTR(const real) Jr = rJ + ROW_S * ir;
+                const GArr<const real> Jr = rJ + ROW_S * ir;
                 const bool packed_s = g >= nlg && ((rs >> 19) & 15) == 0;       // (J M^-1 of a one-tree contact row: second window of its J record)
-                GLB_PTR(const real) Bs = packed_s ? (GLB_PTR(const real))(rJ + ROW_S * is + TREE_W) : (GLB_PTR(const real))(rowsB_() + ROW_S * is);
+                // (one of two bases by a per-lane condition: this address is a VGPR pair, the one access of the phase that stays in the `off` form)
+                const GArr<const real> Bs = packed_s ? GArr<const real>(rJ + ROW_S * is + TREE_W) : GArr<const real>(rowsB_() + ROW_S * is);
 #pragma unroll
                 for (int wr = 0; wr < 2; wr++) {
                     const bool on_r = ((ra >> (13 * wr + 6)) & 15) != 0;
@@ -3039,7 +3047,7 @@ struct Env {
                 mu[j] = in ? real(1) / S[7] : real(1);
                 A[j][j] = in ? real(1) / S[3] : real(1);
 #pragma unroll
-                for (int k = 0; k < j; k++) { const real c = in ? gA[GA_W * g + (j + 1) * j / 2 + (k + 1)] : real(0); A[j][k] = c; A[k][j] = c; }
+                for (int k = 0; k < j; k++) { const real c = in ? (gA + GA_W * g)[(j + 1) * j / 2 + (k + 1)] : real(0); A[j][k] = c; A[k][j] = c; }
             }
 #pragma unroll
             for (int i = 0; i < 5; i++)
@@ -3076,7 +3084,7 @@ struct Env {
             for (int j = 0; j < 5; j++) {
                 // row j of A^-1 = D (D A D)^-1 D and the singular flag, entry k at word 8 k + j: the row's lane fetches six separate
                 // words (a 16-byte load here gets a register copy, and with it a wait for the look-ahead load, in every step)
-                GLB_PTR(real) o = gA + GA_W * g + GA_Q + j;
+                const GArr<real> o = gA + GA_W * g + GA_Q + j;
 #pragma unroll
                 for (int k = 0; k < 5; k++) o[8 * k] = mu[j] * Inv[j][k] * mu[k];
                 o[40] = singular ? real(1) : real(0);
@@ -3100,7 +3108,7 @@ struct Env {
         if constexpr (spec_fixed<SPEC>) { solver = ka->m.solver; newton_iters = ka->m.newton_iters; }      // (the spec's constants: the other solver is not compiled in)
         int *misc = ii + ka->lay.misc, *rmeta = ii + ka->lay.rmeta, *cefc = ii + ka->lay.cefc, *rowI = ii + ka->lay.rowI;
         real *qacc = r + ka->lay.qacc, *as = r + ka->lay.asm_, *rowS = r + ka->lay.rowS, *fcon = r + ka->lay.fcon;
-        GLB_PTR(real) rJ = rows_();
+        const GArr<real> rJ = rows_();
         int nefc = misc[1], ncon = misc[0];
         real* Minv = r + ka->lay.Minv;
         if (solver == 1) {
@@ -3144,7 +3152,7 @@ struct Env {
             int first = cefc[c];
             if (first < 0) continue;
             first &= 0xffff;
-            int dim = ka->m.pair_condim[(ii + ka->lay.cpair)[c]];
+            int dim = TAB(pair_condim)[(ii + ka->lay.cpair)[c]];
             real fn = rowS[RS_S * first + 6], s2 = 0;
             for (int s = 1; s < dim; s++) { real t = rowS[RS_S * (first + s) + 6] * rowS[RS_S * (first + s) + 7]; s2 += t * t; }
             if (s2 > fn * fn) { real sc = fn / sqrt(s2); for (int s = 1; s < dim; s++) rowS[RS_S * (first + s) + 6] *= sc; }
@@ -3194,9 +3202,9 @@ struct Env {
         for (int i = lane; i < ka->m.nv; i += G) bad |= !(fabs(qvel[i]) < real(1e6));
         if (!__any(bad)) return;
         diverged = 1;
-        for (int i = lane; i < ka->m.nq; i += G) qpos[i] = ka->m.qpos_home[i];
+        for (int i = lane; i < ka->m.nq; i += G) qpos[i] = TAB(qpos_home)[i];
         GSYNC();
-        for (int i = lane; i < nobj_() * 7; i += G) qpos[ka->m.obj_qadr[i / 7] + i % 7] = (real)ka->m.obj_reset[((size_t)env * nobj_()) * 7 + i];
+        for (int i = lane; i < nobj_() * 7; i += G) qpos[TAB(obj_qadr)[i / 7] + i % 7] = (real)glb_block((GLB_PTR(const double))ka->m.obj_reset, env, (unsigned)(nobj_() * 7))[i];
         for (int i = lane; i < ka->m.nv; i += G) { qvel[i] = 0; warm[i] = 0; }
         if (lane == 0) (ii + ka->lay.misc)[7] = 0;      // the Verlet list is stale
         GSYNC();
@@ -3211,7 +3219,7 @@ struct Env {
         for (int k = lane; k < ka->m.nv; k += G) out[k] = 0;
         GSYNC();
         rows_jt_force<real>((LDS_PTR(const real))(r + ka->lay.rowS), (LDS_PTR(const int))(ii + ka->lay.rowI), (LDS_PTR(const int))(ii + ka->lay.cefc),
-                            (GLB_PTR(const real))rows_(), (LDS_PTR(real))out, misc[4], misc[0], lane, real(1));
+                            GArr<const real>(rows_()), (LDS_PTR(real))out, misc[4], misc[0], lane, real(1));
         GSYNC();
     }
 
@@ -3841,6 +3849,8 @@ struct PhysHost {
                 }
             }
             if (ovf.size() / 4 >= (1u << 24)) throw std::runtime_error("support table: overflow part too large");
+            // (the device reaches the table with 32-bit byte offsets from its base: GArr)
+            if ((tab.size() + ovf.size()) * sizeof(real) >= (1ull << 32)) throw std::runtime_error("support table: 4 GiB or more, beyond the 32-bit offsets of the device's table reads");
             m.hull_ovf = (int)(tab.size() / 4);
             tab.insert(tab.end(), ovf.begin(), ovf.end());
             if (tab.empty()) tab.assign(4, 0.0);

@@ -1,0 +1,150 @@
+"""The physics kernels' global-memory addressing: per-env scalar bases plus 32-bit lane offsets (GArr, csrc/avsim_math.hip.h).
+
+A wrong per-env base, an offset carried over from one env of a wave slot to the next, or a table reached with a wrong stride shows
+as one env differing from its twin or from the oracle.  Three checks: a ragged batch through the per-model kernel, the generic kernel
+and the oracle; thousands of identical envs against env 0 on the unordered and on the cost-ordered launch; host I/O against device I/O.
+
+The random-walk actions are those of av_aloha_amd/workloads.py (config 4's generator, which serves every model).  Tolerances against
+the f64 oracle: the f32 Newton figures tests/test_gpu_physics.py states for 30 env-steps (2e-5 rad / m, 2e-4 per second), here over 3.
+
+The oracle steps a SUBSET of the ragged batch, seven of the 67 envs (ORACLE_ENVS): the CPU oracle steps one env at a time, and all 67 envs of
+three models would take this file from seconds to the better part of a minute.  The seven are where an addressing mistake would show: the first and last env of a workgroup of eight, both sides of
+the 64 boundary, the last env of the part-filled workgroup.  Every one of the 67 envs is held bit for bit to the other kernel, so an env outside the subset
+that went wrong in one kernel shows there."""
+import numpy as np
+import pytest
+
+from av_aloha_amd import _ffi
+from av_aloha_amd import workloads as W
+from av_aloha_amd.constants import SIM_PHYSICS_ENV_STEP_RATIO
+from avsim_test_util import blob
+from orc_env import OrcEnv
+from test_oracle_physics import model_dict
+
+pytestmark = pytest.mark.gpu
+
+
+def _torch_runtime_first():
+    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
+    import torch as t
+    if t.cuda.is_available():
+        t.zeros(1, device="cuda")
+
+
+_torch_runtime_first()
+
+N_RAGGED = 67                 # more than one workgroup of 8 envs, the last one part-filled, not a multiple of 64
+STEPS = 3
+ORACLE_ENVS = (0, 1, 7, 8, 63, 64, 66)      # first / last of a workgroup, across the 64 boundary, the very last
+MODELS = [("slot_insertion", 3, 1000), ("hook_package", 2, 3000), ("sew_needle", 3, 2000)]      # (the last: two capacity tiers, the generic kernel)
+TOL_QPOS, TOL_QVEL = 2e-5, 2e-4
+
+
+def _inputs(task, arms, seed, n):
+    md = model_dict(task, arms)
+    ids = list(range(n))
+    nj = 21 if arms == 3 else 14
+    return md, W.object_poses(task, ids, seed), W.walk_actions(md["qpos_home"], md["act_ctrlrange"], ids, STEPS, nj, seed)
+
+
+def _rollout(task, arms, poses, acts, specialised):
+    """Per env-step: qpos, qvel, agent_pos, reward, success of every env."""
+    from av_aloha_amd.sim import BatchedSim
+    sim = BatchedSim(task, arms, len(poses), options={"phys_specialised": specialised})
+    sim.reset(poses)
+    out = []
+    for t in range(len(acts)):
+        ap, rw, su = sim.step(acts[t], SIM_PHYSICS_ENV_STEP_RATIO)
+        q, v, _, _ = sim.get_state()
+        out.append((q, v, ap, rw, su))
+    assert not (sim.diag()[:, 3] & 1).any(), "an env diverged"
+    sim.close()
+    return out
+
+
+_cache = {}
+
+
+def _case(task, arms, seed):
+    """The three rollouts of one model, computed once for the tests that share them."""
+    key = (task, arms)
+    if key not in _cache:
+        md, poses, acts = _inputs(task, arms, seed, N_RAGGED)
+        ref = {}
+        for e in ORACLE_ENVS:
+            o = OrcEnv(task, arms)
+            o.d.solver = 1            # Newton on both sides
+            o.reset(poses[e])
+            steps = []
+            for t in range(STEPS):
+                ap, r, s = o.env_step(acts[t, e].astype(np.float64))
+                steps.append((o.qpos.copy(), o.qvel.copy(), ap, r, s))
+            o.close()
+            ref[e] = steps
+        _cache[key] = (poses, acts, _rollout(task, arms, poses, acts, 1), _rollout(task, arms, poses, acts, 0), ref)
+    return _cache[key]
+
+
+@pytest.mark.parametrize("task,arms,seed", MODELS)
+def test_ragged_batch_spec_generic_and_oracle(task, arms, seed):
+    poses, acts, spec, gen, ref = _case(task, arms, seed)
+    assert np.abs(acts).max() > 0
+    for t in range(STEPS):
+        for name, a, b in zip(("qpos", "qvel", "agent_pos", "reward", "success"), spec[t], gen[t]):
+            assert np.array_equal(a, b), f"{task} step {t}: {name} differs between phys_specialised=1 and =0 in envs {np.nonzero((np.asarray(a) != np.asarray(b)).reshape(N_RAGGED, -1).any(1))[0]}"
+    for label, run in (("phys_specialised=1", spec), ("phys_specialised=0", gen)):
+        for e in ORACLE_ENVS:
+            for t in range(STEPS):
+                q, v, ap, rw, su = run[t]
+                rq, rv, rap, rr, rs = ref[e][t]
+                dq, dv = np.abs(q[e] - rq).max(), np.abs(v[e] - rv).max()
+                print(f"{task} {label} env {e} step {t}: |qpos - oracle| {dq:.2e}  |qvel - oracle| {dv:.2e}")
+                assert dq < TOL_QPOS and dv < TOL_QVEL, (task, label, e, t, dq, dv)
+                assert int(rw[e]) == rr and bool(su[e]) == rs, (task, label, e, t)
+
+
+def test_identical_envs_unordered_and_ordered_launch():
+    """4099 envs = two full rounds of the chip's 2048 wave slots plus three: every wave slot takes a second env.  Same state, same
+    action everywhere: every env equals env 0 bit for bit after the first launch (index order: no cost recorded yet) and after the
+    second (the order k_env_order makes of the first launch's costs)."""
+    from av_aloha_amd.sim import BatchedSim
+    n = 4099
+    md, poses, acts = _inputs("slot_insertion", 3, 1000, 1)
+    sim = BatchedSim("slot_insertion", 3, n)
+    sim.reset(np.repeat(poses[:1], n, 0))
+    for t in range(2):
+        ap, rw, su = sim.step(np.repeat(acts[t, :1], n, 0), SIM_PHYSICS_ENV_STEP_RATIO)
+        q, v, c, w = sim.get_state()
+        for name, a in (("qpos", q), ("qvel", v), ("ctrl", c), ("warm", w), ("agent_pos", ap), ("reward", rw), ("success", su)):
+            bad = np.nonzero((a != a[:1]).reshape(n, -1).any(1))[0]
+            assert bad.size == 0, f"launch {t}: {name} of envs {bad[:8]} (of {bad.size}) differs from env 0's"
+        assert np.array_equal(q[-1], q[0]) and np.array_equal(ap[-1], ap[0])
+        ncon = sim.contacts()[0]
+        assert (ncon == ncon[0]).all()
+    assert np.abs(q[0] - md["qpos_home"]).max() > 0      # (the state moved)
+    sim.close()
+
+
+def test_host_io_and_device_io_handles_agree():
+    import torch as T
+    dev = T.device("cuda", T.cuda.current_device())
+    poses, acts, spec, _, _ = _case(*MODELS[0])
+    n, nj = N_RAGGED, 21
+    h = _ffi.Handle(blob("slot_insertion"), n, dev.index, _ffi.AVSIM_IO_DEVICE)
+    h.check(h.L.avsim_set_stream(h.h, T.cuda.current_stream().cuda_stream))
+    d = lambda a: T.from_numpy(np.ascontiguousarray(a)).to(dev)
+    obj = d(poses.astype(np.float64).reshape(n, -1))
+    h.check(h.L.avsim_reset(h.h, None, _ffi.ptr(obj)))
+    for t in range(STEPS):
+        a = d(acts[t].astype(np.float32))
+        ap = T.empty((n, nj), dtype=T.float64, device=dev)
+        rw = T.empty(n, dtype=T.int32, device=dev)
+        su = T.empty(n, dtype=T.uint8, device=dev)
+        h.check(h.L.avsim_step(h.h, _ffi.ptr(a), SIM_PHYSICS_ENV_STEP_RATIO, _ffi.ptr(ap), _ffi.ptr(rw), _ffi.ptr(su)))
+        st = [T.empty((n, k), dtype=T.float64, device=dev) for k in (h.nq, h.nv, h.nu, h.nv)]
+        h.check(h.L.avsim_get_state(h.h, *[_ffi.ptr(x) for x in st]))
+        T.cuda.synchronize()
+        q, v, hap, hrw, hsu = spec[t]
+        assert np.array_equal(st[0].cpu().numpy(), q) and np.array_equal(st[1].cpu().numpy(), v), t
+        assert np.array_equal(ap.cpu().numpy(), hap) and np.array_equal(rw.cpu().numpy(), hrw) and np.array_equal(su.cpu().numpy().astype(bool), hsu), t
+    h.close()
