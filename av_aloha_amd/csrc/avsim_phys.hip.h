@@ -404,6 +404,7 @@ template <> struct QTol<float> { static constexpr float abs = 1e-10f, rel = 2e-6
 // B = J M^-1 is read from the global row scratch next to J (written by the row's lane in make_constraints).
 // ------------------------------------------------------------------------------------------------
 template <bool B> struct BoolTag { static constexpr bool value = B; };
+template <int I> struct IntTag { static constexpr int value = I; };
 
 // The dry-friction rows of a noslip sweep, all kinematic trees at once (see pgs_groups)
 template <typename real>
@@ -1871,6 +1872,7 @@ struct Env {
     int diverged = 0;               // the state left the representable range during this launch and was put back to the home pose
     int nit_sum = 0, nit_max = 0;   // Newton iterations over the launch's substeps (diagnostics)
     bool profiling = false;
+    bool rows_single = false;       // option "rows_paired" = 0: a contact's rows one per lane whatever the trip counts (make_constraints_i)
     real* r;  // real region of this env
     int* ii;  // int region of this env
     int lane, grp;
@@ -1898,6 +1900,8 @@ struct Env {
     // (the model's two integers outside its head: the spec's constants in a per-model kernel)
     AVS_DEV int nobj_() const { if constexpr (spec_fixed<SPEC>) return SPEC::nobj; else return ka->m.nobj; }
     AVS_DEV int hull_ovf_() const { if constexpr (spec_fixed<SPEC>) return SPEC::hull_ovf; else return ka->m.hull_ovf; }
+    // (a per-model kernel is the shipped configuration: it pairs unconditionally, and a handle with the option at 0 does not take it)
+    AVS_DEV bool rows_paired_() const { if constexpr (spec_fixed<SPEC>) return true; else return !rows_single; }
     // the env's blocks of the global scratch: base + env * stride as a 64-bit SCALAR sum, once per phase (the env is wave-uniform; the phases
     // reach it through an object in memory, hence the readfirstlane inside glb_block); the lanes' offsets inside the block fit 32 bits for any N
     AVS_DEV GArr<real> rows_() const { return glb_block((GLB_PTR(real))ka->m.rJ_glob, env, (unsigned)(ka->lay.gefc * ROW_S)); }
@@ -2722,7 +2726,7 @@ struct Env {
         if (lane == 0) { misc[1] = nefc; if (ovf) misc[2] |= 2; }
         GSYNC();
         ROWPROBE(0);
-        // --- fill rows (one row per lane) ---
+        // --- fill rows (one row per lane; a contact's rows two per lane where that saves a trip, below) ---
         const GArr<real> rJ = rows_();
         real *rowS = r + ka->lay.rowS, *warm = r + ka->lay.warm, *Minv = r + ka->lay.Minv, *asm_ = r + ka->lay.asm_;
         const bool newton = ka->m.solver == 1;
@@ -2734,22 +2738,20 @@ struct Env {
         const int *bmask = body_dofmask_(), *tadr = tree_dofadr_(), *tnum = tree_dofnum_();
         const real* cdofp = r + ka->lay.cdof;
         const int nvm = ka->m.nv - 1;
-        // Two passes of one body: the leading rows (equality, dry friction, limits: at most two entries, everything they need comes
-        // from a handful of LDS words) and the contact rows (dense over the two dof windows).  One loop over all rows would run the
+        // Two bodies: the leading rows (equality, dry friction, limits: at most two entries, everything they need comes from a
+        // handful of LDS words) and the contact rows (dense over the two dof windows).  One loop over all rows would run the
         // dense code for every 64 rows, leading or not.
-        auto fill = [&](int i, auto lead_tag) {
-            constexpr bool LEAD = decltype(lead_tag)::value;
-            int meta = rmeta[i], type = meta & 3, id = (meta >> 2) & 1023, sub = (meta >> 12) & 255, dim = meta >> 20;
+        auto fill_lead = [&](int i) {
+            int meta = rmeta[i], type = meta & 3, id = (meta >> 2) & 1023, sub = (meta >> 12) & 255;
             real J[ROW_W];   // kept in registers: every index below is a compile-time constant after unrolling
 #pragma unroll
             for (int k = 0; k < ROW_W; k++) J[k] = 0;
-            int tA = -1, tB = -1;
-            int j1 = -1, j2 = -1;      // slots of the (at most two) non-zero entries of non-contact rows
+            int tA = -1;
+            int j1 = -1, j2 = -1;      // slots of the (at most two) non-zero entries
             real v1 = 0, v2 = 0;
             real pos = 0, margin = 0, diag0 = 0, floss = 0;
             real solref[2], solimp[5];
-            bool valid = true;
-            if (LEAD && type == R_EQ) {
+            if (type == R_EQ) {
                 const GArr<const real> c = TAB(eq_polycoef) + 5 * id;
                 real q1 = qpos[TAB(eq_qpos1)[id]] - TAB(qpos0)[TAB(eq_qpos1)[id]], q2 = qpos[TAB(eq_qpos2)[id]] - TAB(qpos0)[TAB(eq_qpos2)[id]];
                 real poly = c[0] + q2 * (c[1] + q2 * (c[2] + q2 * (c[3] + q2 * c[4])));
@@ -2762,7 +2764,7 @@ struct Env {
                 j2 = d2 - tree_dofadr_()[tA]; v2 = -dpoly;   // both joints of a gripper live in the same tree
                 for (int k = 0; k < 2; k++) solref[k] = (TAB(eq_solref) + 2 * id)[k];
                 for (int k = 0; k < 5; k++) solimp[k] = (TAB(eq_solimp) + 5 * id)[k];
-            } else if (LEAD && type == R_FLOSS) {
+            } else if (type == R_FLOSS) {
                 int d = floss_dof_()[id];
                 tA = dof_tree_()[d];
                 diag0 = dof_invweight0_()[d];
@@ -2770,7 +2772,7 @@ struct Env {
                 j1 = d - tree_dofadr_()[tA]; v1 = 1;
                 for (int k = 0; k < 2; k++) solref[k] = (TAB(dof_solref) + 2 * d)[k];
                 for (int k = 0; k < 5; k++) solimp[k] = (TAB(dof_solimp) + 5 * d)[k];
-            } else if (LEAD && type == R_LIMIT) {
+            } else if (type == R_LIMIT) {
                 int j = id, d = jnt_dofadr_()[j];
                 real q = qpos[jnt_qposadr_()[j]];
                 tA = dof_tree_()[d];
@@ -2780,187 +2782,278 @@ struct Env {
                 j1 = d - tree_dofadr_()[tA]; v1 = sub == 0 ? real(1) : real(-1);
                 for (int k = 0; k < 2; k++) solref[k] = (TAB(jnt_solref) + 2 * j)[k];
                 for (int k = 0; k < 5; k++) solimp[k] = (TAB(jnt_solimp) + 5 * j)[k];
-            } else if (!LEAD) {
-                int c = id, p = cpair[c];
-                int g1 = (TAB(pair_geom) + 2 * p)[0], g2 = (TAB(pair_geom) + 2 * p)[1], b1 = geom_body_()[g1], b2 = geom_body_()[g2];
-                int t1 = body_tree_()[b1], t2 = body_tree_()[b2];
-                tA = t1 >= 0 ? t1 : t2;
-                tB = (t1 >= 0 && t2 >= 0 && t2 != t1) ? t2 : -1;
-                real n[3] = {cnrm[3 * c], cnrm[3 * c + 1], cnrm[3 * c + 2]}, t1v[3], t2v[3], cp[3] = {cpos[3 * c], cpos[3 * c + 1], cpos[3 * c + 2]};
-                make_frame(n, t1v, t2v);
-                const int sm = sub % 3;
-                real ax[3];
-#pragma unroll
-                for (int q = 0; q < 3; q++) ax[q] = sm == 0 ? n[q] : (sm == 1 ? t1v[q] : t2v[q]);
-                const bool rot = sub >= 3;
-                // entry of dof slot k: the axis' component of the dof's motion at the contact point, signed by which of the two bodies
-                // the dof moves.  ax . (lin + ang x cp) = ax . lin + (cp x ax) . ang, so the row is one 6-vector W = (cp x ax, ax) --
-                // (ax, 0) for a rotational row -- against every slot's cdof: six FMAs per slot, no branch, the body masks as factors
-                real cx[3], Wa[3], Wl[3];
-                cross3(cp, ax, cx);
-#pragma unroll
-                for (int q = 0; q < 3; q++) { Wa[q] = rot ? ax[q] : cx[q]; Wl[q] = rot ? real(0) : ax[q]; }
-                const int mA = (t1 == tA ? bmask[b1] : 0), pA = (t2 == tA ? bmask[b2] : 0);
-                const int mB = (tB >= 0 && t1 == tB ? bmask[b1] : 0), pB = (tB >= 0 ? bmask[b2] : 0);
-                const int aA = tadr[tA], aB = tadr[tB >= 0 ? tB : tA];
-#pragma unroll
-                for (int k = 0; k < TREE_W; k++) {
-                    const real* ca = cdofp + 6 * (aA + k < nvm ? aA + k : nvm);
-                    const real ea = Wa[0] * ca[0] + Wa[1] * ca[1] + Wa[2] * ca[2] + Wl[0] * ca[3] + Wl[1] * ca[4] + Wl[2] * ca[5];
-                    J[k] = real(((pA >> k) & 1) - ((mA >> k) & 1)) * ea;
-                }
-                if (tB >= 0) {       // second window: contacts between two kinematic trees only
-#pragma unroll
-                    for (int k = 0; k < TREE_W; k++) {
-                        const real* cb = cdofp + 6 * (aB + k < nvm ? aB + k : nvm);
-                        const real eb = Wa[0] * cb[0] + Wa[1] * cb[1] + Wa[2] * cb[2] + Wl[0] * cb[3] + Wl[1] * cb[4] + Wl[2] * cb[5];
-                        J[TREE_W + k] = real(((pB >> k) & 1) - ((mB >> k) & 1)) * eb;
-                    }
-                }
-                pos = sub == 0 ? cdist[c] : real(0);
-                margin = TAB(pair_margin)[p] - TAB(pair_gap)[p];
-                diag0 = body_invweight0_()[2 * b1] + body_invweight0_()[2 * b2];
-                for (int k = 0; k < 2; k++) solref[k] = (TAB(pair_solref) + 2 * p)[k];
-                for (int k = 0; k < 5; k++) solimp[k] = (TAB(pair_solimp) + 5 * p)[k];
             }
-            (void)valid;
-            const int j2c = j2 >= 0 ? j2 : (j1 >= 0 ? j1 : 0), j1c = j1 >= 0 ? j1 : 0;      // leading rows: the two entries (the second
-            const real v2c = j2 >= 0 ? v2 : real(0);                                       // one repeated with value 0 when absent)
-            if (LEAD) {
+            const int j2c = j2 >= 0 ? j2 : (j1 >= 0 ? j1 : 0), j1c = j1 >= 0 ? j1 : 0;      // the two entries (the second one repeated
+            const real v2c = j2 >= 0 ? v2 : real(0);                                       // with value 0 when absent)
 #pragma unroll
-                for (int k = 0; k < TREE_W; k++) J[k] += (k == j1 ? v1 : real(0)) + (k == j2 ? v2 : real(0));
-            }
+            for (int k = 0; k < TREE_W; k++) J[k] += (k == j1 ? v1 : real(0)) + (k == j2 ? v2 : real(0));
             // K, B, impedance, R [EXT: mj_makeImpedance]
             real dmax = tclamp(solimp[1], real(0.0001), real(0.9999));
             real tc = tmax(solref[0], 2 * ka->m.timestep), dr = solref[1];
             real K = real(1) / tmax(real(1e-15), dmax * dmax * tc * tc * dr * dr), Bd = real(2) / tmax(real(1e-15), dmax * tc);
-            real imp, R;
-            // (a contact's rows all take the impedance at the contact distance: pos is that distance for the normal row)
-            const real imp_row = impedance(solimp, (!LEAD && sub > 0) ? cdist[id] : pos, margin);
-            if (!LEAD && sub > 0) {
-                int c = id, p = cpair[c];
-                real imp0 = imp_row;
-                real R0 = tmax(real(1e-15), (1 - imp0) * diag0 / imp0);
-                real R1 = R0 / tmax(real(1e-15), ka->m.impratio);
-                real mu0 = (TAB(pair_friction) + 5 * p)[0], mur = (TAB(pair_friction) + 5 * p)[sub - 1];
-                R = sub == 1 ? R1 : R1 * mu0 * mu0 / tmax(real(1e-15), mur * mur);
-                imp = imp0;
-                K = 0;
-                floss = mur;
-            } else {
-                imp = imp_row;
-                R = tmax(real(1e-15), (1 - imp) * diag0 / imp);
-            }
+            const real imp = impedance(solimp, pos, margin);
+            const real R = tmax(real(1e-15), (1 - imp) * diag0 / imp);
             // velocity along the row, reference acceleration
-            real vel = 0;
-            if (LEAD) {
-                const int a0 = tadr[tA];
-                vel = v1 * qvel[a0 + j1c] + v2c * qvel[a0 + j2c];
-            } else {
-                // J is zero beyond a tree's dofs: clamped reads instead of per-slot branches
-                const int a0 = tadr[tA], b0 = tadr[tB >= 0 ? tB : tA];
-#pragma unroll
-                for (int k = 0; k < TREE_W; k++) vel += J[k] * qvel[a0 + k < nvm ? a0 + k : nvm];
-                if (tB >= 0) {
-#pragma unroll
-                    for (int k = 0; k < TREE_W; k++) vel += J[TREE_W + k] * qvel[b0 + k < nvm ? b0 + k : nvm];
-                }
-            }
+            const int a0 = tadr[tA], nA = tnum[tA];
+            const real vel = v1 * qvel[a0 + j1c] + v2c * qvel[a0 + j2c];
             const real aref = -Bd * vel - K * imp * (pos - margin);
-            // B = J M^-1 per tree (dense 8x8 inverse), diag = J B^T
-            real dg = 0;
-            real Bv[ROW_W];
-            if (LEAD) {
-                // J M^-1 = v1 (row j1 of the tree's inverse) + v2 (row j2): the diagonal needs four of its entries, the whole row is
-                // made only where something reads it (PGS sweeps)
-                const real* Mi = Minv + 64 * tA;
-                const real s1 = Mi[8 * j1c + j1c] * v1 + Mi[8 * j1c + j2c] * v2c, s2 = Mi[8 * j2c + j1c] * v1 + Mi[8 * j2c + j2c] * v2c;
-                dg = v1 * s1 + v2c * s2;
-                if (!lead_slim) {
+            // J M^-1 = v1 (row j1 of the tree's inverse) + v2 (row j2): the diagonal needs four of its entries, the whole row is
+            // made only where something reads it (PGS sweeps)
+            const real* Mi = Minv + 64 * tA;
+            const real s1 = Mi[8 * j1c + j1c] * v1 + Mi[8 * j1c + j2c] * v2c, s2 = Mi[8 * j2c + j1c] * v1 + Mi[8 * j2c + j2c] * v2c;
+            const real dg = v1 * s1 + v2c * s2;
+            if (!lead_slim) {       // (the Newton solver and the per-tree noslip pass read the leading rows' descriptors)
+                real Bv[ROW_W];
 #pragma unroll
-                    for (int k = 0; k < TREE_W; k++) { Bv[k] = Mi[8 * k + j1c] * v1 + Mi[8 * k + j2c] * v2c; Bv[TREE_W + k] = 0; }
-                }
-            } else {
-#pragma unroll
-            for (int k = 0; k < TREE_W; k++) {
-                real mr[TREE_W], sa = 0;
-                lds_load8(Minv + 64 * tA + 8 * k, mr);          // rows of the 8 x 8 inverse start on 32-byte boundaries
-#pragma unroll
-                for (int j = 0; j < TREE_W; j++) sa += mr[j] * J[j];
-                dg += J[k] * sa;
-                Bv[k] = sa;
-                Bv[TREE_W + k] = 0;
-            }
-            if (tB >= 0) {
-#pragma unroll
-                for (int k = 0; k < TREE_W; k++) {
-                    real mr[TREE_W], sb = 0;
-                    lds_load8(Minv + 64 * tB + 8 * k, mr);
-#pragma unroll
-                    for (int j = 0; j < TREE_W; j++) sb += mr[j] * J[TREE_W + j];
-                    dg += J[TREE_W + k] * sb;
-                    Bv[TREE_W + k] = sb;
-                }
-            }
-            }
-            if (!LEAD && tB < 0) {
-                // one-tree contact row: [J (8) | J M^-1 (8)] in one record; every reader of J masks the second window by the row's dof
-                // counts (nB = 0), the Gauss-Seidel sweeps and the couplings below know where J M^-1 is
-                real JB_[ROW_W];
-#pragma unroll
-                for (int k = 0; k < TREE_W; k++) { JB_[k] = J[k]; JB_[TREE_W + k] = Bv[k]; }
-                store_row16(rJ + ROW_S * i, JB_);
-            } else if (!LEAD || !lead_slim) {       // (the Newton solver and the per-tree noslip pass read the leading rows' descriptors)
+                for (int k = 0; k < TREE_W; k++) { Bv[k] = Mi[8 * k + j1c] * v1 + Mi[8 * k + j2c] * v2c; Bv[TREE_W + k] = 0; }
                 store_row16(rJ + ROW_S * i, J);
                 store_row16(rowsB_() + ROW_S * i, Bv);
             }
             // warm start: force implied by last step's acceleration, f = -D (J qacc_ws - aref), made feasible per row
-            const int a0 = tadr[tA], nA = tnum[tA], b0 = tB >= 0 ? tadr[tB] : 0, nB = tB >= 0 ? tnum[tB] : 0;
-            real jw = 0, jas = 0;      // J . warm start, J . qacc_smooth (the Newton solver's two start candidates)
-            if (LEAD) {
-                jw = v1 * warm[a0 + j1c] + v2c * warm[a0 + j2c];
-                jas = v1 * asm_[a0 + j1c] + v2c * asm_[a0 + j2c];
-            } else {
-#pragma unroll
-            for (int k = 0; k < TREE_W; k++) {
-                const int da = a0 + k < nvm ? a0 + k : nvm;
-                jw += J[k] * warm[da];
-                jas += J[k] * asm_[da];
-            }
-            if (tB >= 0) {
-#pragma unroll
-                for (int k = 0; k < TREE_W; k++) {
-                    const int db = b0 + k < nvm ? b0 + k : nvm;
-                    jw += J[TREE_W + k] * warm[db];
-                    jas += J[TREE_W + k] * asm_[db];
-                }
-            }
-            }
+            // J . warm start, J . qacc_smooth (the Newton solver's two start candidates)
+            const real jw = v1 * warm[a0 + j1c] + v2c * warm[a0 + j2c];
+            const real jas = v1 * asm_[a0 + j1c] + v2c * asm_[a0 + j2c];
             const real big = real(1e30);
-            real lo = -big, hi = big, muinv = 0;
-            bool ns = false;   // takes part in the noslip sweeps (dry friction and contact friction rows)
-            if (LEAD && type == R_FLOSS) { lo = -floss; hi = floss; ns = true; }
-            else if (LEAD && type == R_LIMIT) lo = 0;
-            else if (!LEAD) {
-                if (sub == 0) lo = 0;
-                else { ns = true; muinv = real(1) / tmax(real(1e-15), floss); }
-            }
+            real lo = -big, hi = big;
+            bool ns = false;   // takes part in the noslip sweeps (dry friction rows)
+            if (type == R_FLOSS) { lo = -floss; hi = floss; ns = true; }
+            else if (type == R_LIMIT) lo = 0;
             real f = -(jw - aref) / R;
             f = tmin(tmax(f, lo), hi);
             real* S = rowS + RS_S * i;
             // word 2: PGS 1 / (A_rr + R); Newton: residual of the warm start, with that of qacc_smooth in word 8
             S[0] = aref; S[1] = R; S[2] = newton ? jw - aref : real(1) / (dg + R); S[3] = ns ? real(1) / tmax(dg, real(1e-15)) : real(0);
-            S[4] = lo; S[5] = hi; S[6] = f; S[7] = muinv; S[8] = jas - aref;
-            // leading rows: slots of the (at most two) entries and the sign of the first in the row word, the second value in word 7
+            S[4] = lo; S[5] = hi; S[6] = f; S[8] = jas - aref;
+            // slots of the (at most two) entries and the sign of the first in the row word, the second value in word 7
             // (lead_d1 / lead_d2 / lead_v1 of avsim_newton.hip.h)
-            const int lead_bits = !LEAD ? 0 : ((v1 < 0 ? 1 : 0) << 13) | (j1c << 26) | (j2c << 29);
-            if (LEAD) S[7] = v2c;
-            rowI[i] = a0 | (nA << 6) | (tA << 10) | ((b0 | (nB << 6) | ((tB >= 0 ? tB : 0) << 10)) << 13) | lead_bits;
-            rmeta[i] = (meta & 0xfffff) | ((tA + 1) << 20) | ((tB + 1) << 24);
+            S[7] = v2c;
+            rowI[i] = a0 | (nA << 6) | (tA << 10) | ((v1 < 0 ? 1 : 0) << 13) | (j1c << 26) | (j2c << 29);
+            rmeta[i] = (meta & 0xfffff) | ((tA + 1) << 20);
         };
-        for (int i = lane; i < nlead0; i += G) fill(i, BoolTag<true>{});
+        // The rows of contact c, NR = 1 or 2 of them per lane: row q of the call is row i0 + 3 q of the table and sub-row sub0 + 3 q of the
+        // contact.  With NR = 2 and sub0 < 3 these are the translational and the rotational row along ONE axis of the contact frame: they
+        // share the contact's frame, trees, body masks, impedance and every branch condition below, and differ in W alone -- two
+        // independent chains in the same basic blocks, which the scheduler interleaves.  Row 1 is computed whether the contact has it or
+        // not (its reads stay inside the contact's own records) and stored when live1 says so.  Per row every statement is what it is
+        // with NR = 1: the same operands in the same order, hence the same bits.
+        auto fill_con = [&](const int c, const int i0, const int sub0, const bool live1, auto nr_tag) {
+            constexpr int NR = decltype(nr_tag)::value;
+            const int p = cpair[c];
+            const int g1 = (TAB(pair_geom) + 2 * p)[0], g2 = (TAB(pair_geom) + 2 * p)[1], b1 = geom_body_()[g1], b2 = geom_body_()[g2];
+            const int t1 = body_tree_()[b1], t2 = body_tree_()[b2];
+            const int tA = t1 >= 0 ? t1 : t2;
+            const int tB = (t1 >= 0 && t2 >= 0 && t2 != t1) ? t2 : -1;
+            real n[3] = {cnrm[3 * c], cnrm[3 * c + 1], cnrm[3 * c + 2]}, t1v[3], t2v[3], cp[3] = {cpos[3 * c], cpos[3 * c + 1], cpos[3 * c + 2]};
+            make_frame(n, t1v, t2v);
+            const int mA = (t1 == tA ? bmask[b1] : 0), pA = (t2 == tA ? bmask[b2] : 0);
+            const int mB = (tB >= 0 && t1 == tB ? bmask[b1] : 0), pB = (tB >= 0 ? bmask[b2] : 0);
+            const int a0 = tadr[tA], b0 = tadr[tB >= 0 ? tB : tA];
+            // the pair's parameters (global memory): asked for here, used behind the rows' entries
+            const real margin = TAB(pair_margin)[p] - TAB(pair_gap)[p];
+            const real diag0 = body_invweight0_()[2 * b1] + body_invweight0_()[2 * b2];
+            real solref[2], solimp[5];
+            for (int k = 0; k < 2; k++) solref[k] = (TAB(pair_solref) + 2 * p)[k];
+            for (int k = 0; k < 5; k++) solimp[k] = (TAB(pair_solimp) + 5 * p)[k];
+            int sub[NR];
+            real J[NR][ROW_W];   // kept in registers: every index below is a compile-time constant after unrolling
+            real Wa[NR][3], Wl[NR][3];
+#pragma unroll
+            for (int q = 0; q < NR; q++) {
+                sub[q] = sub0 + 3 * q;
+#pragma unroll
+                for (int k = 0; k < ROW_W; k++) J[q][k] = 0;
+                const int sm = sub[q] % 3;
+                real ax[3];
+#pragma unroll
+                for (int x = 0; x < 3; x++) ax[x] = sm == 0 ? n[x] : (sm == 1 ? t1v[x] : t2v[x]);
+                const bool rot = sub[q] >= 3;
+                // entry of dof slot k: the axis' component of the dof's motion at the contact point, signed by which of the two bodies
+                // the dof moves.  ax . (lin + ang x cp) = ax . lin + (cp x ax) . ang, so the row is one 6-vector W = (cp x ax, ax) --
+                // (ax, 0) for a rotational row -- against every slot's cdof: six FMAs per slot, no branch, the body masks as factors
+                real cx[3];
+                cross3(cp, ax, cx);
+#pragma unroll
+                for (int x = 0; x < 3; x++) { Wa[q][x] = rot ? ax[x] : cx[x]; Wl[q][x] = rot ? real(0) : ax[x]; }
+            }
+#pragma unroll
+            for (int k = 0; k < TREE_W; k++) {
+                const real* ca = cdofp + 6 * (a0 + k < nvm ? a0 + k : nvm);
+#pragma unroll
+                for (int q = 0; q < NR; q++) {
+                    const real ea = Wa[q][0] * ca[0] + Wa[q][1] * ca[1] + Wa[q][2] * ca[2] + Wl[q][0] * ca[3] + Wl[q][1] * ca[4] + Wl[q][2] * ca[5];
+                    J[q][k] = real(((pA >> k) & 1) - ((mA >> k) & 1)) * ea;
+                }
+            }
+            if (tB >= 0) {       // second window: contacts between two kinematic trees only
+#pragma unroll
+                for (int k = 0; k < TREE_W; k++) {
+                    const real* cb = cdofp + 6 * (b0 + k < nvm ? b0 + k : nvm);
+#pragma unroll
+                    for (int q = 0; q < NR; q++) {
+                        const real eb = Wa[q][0] * cb[0] + Wa[q][1] * cb[1] + Wa[q][2] * cb[2] + Wl[q][0] * cb[3] + Wl[q][1] * cb[4] + Wl[q][2] * cb[5];
+                        J[q][TREE_W + k] = real(((pB >> k) & 1) - ((mB >> k) & 1)) * eb;
+                    }
+                }
+            }
+            // (the pair's parameters, asked for above, are needed from here on.  Pinned in registers: left to itself the compiler sinks each
+            // load into the branch of the impedance ladder that uses it, and every one of those global loads then waits alone)
+            asm volatile("" : "+v"(solimp[0]), "+v"(solimp[1]), "+v"(solimp[2]), "+v"(solimp[3]), "+v"(solimp[4]), "+v"(solref[0]), "+v"(solref[1]));
+            // K, B, impedance, R [EXT: mj_makeImpedance]
+            const real dmax = tclamp(solimp[1], real(0.0001), real(0.9999));
+            const real tc = tmax(solref[0], 2 * ka->m.timestep), dr = solref[1];
+            const real K0 = real(1) / tmax(real(1e-15), dmax * dmax * tc * tc * dr * dr), Bd = real(2) / tmax(real(1e-15), dmax * tc);
+            // (a contact's rows all take the impedance at the contact distance)
+            const real imp = impedance(solimp, cdist[c], margin);
+            const real R0 = tmax(real(1e-15), (1 - imp) * diag0 / imp);
+            const real R1 = R0 / tmax(real(1e-15), ka->m.impratio);
+            const real mu0 = (TAB(pair_friction) + 5 * p)[0];
+            real R[NR], K[NR], floss[NR], pos[NR];
+#pragma unroll
+            for (int q = 0; q < NR; q++) {
+                pos[q] = sub[q] == 0 ? cdist[c] : real(0);
+                R[q] = R0; K[q] = K0; floss[q] = 0;
+                if (sub[q] > 0) {
+                    // (the friction coefficient is read HERE, inside the branch: read ahead with the other parameters the block becomes a
+                    // select, and the one-row path's division below then loses its fast form -- other bits than the parent's)
+                    const real mur = (TAB(pair_friction) + 5 * p)[sub[q] - 1];
+                    R[q] = sub[q] == 1 ? R1 : R1 * mu0 * mu0 / tmax(real(1e-15), mur * mur);
+                    K[q] = 0;
+                    floss[q] = mur;
+                }
+            }
+            // velocity along the row, reference acceleration (J is zero beyond a tree's dofs: clamped reads instead of per-slot branches)
+            real vel[NR];
+#pragma unroll
+            for (int q = 0; q < NR; q++) {
+                vel[q] = 0;
+#pragma unroll
+                for (int k = 0; k < TREE_W; k++) vel[q] += J[q][k] * qvel[a0 + k < nvm ? a0 + k : nvm];
+            }
+            if (tB >= 0) {
+#pragma unroll
+                for (int q = 0; q < NR; q++) {
+#pragma unroll
+                    for (int k = 0; k < TREE_W; k++) vel[q] += J[q][TREE_W + k] * qvel[b0 + k < nvm ? b0 + k : nvm];
+                }
+            }
+            real aref[NR];
+#pragma unroll
+            for (int q = 0; q < NR; q++) aref[q] = -Bd * vel[q] - K[q] * imp * (pos[q] - margin);
+            // B = J M^-1 per tree (dense 8x8 inverse), diag = J B^T; a row of the inverse is loaded once for the call's rows
+            real dg[NR];
+            real Bv[NR][ROW_W];
+#pragma unroll
+            for (int q = 0; q < NR; q++) dg[q] = 0;
+#pragma unroll
+            for (int k = 0; k < TREE_W; k++) {
+                real mr[TREE_W];
+                lds_load8(Minv + 64 * tA + 8 * k, mr);          // rows of the 8 x 8 inverse start on 32-byte boundaries
+#pragma unroll
+                for (int q = 0; q < NR; q++) {
+                    real sa = 0;
+#pragma unroll
+                    for (int j = 0; j < TREE_W; j++) sa += mr[j] * J[q][j];
+                    dg[q] += J[q][k] * sa;
+                    Bv[q][k] = sa;
+                    Bv[q][TREE_W + k] = 0;
+                }
+            }
+            if (tB >= 0) {
+#pragma unroll
+                for (int k = 0; k < TREE_W; k++) {
+                    real mr[TREE_W];
+                    lds_load8(Minv + 64 * tB + 8 * k, mr);
+#pragma unroll
+                    for (int q = 0; q < NR; q++) {
+                        real sb = 0;
+#pragma unroll
+                        for (int j = 0; j < TREE_W; j++) sb += mr[j] * J[q][TREE_W + j];
+                        dg[q] += J[q][TREE_W + k] * sb;
+                        Bv[q][TREE_W + k] = sb;
+                    }
+                }
+            }
+            if (tB < 0) {
+                // one-tree contact row: [J (8) | J M^-1 (8)] in one record; every reader of J masks the second window by the row's dof
+                // counts (nB = 0), the Gauss-Seidel sweeps and the couplings below know where J M^-1 is
+#pragma unroll
+                for (int q = 0; q < NR; q++) {
+                    real JB_[ROW_W];
+#pragma unroll
+                    for (int k = 0; k < TREE_W; k++) { JB_[k] = J[q][k]; JB_[TREE_W + k] = Bv[q][k]; }
+                    if (q == 0 || live1) store_row16(rJ + ROW_S * (i0 + 3 * q), JB_);
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < NR; q++)
+                    if (q == 0 || live1) {
+                        store_row16(rJ + ROW_S * (i0 + 3 * q), J[q]);
+                        store_row16(rowsB_() + ROW_S * (i0 + 3 * q), Bv[q]);
+                    }
+            }
+            // warm start: force implied by last step's acceleration, f = -D (J qacc_ws - aref), made feasible per row
+            const int nA = tnum[tA], b0r = tB >= 0 ? tadr[tB] : 0, nB = tB >= 0 ? tnum[tB] : 0;
+            real jw[NR], jas[NR];      // J . warm start, J . qacc_smooth (the Newton solver's two start candidates)
+#pragma unroll
+            for (int q = 0; q < NR; q++) {
+                jw[q] = 0; jas[q] = 0;
+#pragma unroll
+                for (int k = 0; k < TREE_W; k++) {
+                    const int da = a0 + k < nvm ? a0 + k : nvm;
+                    jw[q] += J[q][k] * warm[da];
+                    jas[q] += J[q][k] * asm_[da];
+                }
+            }
+            if (tB >= 0) {
+#pragma unroll
+                for (int q = 0; q < NR; q++) {
+#pragma unroll
+                    for (int k = 0; k < TREE_W; k++) {
+                        const int db = b0r + k < nvm ? b0r + k : nvm;
+                        jw[q] += J[q][TREE_W + k] * warm[db];
+                        jas[q] += J[q][TREE_W + k] * asm_[db];
+                    }
+                }
+            }
+            const real big = real(1e30);
+#pragma unroll
+            for (int q = 0; q < NR; q++) {
+                const int i = i0 + 3 * q;
+                real lo = -big, hi = big, muinv = 0;
+                bool ns = false;   // takes part in the noslip sweeps (contact friction rows)
+                if (sub[q] == 0) lo = 0;
+                else { ns = true; muinv = real(1) / tmax(real(1e-15), floss[q]); }
+                real f = -(jw[q] - aref[q]) / R[q];
+                f = tmin(tmax(f, lo), hi);
+                if (q == 0 || live1) {
+                    real* S = rowS + RS_S * i;
+                    // word 2: PGS 1 / (A_rr + R); Newton: residual of the warm start, with that of qacc_smooth in word 8
+                    S[0] = aref[q]; S[1] = R[q]; S[2] = newton ? jw[q] - aref[q] : real(1) / (dg[q] + R[q]); S[3] = ns ? real(1) / tmax(dg[q], real(1e-15)) : real(0);
+                    S[4] = lo; S[5] = hi; S[6] = f; S[7] = muinv; S[8] = jas[q] - aref[q];
+                    rowI[i] = a0 | (nA << 6) | (tA << 10) | ((b0r | (nB << 6) | ((tB >= 0 ? tB : 0) << 10)) << 13);
+                    rmeta[i] = R_CONTACT | (c << 2) | (sub[q] << 12) | ((tA + 1) << 20) | ((tB + 1) << 24);
+                }
+            }
+        };
+        for (int i = lane; i < nlead0; i += G) fill_lead(i);
         ROWPROBE(1);
-        for (int i = nlead0 + lane; i < nefc; i += G) fill(i, BoolTag<false>{});
+        // Contact rows.  One row per lane, in row order -- or, where that takes fewer trips, one (contact, axis) per lane with the two rows
+        // along that axis: 12 contacts of 6 rows are 72 rows = two trips the first way and 36 lanes = one trip the second.  Never more
+        // trips than rows / 64 (24 contacts of 128 rows take the first way); the choice is the env's (wave-uniform), per substep.
+        // (the lane map and the rule: axis_rows / rows_pair_pays of avsim_phys_layout.h)
+        if (rows_paired_() && rows_pair_pays(ncon, nefc - nlead0, G)) {
+            for (int base = 0; base < 3 * ncon; base += G) {
+                const int item = base + lane, c = item / 3, s = item - 3 * c;
+                int row0 = 0;
+                bool live1 = false;
+                if (axis_rows(c < ncon ? cefc[c] : -1, s, row0, live1)) fill_con(c, row0, s, live1, IntTag<2>{});
+            }
+        } else {
+            for (int i = nlead0 + lane; i < nefc; i += G) {
+                const int meta = rmeta[i];
+                fill_con((meta >> 2) & 1023, i, (meta >> 12) & 255, false, IntTag<1>{});
+            }
+        }
         GSYNC();
         ROWPROBE(2);
         // --- Gauss-Seidel groups: the leading non-contact rows in packs of GRP_MAX, then one group per contact ---
@@ -3434,6 +3527,7 @@ __global__ void __launch_bounds__(64 * MAXW) AVSIM_PHYS_ATTR k_phys(KPtr<real> k
     if (lane == 0) for (int k = 0; k < 8; k++) { ii[ka->lay.misc + k] = 0; ii[ka->lay.nprof + k] = 0; ii[ka->lay.nprof + 8 + k] = 0; }
     if (lane == 0) ii[ka->lay.misc + 8] = 0;
     E.profiling = o_prof != nullptr;
+    E.rows_single = (retry_mode & 16) != 0;      // (bit 4, set by option "rows_paired" = 0: retry_mode 0 stays "as shipped")
     GSYNC();
     if (action) {
         // env.py:203-215: action -> ctrl, grippers un-normalised (env.py:156-161)
@@ -3594,6 +3688,7 @@ struct PhysHost {
     // results are those of the full capacities, the common case runs at the residency of the small ones.  Equal tiers: one pass.
     int maxcon1 = 48, maxefc1 = 144;
     bool f64 = false;
+    int rows_paired = 1;            // option "rows_paired": 1 a contact's rows two per lane where that saves a trip (make_constraints_i), 0 always one per lane
     int specialised = 1;            // option "phys_specialised": 0 never, 1 the kernel compiled for the model when one matches, 2 require one
     bool host_only = false;         // init() assembles the table image, the offsets and the layouts without a device (tools/gen_phys_specs)
     int N = 0, max_reward = 0;
@@ -3872,7 +3967,7 @@ struct PhysHost {
     // Which kernel a one-pass launch of this handle takes as it stands: the one compiled for its model, or null = the generic one.
     // Host only: no launch, no allocation.
     const void* spec_kernel(const char** name) const {
-        if (f64 || specialised == 0 || two_pass()) return nullptr;
+        if (f64 || specialised == 0 || two_pass() || !rows_paired) return nullptr;
         return phys_spec_kernel(*this, name);
     }
     // "phys_specialised" = 2: a launch that would take the generic kernel is refused.  Asked by launch_t and, before their first
@@ -3880,7 +3975,7 @@ struct PhysHost {
     bool refuses(std::string& err) const {
         if (specialised != 2 || spec_kernel(nullptr)) return false;
         err = std::string("phys_specialised = 2: no kernel compiled for this handle's model and layout (") +
-              (f64 ? "f64 handle" : two_pass() ? "two capacity tiers" : "Layout, table offsets, dims or solver options (solver, noslip_*, qcqp_tridiag, newton_*, ls_iterations, num_joints) match no spec of avsim_phys_specs.h") + "); the launch would take the generic k_phys";
+              (f64 ? "f64 handle" : two_pass() ? "two capacity tiers" : !rows_paired ? "rows_paired = 0" :"Layout, table offsets, dims or solver options (solver, noslip_*, qcqp_tridiag, newton_*, ls_iterations, num_joints) match no spec of avsim_phys_specs.h") + "); the launch would take the generic k_phys";
         return true;
     }
     int spec_note = 0;
@@ -3968,6 +4063,7 @@ struct PhysHost {
         if (n == "order_envs") { order_envs = v != 0; return true; }
         if (n == "phys_specialised") { if (v != 0 && v != 1 && v != 2) return false; specialised = (int)v; return true; }
         if (n == "pair_waves") { pair_waves = v != 0; return true; }
+        if (n == "rows_paired") { if (v != 0 && v != 1) return false; rows_paired = (int)v; return true; }
         if (n == "qcqp_tridiag") { mf.qcqp_tridiag = md.qcqp_tridiag = v < 0 ? 0 : (v > 2 ? 2 : (int)v); return true; }
         if (n == "noslip_iters") { if (v < 0 || v > 100) return false; mf.noslip_iters = md.noslip_iters = (int)v; return true; }
         if (n == "noslip_per_tree") { mf.noslip_per_tree = md.noslip_per_tree = v != 0; return true; }
@@ -4069,7 +4165,8 @@ struct PhysHost {
         }
         // (checked BEFORE anything is enqueued: set_option admits 16 .. 1000, so this cannot fire through the API)
         // the second pass gets the first tier's capacities in two 10-bit fields of retry_mode, above the three mode bits and the pairing bit
-        static_assert((8 | 7) < (1 << 8), "retry_mode: mode bits and pairing flag below bit 8");
+        static_assert((16 | 8 | 7) < (1 << 8), "retry_mode: mode bits, pairing flag and the rows_paired = 0 flag below bit 8");
+        const int single = rows_paired ? 0 : 16;
         if (two && (maxcon1 >= 1024 || maxefc1 >= 1024 || maxcon1 < 0 || maxefc1 < 0)) { err = "first-tier capacities do not fit the 10-bit fields of retry_mode (maxcon_first / maxefc_first < 1024)"; return -1; }
         // launch order from the previous step's per-env cost
         const int* order = nullptr;
@@ -4087,7 +4184,7 @@ struct PhysHost {
             hipLaunchKernelGGL(two ? kern2 : kern1, dim3(nblk), dim3(64 * wpb), shmem, st, (KPtr<real>)kargs.ptr(), (const real*)d_img_real, (const int*)d_img_int, N, nsub, pgs_iters, action, want_reward,
                                (real*)qpos, (real*)qvel, (real*)ctrl, (real*)warm, latch, agent, (int*)reward, (unsigned char*)success, d_ncon,
                                cpairs.as<int>(), cdist.as<double>(), d_diag, max_reward, export_contacts, d_prof, d_xpose, order, order_envs ? d_cost : (int*)nullptr, head, next,
-                               d_retry, two ? (1 + 2 * par) | pairing : 0, (KPtr<real>)kargs2.ptr());
+                               d_retry, (two ? (1 + 2 * par) | pairing : 0) | single, (KPtr<real>)kargs2.ptr());
         }
         if (two) {
             // second pass: the envs the first one gave up on, with the full capacities; one workgroup per CU is plenty for the few there
@@ -4101,7 +4198,7 @@ struct PhysHost {
             hipLaunchKernelGGL(kern2, dim3(nblk2), dim3(64 * wpb2), shmem2, st, (KPtr<real>)kargs2.ptr(), (const real*)d_img_real, (const int*)d_img_int, N, nsub, pgs_iters, action, want_reward,
                                (real*)qpos, (real*)qvel, (real*)ctrl, (real*)warm, latch, agent, (int*)reward, (unsigned char*)success, d_ncon,
                                cpairs.as<int>(), cdist.as<double>(), d_diag, max_reward, export_contacts, d_prof, d_xpose, (const int*)rlist, order_envs ? d_cost : (int*)nullptr, head, next,
-                               d_retry, (2 + 2 * par) | (maxcon1 << 8) | (maxefc1 << 18), (KPtr<real>)kargs2.ptr());      // (+ the FIRST tier's capacities: what "needed the full record" is measured against)
+                               d_retry, (2 + 2 * par) | single | (maxcon1 << 8) | (maxefc1 << 18), (KPtr<real>)kargs2.ptr());      // (+ the FIRST tier's capacities: what "needed the full record" is measured against)
         }
         if (nsub > 0) have_cost = true;
         hipError_t e = hipGetLastError();

@@ -136,4 +136,21 @@ constexpr Layout make_layout_of(int maxcon, int maxefc, int full_maxcon, int ful
 constexpr int CAP_EFC[5] = {176, 176, 336, 480, 176}, CAP_CON[5] = {48, 48, 72, 96, 48};
 constexpr int CAP_EFC1[5] = {176, 176, 224, 288, 176}, CAP_CON1[5] = {48, 48, 56, 64, 48};
 
+// ---- contact rows two per lane (Env::make_constraints_i; tests/test_rows_paired_host.py runs these on the host) ----
+// A contact of dim rows (1, 3, 4 or 6) has up to three axes: axis s carries the contact's sub-row s and, where the contact has it,
+// sub-row s + 3 -- the translational and the rotational row along one direction of the contact frame.  Item 3 c + s of a substep is
+// axis s of contact c; the items are dealt to the wave's lanes 64 at a time like the rows are.
+constexpr int row_trips(int n, int lanes) { return (n + lanes - 1) / lanes; }
+// two rows per lane only where that takes FEWER trips than one row per lane: never more trips than the rows themselves need
+constexpr bool rows_pair_pays(int ncon, int ncontact_rows, int lanes) { return row_trips(3 * ncon, lanes) < row_trips(ncontact_rows, lanes); }
+// The rows of axis s of a contact whose row word is ce (first row | rows << 16; negative: the contact has no rows -- inactive, or cut
+// off by the row cap): false = nothing to fill, else row0 = the table row of sub-row s and live1 = row0 + 3 (sub-row s + 3) exists too.
+constexpr bool axis_rows(int ce, int s, int& row0, bool& live1) {
+    const int first = ce & 0xffff, dim = ce >> 16;
+    if (ce < 0 || s >= dim) return false;
+    row0 = first + s;
+    live1 = s + 3 < dim;
+    return true;
+}
+
 }  // namespace avs

@@ -91,6 +91,10 @@ int avsim_dims(const avsim_t* h, int32_t dims[AVSIM_NDIMS]);
  *                       fails with AVSIM_EINVAL before anything is enqueued -- avsim_step*,
  *                       avsim_reset, avsim_set_state / avsim_set_qpos and avsim_observe ask before their IK / reset / conversion kernels.
  *                       Same results to the last bit in all three settings
+ *   "rows_paired"       1 (default): the contact rows of a substep are filled two per lane -- the translational and the rotational row along
+ *                       one axis of a contact's frame -- whenever that takes fewer trips of the wave than one row per lane (12 contacts of
+ *                       6 rows: one trip instead of two); 0 = always one row per lane, and the generic kernel (the per-model kernels pair
+ *                       unconditionally: "phys_specialised" 2 refuses).  Same results to the last bit
  *   "noslip_iters"      0 .. 100: sweeps of the noslip pass after the solver (default: the model's own, 3 in the committed models)
  *   "noslip_per_tree"   1 (default): the dry-friction rows of the noslip pass are relaxed per kinematic tree, all trees at once
  *                       (models with <= 8 trees); 0 = six rows at a time through the Gauss-Seidel groups (what models with more
