@@ -528,7 +528,7 @@ int avsim_observe(avsim_t* h, double* agent_pos, int32_t* reward, uint8_t* succe
     uint8_t* dsu = io.out(success, N);
     if (io.failed()) return AVSIM_EHIP;
     h->phys.force_reward = 1;
-    const int rc = h->phys.launch(h->stream, h->N, 0, nullptr, h->nj, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, dap, drw, dsu, h->err);
+    const int rc = h->phys.launch(h->stream, 0, nullptr, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, dap, drw, dsu, h->err);
     h->phys.force_reward = 0;
     if (rc) return rc;
     return io.done();
@@ -587,7 +587,7 @@ static int reset_impl(avsim_t* h, Call& io, const uint8_t* mask, const double* o
                        h->phys.d_obj_reset);
     HIPCHK(h, hipGetLastError());
     // mj_forward (env.py:244, 538): refresh kinematics + contacts of the new state, no time stepping
-    if (int rc = h->phys.launch(h->stream, h->N, 0, nullptr, h->nj, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, nullptr, nullptr, nullptr, h->err))
+    if (int rc = h->phys.launch(h->stream, 0, nullptr, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, nullptr, nullptr, nullptr, h->err))
         return rc;
     return io.done();
 }
@@ -611,7 +611,7 @@ int avsim_reset(avsim_t* h, const uint8_t* mask, const double* obj_qpos) {
 // the physics launch of the steps, between its pair of timing events.  Device pointers all: the callers stage, and finish, round it
 static int step_common(avsim_t* h, const float* d_action, int nsub, double* dap, int32_t* drw, uint8_t* dsu) {
     if (h->ktiming) HIPCHK(h, h->ktimer.begin(h->stream));      // (once per EV_RING launches this waits for the pairs held and folds them into the sum)
-    if (int rc = h->phys.launch(h->stream, h->N, nsub, d_action, h->nj, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, dap, drw, dsu, h->err)) return rc;
+    if (int rc = h->phys.launch(h->stream, nsub, d_action, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, dap, drw, dsu, h->err)) return rc;
     if (h->ktiming) HIPCHK(h, h->ktimer.end(h->stream));
     return AVSIM_OK;
 }
@@ -719,7 +719,7 @@ int avsim_set_state(avsim_t* h, const double* qpos, const double* qvel, const do
     put(h, io, warm, h->d_warm, N * h->nv);
     if (io.failed()) return AVSIM_EHIP;
     HIPCHK(h, hipGetLastError());
-    if (int rc = h->phys.launch(h->stream, h->N, 0, nullptr, h->nj, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, nullptr, nullptr, nullptr, h->err))
+    if (int rc = h->phys.launch(h->stream, 0, nullptr, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, nullptr, nullptr, nullptr, h->err))
         return rc;
     return io.done();
 }
@@ -808,7 +808,7 @@ extern "C" {
 static int refresh_xpose(avsim_t* h) {
     if (h->xpose_ver != h->state_ver) {
         h->phys.d_xpose = h->render.d_xpose;
-        const int rc = h->phys.launch(h->stream, h->N, 0, nullptr, h->nj, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, nullptr, nullptr, nullptr, h->err);
+        const int rc = h->phys.launch(h->stream, 0, nullptr, h->d_qpos, h->d_qvel, h->d_ctrl, h->d_warm, h->d_latch, nullptr, nullptr, nullptr, h->err);
         h->phys.d_xpose = nullptr;
         if (rc) return rc;
         h->xpose_ver = h->state_ver;

@@ -1911,58 +1911,13 @@ struct Env {
     AVS_DEV GArr<int> cand_() const { return glb_block((GLB_PTR(int))ka->m.cand_glob, env, (unsigned)CAND_MAX); }
     AVS_DEV GArr<real> bxo_() const { return glb_block((GLB_PTR(real))ka->m.bxo_glob, env, (unsigned)(64 * BOX_OVF_W)); }
     AVS_DEV GArr<real> gref_() const { return glb_block((GLB_PTR(real))ka->m.gref_glob, env, (unsigned)(ka->m.ngeom * 3)); }
-    AVS_DEV const int* body_parent_() const { return LI() + ka->mo.body_parent; }
-    AVS_DEV const int* body_jntadr_() const { return LI() + ka->mo.body_jntadr; }
-    AVS_DEV const int* body_jntnum_() const { return LI() + ka->mo.body_jntnum; }
-    AVS_DEV const int* body_dofadr_() const { return LI() + ka->mo.body_dofadr; }
-    AVS_DEV const int* body_dofnum_() const { return LI() + ka->mo.body_dofnum; }
-    AVS_DEV const int* body_tree_() const { return LI() + ka->mo.body_tree; }
-    AVS_DEV const int* body_dofmask_() const { return LI() + ka->mo.body_dofmask; }
-    AVS_DEV const int* body_last_() const { return LI() + ka->mo.body_last; }
-    AVS_DEV const int* tree_bodyadr_() const { return LI() + ka->mo.tree_bodyadr; }
-    AVS_DEV const int* tree_bodylist_() const { return LI() + ka->mo.tree_bodylist; }
-    AVS_DEV const int* tree_dofadr_() const { return LI() + ka->mo.tree_dofadr; }
-    AVS_DEV const int* tree_dofnum_() const { return LI() + ka->mo.tree_dofnum; }
-    AVS_DEV const int* tree_madr_() const { return LI() + ka->mo.tree_madr; }
-    AVS_DEV const int* jnt_type_() const { return LI() + ka->mo.jnt_type; }
-    AVS_DEV const int* jnt_qposadr_() const { return LI() + ka->mo.jnt_qposadr; }
-    AVS_DEV const int* jnt_dofadr_() const { return LI() + ka->mo.jnt_dofadr; }
-    AVS_DEV const int* jnt_actfrclimited_() const { return LI() + ka->mo.jnt_actfrclimited; }
-    AVS_DEV const int* limited_jnt_() const { return LI() + ka->mo.limited_jnt; }
-    AVS_DEV const int* dof_body_() const { return LI() + ka->mo.dof_body; }
-    AVS_DEV const int* dof_parent_() const { return LI() + ka->mo.dof_parent; }
-    AVS_DEV const int* dof_tree_() const { return LI() + ka->mo.dof_tree; }
-    AVS_DEV const int* dof_jnt_() const { return LI() + ka->mo.dof_jnt; }
-    AVS_DEV const int* floss_dof_() const { return LI() + ka->mo.floss_dof; }
-    AVS_DEV const int* ment_i_() const { return LI() + ka->mo.ment_i; }
-    AVS_DEV const int* ment_j_() const { return LI() + ka->mo.ment_j; }
-    AVS_DEV const int* act_dof_() const { return LI() + ka->mo.act_dof; }
-    AVS_DEV const int* act_qposadr_() const { return LI() + ka->mo.act_qposadr; }
-    AVS_DEV const int* act_ctrllimited_() const { return LI() + ka->mo.act_ctrllimited; }
-    AVS_DEV const int* geom_type_() const { return LI() + ka->mo.geom_type; }
-    AVS_DEV const int* geom_body_() const { return LI() + ka->mo.geom_body; }
-    AVS_DEV const int* geom_static_() const { return LI() + ka->mo.geom_static; }
-    AVS_DEV const real* body_pos_() const { return LR() + ka->mo.body_pos; }
-    AVS_DEV const real* body_quat_() const { return LR() + ka->mo.body_quat; }
-    AVS_DEV const real* body_mass_() const { return LR() + ka->mo.body_mass; }
-    AVS_DEV const real* body_ipos_() const { return LR() + ka->mo.body_ipos; }
-    AVS_DEV const real* body_inertia_() const { return LR() + ka->mo.body_inertia; }
-    AVS_DEV const real* body_invweight0_() const { return LR() + ka->mo.body_invweight0; }
-    AVS_DEV const real* jnt_pos_() const { return LR() + ka->mo.jnt_pos; }
-    AVS_DEV const real* jnt_axis_() const { return LR() + ka->mo.jnt_axis; }
-    AVS_DEV const real* jnt_range_() const { return LR() + ka->mo.jnt_range; }
-    AVS_DEV const real* jnt_actfrcrange_() const { return LR() + ka->mo.jnt_actfrcrange; }
-    AVS_DEV const real* jnt_margin_() const { return LR() + ka->mo.jnt_margin; }
-    AVS_DEV const real* dof_armature_() const { return LR() + ka->mo.dof_armature; }
-    AVS_DEV const real* dof_damping_() const { return LR() + ka->mo.dof_damping; }
-    AVS_DEV const real* dof_frictionloss_() const { return LR() + ka->mo.dof_frictionloss; }
-    AVS_DEV const real* dof_invweight0_() const { return LR() + ka->mo.dof_invweight0; }
-    AVS_DEV const real* act_kp_() const { return LR() + ka->mo.act_kp; }
-    AVS_DEV const real* act_kv_() const { return LR() + ka->mo.act_kv; }
-    AVS_DEV const real* act_gear_() const { return LR() + ka->mo.act_gear; }
-    AVS_DEV const real* act_ctrlrange_() const { return LR() + ka->mo.act_ctrlrange; }
-    AVS_DEV const real* geom_cpos_() const { return LR() + ka->mo.geom_cpos; }
-    AVS_DEV const real* geom_rbound_() const { return LR() + ka->mo.geom_rbound; }
+    // the tables of the block's image, X_(): one accessor per entry of the two lists of avsim_phys_layout.h
+#define AVS_IMG_INT_ACCESSOR(x) AVS_DEV const int* x##_() const { return LI() + ka->mo.x; }
+#define AVS_IMG_REAL_ACCESSOR(x) AVS_DEV const real* x##_() const { return LR() + ka->mo.x; }
+    AVSIM_IMG_INT_TABLES(AVS_IMG_INT_ACCESSOR)
+    AVSIM_IMG_REAL_TABLES(AVS_IMG_REAL_ACCESSOR)
+#undef AVS_IMG_INT_ACCESSOR
+#undef AVS_IMG_REAL_ACCESSOR
 
 
     // ---- P1 ------------------------------------------------------------------------------------
@@ -3754,8 +3709,10 @@ struct PhysHost {
         m.nj = b.scalar("num_arms") == 3 ? 21 : 14;
         auto opt = F("opt");
         m.timestep = (real)opt[0]; m.gravity[0] = (real)opt[1]; m.gravity[1] = (real)opt[2]; m.gravity[2] = (real)opt[3];
-        m.impratio = (real)opt[4]; m.noslip_iters = (int)opt[5]; m.noslip_per_tree = 1; m.noslip_trees = 1; m.newton_component = 1; m.newton_early_exit = 1; m.qcqp_tridiag = sizeof(real) == 4 ? 2 : 0;
-        m.solver = 1; m.newton_iters = 100; m.newton_tol = sizeof(real) == 8 ? (real)1e-8 : (real)1e-6; m.ls_tolerance = sizeof(real) == 8 ? (real)1e-10 : (real)1e-4; m.ls_iterations = 50;     // MuJoCo defaults: iterations 100, tolerance 1e-8
+        m.impratio = (real)opt[4]; m.noslip_iters = (int)opt[5]; m.noslip_per_tree = 1; m.noslip_trees = 1; m.newton_component = 1; m.newton_early_exit = 1;
+        m.qcqp_tridiag = sizeof(real) == 4 ? 2 : 0;
+        m.solver = 1; m.newton_iters = 100; m.newton_tol = sizeof(real) == 8 ? (real)1e-8 : (real)1e-6;     // MuJoCo defaults: iterations 100, tolerance 1e-8
+        m.ls_tolerance = sizeof(real) == 8 ? (real)1e-10 : (real)1e-4; m.ls_iterations = 50;
         m.nscale = (real)(1.0 / ((opt.size() > 7 && opt[7] > 0 ? opt[7] : 1.0) * std::max(1, m.nv)));
         auto gr = F("grip_range");
         m.grip_lo = (real)gr[0]; m.grip_hi = (real)gr[1];
@@ -3818,36 +3775,84 @@ struct PhysHost {
         for (int j = 0; j < m.njnt; j++) if (jl[j]) lj.push_back(j);
         m.nfloss = (int)fl.size();
         m.nlimited = (int)lj.size();
-        m.body_parent = up(body_parent); moff.body_parent = (int)img_int.size(); { auto v_ = body_parent; img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.body_jntadr = up(I("body_jntadr")); moff.body_jntadr = (int)img_int.size(); { auto v_ = I("body_jntadr"); img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.body_jntnum = up(I("body_jntnum")); moff.body_jntnum = (int)img_int.size(); { auto v_ = I("body_jntnum"); img_int.insert(img_int.end(), v_.begin(), v_.end()); }
-        m.body_dofadr = up(body_dofadr); moff.body_dofadr = (int)img_int.size(); { auto v_ = body_dofadr; img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.body_dofnum = up(body_dofnum); moff.body_dofnum = (int)img_int.size(); { auto v_ = body_dofnum; img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.body_tree = up(body_tree); moff.body_tree = (int)img_int.size(); { auto v_ = body_tree; img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.body_dofmask = up(mask); moff.body_dofmask = (int)img_int.size(); { auto v_ = mask; img_int.insert(img_int.end(), v_.begin(), v_.end()); }
+        // A table of the image (the lists of avsim_phys_layout.h) is uploaded as a table of its own, m.x, and appended to its half of the
+        // image, where moff.x says it starts.  MOff starts at -1: the check behind the last fill line names a listed table that no line
+        // filled, or one filled out of list order, instead of letting the kernels read another table's words.
+        auto img_ints = [&](auto& dst, int& off, const std::vector<int>& v) { dst = up(v); off = (int)img_int.size(); img_int.insert(img_int.end(), v.begin(), v.end()); };
+        auto img_reals = [&](auto& dst, int& off, const std::vector<double>& v) { dst = upr<real>(v); off = (int)img_real.size(); img_real.insert(img_real.end(), v.begin(), v.end()); };
+#define IMG_INT(x, v) img_ints(m.x, moff.x, v)
+#define IMG_REAL(x, v) img_reals(m.x, moff.x, v)
+        IMG_INT(body_parent, body_parent);
+        IMG_INT(body_jntadr, I("body_jntadr"));
+        IMG_INT(body_jntnum, I("body_jntnum"));
+        IMG_INT(body_dofadr, body_dofadr);
+        IMG_INT(body_dofnum, body_dofnum);
+        IMG_INT(body_tree, body_tree);
+        IMG_INT(body_dofmask, mask);
         {   // bodies are numbered depth first: the subtree of body p is the id range p .. body_last[p] (checked)
             std::vector<int> last(nb);
             for (int bb = 0; bb < nb; bb++) last[bb] = bb;
             for (int bb = nb - 1; bb > 0; bb--) { int pp = body_parent[bb]; if (last[bb] > last[pp]) last[pp] = last[bb]; }
             for (int bb = 1; bb < nb; bb++) { int pp = body_parent[bb]; if (!(pp < bb && bb <= last[pp])) throw std::runtime_error("bodies are not in depth-first order"); }
             for (int pp = 0; pp < nb; pp++) for (int d = pp + 1; d <= last[pp]; d++) { int a = d; while (a > pp) a = body_parent[a]; if (a != pp) throw std::runtime_error("bodies are not in depth-first order"); }
-            m.body_last = up(last); moff.body_last = (int)img_int.size(); img_int.insert(img_int.end(), last.begin(), last.end());
+            IMG_INT(body_last, last);
         }
-        m.body_pos = upr<real>(bpos); moff.body_pos = (int)img_real.size(); { auto v_ = bpos; img_real.insert(img_real.end(), v_.begin(), v_.end()); } m.body_quat = upr<real>(bquat); moff.body_quat = (int)img_real.size(); { auto v_ = bquat; img_real.insert(img_real.end(), v_.begin(), v_.end()); } m.body_mass = upr<real>(F("body_mass")); moff.body_mass = (int)img_real.size(); { auto v_ = F("body_mass"); img_real.insert(img_real.end(), v_.begin(), v_.end()); } m.body_ipos = upr<real>(F("body_ipos")); moff.body_ipos = (int)img_real.size(); { auto v_ = F("body_ipos"); img_real.insert(img_real.end(), v_.begin(), v_.end()); }
-        m.body_inertia = upr<real>(F("body_inertia")); moff.body_inertia = (int)img_real.size(); { auto v_ = F("body_inertia"); img_real.insert(img_real.end(), v_.begin(), v_.end()); } m.body_invweight0 = upr<real>(F("body_invweight0")); moff.body_invweight0 = (int)img_real.size(); { auto v_ = F("body_invweight0"); img_real.insert(img_real.end(), v_.begin(), v_.end()); }
-        m.static_xpos = upr<real>(sx); m.static_xmat = upr<real>(sm);
-        m.tree_bodyadr = up(tba); moff.tree_bodyadr = (int)img_int.size(); { auto v_ = tba; img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.tree_bodylist = up(tbl); moff.tree_bodylist = (int)img_int.size(); { auto v_ = tbl; img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.tree_dofadr = up(tree_dofadr); moff.tree_dofadr = (int)img_int.size(); { auto v_ = tree_dofadr; img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.tree_dofnum = up(tree_dofnum); moff.tree_dofnum = (int)img_int.size(); { auto v_ = tree_dofnum; img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.tree_madr = up(madr); moff.tree_madr = (int)img_int.size(); { auto v_ = madr; img_int.insert(img_int.end(), v_.begin(), v_.end()); }
-        m.jnt_type = up(I("jnt_type")); moff.jnt_type = (int)img_int.size(); { auto v_ = I("jnt_type"); img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.jnt_qposadr = up(I("jnt_qposadr")); moff.jnt_qposadr = (int)img_int.size(); { auto v_ = I("jnt_qposadr"); img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.jnt_dofadr = up(I("jnt_dofadr")); moff.jnt_dofadr = (int)img_int.size(); { auto v_ = I("jnt_dofadr"); img_int.insert(img_int.end(), v_.begin(), v_.end()); }
-        m.jnt_actfrclimited = up(I("jnt_actfrclimited")); moff.jnt_actfrclimited = (int)img_int.size(); { auto v_ = I("jnt_actfrclimited"); img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.limited_jnt = up(lj); moff.limited_jnt = (int)img_int.size(); { auto v_ = lj; img_int.insert(img_int.end(), v_.begin(), v_.end()); }
-        m.jnt_pos = upr<real>(F("jnt_pos")); moff.jnt_pos = (int)img_real.size(); { auto v_ = F("jnt_pos"); img_real.insert(img_real.end(), v_.begin(), v_.end()); } m.jnt_axis = upr<real>(F("jnt_axis")); moff.jnt_axis = (int)img_real.size(); { auto v_ = F("jnt_axis"); img_real.insert(img_real.end(), v_.begin(), v_.end()); } m.jnt_range = upr<real>(F("jnt_range")); moff.jnt_range = (int)img_real.size(); { auto v_ = F("jnt_range"); img_real.insert(img_real.end(), v_.begin(), v_.end()); }
-        m.jnt_actfrcrange = upr<real>(F("jnt_actfrcrange")); moff.jnt_actfrcrange = (int)img_real.size(); { auto v_ = F("jnt_actfrcrange"); img_real.insert(img_real.end(), v_.begin(), v_.end()); } m.jnt_solref = upr<real>(F("jnt_solref")); m.jnt_solimp = upr<real>(F("jnt_solimp"));
-        m.jnt_margin = upr<real>(F("jnt_margin")); moff.jnt_margin = (int)img_real.size(); { auto v_ = F("jnt_margin"); img_real.insert(img_real.end(), v_.begin(), v_.end()); }
-        m.dof_body = up(dof_body); moff.dof_body = (int)img_int.size(); { auto v_ = dof_body; img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.dof_parent = up(dof_parent); moff.dof_parent = (int)img_int.size(); { auto v_ = dof_parent; img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.dof_tree = up(dof_tree); moff.dof_tree = (int)img_int.size(); { auto v_ = dof_tree; img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.dof_jnt = up(I("dof_jnt")); moff.dof_jnt = (int)img_int.size(); { auto v_ = I("dof_jnt"); img_int.insert(img_int.end(), v_.begin(), v_.end()); }
-        m.floss_dof = up(fl); moff.floss_dof = (int)img_int.size(); { auto v_ = fl; img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.ment_i = up(mi); moff.ment_i = (int)img_int.size(); { auto v_ = mi; img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.ment_j = up(mj); moff.ment_j = (int)img_int.size(); { auto v_ = mj; img_int.insert(img_int.end(), v_.begin(), v_.end()); }
-        m.dof_armature = upr<real>(F("dof_armature")); moff.dof_armature = (int)img_real.size(); { auto v_ = F("dof_armature"); img_real.insert(img_real.end(), v_.begin(), v_.end()); } m.dof_damping = upr<real>(F("dof_damping")); moff.dof_damping = (int)img_real.size(); { auto v_ = F("dof_damping"); img_real.insert(img_real.end(), v_.begin(), v_.end()); } m.dof_frictionloss = upr<real>(floss); moff.dof_frictionloss = (int)img_real.size(); { auto v_ = floss; img_real.insert(img_real.end(), v_.begin(), v_.end()); }
-        m.dof_invweight0 = upr<real>(F("dof_invweight0")); moff.dof_invweight0 = (int)img_real.size(); { auto v_ = F("dof_invweight0"); img_real.insert(img_real.end(), v_.begin(), v_.end()); } m.dof_solref = upr<real>(F("dof_solref")); m.dof_solimp = upr<real>(F("dof_solimp"));
-        m.act_dof = up(I("act_dof")); moff.act_dof = (int)img_int.size(); { auto v_ = I("act_dof"); img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.act_qposadr = up(I("act_qposadr")); moff.act_qposadr = (int)img_int.size(); { auto v_ = I("act_qposadr"); img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.act_ctrllimited = up(I("act_ctrllimited")); moff.act_ctrllimited = (int)img_int.size(); { auto v_ = I("act_ctrllimited"); img_int.insert(img_int.end(), v_.begin(), v_.end()); }
-        m.act_kp = upr<real>(F("act_kp")); moff.act_kp = (int)img_real.size(); { auto v_ = F("act_kp"); img_real.insert(img_real.end(), v_.begin(), v_.end()); } m.act_kv = upr<real>(F("act_kv")); moff.act_kv = (int)img_real.size(); { auto v_ = F("act_kv"); img_real.insert(img_real.end(), v_.begin(), v_.end()); } m.act_gear = upr<real>(F("act_gear")); moff.act_gear = (int)img_real.size(); { auto v_ = F("act_gear"); img_real.insert(img_real.end(), v_.begin(), v_.end()); } m.act_ctrlrange = upr<real>(F("act_ctrlrange")); moff.act_ctrlrange = (int)img_real.size(); { auto v_ = F("act_ctrlrange"); img_real.insert(img_real.end(), v_.begin(), v_.end()); }
-        m.eq_dof1 = up(I("eq_dof1")); m.eq_dof2 = up(I("eq_dof2")); m.eq_qpos1 = up(I("eq_qpos1")); m.eq_qpos2 = up(I("eq_qpos2"));
-        m.eq_polycoef = upr<real>(F("eq_polycoef")); m.eq_solref = upr<real>(F("eq_solref")); m.eq_solimp = upr<real>(F("eq_solimp"));
+        IMG_REAL(body_pos, bpos);
+        IMG_REAL(body_quat, bquat);
+        IMG_REAL(body_mass, F("body_mass"));
+        IMG_REAL(body_ipos, F("body_ipos"));
+        IMG_REAL(body_inertia, F("body_inertia"));
+        IMG_REAL(body_invweight0, F("body_invweight0"));
+        m.static_xpos = upr<real>(sx);
+        m.static_xmat = upr<real>(sm);
+        IMG_INT(tree_bodyadr, tba);
+        IMG_INT(tree_bodylist, tbl);
+        IMG_INT(tree_dofadr, tree_dofadr);
+        IMG_INT(tree_dofnum, tree_dofnum);
+        IMG_INT(tree_madr, madr);
+        IMG_INT(jnt_type, I("jnt_type"));
+        IMG_INT(jnt_qposadr, I("jnt_qposadr"));
+        IMG_INT(jnt_dofadr, I("jnt_dofadr"));
+        IMG_INT(jnt_actfrclimited, I("jnt_actfrclimited"));
+        IMG_INT(limited_jnt, lj);
+        IMG_REAL(jnt_pos, F("jnt_pos"));
+        IMG_REAL(jnt_axis, F("jnt_axis"));
+        IMG_REAL(jnt_range, F("jnt_range"));
+        IMG_REAL(jnt_actfrcrange, F("jnt_actfrcrange"));
+        m.jnt_solref = upr<real>(F("jnt_solref"));
+        m.jnt_solimp = upr<real>(F("jnt_solimp"));
+        IMG_REAL(jnt_margin, F("jnt_margin"));
+        IMG_INT(dof_body, dof_body);
+        IMG_INT(dof_parent, dof_parent);
+        IMG_INT(dof_tree, dof_tree);
+        IMG_INT(dof_jnt, I("dof_jnt"));
+        IMG_INT(floss_dof, fl);
+        IMG_INT(ment_i, mi);
+        IMG_INT(ment_j, mj);
+        IMG_REAL(dof_armature, F("dof_armature"));
+        IMG_REAL(dof_damping, F("dof_damping"));
+        IMG_REAL(dof_frictionloss, floss);
+        IMG_REAL(dof_invweight0, F("dof_invweight0"));
+        m.dof_solref = upr<real>(F("dof_solref"));
+        m.dof_solimp = upr<real>(F("dof_solimp"));
+        IMG_INT(act_dof, I("act_dof"));
+        IMG_INT(act_qposadr, I("act_qposadr"));
+        IMG_INT(act_ctrllimited, I("act_ctrllimited"));
+        IMG_REAL(act_kp, F("act_kp"));
+        IMG_REAL(act_kv, F("act_kv"));
+        IMG_REAL(act_gear, F("act_gear"));
+        IMG_REAL(act_ctrlrange, F("act_ctrlrange"));
+        m.eq_dof1 = up(I("eq_dof1"));
+        m.eq_dof2 = up(I("eq_dof2"));
+        m.eq_qpos1 = up(I("eq_qpos1"));
+        m.eq_qpos2 = up(I("eq_qpos2"));
+        m.eq_polycoef = upr<real>(F("eq_polycoef"));
+        m.eq_solref = upr<real>(F("eq_solref"));
+        m.eq_solimp = upr<real>(F("eq_solimp"));
         m.qpos0 = upr<real>(F("qpos0"));
         m.qpos_home = upr<real>(F("qpos_home"));
-        m.obj_qadr = up(I("objects_qposadr")); m.nobj = (int)I("objects_qposadr").size();
+        m.obj_qadr = up(I("objects_qposadr"));
+        m.nobj = (int)I("objects_qposadr").size();
         {   // the poses an episode starts with: the model's own until avsim_reset says otherwise
             auto home = F("qpos_home"); auto oa = I("objects_qposadr");
             std::vector<double> o((size_t)N * oa.size() * 7);
@@ -3862,6 +3867,12 @@ struct PhysHost {
         std::vector<int> gstat(ng);
         std::vector<double> gaabb(6 * ng, 0.0), glbox(6 * ng, 0.0);   // world AABB of static geoms; local box (centre, half extents) of every geom
         auto ghull = I("geom_chull"); auto gtype = I("geom_type"); auto gsize = F("geom_size"); auto hv = F("chull_vert");      // the COLLISION hulls (hull_vert / geom_hull: the depth images' polyhedra)
+        // half extents of a primitive's bounding box in its own frame (a sphere's size is its radius, a cylinder's radius and half length)
+        auto half_extents = [&](int g, double* ex) {
+            for (int k = 0; k < 3; k++) ex[k] = gsize[3 * g + k];
+            if (gtype[g] == G_SPHERE) ex[1] = ex[2] = ex[0];
+            if (gtype[g] == G_CYLINDER) { ex[2] = ex[1]; ex[1] = ex[0]; }
+        };
         for (int g = 0; g < ng; g++) {
             q2m(&gquat[4 * g], &gmat[9 * g]);
             for (int i = 0; i < 3; i++)
@@ -3872,9 +3883,8 @@ struct PhysHost {
                     for (int v = 0; v < ghull[2 * g + 1]; v++)
                         for (int k = 0; k < 3; k++) { double x = hv[3 * (ghull[2 * g] + v) + k]; if (x < lo[k]) lo[k] = x; if (x > hi[k]) hi[k] = x; }
                 } else {
-                    double ex[3] = {gsize[3 * g], gsize[3 * g + 1], gsize[3 * g + 2]};
-                    if (gtype[g] == G_SPHERE) ex[1] = ex[2] = ex[0];
-                    if (gtype[g] == G_CYLINDER) { ex[2] = ex[1]; ex[1] = ex[0]; }
+                    double ex[3];
+                    half_extents(g, ex);
                     for (int k = 0; k < 3; k++) { lo[k] = -ex[k]; hi[k] = ex[k]; }
                 }
                 for (int k = 0; k < 3; k++) { glbox[6 * g + k] = 0.5 * (lo[k] + hi[k]); glbox[6 * g + 3 + k] = 0.5 * (hi[k] - lo[k]); }
@@ -3893,9 +3903,8 @@ struct PhysHost {
                 if (gtype[g] == G_MESH) {
                     for (int v = 0; v < ghull[2 * g + 1]; v++) for (int k = 0; k < 3; k++) pts.push_back(hv[3 * (ghull[2 * g] + v) + k]);
                 } else {
-                    double ex[3] = {gsize[3 * g], gsize[3 * g + 1], gsize[3 * g + 2]};
-                    if (gtype[g] == G_SPHERE) ex[1] = ex[2] = ex[0];
-                    if (gtype[g] == G_CYLINDER) { ex[2] = ex[1]; ex[1] = ex[0]; }
+                    double ex[3];
+                    half_extents(g, ex);
                     for (int c = 0; c < 8; c++) for (int k = 0; k < 3; k++) pts.push_back(((c >> k) & 1) ? ex[k] : -ex[k]);
                 }
                 for (int k = 0; k < 3; k++) { gaabb[6 * g + k] = 1e30; gaabb[6 * g + 3 + k] = -1e30; }
@@ -3907,9 +3916,21 @@ struct PhysHost {
                     }
             }
         }
-        m.geom_type = up(I("geom_type")); moff.geom_type = (int)img_int.size(); { auto v_ = I("geom_type"); img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.geom_body = up(gbody); moff.geom_body = (int)img_int.size(); { auto v_ = gbody; img_int.insert(img_int.end(), v_.begin(), v_.end()); } m.geom_hull = up(I("geom_ctab")); m.geom_class = up(I("geom_class")); m.geom_static = up(gstat); moff.geom_static = (int)img_int.size(); { auto v_ = gstat; img_int.insert(img_int.end(), v_.begin(), v_.end()); }
-        m.geom_pos = upr<real>(gpos); m.geom_mat = upr<real>(gmat); m.geom_size = upr<real>(F("geom_size")); m.geom_cpos = upr<real>(gcp); moff.geom_cpos = (int)img_real.size(); { auto v_ = gcp; img_real.insert(img_real.end(), v_.begin(), v_.end()); }
-        m.geom_rbound = upr<real>(F("geom_rbound")); moff.geom_rbound = (int)img_real.size(); { auto v_ = F("geom_rbound"); img_real.insert(img_real.end(), v_.begin(), v_.end()); } m.geom_xpos0 = upr<real>(gx0); m.geom_xmat0 = upr<real>(gm0); m.geom_cen0 = upr<real>(gc0); m.geom_aabb0 = upr<real>(gaabb); m.geom_lbox = upr<real>(glbox);
+        IMG_INT(geom_type, I("geom_type"));
+        IMG_INT(geom_body, gbody);
+        m.geom_hull = up(I("geom_ctab"));
+        m.geom_class = up(I("geom_class"));
+        IMG_INT(geom_static, gstat);
+        m.geom_pos = upr<real>(gpos);
+        m.geom_mat = upr<real>(gmat);
+        m.geom_size = upr<real>(F("geom_size"));
+        IMG_REAL(geom_cpos, gcp);
+        IMG_REAL(geom_rbound, F("geom_rbound"));
+        m.geom_xpos0 = upr<real>(gx0);
+        m.geom_xmat0 = upr<real>(gm0);
+        m.geom_cen0 = upr<real>(gc0);
+        m.geom_aabb0 = upr<real>(gaabb);
+        m.geom_lbox = upr<real>(glbox);
         {   // support tables of the collision hulls (compiler/hull.py support_table).  The blob holds, per cube-map cell, a list of vertex
             // indices local to the cell's hull; the device gets one record of eight (x, y, z, w) entries per cell -- the first eight
             // candidates, a shorter list padded with its last vertex; w of entry 0 = the count, w of entry 1 = where the cell's further
@@ -3951,10 +3972,26 @@ struct PhysHost {
             if (tab.empty()) tab.assign(4, 0.0);
             m.hull_vert = upr<real>(tab);
         }
-        m.pair_geom = up(I("pair_geom")); m.pair_condim = up(I("pair_condim"));
-        m.pair_friction = upr<real>(F("pair_friction")); m.pair_solref = upr<real>(F("pair_solref")); m.pair_solimp = upr<real>(F("pair_solimp"));
-        m.pair_margin = upr<real>(F("pair_margin")); m.pair_gap = upr<real>(F("pair_gap"));
-        m.obs_qposadr = up(I("obs_qposadr")); m.obs_offset = upr<real>(F("obs_offset")); m.obs_scale = upr<real>(F("obs_scale"));
+        m.pair_geom = up(I("pair_geom"));
+        m.pair_condim = up(I("pair_condim"));
+        m.pair_friction = upr<real>(F("pair_friction"));
+        m.pair_solref = upr<real>(F("pair_solref"));
+        m.pair_solimp = upr<real>(F("pair_solimp"));
+        m.pair_margin = upr<real>(F("pair_margin"));
+        m.pair_gap = upr<real>(F("pair_gap"));
+        m.obs_qposadr = up(I("obs_qposadr"));
+        m.obs_offset = upr<real>(F("obs_offset"));
+        m.obs_scale = upr<real>(F("obs_scale"));
+#undef IMG_INT
+#undef IMG_REAL
+        int prev = 0;
+#define AVS_IMG_CHECK(x) \
+        if (moff.x < prev) throw std::runtime_error(moff.x < 0 ? "table image: " #x " is listed but was not filled" : "table image: " #x " was filled out of list order"); \
+        prev = moff.x;
+        AVSIM_IMG_INT_TABLES(AVS_IMG_CHECK)
+        prev = 0;
+        AVSIM_IMG_REAL_TABLES(AVS_IMG_CHECK)
+#undef AVS_IMG_CHECK
         // packed image of the hot tables: copied into LDS by every block (global latency is paid once per launch)
         while (img_real.size() % 4) img_real.push_back(0.0);
         while (img_int.size() % 4) img_int.push_back(0);
@@ -3974,29 +4011,32 @@ struct PhysHost {
     // enqueue, by the API entry points that change state ahead of the physics launch (reset, set_state, the Cartesian step's IK).
     bool refuses(std::string& err) const {
         if (specialised != 2 || spec_kernel(nullptr)) return false;
+        const char* const no_spec =
+            "Layout, table offsets, dims or solver options (solver, noslip_*, qcqp_tridiag, newton_*, ls_iterations, num_joints) match no spec of avsim_phys_specs.h";
         err = std::string("phys_specialised = 2: no kernel compiled for this handle's model and layout (") +
-              (f64 ? "f64 handle" : two_pass() ? "two capacity tiers" : !rows_paired ? "rows_paired = 0" :"Layout, table offsets, dims or solver options (solver, noslip_*, qcqp_tridiag, newton_*, ls_iterations, num_joints) match no spec of avsim_phys_specs.h") + "); the launch would take the generic k_phys";
+              (f64 ? "f64 handle" : two_pass() ? "two capacity tiers" : !rows_paired ? "rows_paired = 0" : no_spec) + "); the launch would take the generic k_phys";
         return true;
     }
     int spec_note = 0;
 
-    void make_layout(int nq, int nv, int nu, int nb, int ng, int msize, int ntree) {
+    int dims[7] = {0, 0, 0, 0, 0, 0, 0};      // nq, nv, nu, nbody, ngeom, msize, ntree
+    // both tiers' layouts from the capacities and dims as they stand
+    void make_layout() {
         if (maxcon1 > maxcon) maxcon1 = maxcon;
         if (maxefc1 > maxefc) maxefc1 = maxefc;
-        make_layout_of(lay, maxcon1, maxefc1, nq, nv, nu, nb, ng, msize, ntree);
-        make_layout_of(lay2, maxcon, maxefc, nq, nv, nu, nb, ng, msize, ntree);
+        make_layout_of(lay, maxcon1, maxefc1);
+        make_layout_of(lay2, maxcon, maxefc);
     }
-    void make_layout_of(Layout& L, const int maxcon, const int maxefc, int nq, int nv, int nu, int nb, int ng, int msize, int ntree) {
+    void make_layout_of(Layout& L, const int maxcon, const int maxefc) {
         kargs_dirty = true;
-        L = avs::make_layout_of(maxcon, maxefc, this->maxcon, this->maxefc, nq, nv, nu, nb, ng, msize, ntree, f64 ? 8 : 4);
+        L = avs::make_layout_of(maxcon, maxefc, this->maxcon, this->maxefc, dims[0], dims[1], dims[2], dims[3], dims[4], dims[5], dims[6], f64 ? 8 : 4);
         if (getenv("AVSIM_DEBUG_LAYOUT")) {
             const int pb = L.rowS + RS_S * maxefc > L.scr + NARROW_SCR_W ? L.rowS + RS_S * maxefc : L.scr + NARROW_SCR_W;
             fprintf(stderr, "avsim layout: %d reals + %d ints = %d B per env (U at %d: phase A %d, phase B %d words); tables %zu B\n", L.nreal, L.nint,
-                    L.bytes_per_env, L.U, 38 * nb, pb - L.U, (size_t)moff.nreal * (f64 ? 8 : 4) + (size_t)moff.nint * 4);
+                    L.bytes_per_env, L.U, 38 * dims[3], pb - L.U, (size_t)moff.nreal * (f64 ? 8 : 4) + (size_t)moff.nint * 4);
         }
     }
 
-    int dims[7] = {0, 0, 0, 0, 0, 0, 0};
     size_t lds_bytes() const { return (size_t)lay.bytes_per_env + (size_t)moff.nreal * (f64 ? 8 : 4) + (size_t)moff.nint * 4; }   // WPB = 1 figure (first pass)
     DevBuf rows, coup, near, gref;
     // sized by maxcon / maxefc exactly, which an option may raise and lower: always reallocated
@@ -4033,7 +4073,7 @@ struct PhysHost {
             maxefc1 = cap_efc1[b.scalar("task_id")];
             maxcon1 = cap_con1[b.scalar("task_id")];
             dims[0] = b.scalar("nq"); dims[1] = b.scalar("nv"); dims[2] = b.scalar("nu"); dims[3] = b.scalar("nbody"); dims[4] = b.scalar("ngeom"); dims[5] = ms; dims[6] = b.scalar("ntree");
-            make_layout(dims[0], dims[1], dims[2], dims[3], dims[4], dims[5], dims[6]);
+            make_layout();
             d_qpos_home = up(b.f("qpos_home"));
             d_ctrl_home = up(b.f("ctrl_home"));
             d_obj_qadr = up(b.i("objects_qposadr"));
@@ -4084,7 +4124,7 @@ struct PhysHost {
             (void)hipDeviceSynchronize();
             if (n == "maxefc") maxefc = maxefc1 = x; else if (n == "maxcon") maxcon = maxcon1 = x;
             else if (n == "maxefc_first") maxefc1 = x < maxefc ? x : maxefc; else maxcon1 = x < maxcon ? x : maxcon;
-            make_layout(dims[0], dims[1], dims[2], dims[3], dims[4], dims[5], dims[6]);
+            make_layout();
             alloc_contacts();           // a failed hipMalloc throws: avsim_set_option reports it as AVSIM_EHIP, not as an unknown option
             return true;
         }
@@ -4160,14 +4200,20 @@ struct PhysHost {
             KArgs<real> ka{m, lay, moff}, ka2{m, lay2, moff};
             if (kargs.reserve(sizeof(KArgs<double>)) != hipSuccess || kargs2.reserve(sizeof(KArgs<double>)) != hipSuccess) { err = "hipMalloc(kernel arguments) failed"; return -3; }
             (void)hipStreamSynchronize(st);
-            if (hipMemcpy(kargs.ptr(), &ka, sizeof(ka), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(kargs2.ptr(), &ka2, sizeof(ka2), hipMemcpyHostToDevice) != hipSuccess) { err = "hipMemcpy(kernel arguments) failed"; return -3; }
+            if (hipMemcpy(kargs.ptr(), &ka, sizeof(ka), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(kargs2.ptr(), &ka2, sizeof(ka2), hipMemcpyHostToDevice) != hipSuccess) {
+                err = "hipMemcpy(kernel arguments) failed";
+                return -3;
+            }
             kargs_dirty = false;
         }
         // (checked BEFORE anything is enqueued: set_option admits 16 .. 1000, so this cannot fire through the API)
         // the second pass gets the first tier's capacities in two 10-bit fields of retry_mode, above the three mode bits and the pairing bit
         static_assert((16 | 8 | 7) < (1 << 8), "retry_mode: mode bits, pairing flag and the rows_paired = 0 flag below bit 8");
         const int single = rows_paired ? 0 : 16;
-        if (two && (maxcon1 >= 1024 || maxefc1 >= 1024 || maxcon1 < 0 || maxefc1 < 0)) { err = "first-tier capacities do not fit the 10-bit fields of retry_mode (maxcon_first / maxefc_first < 1024)"; return -1; }
+        if (two && (maxcon1 >= 1024 || maxefc1 >= 1024 || maxcon1 < 0 || maxefc1 < 0)) {
+            err = "first-tier capacities do not fit the 10-bit fields of retry_mode (maxcon_first / maxefc_first < 1024)";
+            return -1;
+        }
         // launch order from the previous step's per-env cost
         const int* order = nullptr;
         if (order_envs && have_cost && nsub > 0 && N > wpb) {
@@ -4177,28 +4223,25 @@ struct PhysHost {
         const int want_reward = (reward || success) && (nsub > 0 || force_reward) ? 1 : 0;
         const int par = (int)(retry_parity & 1);      // which of the two list counters this step uses (its second pass zeroes the other)
         int* const rlist = d_retry + 2;
-        {
+        // one pass: what the two passes of a launch do not share.  Each takes its envs from one of the two work counters and zeroes the other.
+        auto pass = [&](decltype(kern1) kern, int blocks, int waves, size_t lds, const DevBuf& ka, const int* env_list, int retry_mode) {
             int* head = this->head.as<int>() + (launch_count & 1);
             int* next = this->head.as<int>() + ((launch_count + 1) & 1);
             launch_count++;
-            hipLaunchKernelGGL(two ? kern2 : kern1, dim3(nblk), dim3(64 * wpb), shmem, st, (KPtr<real>)kargs.ptr(), (const real*)d_img_real, (const int*)d_img_int, N, nsub, pgs_iters, action, want_reward,
-                               (real*)qpos, (real*)qvel, (real*)ctrl, (real*)warm, latch, agent, (int*)reward, (unsigned char*)success, d_ncon,
-                               cpairs.as<int>(), cdist.as<double>(), d_diag, max_reward, export_contacts, d_prof, d_xpose, order, order_envs ? d_cost : (int*)nullptr, head, next,
-                               d_retry, (two ? (1 + 2 * par) | pairing : 0) | single, (KPtr<real>)kargs2.ptr());
-        }
+            hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * waves), lds, st, (KPtr<real>)ka.ptr(), (const real*)d_img_real, (const int*)d_img_int, N, nsub, pgs_iters,
+                               action, want_reward, (real*)qpos, (real*)qvel, (real*)ctrl, (real*)warm, latch, agent, (int*)reward, (unsigned char*)success, d_ncon,
+                               cpairs.as<int>(), cdist.as<double>(), d_diag, max_reward, export_contacts, d_prof, d_xpose, env_list,
+                               order_envs ? d_cost : (int*)nullptr, head, next, d_retry, retry_mode, (KPtr<real>)kargs2.ptr());
+        };
+        pass(two ? kern2 : kern1, nblk, wpb, shmem, kargs, order, (two ? (1 + 2 * par) | pairing : 0) | single);
         if (two) {
             // second pass: the envs the first one gave up on, with the full capacities; one workgroup per CU is plenty for the few there
             // are (the workgroups loop over the list), and a launch that finds the list empty returns at once
-            int* head = this->head.as<int>() + (launch_count & 1);
-            int* next = this->head.as<int>() + ((launch_count + 1) & 1);
-            launch_count++;
             retry_parity++;
             int nblk2 = num_cu;
             if (nblk2 > (N + wpb2 - 1) / wpb2) nblk2 = (N + wpb2 - 1) / wpb2;
-            hipLaunchKernelGGL(kern2, dim3(nblk2), dim3(64 * wpb2), shmem2, st, (KPtr<real>)kargs2.ptr(), (const real*)d_img_real, (const int*)d_img_int, N, nsub, pgs_iters, action, want_reward,
-                               (real*)qpos, (real*)qvel, (real*)ctrl, (real*)warm, latch, agent, (int*)reward, (unsigned char*)success, d_ncon,
-                               cpairs.as<int>(), cdist.as<double>(), d_diag, max_reward, export_contacts, d_prof, d_xpose, (const int*)rlist, order_envs ? d_cost : (int*)nullptr, head, next,
-                               d_retry, (2 + 2 * par) | single | (maxcon1 << 8) | (maxefc1 << 18), (KPtr<real>)kargs2.ptr());      // (+ the FIRST tier's capacities: what "needed the full record" is measured against)
+            // (+ the FIRST tier's capacities: what "needed the full record" is measured against)
+            pass(kern2, nblk2, wpb2, shmem2, kargs2, rlist, (2 + 2 * par) | single | (maxcon1 << 8) | (maxefc1 << 18));
         }
         if (nsub > 0) have_cost = true;
         hipError_t e = hipGetLastError();
@@ -4207,9 +4250,8 @@ struct PhysHost {
     }
 
 #if !defined(AVSIM_TU_F64) && !defined(AVSIM_NO_F32_LAUNCH)      // (a unit that defines the latter does not instantiate the generic f32 kernels)
-    int launch(hipStream_t st, int N_, int nsub, const float* action, int nj, void* qpos, void* qvel, void* ctrl, void* warm, int* latch,
+    int launch(hipStream_t st, int nsub, const float* action, void* qpos, void* qvel, void* ctrl, void* warm, int* latch,
                double* agent, int32_t* reward, uint8_t* success, std::string& err) {
-        (void)N_; (void)nj;
         // the double-precision kernel lives in its own translation unit (avsim_phys_f64.hip), compiled without FMA contraction
         if (f64) return phys_launch_f64(*this, st, nsub, action, qpos, qvel, ctrl, warm, latch, agent, reward, success, err);
         // as many envs (wavefronts) per block as fit next to one copy of the tables in 160 KiB, at most 8 (two per SIMD).

@@ -10,60 +10,27 @@ constexpr int RS_S = 9;            // solver record: 8 words used
 constexpr int ANC_MAX = 64;        // LDS ints of the kinematics' pointer-jumping table (one per body)
 constexpr int NARROW_SCR_W = 64 * 24 + 4 * 56;   // narrow phase: 64 result slots (SLOT_W words each) + 4 box work areas
 
+// The table image: the hot model tables that every block copies into LDS, ints and reals apart.  These two lists ARE the image, in image
+// order: MOff, Env's accessors X_() (avsim_phys.hip.h) and PhysHost::build's check that every table was filled come from them.  A new
+// table is one entry here and one fill line in PhysHost::build (plus its pointer in DevModelT).
+#define AVSIM_IMG_INT_TABLES(X) \
+    X(body_parent) X(body_jntadr) X(body_jntnum) X(body_dofadr) X(body_dofnum) X(body_tree) X(body_dofmask) X(body_last) \
+    X(tree_bodyadr) X(tree_bodylist) X(tree_dofadr) X(tree_dofnum) X(tree_madr) X(jnt_type) X(jnt_qposadr) X(jnt_dofadr) \
+    X(jnt_actfrclimited) X(limited_jnt) X(dof_body) X(dof_parent) X(dof_tree) X(dof_jnt) X(floss_dof) X(ment_i) X(ment_j) \
+    X(act_dof) X(act_qposadr) X(act_ctrllimited) X(geom_type) X(geom_body) X(geom_static)
+#define AVSIM_IMG_REAL_TABLES(X) \
+    X(body_pos) X(body_quat) X(body_mass) X(body_ipos) X(body_inertia) X(body_invweight0) X(jnt_pos) X(jnt_axis) X(jnt_range) \
+    X(jnt_actfrcrange) X(jnt_margin) X(dof_armature) X(dof_damping) X(dof_frictionloss) X(dof_invweight0) X(act_kp) X(act_kv) \
+    X(act_gear) X(act_ctrlrange) X(geom_cpos) X(geom_rbound)
+
+// where each table starts in its half of the image (in words of that half; -1: not filled -- PhysHost::build refuses to leave one so);
+// nreal / nint: the halves' sizes, multiples of four
 struct MOff {
-    int nreal, nint;
-    int body_parent;
-    int body_jntadr;
-    int body_jntnum;
-    int body_dofadr;
-    int body_dofnum;
-    int body_tree;
-    int body_dofmask;
-    int body_last;
-    int tree_bodyadr;
-    int tree_bodylist;
-    int tree_dofadr;
-    int tree_dofnum;
-    int tree_madr;
-    int jnt_type;
-    int jnt_qposadr;
-    int jnt_dofadr;
-    int jnt_actfrclimited;
-    int limited_jnt;
-    int dof_body;
-    int dof_parent;
-    int dof_tree;
-    int dof_jnt;
-    int floss_dof;
-    int ment_i;
-    int ment_j;
-    int act_dof;
-    int act_qposadr;
-    int act_ctrllimited;
-    int geom_type;
-    int geom_body;
-    int geom_static;
-    int body_pos;
-    int body_quat;
-    int body_mass;
-    int body_ipos;
-    int body_inertia;
-    int body_invweight0;
-    int jnt_pos;
-    int jnt_axis;
-    int jnt_range;
-    int jnt_actfrcrange;
-    int jnt_margin;
-    int dof_armature;
-    int dof_damping;
-    int dof_frictionloss;
-    int dof_invweight0;
-    int act_kp;
-    int act_kv;
-    int act_gear;
-    int act_ctrlrange;
-    int geom_cpos;
-    int geom_rbound;
+    int nreal = 0, nint = 0;
+#define AVSIM_MOFF_MEMBER(x) int x = -1;
+    AVSIM_IMG_INT_TABLES(AVSIM_MOFF_MEMBER)
+    AVSIM_IMG_REAL_TABLES(AVSIM_MOFF_MEMBER)
+#undef AVSIM_MOFF_MEMBER
 };
 constexpr int MOFF_WORDS = sizeof(MOff) / sizeof(int);
 
