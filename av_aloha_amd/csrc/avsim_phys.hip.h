@@ -26,6 +26,7 @@
 #include "avsim_math.hip.h"
 #include "avsim_model.h"
 #include "avsim_phys_layout.h"
+#include "avsim_qcqp.hip.h"
 
 namespace avs {
 
@@ -377,17 +378,6 @@ constexpr int GRP_MAX = 6;   // rows per Gauss-Seidel group (a condim-6 contact 
 // inverse of its friction block for the noslip pass, transposed (entry k of row r at word 16 + 8 k + r, so that row r's lane fetches
 // six separate words), and the rows' singular flags at words 56 ..
 constexpr int GA_W = 64, GA_Q = 16, GA_QW = 6;   // group record: 15 couplings, then the noslip block transposed: word 8 k + r = entry k of row r
-// convergence thresholds of the multiplier iteration in the noslip QCQP: MuJoCo's absolute 1e-10 in double; in float a relative
-// part on top, since v.v - r^2 and the multiplier carry 1e-7 relative rounding
-// t / d with 1 / d at hand.  The product kernel (float) multiplies: a division there is ten instructions (range scaling around
-// v_rcp_f32), and the multiplier iteration of the noslip QCQP is thirty divisions per step.  The parity kernel (double) divides, as
-// the oracle does.
-template <typename T> AVS_DEV T qdiv(T t, T d, T dinv) { return sizeof(T) == 4 ? t * dinv : t / d; }
-AVS_DEV float qrsqrt(float x) { return __builtin_amdgcn_rsqf(x); }
-AVS_DEV double qrsqrt(double x) { return 1.0 / sqrt(x); }
-template <typename T> struct QTol;
-template <> struct QTol<double> { static constexpr double abs = 1e-10, rel = 0.0; };
-template <> struct QTol<float> { static constexpr float abs = 1e-10f, rel = 2e-6f; };
 
 // ------------------------------------------------------------------------------------------------
 // P8 inner loop, one env per wavefront: projected Gauss-Seidel over GROUPS of up to 6 consecutive rows.
@@ -403,7 +393,6 @@ template <> struct QTol<float> { static constexpr float abs = 1e-10f, rel = 2e-6
 // rowI[i] = two 13-bit dof windows of row i: first dof (6) | count (4) | kinematic tree (3).
 // B = J M^-1 is read from the global row scratch next to J (written by the row's lane in make_constraints).
 // ------------------------------------------------------------------------------------------------
-template <bool B> struct BoolTag { static constexpr bool value = B; };
 template <int I> struct IntTag { static constexpr int value = I; };
 
 // The dry-friction rows of a noslip sweep, all kinematic trees at once (see pgs_groups)
@@ -448,17 +437,6 @@ template <typename T> AVS_DEV GLB_PTR(T) uni_glb(GLB_PTR(T) p) { return glb_unif
 template <typename T> AVS_DEV GArr<T> garr(GLB_PTR(T) p) { return GArr<T>(p); }      // (a base the compiler already has in SGPRs)
 // a model table in global memory: a pointer member of ka->m, scalar-loaded through the (laundered) ka
 #define TAB(name) garr(ka->m.name)
-
-// Step of the multiplier iteration of a sliding contact's QCQP, |y(la)| = r with y = -(A + la I)^-1 b.  MuJoCo's mju_QCQP takes
-// Newton steps on |y|^2 - r^2 from la = 0 (val / (2 y.w), w = (A + la I)^-1 y); that function is strongly convex in la and the
-// iteration needs about nine steps on a dragging arm.  1 / |y(la)| is nearly linear in la (the trust-region secular equation, More
-// and Sorensen 1983), so Newton on 1 / r - 1 / |y| reaches the SAME root in two to four steps, also monotonically from the left:
-// delta = (|y| - r) / r * |y|^2 / (y.w), with |y| - r taken as val / (|y| + r).  Product mode (f32, option qcqp_tridiag = 2); the
-// f64 parity kernel keeps MuJoCo's steps.
-template <typename T> AVS_DEV T secular_step(T val, T r2, T r, T yw) {
-    const T yy = val + r2, ny = sqrt(yy);
-    return val * yy / ((ny + r) * r * yw);
-}
 
 template <typename real>
 __device__ AVS_OUTLINE_2 void pgs_groups(LDS_PTR(real) rowS, LDS_PTR(const int) rowI, GLB_PTR(const real) rJ, GLB_PTR(const real) rB,
@@ -662,227 +640,25 @@ __device__ AVS_OUTLINE_2 void pgs_groups(LDS_PTR(real) rowS, LDS_PTR(const int) 
                 real acs[GRP_MAX - 1];      // this group's couplings, fetched here: the sliding case pays the memory round trip, not every step
 #pragma unroll
                 for (int s = 0; s < GRP_MAX - 1; s++) acs[s] = gA[GA_W * g + tri + s];
-                real Aq[5][5], bq[5], dq[5], oldf[5], resq[5], v[5];
-#pragma unroll
-                for (int j = 0; j < 5; j++) {
-                    const bool in = j < n;
-                    resq[j] = in ? lane_get(dot - aref, j + 1) : real(0);
-                    oldf[j] = in ? lane_get(f0, j + 1) : real(0);
-                    const real mi = lane_get(muinv, j + 1);
-                    dq[j] = in ? real(1) / mi : real(1);
-                    const real di = lane_get(inv3, j + 1);
-                    Aq[j][j] = in ? real(1) / di : real(1);
-#pragma unroll
-                    for (int k = 0; k < j; k++) { const real c = in ? lane_get(acs[k + 1], j + 1) : real(0); Aq[j][k] = c; Aq[k][j] = c; }
-                }
-#pragma unroll
-                for (int j = 0; j < 5; j++) {
-                    real t = resq[j];
-#pragma unroll
-                    for (int k = 0; k < 5; k++) t -= (j < n && k < n) ? Aq[j][k] * oldf[k] : real(0);
-                    bq[j] = t;
-                    v[j] = 0;
-                }
+                real Aq[5][5], bq[5], dq[5], oldf[5], resq[5], v[5] = {0, 0, 0, 0, 0};
+                qcqp_gather([](real x, int l) { return lane_get(x, l); }, n, dot - aref, f0, muinv, inv3, acs, Aq, bq, dq, oldf, resq);
                 if (prof) { asm volatile("" :: "v"(bq[0]), "v"(bq[1]), "v"(bq[2]), "v"(bq[3]), "v"(bq[4])); tsl1 = __builtin_readcyclecounter(); }
                 if (!(fn < real(1e-15))) {
-                    const real r2 = fn * fn, vtol = QTol<real>::abs + QTol<real>::rel * r2;
-                    real la = 0;
-                    bool active;
-                    if (n == 2) {
-                        const real b1 = bq[0] * dq[0], b2 = bq[1] * dq[1];
-                        const real A11 = Aq[0][0] * dq[0] * dq[0], A22 = Aq[1][1] * dq[1] * dq[1], A12 = Aq[1][0] * dq[0] * dq[1];
-                        real v1 = 0, v2 = 0;
-                        bool singular = false;
-                        for (int iter = 0; iter < 20; iter++) {
-                            const real det = (A11 + la) * (A22 + la) - A12 * A12;
-                            if (det < real(1e-10)) { singular = true; break; }
-                            const real detinv = real(1) / det, P11 = (A22 + la) * detinv, P22 = (A11 + la) * detinv, P12 = -A12 * detinv;
-                            v1 = -P11 * b1 - P12 * b2;
-                            v2 = -P12 * b1 - P22 * b2;
-                            const real val = v1 * v1 + v2 * v2 - r2;
-                            if (val < vtol) break;
-                            const real yw = P11 * v1 * v1 + 2 * P12 * v1 * v2 + P22 * v2 * v2;
-                            const real delta = nl.tridiag == 2 ? secular_step(val, r2, fn, yw) : val / (2 * yw);
-                            if (delta < QTol<real>::abs + QTol<real>::rel * la) break;
-                            la += delta;
-                        }
-                        v[0] = singular ? real(0) : v1 * dq[0];
-                        v[1] = singular ? real(0) : v2 * dq[1];
-                        active = !singular && la != 0;
-                    } else {
-                        real y[5];
-                        bool singular = false;
+                    if (n == 2) qcqp2(Aq[0][0], Aq[1][0], Aq[1][1], bq[0], bq[1], dq[0], dq[1], fn, nl.tridiag, v[0], v[1]);
+                    else {
+                        real y[5], la = 0;
+                        bool singular;
                         if (nl.tridiag) {
-                            // mju_QCQP's Newton iteration on the multiplier needs y = -(As + la I)^-1 bs and (As + la I)^-1 y for a dozen
-                            // values of la.  MuJoCo factors As + la I afresh every time (a 5 x 5 Cholesky: a chain of ~150 dependent
-                            // instructions, 1.2 k cycles, redundantly on every lane).  Here As is reduced once to tridiagonal form by
-                            // three Householder reflections, As = H T H^T; (As + la I)^-1 = H (T + la I)^-1 H^T, |y| and y . w are the
-                            // same in the rotated basis, and T + la I is factored by the four-step LDL^T recurrence: the same iterates
-                            // up to rounding, a quarter of the instructions per iterate.  Singularity is MuJoCo's pivot rule at la = 0
-                            // (the flag make_constraints left with the block's inverse; the pivots only grow with la).
-                            real As[5][5], cs[5], w[5], hv[3][5], hb[3];
-#pragma unroll
-                            for (int j = 0; j < 5; j++) {
-                                cs[j] = j < n ? bq[j] * dq[j] : real(0);
-                                y[j] = 0;
-#pragma unroll
-                                for (int k = 0; k < 5; k++) As[j][k] = (j < n && k < n) ? Aq[j][k] * dq[j] * dq[k] : (j == k ? real(1) : real(0));
-                            }
                             singular = lane_get(qc[5], 1) != real(0);
-                            if (!singular) {
-#pragma unroll
-                                for (int k = 0; k < 3; k++) {
-                                    real sigma = 0;
-#pragma unroll
-                                    for (int i = k + 2; i < 5; i++) sigma += As[i][k] * As[i][k];
-                                    const real x0 = As[k + 1][k];
-#pragma unroll
-                                    for (int i = 0; i < 5; i++) hv[k][i] = 0;
-                                    hb[k] = 0;
-                                    if (sigma != real(0)) {       // (wave-uniform: the column is tridiagonal already otherwise)
-                                        const real nrm = sqrt(x0 * x0 + sigma), alpha = x0 > 0 ? -nrm : nrm;
-                                        hv[k][k + 1] = x0 - alpha;
-#pragma unroll
-                                        for (int i = k + 2; i < 5; i++) hv[k][i] = As[i][k];
-                                        const real beta = real(2) / (hv[k][k + 1] * hv[k][k + 1] + sigma);
-                                        hb[k] = beta;
-                                        real pv[5], vp = 0;
-#pragma unroll
-                                        for (int i = k + 1; i < 5; i++) {
-                                            real t = 0;
-#pragma unroll
-                                            for (int j = k + 1; j < 5; j++) t += As[i][j] * hv[k][j];
-                                            pv[i] = beta * t;
-                                            vp += hv[k][i] * pv[i];
-                                        }
-                                        const real K = real(0.5) * beta * vp;
-#pragma unroll
-                                        for (int i = k + 1; i < 5; i++) pv[i] -= K * hv[k][i];
-#pragma unroll
-                                        for (int i = k + 1; i < 5; i++)
-#pragma unroll
-                                            for (int j = k + 1; j <= i; j++) { As[i][j] -= hv[k][i] * pv[j] + pv[i] * hv[k][j]; As[j][i] = As[i][j]; }
-                                        As[k + 1][k] = alpha; As[k][k + 1] = alpha;
-#pragma unroll
-                                        for (int i = k + 2; i < 5; i++) { As[i][k] = 0; As[k][i] = 0; }
-                                        // right-hand side into the rotated basis
-                                        real t = 0;
-#pragma unroll
-                                        for (int i = k + 1; i < 5; i++) t += hv[k][i] * cs[i];
-                                        t *= beta;
-#pragma unroll
-                                        for (int i = k + 1; i < 5; i++) cs[i] -= t * hv[k][i];
-                                    }
-                                }
-                                const real b0 = As[1][0], b1 = As[2][1], b2 = As[3][2], b3 = As[4][3];
-                                for (int iter = 0; iter < 20; iter++) {
-                                    nit_q++;
-                                    // LDL^T of T + la I (la on the contact's own dimensions only, as in mju_QCQP's padded loops)
-                                    const real d0 = As[0][0] + la, r0 = real(1) / d0, l0 = b0 * r0;
-                                    const real d1 = As[1][1] + la - l0 * b0, r1 = real(1) / d1, l1 = b1 * r1;
-                                    const real d2 = As[2][2] + la - l1 * b1, r2_ = real(1) / d2, l2 = b2 * r2_;
-                                    const real d3 = As[3][3] + (3 < n ? la : real(0)) - l2 * b2, r3 = real(1) / d3, l3 = b3 * r3;
-                                    const real d4 = As[4][4] + (4 < n ? la : real(0)) - l3 * b3, r4 = real(1) / d4;
-                                    real z0 = -cs[0], z1 = -cs[1] - l0 * z0, z2 = -cs[2] - l1 * z1, z3 = -cs[3] - l2 * z2, z4 = -cs[4] - l3 * z3;
-                                    y[4] = z4 * r4; y[3] = z3 * r3 - l3 * y[4]; y[2] = z2 * r2_ - l2 * y[3]; y[1] = z1 * r1 - l1 * y[2]; y[0] = z0 * r0 - l0 * y[1];
-                                    real val = -r2;
-#pragma unroll
-                                    for (int i = 0; i < 5; i++) val += y[i] * y[i];
-                                    if (val < vtol) break;
-                                    z0 = y[0]; z1 = y[1] - l0 * z0; z2 = y[2] - l1 * z1; z3 = y[3] - l2 * z2; z4 = y[4] - l3 * z3;
-                                    w[4] = z4 * r4; w[3] = z3 * r3 - l3 * w[4]; w[2] = z2 * r2_ - l2 * w[3]; w[1] = z1 * r1 - l1 * w[2]; w[0] = z0 * r0 - l0 * w[1];
-                                    real yw = 0;
-#pragma unroll
-                                    for (int i = 0; i < 5; i++) yw += y[i] * w[i];
-                                    const real delta = nl.tridiag == 2 ? secular_step(val, r2, fn, yw) : val / (2 * yw);
-                                    if (delta < QTol<real>::abs + QTol<real>::rel * la) break;
-                                    la += delta;
-                                }
-                                // back to the contact's basis: y <- H y
-#pragma unroll
-                                for (int k = 2; k >= 0; k--) {
-                                    real t = 0;
-#pragma unroll
-                                    for (int i = k + 1; i < 5; i++) t += hv[k][i] * y[i];
-                                    t *= hb[k];
-#pragma unroll
-                                    for (int i = k + 1; i < 5; i++) y[i] -= t * hv[k][i];
-                                }
-                            }
-                        } else {
-                            // MuJoCo's own evaluation (the f64 parity mode's default: the oracle's arithmetic, operation for operation)
-                            real As[5][5], bs[5], L[5][5], w[5], rd[5];
-#pragma unroll
-                            for (int j = 0; j < 5; j++) {
-                                bs[j] = j < n ? bq[j] * dq[j] : real(0);
-                                y[j] = 0;
-#pragma unroll
-                                for (int k = 0; k < 5; k++) As[j][k] = (j < n && k < n) ? Aq[j][k] * dq[j] * dq[k] : (j == k ? real(1) : real(0));
-                            }
-                            for (int iter = 0; iter < 20; iter++) {
-                                nit_q++;
-#pragma unroll
-                                for (int j = 0; j < 5; j++) {
-                                    real dd = As[j][j] + (j < n ? la : real(0));
-#pragma unroll
-                                    for (int k = 0; k < j; k++) dd -= L[j][k] * L[j][k];
-                                    if (j < n && dd < real(1e-10)) singular = true;
-                                    dd = tmax(dd, real(1e-30));
-                                    if (sizeof(real) == 4) { rd[j] = qrsqrt(dd); dd = dd * rd[j]; }
-                                    else { dd = sqrt(dd); rd[j] = real(1) / dd; }
-                                    L[j][j] = dd;
-#pragma unroll
-                                    for (int i = j + 1; i < 5; i++) {
-                                        real t = As[i][j];
-#pragma unroll
-                                        for (int k = 0; k < j; k++) t -= L[i][k] * L[j][k];
-                                        L[i][j] = qdiv(t, dd, rd[j]);
-                                    }
-                                }
-                                if (singular) break;
-#pragma unroll
-                                for (int i = 0; i < 5; i++) { real t = -bs[i]; for (int k = 0; k < i; k++) t -= L[i][k] * y[k]; y[i] = qdiv(t, L[i][i], rd[i]); }
-#pragma unroll
-                                for (int i = 4; i >= 0; i--) { real t = y[i]; for (int k = i + 1; k < 5; k++) t -= L[k][i] * y[k]; y[i] = qdiv(t, L[i][i], rd[i]); }
-                                real val = -r2;
-#pragma unroll
-                                for (int i = 0; i < 5; i++) val += y[i] * y[i];
-                                if (val < vtol) break;
-#pragma unroll
-                                for (int i = 0; i < 5; i++) { real t = y[i]; for (int k = 0; k < i; k++) t -= L[i][k] * w[k]; w[i] = qdiv(t, L[i][i], rd[i]); }
-#pragma unroll
-                                for (int i = 4; i >= 0; i--) { real t = w[i]; for (int k = i + 1; k < 5; k++) t -= L[k][i] * w[k]; w[i] = qdiv(t, L[i][i], rd[i]); }
-                                real deriv = 0;
-#pragma unroll
-                                for (int i = 0; i < 5; i++) deriv += y[i] * w[i];
-                                deriv *= -2;
-                                const real delta = -val / deriv;
-                                if (delta < QTol<real>::abs + QTol<real>::rel * la) break;
-                                la += delta;
-                            }
-                        }
+                            qcqp5_tridiag(Aq, bq, dq, n, fn, nl.tridiag, singular, y, la, nit_q);
+                        } else singular = qcqp5_cholesky(Aq, bq, dq, n, fn, y, la, nit_q);
 #pragma unroll
                         for (int j = 0; j < 5; j++) v[j] = (singular || !(j < n)) ? real(0) : y[j] * dq[j];
-                        active = !singular && la != 0;
-                    }
-                    if (active) {       // exactly onto the ellipsoid
-                        real sq = 0;
-#pragma unroll
-                        for (int j = 0; j < 5; j++) sq += j < n ? v[j] * v[j] / (dq[j] * dq[j]) : real(0);
-                        const real sc = sqrt(r2 / tmax(real(1e-15), sq));
-#pragma unroll
-                        for (int j = 0; j < 5; j++) v[j] *= sc;
+                        if (!singular && la != 0) qcqp_onto_ellipsoid(v, dq, n, fn * fn);
                     }
                 }
-                // change of the cost [EXT: costChange]; an update that would raise it by more than 1e-10 is not made
-                real change = 0;
-#pragma unroll
-                for (int j = 0; j < 5; j++) {
-                    real t = 0;
-#pragma unroll
-                    for (int k = 0; k < 5; k++) t += (j < n && k < n) ? Aq[j][k] * (v[k] - oldf[k]) : real(0);
-                    change += j < n ? (v[j] - oldf[j]) * (real(0.5) * t + resq[j]) : real(0);
-                }
+                // an update that would raise the cost by more than 1e-10 is not made
+                const real change = qcqp_cost_change(Aq, v, oldf, resq, n);
                 if (!(change > real(1e-10))) {
                     imp_c -= change;
 #pragma unroll
@@ -966,146 +742,24 @@ __device__ AVS_OUTLINE_2 void pgs_groups(LDS_PTR(real) rowS, LDS_PTR(const int) 
 
 
 // The friction block of a SLIDING contact in noslip_trees: mju_QCQP's multiplier iteration on the Householder-tridiagonal form of the
-// scaled block, as in pgs_groups (same operations in the same order), the block gathered by octet broadcasts instead of wave-wide
+// scaled block, pgs_groups' own (qcqp5_tridiag and the helpers around it), the block gathered by octet broadcasts instead of wave-wide
 // ones; redundantly on the eight lanes of the octet.  Returns the new force of this lane's row (lanes 1..n), *change = the cost change.
 template <typename real>
 __device__ AVS_OUTLINE_3 real qcqp_slide_octet(GLB_PTR(const real) gA, int g, int n, int fi, real res_r, real f0, real muinv, real invn, real qc5, real fn,
                                                           int tridiag, real* change_out) {
-    struct { int tridiag; } nl{tridiag};
-    struct { real f0, muinv, invn; real qc[GA_QW]; int g; } cur;
-    cur.f0 = f0; cur.muinv = muinv; cur.invn = invn; cur.qc[5] = qc5; cur.g = g;
-    const real r2 = fn * fn;
     const int tri = fi <= 5 ? fi * (fi - 1) / 2 : 0;
     real acs[GRP_MAX - 1];
 #pragma unroll
-    for (int k = 0; k < GRP_MAX - 1; k++) acs[k] = gA[GA_W * cur.g + tri + k];
-    real Aq[5][5], bq[5], dq[5], oldf[5], resq[5], v[5];
-#pragma unroll
-    for (int j = 0; j < 5; j++) {
-        const bool in = j < n;
-        resq[j] = in ? oct_bcast_n(res_r, j + 1) : real(0);
-        oldf[j] = in ? oct_bcast_n(cur.f0, j + 1) : real(0);
-        const real mi = oct_bcast_n(cur.muinv, j + 1);
-        dq[j] = in ? real(1) / mi : real(1);
-        const real di = oct_bcast_n(cur.invn, j + 1);
-        Aq[j][j] = in ? real(1) / di : real(1);
-#pragma unroll
-        for (int k = 0; k < j; k++) { const real c = in ? oct_bcast_n(acs[k + 1], j + 1) : real(0); Aq[j][k] = c; Aq[k][j] = c; }
-    }
-#pragma unroll
-    for (int j = 0; j < 5; j++) {
-        real t = resq[j];
-#pragma unroll
-        for (int k = 0; k < 5; k++) t -= (j < n && k < n) ? Aq[j][k] * oldf[k] : real(0);
-        bq[j] = t;
-        v[j] = 0;
-    }
-    const real vtol = QTol<real>::abs + QTol<real>::rel * r2;
-    real la = 0, y[5];
-    bool singular = oct_bcast<1>(cur.qc[5]) != real(0);
-    real As[5][5], cs[5], w[5], hv[3][5], hb[3];
-#pragma unroll
-    for (int j = 0; j < 5; j++) {
-        cs[j] = j < n ? bq[j] * dq[j] : real(0);
-        y[j] = 0;
-#pragma unroll
-        for (int k = 0; k < 5; k++) As[j][k] = (j < n && k < n) ? Aq[j][k] * dq[j] * dq[k] : (j == k ? real(1) : real(0));
-    }
-    if (!singular) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            real sigma = 0;
-#pragma unroll
-            for (int i = k + 2; i < 5; i++) sigma += As[i][k] * As[i][k];
-            const real x0 = As[k + 1][k];
-#pragma unroll
-            for (int i = 0; i < 5; i++) hv[k][i] = 0;
-            hb[k] = 0;
-            if (sigma != real(0)) {
-                const real nrm = sqrt(x0 * x0 + sigma), alpha = x0 > 0 ? -nrm : nrm;
-                hv[k][k + 1] = x0 - alpha;
-#pragma unroll
-                for (int i = k + 2; i < 5; i++) hv[k][i] = As[i][k];
-                const real beta = real(2) / (hv[k][k + 1] * hv[k][k + 1] + sigma);
-                hb[k] = beta;
-                real pv[5], vp = 0;
-#pragma unroll
-                for (int i = k + 1; i < 5; i++) {
-                    real t = 0;
-#pragma unroll
-                    for (int j = k + 1; j < 5; j++) t += As[i][j] * hv[k][j];
-                    pv[i] = beta * t;
-                    vp += hv[k][i] * pv[i];
-                }
-                const real K = real(0.5) * beta * vp;
-#pragma unroll
-                for (int i = k + 1; i < 5; i++) pv[i] -= K * hv[k][i];
-#pragma unroll
-                for (int i = k + 1; i < 5; i++)
-#pragma unroll
-                    for (int j = k + 1; j <= i; j++) { As[i][j] -= hv[k][i] * pv[j] + pv[i] * hv[k][j]; As[j][i] = As[i][j]; }
-                As[k + 1][k] = alpha; As[k][k + 1] = alpha;
-#pragma unroll
-                for (int i = k + 2; i < 5; i++) { As[i][k] = 0; As[k][i] = 0; }
-                real t = 0;
-#pragma unroll
-                for (int i = k + 1; i < 5; i++) t += hv[k][i] * cs[i];
-                t *= beta;
-#pragma unroll
-                for (int i = k + 1; i < 5; i++) cs[i] -= t * hv[k][i];
-            }
-        }
-        const real b0 = As[1][0], b1 = As[2][1], b2 = As[3][2], b3 = As[4][3];
-        for (int iter = 0; iter < 20; iter++) {
-            const real d0 = As[0][0] + la, r0 = real(1) / d0, l0 = b0 * r0;
-            const real d1 = As[1][1] + la - l0 * b0, r1 = real(1) / d1, l1 = b1 * r1;
-            const real d2 = As[2][2] + la - l1 * b1, r2_ = real(1) / d2, l2 = b2 * r2_;
-            const real d3 = As[3][3] + (3 < n ? la : real(0)) - l2 * b2, r3 = real(1) / d3, l3 = b3 * r3;
-            const real d4 = As[4][4] + (4 < n ? la : real(0)) - l3 * b3, r4 = real(1) / d4;
-            real z0 = -cs[0], z1 = -cs[1] - l0 * z0, z2 = -cs[2] - l1 * z1, z3 = -cs[3] - l2 * z2, z4 = -cs[4] - l3 * z3;
-            y[4] = z4 * r4; y[3] = z3 * r3 - l3 * y[4]; y[2] = z2 * r2_ - l2 * y[3]; y[1] = z1 * r1 - l1 * y[2]; y[0] = z0 * r0 - l0 * y[1];
-            real val = -r2;
-#pragma unroll
-            for (int i = 0; i < 5; i++) val += y[i] * y[i];
-            if (val < vtol) break;
-            z0 = y[0]; z1 = y[1] - l0 * z0; z2 = y[2] - l1 * z1; z3 = y[3] - l2 * z2; z4 = y[4] - l3 * z3;
-            w[4] = z4 * r4; w[3] = z3 * r3 - l3 * w[4]; w[2] = z2 * r2_ - l2 * w[3]; w[1] = z1 * r1 - l1 * w[2]; w[0] = z0 * r0 - l0 * w[1];
-            real yw = 0;
-#pragma unroll
-            for (int i = 0; i < 5; i++) yw += y[i] * w[i];
-            const real delta = nl.tridiag == 2 ? secular_step(val, r2, fn, yw) : val / (2 * yw);
-            if (delta < QTol<real>::abs + QTol<real>::rel * la) break;
-            la += delta;
-        }
-#pragma unroll
-        for (int k = 2; k >= 0; k--) {
-            real t = 0;
-#pragma unroll
-            for (int i = k + 1; i < 5; i++) t += hv[k][i] * y[i];
-            t *= hb[k];
-#pragma unroll
-            for (int i = k + 1; i < 5; i++) y[i] -= t * hv[k][i];
-        }
-    }
+    for (int k = 0; k < GRP_MAX - 1; k++) acs[k] = gA[GA_W * g + tri + k];
+    real Aq[5][5], bq[5], dq[5], oldf[5], resq[5], v[5], y[5], la = 0;
+    qcqp_gather([](real x, int l) { return oct_bcast_n(x, l); }, n, res_r, f0, muinv, invn, acs, Aq, bq, dq, oldf, resq);
+    const bool singular = oct_bcast<1>(qc5) != real(0);
+    int nit = 0;
+    qcqp5_tridiag(Aq, bq, dq, n, fn, tridiag, singular, y, la, nit);
 #pragma unroll
     for (int j = 0; j < 5; j++) v[j] = (singular || !(j < n)) ? real(0) : y[j] * dq[j];
-    if (!singular && la != 0) {       // exactly onto the ellipsoid
-        real sq = 0;
-#pragma unroll
-        for (int j = 0; j < 5; j++) sq += j < n ? v[j] * v[j] / (dq[j] * dq[j]) : real(0);
-        const real sc = sqrt(r2 / tmax(real(1e-15), sq));
-#pragma unroll
-        for (int j = 0; j < 5; j++) v[j] *= sc;
-    }
-    real change = 0;
-#pragma unroll
-    for (int j = 0; j < 5; j++) {
-        real t = 0;
-#pragma unroll
-        for (int k = 0; k < 5; k++) t += (j < n && k < n) ? Aq[j][k] * (v[k] - oldf[k]) : real(0);
-        change += j < n ? (v[j] - oldf[j]) * (real(0.5) * t + resq[j]) : real(0);
-    }
-    *change_out = change;
+    if (!singular && la != 0) qcqp_onto_ellipsoid(v, dq, n, fn * fn);
+    *change_out = qcqp_cost_change(Aq, v, oldf, resq, n);
     real fv = 0;
 #pragma unroll
     for (int j = 0; j < 5; j++) if (fi == j + 1 && j < n) fv = v[j];
@@ -1133,248 +787,25 @@ __device__ AVS_OUTLINE_3 real qcqp_slide_octet(GLB_PTR(const real) gA, int g, in
 // then gives up -- it has written nothing but the rows' spare word -- and the caller runs pgs_groups from the untouched state.
 // Returns 1 when the pass is done, 0 for "use pgs_groups" (two-tree contact, more than 64 contacts, sliding contact, odd layout).
 // ------------------------------------------------------------------------------------------------
-template <typename real>
-__device__ AVS_OUTLINE_1 int noslip_trees(LDS_PTR(real) rowS, LDS_PTR(const int) rowI, LDS_PTR(const int) cefc, GLB_PTR(const real) rJ,
-                                                      LDS_PTR(real) q, LDS_PTR(const int) gI, GLB_PTR(const real) gA, int ncon, int nefc, int noslip_iters,
-                                                      real noslip_tol_scaled, NL_PARAMS) {
-    NL_UNPACK(real);
-    rowS = uni_lds(rowS); rowI = uni_lds(rowI); cefc = uni_lds(cefc); q = uni_lds(q); gI = uni_lds(gI);
-    rJ = uni_glb(rJ); gA = uni_glb(gA);
-    ncon = __builtin_amdgcn_readfirstlane(ncon); nefc = __builtin_amdgcn_readfirstlane(nefc); noslip_iters = __builtin_amdgcn_readfirstlane(noslip_iters);
-    noslip_tol_scaled = lane_get(noslip_tol_scaled, 0);
-    nl.Minv = uni_lds(nl.Minv); nl.tadr = uni_lds(nl.tadr); nl.tnum = uni_lds(nl.tnum); nl.floss_dof = uni_lds(nl.floss_dof); nl.dmap = uni_lds(nl.dmap);
-    nl.ntree = __builtin_amdgcn_readfirstlane(nl.ntree); nl.nv = __builtin_amdgcn_readfirstlane(nl.nv); nl.neq = __builtin_amdgcn_readfirstlane(nl.neq);
-    nl.nfloss = __builtin_amdgcn_readfirstlane(nl.nfloss); nl.nlg = __builtin_amdgcn_readfirstlane(nl.nlg); nl.tridiag = __builtin_amdgcn_readfirstlane(nl.tridiag);
-    const int lane = threadIdx.x & 63, ft = lane >> 3, fi = lane & 7;
-    if (noslip_iters <= 0 || nl.nlg < 0 || ncon <= 0 || ncon > 64) return 0;
-    // ---- the contacts' trees; every contact must have its rows, one tree, and the group pgs_groups would give it ----
-    // (a contact without rows -- the reward-only pins of the needle and of the hook -- is in no chain and has no group: the groups
-    // count the contacts WITH rows)
-    int ctree = -1;
-    bool bad = false, two_ = false;
-    const int ce_l = lane < ncon ? cefc[lane] : -1;
-    const unsigned long long hasrows = __ballot(ce_l >= 0);
-    const int g_lane = nl.nlg + __popcll(hasrows & ((1ull << lane) - 1ull));      // the group of this lane's contact
-    if (ce_l >= 0) {
-        const int ce = ce_l, g = g_lane;
-        const int h = ce & 0xffff, ra = rowI[h];
-        ctree = (ra >> 10) & 7;
-        two_ = ((ra >> 19) & 15) != 0;
-        bad = two_ || ctree >= nl.ntree || (gI[g] & 0xffff) != h || ((gI[g] >> 16) & 15) != (ce >> 16) || (ce >> 16) > GRP_MAX || (ce >> 16) == 2;
-    }
-    LDS_PTR(int) prof = uni_lds(nl.prof);
-    if (__any(bad)) { if (prof && lane == 0) prof[1] += 1; return __any(two_) ? 2 : 0; }      // 2: a contact between two trees (noslip_trees2)
-    unsigned long long chain = 0;      // this octet's contacts (bit c = contact c), walked in index order
-    int nstep = 0;
-#pragma unroll
-    for (int t = 0; t < 8; t++) {
-        const unsigned long long m = __ballot(ctree == t);
-        if (ft == t) chain = m;
-        const int n = __popcll(m);
-        nstep = n > nstep ? n : nstep;
-    }
-    // ---- dry-friction rows, as in pgs_groups: lane 8 t + i = dof i of tree t ----
-    for (int k = lane; k < nl.nv; k += 64) nl.dmap[k] = -1;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    for (int r = lane; r < nl.nfloss; r += 64) nl.dmap[nl.floss_dof[r]] = nl.neq + r;
-    // the spare word of every row record takes the forces of the pass; the rows' own word is written when the pass has succeeded
-    for (int i = lane; i < nefc; i += 64) rowS[RS_S * i + 8] = rowS[RS_S * i + 6];
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const bool fm = ft < nl.ntree && fi < nl.tnum[ft < nl.ntree ? ft : 0];
-    const int fdof = fm ? nl.tadr[ft] + fi : 0;
-    const int frow = fm ? nl.dmap[fdof] : -1;
-    real mrow[TREE_W];
-#pragma unroll
-    for (int s = 0; s < TREE_W; s++) mrow[s] = fm ? nl.Minv[64 * ft + 8 * fi + s] : real(0);
-    LDS_PTR(real) FS = rowS + RS_S * (frow >= 0 ? frow : 0);
-    const real faref = FS[0], finv = frow >= 0 ? FS[3] : real(0), flo = FS[4], fhi = FS[5];
-    const real fdiag = finv != 0 ? real(1) / finv : real(0);
-    real ff = frow >= 0 ? FS[6] : real(0);
-    real x = fm ? q[fdof] : real(0);
-    // ---- contact data, one step ahead ----
-    struct CD { int h, dim, g; real J[GRP_MAX], B[GRP_MAX], qc[GA_QW], ar[GRP_MAX], a1, aref, invn, f0, muinv; };
-    auto fetch = [&](unsigned long long& rem, CD& d) {
-        const bool on = rem != 0;
-        const int c = on ? __builtin_ctzll(rem) : 0;
-        rem &= rem - 1;
-        const int ce = cefc[c];
-        d.h = on ? (ce & 0xffff) : 0; d.dim = on ? (ce >> 16) : 0; d.g = __shfl(g_lane, c, 64);
-        // the six records from the contact's first row on, whatever its row count: one address, constant offsets (what lies past
-        // the contact -- the next contact's rows, the env's spare capacity, for the launch's last env the J M^-1 half of the
-        // buffer -- is masked where it is used)
-        GLB_PTR(const real) R = rJ + ROW_S * d.h + fi;
-#pragma unroll
-        for (int r = 0; r < GRP_MAX; r++) { d.J[r] = R[ROW_S * r]; d.B[r] = R[ROW_S * r + TREE_W]; }
-        const int qr = (fi >= 1 && fi <= 5) ? fi - 1 : 0;
-        GLB_PTR(const real) Q = gA + GA_W * d.g + GA_Q + qr;
-#pragma unroll
-        for (int s = 0; s < GA_QW; s++) d.qc[s] = Q[8 * s];
-        d.a1 = gA[GA_W * d.g + 2];      // the coupling of the two friction rows of a condim-3 contact (rows 2 and 1)
-        LDS_PTR(const real) S0 = rowS + RS_S * d.h;
-#pragma unroll
-        for (int r = 1; r < GRP_MAX; r++) d.ar[r] = S0[RS_S * r];       // the rows' reference accelerations, for every lane
-        LDS_PTR(const real) S = S0 + RS_S * (fi < d.dim ? fi : 0);
-        d.aref = S[0]; d.invn = S[3]; d.f0 = S[8]; d.muinv = S[7];
-    };
-    bool slid = false;
-    for (int sweep = 0; sweep < noslip_iters; sweep++) {
-        real imp = 0;
-        // dry-friction rows of mj_solNoSlip [EXT]: clamped scalar update, undone when it would raise the cost (costChange)
-#pragma unroll
-        for (int s = 0; s < TREE_W; s++) {
-            const real res = x - faref;
-            const real fs = tmin(tmax(ff - res * finv, flo), fhi);
-            const real dl_ = fs - ff, ch = dl_ * (real(0.5) * dl_ * fdiag + res);
-            const bool take = frow >= 0 && fi == s && !(ch > real(1e-10));
-            if (take) { imp -= ch; ff = fs; }
-            const real ds = oct_bcast_n(take ? dl_ : real(0), s);
-            x += mrow[s] * ds;
-        }
-        // the contacts of this octet's tree, in order
-        unsigned long long rem = chain;
-        CD ca, cb;      // two sets, used alternately: the next contact's data lands in one while the other is worked on
-        auto one_step = [&](const CD& cur) {
-            const int dim = cur.dim, n = dim - 1;
-            const bool row = fi >= 1 && fi < dim;
-            // row residuals J_r . qacc: every lane ends up with all of them
-            real res_r = 0, ra[5];
-#pragma unroll
-            for (int r = 1; r < GRP_MAX; r++) {
-                const real sr = oct_sum(r < dim ? cur.J[r] * x : real(0));
-                ra[r - 1] = r < dim ? sr - cur.ar[r] : real(0);
-                if (fi == r) res_r = ra[r - 1];
-            }
-            const real fn = oct_bcast<0>(cur.f0), r2 = fn * fn;
-            real f = cur.f0;
-            if (n >= 3) {
-                // multiplier 0 first: the unconstrained minimiser f - A^-1 res (the inverse made with the rows); inside the cone section
-                // this is mju_QCQP's answer, and its cost change is dl . res / 2
-                bool done = false;
-                if (!(fn < real(1e-15)) && oct_bcast<1>(cur.qc[5]) == real(0)) {
-                    real t = 0;
-#pragma unroll
-                    for (int k = 0; k < 5; k++) t += cur.qc[k] * ra[k];
-                    const real dl_ = row ? -t : real(0), vr = cur.f0 + dl_;
-                    const real w = row ? vr * cur.muinv : real(0);
-                    const real val = oct_sum(w * w) - r2;
-                    if (val < QTol<real>::abs + QTol<real>::rel * r2) {
-                        const real change = real(0.5) * oct_sum(dl_ * res_r);
-                        if (!(change > real(1e-10))) {
-                            if (fi == 0) imp -= change;
-                            if (row) f = vr;
-                        }
-                        done = true;
-                    }
-                }
-                // No normal force: mj_solNoSlip takes the friction forces to zero (subject to the cost test).  They are zero already when
-                // the primal solution had no normal force either -- nothing to do; anything else, and the multiplier iteration of a
-                // sliding contact, is pgs_groups' business
-                if (!done && fn < real(1e-15) && oct_sum(row ? fabs(cur.f0) : real(0)) == real(0)) done = true;
-                if (!done && (nl.tridiag == 0 || fn < real(1e-15))) slid = true;
-                else if (__builtin_expect(!done, 0)) {
-                    // the contact slides: the multiplier iteration, out of line (rare; its forty-odd live values would otherwise sit in
-                    // the registers of every step)
-                    real change;
-                    const real fv = qcqp_slide_octet<real>(gA, cur.g, n, fi, res_r, cur.f0, cur.muinv, cur.invn, cur.qc[5], fn, nl.tridiag, &change);
-                    if (!(change > real(1e-10))) {
-                        if (fi == 0) imp -= change;
-                        if (row) f = fv;
-                    }
-                }
-            } else if (n == 2) {
-                // mju_QCQP2 [EXT] as pgs_groups evaluates it, on the lanes of the octet
-                const real resq0 = ra[0], resq1 = ra[1];
-                const real of0 = oct_bcast<1>(cur.f0), of1 = oct_bcast<2>(cur.f0);
-                const real dq0 = real(1) / oct_bcast<1>(cur.muinv), dq1 = real(1) / oct_bcast<2>(cur.muinv);
-                const real A00 = real(1) / oct_bcast<1>(cur.invn), A11 = real(1) / oct_bcast<2>(cur.invn), A10 = oct_bcast<2>(cur.a1);
-                real bq0 = resq0, bq1 = resq1;
-                bq0 -= A00 * of0; bq0 -= A10 * of1;
-                bq1 -= A10 * of0; bq1 -= A11 * of1;
-                real v0 = 0, v1 = 0;
-                if (!(fn < real(1e-15))) {
-                    const real vtol = QTol<real>::abs + QTol<real>::rel * r2;
-                    real la = 0;
-                    const real b1 = bq0 * dq0, b2 = bq1 * dq1;
-                    const real A11s = A00 * dq0 * dq0, A22s = A11 * dq1 * dq1, A12s = A10 * dq0 * dq1;
-                    real y1 = 0, y2 = 0;
-                    bool singular = false;
-                    for (int iter = 0; iter < 20; iter++) {
-                        const real det = (A11s + la) * (A22s + la) - A12s * A12s;
-                        if (det < real(1e-10)) { singular = true; break; }
-                        const real detinv = real(1) / det, P11 = (A22s + la) * detinv, P22 = (A11s + la) * detinv, P12 = -A12s * detinv;
-                        y1 = -P11 * b1 - P12 * b2;
-                        y2 = -P12 * b1 - P22 * b2;
-                        const real val = y1 * y1 + y2 * y2 - r2;
-                        if (val < vtol) break;
-                        const real yw = P11 * y1 * y1 + 2 * P12 * y1 * y2 + P22 * y2 * y2;
-                        const real delta = nl.tridiag == 2 ? secular_step(val, r2, fn, yw) : val / (2 * yw);
-                        if (delta < QTol<real>::abs + QTol<real>::rel * la) break;
-                        la += delta;
-                    }
-                    v0 = singular ? real(0) : y1 * dq0;
-                    v1 = singular ? real(0) : y2 * dq1;
-                    if (!singular && la != 0) {       // exactly onto the ellipsoid
-                        const real sq = v0 * v0 / (dq0 * dq0) + v1 * v1 / (dq1 * dq1);
-                        const real sc = sqrt(r2 / tmax(real(1e-15), sq));
-                        v0 *= sc; v1 *= sc;
-                    }
-                }
-                const real change = (v0 - of0) * (real(0.5) * (A00 * (v0 - of0) + A10 * (v1 - of1)) + resq0) + (v1 - of1) * (real(0.5) * (A10 * (v0 - of0) + A11 * (v1 - of1)) + resq1);
-                if (!(change > real(1e-10)) && dim == 3) {
-                    if (fi == 0) imp -= change;
-                    if (fi == 1) f = v0;
-                    if (fi == 2) f = v1;
-                }
-            }
-            // x += B^T (f - f0); the normal row does not move
-            const real dl = row ? f - cur.f0 : real(0);
-#pragma unroll
-            for (int r = 1; r < GRP_MAX; r++) x += (r < dim ? cur.B[r] : real(0)) * oct_bcast_n(dl, r);
-            if (row) rowS[RS_S * (cur.h + fi) + 8] = f;
-        };
-        fetch(rem, ca);
-        for (int step = 0; step < nstep; step += 2) {
-            fetch(rem, cb);
-            one_step(ca);
-            if (step + 1 < nstep) {
-                fetch(rem, ca);
-                one_step(cb);
-            }
-        }
-        if (__any(slid)) { if (prof && lane == 0) prof[2] += 1; return 0; }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // the next sweep reads the forces this one has stored
-        __builtin_amdgcn_wave_barrier();
-        if (lane_get(wave_sum(imp), 0) < noslip_tol_scaled) break;
-    }
-    // ---- the pass has succeeded: accelerations and forces to their places ----
-    if (prof && lane == 0) prof[3] += 1;
-    if (fm) q[fdof] = x;
-    if (frow >= 0) FS[8] = ff;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    for (int i = lane; i < nefc; i += 64) rowS[RS_S * i + 6] = rowS[RS_S * i + 8];
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    return 1;
-}
-
-// noslip_trees for passes with a contact BETWEEN TWO kinematic trees (a gripper holding something, an object lying on another): such a
+// TWO: passes with a contact BETWEEN TWO kinematic trees (a gripper holding something, an object lying on another).  Such a
 // contact sits in both trees' chains and is relaxed by both octets in the same step -- its level is one more than the larger of its
 // two predecessors' levels, a tree has at most one contact per level --, each octet sums its tree's half of the row residuals and gets
 // the other half from its partner (ds_bpermute; first tree's part + second tree's part on both sides, so that the two octets go on
 // with identical numbers), both run the friction block, each moves its own tree's accelerations, the first tree's octet stores the
 // forces; a sliding contact runs the multiplier iteration on both octets (identical inputs, identical results: oct_sum keeps FMA
-// contraction out of the sums).  A function of its own, entered when noslip_trees returns 2: with the two-tree bookkeeping in
-// noslip_trees the headline workload, which has no such contact, lost 1.6 %; this way 0.3 %.
-template <typename real>
-__device__ AVS_OUTLINE_1 int noslip_trees2(LDS_PTR(real) rowS, LDS_PTR(const int) rowI, LDS_PTR(const int) cefc, GLB_PTR(const real) rJ, GLB_PTR(const real) rB,
-                                                      LDS_PTR(real) q, LDS_PTR(const int) gI, GLB_PTR(const real) gA, int ncon, int nefc, int noslip_iters,
-                                                      real noslip_tol_scaled, NL_PARAMS) {
+// contraction out of the sums).  Without TWO such a contact ends the pass with the return value 2.
+// One body, instantiated once per entry point below: noslip_trees (TWO = false) is tried first, noslip_trees2 (TWO = true) is entered
+// when it returns 2 -- with the two-tree bookkeeping in noslip_trees the headline workload, which has no such contact, lost 1.6 %;
+// this way 0.3 %.
+template <typename real, bool TWO>
+AVS_DEV int noslip_pass(LDS_PTR(real) rowS, LDS_PTR(const int) rowI, LDS_PTR(const int) cefc, GLB_PTR(const real) rJ, GLB_PTR(const real) rB,
+                        LDS_PTR(real) q, LDS_PTR(const int) gI, GLB_PTR(const real) gA, int ncon, int nefc, int noslip_iters,
+                        real noslip_tol_scaled, NL_PARAMS) {
     NL_UNPACK(real);
     rowS = uni_lds(rowS); rowI = uni_lds(rowI); cefc = uni_lds(cefc); q = uni_lds(q); gI = uni_lds(gI);
-    rJ = uni_glb(rJ); rB = uni_glb(rB); gA = uni_glb(gA);
+    rJ = uni_glb(rJ);
+    if constexpr (TWO) rB = uni_glb(rB);      // (J M^-1 of a contact between two trees; a one-tree contact keeps it in its J record)
+    gA = uni_glb(gA);
     ncon = __builtin_amdgcn_readfirstlane(ncon); nefc = __builtin_amdgcn_readfirstlane(nefc); noslip_iters = __builtin_amdgcn_readfirstlane(noslip_iters);
     noslip_tol_scaled = lane_get(noslip_tol_scaled, 0);
     nl.Minv = uni_lds(nl.Minv); nl.tadr = uni_lds(nl.tadr); nl.tnum = uni_lds(nl.tnum); nl.floss_dof = uni_lds(nl.floss_dof); nl.dmap = uni_lds(nl.dmap);
@@ -1384,19 +815,23 @@ __device__ AVS_OUTLINE_1 int noslip_trees2(LDS_PTR(real) rowS, LDS_PTR(const int
     if (noslip_iters <= 0 || nl.nlg < 0 || ncon <= 0 || ncon > 64) return 0;
     // ---- the contacts' trees (one, or two for a contact between two trees); every contact must have its rows and the group
     // pgs_groups would give it ----
+    // (a contact without rows -- the reward-only pins of the needle and of the hook -- is in no chain and has no group: the groups
+    // count the contacts WITH rows)
     int tA = -1, tB = -1;
-    bool bad = false;
+    bool bad = false, two_ = false;
     const int ce_l = lane < ncon ? cefc[lane] : -1;
-    const unsigned long long hasrows = __ballot(ce_l >= 0);      // (contacts without rows -- reward-only pins -- are in no chain and have no group)
-    const int g_lane = nl.nlg + __popcll(hasrows & ((1ull << lane) - 1ull));
+    const unsigned long long hasrows = __ballot(ce_l >= 0);
+    const int g_lane = nl.nlg + __popcll(hasrows & ((1ull << lane) - 1ull));      // the group of this lane's contact
     if (ce_l >= 0) {
         const int ce = ce_l, h = ce & 0xffff, ra = rowI[h];
         tA = (ra >> 10) & 7;
-        tB = ((ra >> 19) & 15) != 0 ? (ra >> 23) & 7 : -1;
-        bad = tA >= nl.ntree || tB >= nl.ntree || tB == tA || (gI[g_lane] & 0xffff) != h || ((gI[g_lane] >> 16) & 15) != (ce >> 16) || (ce >> 16) > GRP_MAX || (ce >> 16) == 2;
+        two_ = ((ra >> 19) & 15) != 0;
+        if constexpr (TWO) tB = two_ ? (ra >> 23) & 7 : -1;
+        const bool trees_bad = TWO ? (tA >= nl.ntree || tB >= nl.ntree || tB == tA) : (two_ || tA >= nl.ntree);
+        bad = trees_bad || (gI[g_lane] & 0xffff) != h || ((gI[g_lane] >> 16) & 15) != (ce >> 16) || (ce >> 16) > GRP_MAX || (ce >> 16) == 2;
     }
     LDS_PTR(int) prof = uni_lds(nl.prof);
-    if (__any(bad)) { if (prof && lane == 0) prof[1] += 1; return 0; }
+    if (__any(bad)) { if (prof && lane == 0) prof[1] += 1; return (!TWO && __any(two_)) ? 2 : 0; }      // 2: a contact between two trees (noslip_trees2)
     // The order: a tree's contacts in index order (its chain); a contact between two trees sits in both chains and is relaxed by both
     // octets in the same step, so it waits for its predecessors in BOTH.  Level of a contact = the step it is relaxed in = 1 + the
     // larger of its two predecessors' levels; a tree has at most one contact per level.
@@ -1406,22 +841,24 @@ __device__ AVS_OUTLINE_1 int noslip_trees2(LDS_PTR(real) rowS, LDS_PTR(const int
     for (int t = 0; t < 8; t++) {
         const unsigned long long m = __ballot(tA == t || tB == t);
         if (ft == t) chain = m;
-        if (tA == t) mA = m;
-        if (tB == t) mB = m;
+        if constexpr (TWO) { if (tA == t) mA = m; if (tB == t) mB = m; }
         const int n = __popcll(m);
         nstep = n > nstep ? n : nstep;
     }
-    const unsigned long long below = (1ull << lane) - 1ull;
-    int lev = ce_l >= 0 ? __popcll(mA & below) : 1 << 20;       // no contact between two trees: the position in the chain
-    if (__any(tB >= 0)) {
-        const int pA = (mA & below) ? 63 - __builtin_clzll(mA & below) : -1, pB = (tB >= 0 && (mB & below)) ? 63 - __builtin_clzll(mB & below) : -1;
-        lev = ce_l >= 0 ? -1 : 1 << 20;
-        nstep = 0;
-        for (int L = 0; L < 64; L++) {
-            const int la = __shfl(lev, pA >= 0 ? pA : 0, 64), lb = __shfl(lev, pB >= 0 ? pB : 0, 64);
-            if (lev < 0 && (pA < 0 || la >= 0) && (pB < 0 || lb >= 0)) lev = L;
-            nstep = L + 1;
-            if (!__any(lev < 0)) break;
+    int lev = 0;      // (without TWO the level is the position in the chain: the octets walk their chains bit by bit and need no levels)
+    if constexpr (TWO) {
+        const unsigned long long below = (1ull << lane) - 1ull;
+        lev = ce_l >= 0 ? __popcll(mA & below) : 1 << 20;       // no contact between two trees: the position in the chain
+        if (__any(tB >= 0)) {
+            const int pA = (mA & below) ? 63 - __builtin_clzll(mA & below) : -1, pB = (tB >= 0 && (mB & below)) ? 63 - __builtin_clzll(mB & below) : -1;
+            lev = ce_l >= 0 ? -1 : 1 << 20;
+            nstep = 0;
+            for (int L = 0; L < 64; L++) {
+                const int la = __shfl(lev, pA >= 0 ? pA : 0, 64), lb = __shfl(lev, pB >= 0 ? pB : 0, 64);
+                if (lev < 0 && (pA < 0 || la >= 0) && (pB < 0 || lb >= 0)) lev = L;
+                nstep = L + 1;
+                if (!__any(lev < 0)) break;
+            }
         }
     }
     // ---- dry-friction rows, as in pgs_groups: lane 8 t + i = dof i of tree t ----
@@ -1445,24 +882,21 @@ __device__ AVS_OUTLINE_1 int noslip_trees2(LDS_PTR(real) rowS, LDS_PTR(const int
     real ff = frow >= 0 ? FS[6] : real(0);
     real x = fm ? q[fdof] : real(0);
     // ---- contact data, one step ahead ----
-    // the sweeps, compiled twice: for passes whose contacts all touch one tree (nothing of the two-tree bookkeeping in the steps) and for
-    // passes with a contact between two trees
-    auto sweeps = [&](auto two_tag) -> int {
-    constexpr bool TWO = decltype(two_tag)::value;
     struct CD { int h, dim, g, side, partner; bool two; real J[GRP_MAX], B[GRP_MAX], qc[GA_QW], ar[GRP_MAX], a1, aref, invn, f0, muinv; };
     unsigned long long rem = 0;      // (one-tree passes: what is left of this octet's chain in the current sweep)
     auto fetch = [&](int L, CD& d) {
         // this octet's contact of level L, if it has one; without contacts between two trees the levels are the positions in the chain
-        const unsigned long long m = TWO ? __ballot(lev == L) & chain : rem;
+        unsigned long long m = rem;
+        if constexpr (TWO) m = __ballot(lev == L) & chain;
         const bool on = m != 0;
         const int c = on ? __builtin_ctzll(m) : 0;
-        if (!TWO) rem &= rem - 1;
+        if constexpr (!TWO) rem &= rem - 1;
         const int ce = cefc[c];
         d.h = on ? (ce & 0xffff) : 0; d.dim = on ? (ce >> 16) : 0; d.g = __shfl(g_lane, c, 64);
         // a contact between two trees: this octet's tree is its first (side 0: words 0..7 of the row records) or its second (side 1:
         // words 8..15); its J M^-1 rows are in the second buffer (a one-tree contact keeps them in words 8..15 of the J record)
         d.two = false; d.side = 0; d.partner = ft;
-        if (TWO) {
+        if constexpr (TWO) {
             const int ra_ = rowI[d.h];
             d.two = on && ((ra_ >> 19) & 15) != 0;
             d.side = (d.two && ((ra_ >> 10) & 7) != ft) ? 1 : 0;
@@ -1505,17 +939,20 @@ __device__ AVS_OUTLINE_1 int noslip_trees2(LDS_PTR(real) rowS, LDS_PTR(const int
         auto one_step = [&](const CD& cur) {
             const int dim = cur.dim, n = dim - 1;
             const bool row = fi >= 1 && fi < dim;
+            const bool first = !TWO || cur.side == 0;      // the octet of a contact's first tree adds to the improvement sum and stores the forces
             // row residuals J_r . qacc: every lane ends up with all of them
             real res_r = 0, ra[5], sr[GRP_MAX];
 #pragma unroll
             for (int r = 1; r < GRP_MAX; r++) sr[r] = oct_sum(r < dim ? cur.J[r] * x : real(0));
-            if (TWO && __any(cur.two)) {
+            if constexpr (TWO) {
                 // a contact between two trees: the other tree's octet has the other half of every sum (first tree's part + second tree's
                 // part, in that order on both sides, so that the two octets go on with identical numbers)
+                if (__any(cur.two)) {
 #pragma unroll
-                for (int r = 1; r < GRP_MAX; r++) {
-                    const real other = __shfl(sr[r], 8 * cur.partner + fi, 64);
-                    if (cur.two) sr[r] = cur.side == 0 ? sr[r] + other : other + sr[r];
+                    for (int r = 1; r < GRP_MAX; r++) {
+                        const real other = __shfl(sr[r], 8 * cur.partner + fi, 64);
+                        if (cur.two) sr[r] = cur.side == 0 ? sr[r] + other : other + sr[r];
+                    }
                 }
             }
 #pragma unroll
@@ -1539,7 +976,7 @@ __device__ AVS_OUTLINE_1 int noslip_trees2(LDS_PTR(real) rowS, LDS_PTR(const int
                     if (val < QTol<real>::abs + QTol<real>::rel * r2) {
                         const real change = real(0.5) * oct_sum(dl_ * res_r);
                         if (!(change > real(1e-10))) {
-                            if (fi == 0 && cur.side == 0) imp -= change;
+                            if (fi == 0 && first) imp -= change;
                             if (row) f = vr;
                         }
                         done = true;
@@ -1556,7 +993,7 @@ __device__ AVS_OUTLINE_1 int noslip_trees2(LDS_PTR(real) rowS, LDS_PTR(const int
                     real change;
                     const real fv = qcqp_slide_octet<real>(gA, cur.g, n, fi, res_r, cur.f0, cur.muinv, cur.invn, cur.qc[5], fn, nl.tridiag, &change);
                     if (!(change > real(1e-10))) {
-                        if (fi == 0 && cur.side == 0) imp -= change;
+                        if (fi == 0 && first) imp -= change;
                         if (row) f = fv;
                     }
                 }
@@ -1570,37 +1007,10 @@ __device__ AVS_OUTLINE_1 int noslip_trees2(LDS_PTR(real) rowS, LDS_PTR(const int
                 bq0 -= A00 * of0; bq0 -= A10 * of1;
                 bq1 -= A10 * of0; bq1 -= A11 * of1;
                 real v0 = 0, v1 = 0;
-                if (!(fn < real(1e-15))) {
-                    const real vtol = QTol<real>::abs + QTol<real>::rel * r2;
-                    real la = 0;
-                    const real b1 = bq0 * dq0, b2 = bq1 * dq1;
-                    const real A11s = A00 * dq0 * dq0, A22s = A11 * dq1 * dq1, A12s = A10 * dq0 * dq1;
-                    real y1 = 0, y2 = 0;
-                    bool singular = false;
-                    for (int iter = 0; iter < 20; iter++) {
-                        const real det = (A11s + la) * (A22s + la) - A12s * A12s;
-                        if (det < real(1e-10)) { singular = true; break; }
-                        const real detinv = real(1) / det, P11 = (A22s + la) * detinv, P22 = (A11s + la) * detinv, P12 = -A12s * detinv;
-                        y1 = -P11 * b1 - P12 * b2;
-                        y2 = -P12 * b1 - P22 * b2;
-                        const real val = y1 * y1 + y2 * y2 - r2;
-                        if (val < vtol) break;
-                        const real yw = P11 * y1 * y1 + 2 * P12 * y1 * y2 + P22 * y2 * y2;
-                        const real delta = nl.tridiag == 2 ? secular_step(val, r2, fn, yw) : val / (2 * yw);
-                        if (delta < QTol<real>::abs + QTol<real>::rel * la) break;
-                        la += delta;
-                    }
-                    v0 = singular ? real(0) : y1 * dq0;
-                    v1 = singular ? real(0) : y2 * dq1;
-                    if (!singular && la != 0) {       // exactly onto the ellipsoid
-                        const real sq = v0 * v0 / (dq0 * dq0) + v1 * v1 / (dq1 * dq1);
-                        const real sc = sqrt(r2 / tmax(real(1e-15), sq));
-                        v0 *= sc; v1 *= sc;
-                    }
-                }
+                if (!(fn < real(1e-15))) qcqp2(A00, A10, A11, bq0, bq1, dq0, dq1, fn, nl.tridiag, v0, v1);
                 const real change = (v0 - of0) * (real(0.5) * (A00 * (v0 - of0) + A10 * (v1 - of1)) + resq0) + (v1 - of1) * (real(0.5) * (A10 * (v0 - of0) + A11 * (v1 - of1)) + resq1);
                 if (!(change > real(1e-10)) && dim == 3) {
-                    if (fi == 0 && cur.side == 0) imp -= change;
+                    if (fi == 0 && first) imp -= change;
                     if (fi == 1) f = v0;
                     if (fi == 2) f = v1;
                 }
@@ -1609,7 +1019,7 @@ __device__ AVS_OUTLINE_1 int noslip_trees2(LDS_PTR(real) rowS, LDS_PTR(const int
             const real dl = row ? f - cur.f0 : real(0);
 #pragma unroll
             for (int r = 1; r < GRP_MAX; r++) x += (r < dim ? cur.B[r] : real(0)) * oct_bcast_n(dl, r);
-            if (row && cur.side == 0) rowS[RS_S * (cur.h + fi) + 8] = f;
+            if (row && first) rowS[RS_S * (cur.h + fi) + 8] = f;
         };
         rem = chain;
         fetch(0, ca);
@@ -1626,9 +1036,6 @@ __device__ AVS_OUTLINE_1 int noslip_trees2(LDS_PTR(real) rowS, LDS_PTR(const int
         __builtin_amdgcn_wave_barrier();
         if (lane_get(wave_sum(imp), 0) < noslip_tol_scaled) break;
     }
-    return 1;
-    };
-    if (!(__any(tB >= 0) ? sweeps(BoolTag<true>{}) : sweeps(BoolTag<false>{}))) return 0;
     // ---- the pass has succeeded: accelerations and forces to their places ----
     if (prof && lane == 0) prof[3] += 1;
     if (fm) q[fdof] = x;
@@ -1639,6 +1046,20 @@ __device__ AVS_OUTLINE_1 int noslip_trees2(LDS_PTR(real) rowS, LDS_PTR(const int
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     return 1;
+}
+
+// The two out-of-line entry points of the pass (each with its own register allocation; the call sequence is solve's).
+template <typename real>
+__device__ AVS_OUTLINE_1 int noslip_trees(LDS_PTR(real) rowS, LDS_PTR(const int) rowI, LDS_PTR(const int) cefc, GLB_PTR(const real) rJ,
+                                                      LDS_PTR(real) q, LDS_PTR(const int) gI, GLB_PTR(const real) gA, int ncon, int nefc, int noslip_iters,
+                                                      real noslip_tol_scaled, NL_PARAMS) {
+    return noslip_pass<real, false>(rowS, rowI, cefc, rJ, (GLB_PTR(const real))nullptr, q, gI, gA, ncon, nefc, noslip_iters, noslip_tol_scaled, nl_a_, nl_b_, nl_c_);
+}
+template <typename real>
+__device__ AVS_OUTLINE_1 int noslip_trees2(LDS_PTR(real) rowS, LDS_PTR(const int) rowI, LDS_PTR(const int) cefc, GLB_PTR(const real) rJ, GLB_PTR(const real) rB,
+                                                      LDS_PTR(real) q, LDS_PTR(const int) gI, GLB_PTR(const real) gA, int ncon, int nefc, int noslip_iters,
+                                                      real noslip_tol_scaled, NL_PARAMS) {
+    return noslip_pass<real, true>(rowS, rowI, cefc, rJ, rB, q, gI, gA, ncon, nefc, noslip_iters, noslip_tol_scaled, nl_a_, nl_b_, nl_c_);
 }
 
 

@@ -174,6 +174,9 @@ void orc_make_constraints(orc_data* d);
 void orc_solve(orc_data* d);
 void orc_solve_newton(orc_data* d);
 void orc_noslip(orc_data* d);
+/* orc_noslip's QCQP on its own, for tests: res = argmin 1/2 x'Ax + x'b over sum (x_i / d_i)^2 <= r^2 (A n x n row-major, 2 <= n <= 5),
+ * before the projection onto the ellipsoid; returns 1 when the constraint is active */
+int orc_qcqp(double* res, const double* A, const double* b, const double* d, double r, int n);
 
 /* box-box manifolds: 8 (default; every clipped vertex, as MuJoCo's mjc_BoxBox [EXT]) or 4 (the reduced manifold of rounds 1-4) */
 void orc_set_boxbox_maxpoints(int n);

@@ -676,6 +676,10 @@ static int qcqpn(double* res, const double* Ain, const double* bin, const double
     return la != 0;
 }
 
+int orc_qcqp(double* res, const double* A, const double* b, const double* d, double r, int n) {
+    return n == 2 ? qcqp2(res, A, b, d, r) : qcqpn(res, A, b, d, r, n);
+}
+
 /* Inverse of the scaled friction block As = D A D (n x n, n <= 5) through its Cholesky factor; 0 when a pivot falls below 1e-10
  * (the singularity rule of mju_QCQP).  Computed once per contact and substep: at the multiplier 0 the QCQP's candidate is
  * y = -As^-1 (D b), and most resting contacts end there (inside the cone).  Same loops as the device (qc_inverse5). */
