@@ -54,6 +54,7 @@ def lib():
         L.avsim_get_phase_cycles.argtypes = [vp, vp]
         L.avsim_render_depth.argtypes = [vp, vp, i32, i32, i32, vp]
         L.avsim_render_rgb.argtypes = [vp, vp, i32, i32, i32, vp]
+        L.avsim_render_labels.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
         L.avsim_camera_count.argtypes = [vp]
         L.avsim_load_visual.argtypes = [vp, vp, C.c_size_t]
         L.avsim_visual_info.argtypes = [vp, vp]

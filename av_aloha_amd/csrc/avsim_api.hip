@@ -93,6 +93,7 @@ struct avsim {
     ObsHistHost obshist; // per-env observation histories (avsim_obshist.hip.h), once avsim_obs_history_setup has run
     PcHost pointcloud;   // point clouds from depth images (avsim_pointcloud.hip.h): a chunk of envs' pose records and candidate lists
     int virtviews_form = 0;          // option "virtviews_form": 0 = avsim_virtual_views runs the scatter form AVSIM_VV_FORM, f + 1 = form f (the same bits; there to be measured)
+    bool labels_unpacked = false;    // option "render_labels_form": avsim_render_labels keeps a lane's eight winners in eight registers (1) instead of two (0, the default); the same images, there to be measured
     bool voxel_other_form = false;   // option "voxel_other_form": avsim_voxel_grid runs the accumulate form that AVSIM_VOXEL_MERGE did NOT pick (the same bits; there to be measured)
     bool jpegdec_events = false;   // option "jpeg_decode_events": avsim_jpeg_decode records ev[12..15] around its three kernels
     // the state's version: bumped by everything that writes qpos (reset, the steps, set_state); the image calls skip their pose pass and the shadow
@@ -443,6 +444,7 @@ int avsim_set_option(avsim_t* h, const char* name, double value) {
     if (!std::strcmp(name, "render_shadow_size")) { if (value != 512 && value != 1024 && value != 2048) { h->set_error("render_shadow_size is 512, 1024 or 2048"); return AVSIM_EINVAL; } h->vis.shadow_size = (int)value; return AVSIM_OK; }
     if (!std::strcmp(name, "render_cam_major")) { h->vis.cam_major = value != 0; return AVSIM_OK; }
     if (!std::strcmp(name, "render_chunk")) { if (value < 1) { h->set_error("render_chunk is a number of envs >= 1"); return AVSIM_EINVAL; } h->render.env_chunk = (int)value; return AVSIM_OK; }
+    if (!std::strcmp(name, "render_labels_form")) { h->labels_unpacked = value != 0; return AVSIM_OK; }
     if (!std::strcmp(name, "voxel_other_form")) { h->voxel_other_form = value != 0; return AVSIM_OK; }
     if (!std::strcmp(name, "virtviews_form")) { if (!(value >= 0 && value <= 5 && value == (int)value)) { h->set_error("virtviews_form is 0 (the form the build ships) or 1 + a form 0..4"); return AVSIM_EINVAL; } h->virtviews_form = (int)value; return AVSIM_OK; }
     if (!std::strcmp(name, "jpeg_decode_events")) { h->jpegdec_events = value != 0; return AVSIM_OK; }
@@ -846,6 +848,46 @@ int avsim_render_rgb(avsim_t* h, const int32_t* cam_ids, int ncam, int height, i
 // the visual scene's colour images as a policy reads them (eval.py preprocess_observation): float32 planar CHW, (float)u8 / 255
 int avsim_render_rgb_f32(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, float* out) {
     return render_images(h, cam_ids, ncam, height, width, out, true, true);
+}
+
+// ---- what every pixel shows (av_aloha_amd/segment.py is the specification): k_render_depth's labels mode, the depth mode's cast with the winning
+// record kept.  table and drop are folded into one entry per geom here -- label | LUT_DROP where drop[label] -- and go through the pinned staging.
+int avsim_render_labels(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, const uint8_t* table, const uint8_t* drop, float* depth, uint8_t* labels) {
+    if (!h) return AVSIM_EINVAL;
+    if (!cam_ids) { h->set_error("avsim_render_labels: cam_ids is null"); return AVSIM_EINVAL; }
+    if (!depth && !labels) { h->set_error("avsim_render_labels: depth and labels are both null"); return AVSIM_EINVAL; }
+    if (drop && !depth) { h->set_error("avsim_render_labels: drop changes the depth image, and depth is null"); return AVSIM_EINVAL; }
+    if (ncam < 1 || ncam > 16 || height < 1 || width < 1 || height > 4096 || width > 4096) { h->set_error("avsim_render_labels: bad camera count or image size"); return AVSIM_EINVAL; }
+    for (int c = 0; c < ncam; c++)
+        if (cam_ids[c] < 0 || cam_ids[c] >= h->render.m.ncam) { h->set_error("avsim_render_labels: camera index out of range"); return AVSIM_EINVAL; }
+    const int ngeom = h->render.m.ngeom;
+    if (ngeom > BL_MAX) { h->set_error("avsim_render_labels: the model has more geoms than a bin's list holds (BL_MAX)"); return AVSIM_EINVAL; }
+    if (h->io_device && (width & 3) == 0 && ((depth && ((uintptr_t)depth & 15)) || (labels && ((uintptr_t)labels & 3)))) {
+        h->set_error("avsim_render_labels: with a width that is a multiple of 4, depth is 16-byte and labels 4-byte aligned (a row's four pixels leave in one store)");
+        return AVSIM_EINVAL;
+    }
+    AVS_ON_DEVICE(h);
+    Call io(h);
+    const size_t npx = (size_t)h->N * ncam * height * width;
+    float* ddepth = io.out(depth, sizeof(float) * npx);
+    uint8_t* dlabels = io.out(labels, npx);
+    if (io.failed()) return AVSIM_EHIP;
+    if (int rc = refresh_xpose(h)) return rc;
+    const size_t bytes = sizeof(uint16_t) * (size_t)(ngeom + 1);
+    StageRing::Slot* s = h->stage.acquire(bytes, h->err);
+    if (!s) return AVSIM_EHIP;
+    uint16_t* lut = (uint16_t*)s->pin;
+    for (int g = 0; g <= ngeom; g++) {
+        const unsigned l = table ? table[g] : (g < ngeom ? (unsigned)g : 255u);
+        lut[g] = (uint16_t)(l | (drop && drop[l] ? LUT_DROP : 0));
+    }
+    if (h->stage.upload(*s, bytes, h->stream, h->err)) return AVSIM_EHIP;
+    const int lrc = h->render.launch_mode(h->stream, (const int*)cam_ids, ncam, height, width, h->labels_unpacked ? RM_LABELS : RM_LABELS_PK, ddepth, dlabels, (const unsigned short*)s->dev.ptr(), h->err);
+    const std::string lerr = h->err;
+    const int rrc = h->stage.release(*s, h->stream, h->err);
+    if (lrc) { h->err = lerr; return lrc < -1 ? AVSIM_EHIP : AVSIM_EINVAL; }
+    if (rrc) return AVSIM_EHIP;
+    return io.done();
 }
 
 // ---- point clouds from depth images (av_aloha_amd/pointcloud.py is the specification; the kernels: csrc/avsim_pointcloud.hip, a unit of its own flags)

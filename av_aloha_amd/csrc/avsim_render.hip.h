@@ -370,6 +370,20 @@ __device__ inline float wave_max(float x) {
     return fmaxf(fmaxf(a, b), fmaxf(c, d));
 }
 
+// 1 / x correctly rounded, the division sequence spelled out (v_div_scale x 2, v_rcp, v_fma x 5, v_div_fmas, v_div_fixup).  A primitive's entry depth
+// becomes an inverse depth through it.  Written `1.0f / t0`, the build's approximate-division flag decided per INSTANTIATION of the cast: the
+// depth and colour modes compiled to this very sequence (the flag's mark on the division did not survive the merge of the primitives' branches),
+// a mode with other code around it to a bare v_rcp, and the two depth images differed by up to 2 ulp on spheres and cylinders
+__device__ __forceinline__ float rcp_rn(const float x) {
+    bool flag;
+    const float d = __builtin_amdgcn_div_scalef(1.0f, x, false, &flag), n = __builtin_amdgcn_div_scalef(1.0f, x, true, &flag);
+    float r = __builtin_amdgcn_rcpf(d);
+    r = __builtin_fmaf(__builtin_fmaf(-d, r, 1.0f), r, r);
+    float q = n * r;
+    q = __builtin_fmaf(__builtin_fmaf(-d, q, n), r, q);
+    return __builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(__builtin_fmaf(-d, q, n), r, q, flag), x, 1.0f);
+}
+
 // parametric interval of the ray t * v from origin o (geom frame) inside the convex geom; v differs per pixel
 __device__ inline bool ray_prim(int type, const float* sz, const float* o, const float* v, float* t0) {
     float lo = -1e30f, hi = 1e30f;
@@ -421,11 +435,28 @@ constexpr int BL_MAX = 128;      // list entries per bin (the models have <= 91 
 #define AVSIM_RD_ARENA4 1600
 #endif
 constexpr int ARENA4 = AVSIM_RD_ARENA4;     // float4 slots of a bin's staging arena: 25 KB (with the headers 31.3 KB per block: five blocks = five waves per SIMD at 82 VGPRs)
-template <bool RGB>
+// What a cast leaves behind.  RM_DEPTH: the depth image.  RM_RGB: the shaded colour image; the cast remembers record and entry face per pixel.
+// RM_LABELS: the depth mode's cast (two faces per round) with the record remembered, a u8 label image through a table and the depth image, either
+// optional.  RM_LABELS_PK: the same with the eight winners of a lane in two registers, a byte each (record indices are below BL_MAX = 128, 255 =
+// nothing), where RM_LABELS spends eight; both are compiled, option "render_labels_form" picks (DESIGN 8.am has the measurement).
+enum RenderMode : int { RM_DEPTH = 0, RM_RGB = 1, RM_LABELS = 2, RM_LABELS_PK = 3 };
+constexpr int LUT_DROP = 0x100;      // a label table entry (u16): the label, and this bit where a pixel of that label gets the far plane as its depth
+// pixel q of the lane now sees record k (entry face `face`) where `c`
+template <int MODE>
+__device__ __forceinline__ void win_set(int (&win)[NPX], unsigned (&wpk)[TILE_R], const int q, const bool c, const int k, const int face) {
+    if constexpr (MODE == RM_RGB) { if (c) win[q] = k | (face << 8); }
+    if constexpr (MODE == RM_LABELS) { if (c) win[q] = k; }
+    if constexpr (MODE == RM_LABELS_PK) {
+        const unsigned m = 0xffu << (8 * (q & 3));
+        if (c) wpk[q >> 2] = (wpk[q >> 2] & ~m) | (((unsigned)k * 0x01010101u) & m);
+    }
+}
+template <int MODE>
 __device__ __forceinline__ void render_tile(const int lane, const int tx0, const int ty0, const int cs, const int env, const float4* hA, const float4* hB, const float4* hC, const float4* arena, const int cnt,
                                             const float* __restrict__ R, const float4* __restrict__ tplanes, const float4* __restrict__ fboxes, const float4* __restrict__ sedges, int nplane, int nedge, const float scale, int ncam_sel, int H,
                                             int W, float znear, float zfar, float* __restrict__ out, const float* __restrict__ geom_rgba, const float* __restrict__ light,
-                                            const float* __restrict__ camaux, unsigned char* __restrict__ out_rgb) {
+                                            const float* __restrict__ camaux, unsigned char* __restrict__ out_u8, const unsigned short* __restrict__ lut, const int ngeom) {
+    constexpr bool RGB = MODE == RM_RGB, LAB = MODE == RM_LABELS || MODE == RM_LABELS_PK;
     // lane -> 4 adjacent pixels in each of TILE_R rows (rows 8 apart, so that a row of the tile is still written by 8 lanes)
     const int px = tx0 + 4 * (lane & 7), py0 = ty0 + (lane >> 3);
     // tile pyramid: x in [xl, xr], y in [yb, yt] at z = -1
@@ -435,7 +466,10 @@ __device__ __forceinline__ void render_tile(const int lane, const int tx0, const
     // s = (a / no) x + (b / no) y - c / no is affine in the pixel -- one fma per pixel and face instead of fma + rcp + mul, the nearest surface
     // is the LARGEST s, the entry face of a polyhedron the one with the SMALLEST s, and one rcp per pixel at the very end gives the depth.
     float dyr[TILE_R], dx[4], best[NPX];      // best: inverse depth of what the pixel sees so far (1 / zfar: nothing; off-image pixels hold a value no surface beats)
-    int win[NPX];     // RGB: record index | entry face << 8 of what the pixel sees; pixel q = 4 * row + column
+    int win[NPX];     // RGB: record index | entry face << 8 of what the pixel sees; pixel q = 4 * row + column.  RM_LABELS: the record index
+    unsigned wpk[TILE_R];      // RM_LABELS_PK: the record indices of a row's four pixels, a byte each
+#pragma unroll
+    for (int r = 0; r < TILE_R; r++) wpk[r] = 0xffffffffu;
     const float sfar0 = 1.0f / zfar, sznear = 1.0f / znear;
 #pragma unroll
     for (int r = 0; r < TILE_R; r++) dyr[r] = -(py0 + 8 * r + 0.5f - 0.5f * H) * scale;
@@ -538,7 +572,7 @@ __device__ __forceinline__ void render_tile(const int lane, const int tx0, const
                             const v2f n0v = {n0, n0}, n1v = {n1, n1};
                             const v2f s0a = a0v * dxa + n0v, s0b = a0v * dxb + n0v, s1a = a1v * dxa + n1v, s1b = a1v * dxb + n1v;
                             // (a pixel inside the silhouette approaches every face seen from outside: s > 0 there; elsewhere the value is unused)
-                            if (RGB) {
+                            if constexpr (RGB) {
                                 if (s0a.x < lo[4 * r]) face[4 * r] = p0;
                                 if (s0a.y < lo[4 * r + 1]) face[4 * r + 1] = p0;
                                 if (s0b.x < lo[4 * r + 2]) face[4 * r + 2] = p0;
@@ -637,7 +671,7 @@ __device__ __forceinline__ void render_tile(const int lane, const int tx0, const
                             const float nv = nb[q >> 2] + f.x * dx[q & 3];
                             const float t = f.w * __builtin_amdgcn_rcpf(nv);
                             if (!(nv < 0)) em[q] = -1.0f;
-                            if (RGB) { if (t > lo[q]) face[q] = p; }
+                            if constexpr (RGB) { if (t > lo[q]) face[q] = p; }
                             lo[q] = vmax1(lo[q], t);
                         }
                     }
@@ -653,7 +687,7 @@ __device__ __forceinline__ void render_tile(const int lane, const int tx0, const
                             const float nv = nb[q >> 2] + f.x * dx[q & 3];
                             const float t = f.w * __builtin_amdgcn_rcpf(nv);
                             if (!(nv < 0)) em[q] = -1.0f;
-                            if (RGB) { if (t > lo[q]) face[q] = p; }
+                            if constexpr (RGB) { if (t > lo[q]) face[q] = p; }
                             lo[q] = vmax1(lo[q], t);
                         }
                     }
@@ -702,7 +736,7 @@ __device__ __forceinline__ void render_tile(const int lane, const int tx0, const
                 for (int q = 0; q < NPX; q++) {
                     float c = em[q] >= 0 ? lo[q] : 0.0f;      // (two selects and a max per pixel: no mask logic on the scalar unit)
                     c = lo[q] <= sznear ? c : 0.0f;
-                    if (RGB) { if (c > best[q]) win[q] = k | (face[q] << 8); }
+                    win_set<MODE>(win, wpk, q, c > best[q], k, face[q]);
                     best[q] = vmax1(best[q], c);
                 }
                 {
@@ -727,7 +761,7 @@ __device__ __forceinline__ void render_tile(const int lane, const int tx0, const
                     const float dyq = dyr[q >> 2], dxq = dx[q & 3];
                     const float v[3] = {rec[4] * dyq - rec[5] + va[0] * dxq, rec[7] * dyq - rec[8] + va[1] * dxq, rec[10] * dyq - rec[11] + va[2] * dxq};
                     float t0;
-                    if (ray_prim(type, sz, o, v, &t0) && t0 >= znear && t0 * best[q] < 1.0f) { best[q] = 1.0f / t0; if (RGB) win[q] = k; }
+                    if (ray_prim(type, sz, o, v, &t0) && t0 >= znear && t0 * best[q] < 1.0f) { best[q] = rcp_rn(t0); win_set<MODE>(win, wpk, q, true, k, 0); }
                 }
                 {
                     float bm = best[0];
@@ -741,7 +775,36 @@ __device__ __forceinline__ void render_tile(const int lane, const int tx0, const
     }
 #pragma unroll
     for (int q = 0; q < NPX; q++) best[q] = best[q] == sfar0 ? zfar : __builtin_amdgcn_rcpf(best[q]);      // (the far plane itself where nothing was hit)
-    if (!RGB) {
+    if constexpr (LAB) {
+        // the label of what each pixel sees: record -> geom (rec[22]) -> table entry, the table's last entry where nothing was hit; a dropped
+        // label's pixel gets the far plane as its depth, the value of a ray that hits nothing
+#pragma unroll
+        for (int r = 0; r < TILE_R; r++) {
+            const int py = py0 + 8 * r;
+            unsigned lab[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                int k;
+                if constexpr (MODE == RM_LABELS_PK) { k = (int)((wpk[r] >> (8 * q)) & 0xffu); k = k == 255 ? -1 : k; }
+                else k = win[4 * r + q];
+                // (32-bit lane offsets from the two wave-uniform bases; record 0 is inside the buffer, and what it holds is not used)
+                const int g = __float_as_int(R[(unsigned)(k < 0 ? 0 : k) * (unsigned)REC_W + 22u]);
+                const unsigned e = lut[(unsigned)(k < 0 ? ngeom : g)];
+                lab[q] = e & 0xffu;
+                if (e & LUT_DROP) best[4 * r + q] = zfar;
+            }
+            if (py < H && out_u8) {
+                unsigned char* dst = out_u8 + (((size_t)env * ncam_sel + cs) * H + py) * W + px;
+                if (px + 3 < W && (W & 3) == 0) *reinterpret_cast<unsigned int*>(dst) = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
+                else {
+#pragma unroll
+                    for (int q = 0; q < 4; q++) if (px + q < W) dst[q] = (unsigned char)lab[q];
+                }
+            }
+        }
+        if (!out) return;
+    }
+    if constexpr (!RGB) {
 #pragma unroll
         for (int r = 0; r < TILE_R; r++) {
             const int py = py0 + 8 * r;
@@ -764,7 +827,7 @@ __device__ __forceinline__ void render_tile(const int lane, const int tx0, const
             }
         }
         return;
-    }
+    } else {
     const float* aux = camaux + ((size_t)env * ncam_sel + cs) * 8;
     const float amb = light[0], hd = light[1], ld = light[2];
 #pragma unroll
@@ -817,7 +880,7 @@ __device__ __forceinline__ void render_tile(const int lane, const int tx0, const
 #pragma unroll
         for (int j = 0; j < 3; j++) col[3 * q + j] = (unsigned char)(fminf(fmaxf(rgb[j], 0.0f), 1.0f) * 255.0f + 0.5f);
     }
-    unsigned char* dst = out_rgb + ((((size_t)env * ncam_sel + cs) * H + py) * W + px) * 3;
+    unsigned char* dst = out_u8 + ((((size_t)env * ncam_sel + cs) * H + py) * W + px) * 3;
     if (px + 3 < W && (W & 3) == 0) {
         unsigned int w3[3];
 #pragma unroll
@@ -828,6 +891,7 @@ __device__ __forceinline__ void render_tile(const int lane, const int tx0, const
 #pragma unroll
         for (int q = 0; q < 4; q++)
             if (px + q < W) { dst[3 * q] = col[3 * q]; dst[3 * q + 1] = col[3 * q + 1]; dst[3 * q + 2] = col[3 * q + 2]; }
+    }
     }
     }
 }
@@ -848,12 +912,12 @@ __device__ __forceinline__ void render_tile(const int lane, const int tx0, const
 #ifndef AVSIM_RD_WAVES
 #define AVSIM_RD_WAVES 1
 #endif
-template <bool RGB>
-__global__ void __launch_bounds__(256, RGB ? 1 : AVSIM_RD_WAVES) k_render_depth(const float* __restrict__ recs, const int* __restrict__ counts, const float4* __restrict__ heads,
+template <int MODE>
+__global__ void __launch_bounds__(256, MODE == RM_DEPTH ? AVSIM_RD_WAVES : 1) k_render_depth(const float* __restrict__ recs, const int* __restrict__ counts, const float4* __restrict__ heads,
                                                       const float4* __restrict__ tplanes, const float4* __restrict__ fboxes, const float4* __restrict__ sedges, int nplane, int nedge,
                                                       const float* __restrict__ cam_fovy, const int* __restrict__ cam_ids, int ncam_sel, int ngeom, int H,
                                                       int W, float znear, float zfar, float* __restrict__ out, const float* __restrict__ geom_rgba, const float* __restrict__ light,
-                                                      const float* __restrict__ camaux, unsigned char* __restrict__ out_rgb, const int bin_tx) {
+                                                      const float* __restrict__ camaux, unsigned char* __restrict__ out_u8, const int bin_tx, const unsigned short* __restrict__ lut) {
     __shared__ float4 hA[BL_MAX], hB[BL_MAX], hC[BL_MAX];
     __shared__ float4 arena[ARENA4];
     __shared__ int ncand, arena_top, next_tile;
@@ -965,7 +1029,7 @@ __global__ void __launch_bounds__(256, RGB ? 1 : AVSIM_RD_WAVES) k_render_depth(
 #else
         const int cast_cnt = cnt;
 #endif
-        render_tile<RGB>(lane, tix * TILE_W, tiy * TILE_H, cs, env, hA, hB, hC, arena, cast_cnt, R, tplanes, fboxes, sedges, nplane, nedge, scale, ncam_sel, H, W, znear, zfar, out, geom_rgba, light, camaux, out_rgb);
+        render_tile<MODE>(lane, tix * TILE_W, tiy * TILE_H, cs, env, hA, hB, hC, arena, cast_cnt, R, tplanes, fboxes, sedges, nplane, nedge, scale, ncam_sel, H, W, znear, zfar, out, geom_rgba, light, camaux, out_u8, lut, ngeom);
     }
 }
 
@@ -1098,6 +1162,11 @@ struct RenderHost {
     }
     // d_out: device float[N][ncam_sel][H][W], or (rgb) u8[N][ncam_sel][H][W][3]; body poses must already be in d_xpose (same stream)
     int launch(hipStream_t st, const int* cam_ids_host, int ncam_sel, int H, int W, void* d_out, bool rgb, std::string& err) {
+        return launch_mode(st, cam_ids_host, ncam_sel, H, W, rgb ? RM_RGB : RM_DEPTH, rgb ? nullptr : (float*)d_out, rgb ? (unsigned char*)d_out : nullptr, nullptr, err);
+    }
+    // mode RM_LABELS / RM_LABELS_PK: d_depth float[N][ncam_sel][H][W] and d_u8 u8[N][ncam_sel][H][W], either may be null; d_lut: ngeom + 1 table entries
+    // (label | LUT_DROP), device memory that stays as it is until the pass has run
+    int launch_mode(hipStream_t st, const int* cam_ids_host, int ncam_sel, int H, int W, int mode, float* d_depth, unsigned char* d_u8, const unsigned short* d_lut, std::string& err) {
         if (ncam_sel < 1 || ncam_sel > 16 || H < 1 || W < 1 || H > 4096 || W > 4096) { err = "avsim_render_depth: bad camera count or image size"; return -1; }
         for (int c = 0; c < ncam_sel; c++)
             if (cam_ids_host[c] < 0 || cam_ids_host[c] >= m.ncam) { err = "avsim_render_depth: camera index out of range"; return -1; }
@@ -1133,13 +1202,18 @@ struct RenderHost {
             hipLaunchKernelGGL(k_render_heads, dim3(ncam_sel * n), dim3(256), 0, st, (const float*)d_recs, (const int*)d_counts, (const int*)d_order, (const float4*)d_sedge, m.nedge, m.cam_fovy,
                                (const int*)d_cam_ids, ncam_sel, m.ngeom, H, W, (float4*)d_heads, bin_tx);
             if (timing && e0 == 0 && timer.begin(st) != hipSuccess) { err = "hipEventCreate failed"; return -3; }       // (the image kernel's time; with more than one chunk the later chunks' set-up kernels are inside)
-            const size_t px = (size_t)e0 * ncam_sel * H * W;
-            if (rgb)
-                hipLaunchKernelGGL(k_render_depth<true>, dim3(nblk), dim3(256), 0, st, (const float*)d_recs, (const int*)d_counts, (const float4*)d_heads, (const float4*)d_tplanes, (const float4*)d_fbox, (const float4*)d_sedge, m.nplane, m.nedge,
-                                   m.cam_fovy, (const int*)d_cam_ids, ncam_sel, m.ngeom, H, W, m.znear, m.zfar, (float*)nullptr, m.geom_rgba, m.light, (const float*)aux, (unsigned char*)d_out + px * 3, bin_tx);
-            else
-                hipLaunchKernelGGL(k_render_depth<false>, dim3(nblk), dim3(256), 0, st, (const float*)d_recs, (const int*)d_counts, (const float4*)d_heads, (const float4*)d_tplanes, (const float4*)d_fbox, (const float4*)d_sedge, m.nplane, m.nedge,
-                                   m.cam_fovy, (const int*)d_cam_ids, ncam_sel, m.ngeom, H, W, m.znear, m.zfar, (float*)d_out + px, m.geom_rgba, m.light, (const float*)aux, (unsigned char*)nullptr, bin_tx);
+            const size_t px = (size_t)e0 * ncam_sel * H * W;      // the chunk's first pixel: floats of the depth image, bytes of the label image, three bytes of the colour image
+            float* const o_f = d_depth ? d_depth + px : nullptr;
+            unsigned char* const o_u8 = d_u8 ? d_u8 + px * (mode == RM_RGB ? 3 : 1) : nullptr;
+#define AVS_RENDER_LAUNCH(M)                                                                                                                                                                \
+            hipLaunchKernelGGL(k_render_depth<M>, dim3(nblk), dim3(256), 0, st, (const float*)d_recs, (const int*)d_counts, (const float4*)d_heads, (const float4*)d_tplanes, (const float4*)d_fbox, \
+                               (const float4*)d_sedge, m.nplane, m.nedge, m.cam_fovy, (const int*)d_cam_ids, ncam_sel, m.ngeom, H, W, m.znear, m.zfar, o_f, m.geom_rgba, m.light, (const float*)aux, o_u8,  \
+                               bin_tx, d_lut)
+            if (mode == RM_RGB) AVS_RENDER_LAUNCH(RM_RGB);
+            else if (mode == RM_LABELS) AVS_RENDER_LAUNCH(RM_LABELS);
+            else if (mode == RM_LABELS_PK) AVS_RENDER_LAUNCH(RM_LABELS_PK);
+            else AVS_RENDER_LAUNCH(RM_DEPTH);
+#undef AVS_RENDER_LAUNCH
         }
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) { err = std::string("render kernel launch: ") + hipGetErrorString(e); return -3; }

@@ -221,6 +221,16 @@ class GuidedVisionEnv(_EnvBase):
         img = self.sim.render_depth(list(cameras), h, w)
         return {c: self._squeeze(img[:, i]) for i, c in enumerate(cameras)}
 
+    def render_segmentation(self, cameras=("zed_cam_left", "zed_cam_right", "wrist_cam_left", "wrist_cam_right"), height=None, width=None, kind="class"):
+        """Label images (uint8: what each pixel of render_depth's image shows) of the named cameras at the current state, the reference
+        stack's render(segmentation=True): {camera: [H, W]} for one env, {camera: [num_envs, H, W]} for a batch.  kind: "class" (the names:
+        self.sim.label_table("class")[1]), "body", "geom" or a table (BatchedSim.render_labels)."""
+        assert all(c in CAMERAS for c in cameras), f"Invalid camera names: {cameras}"
+        h = self.observation_height if height is None else height
+        w = self.observation_width if width is None else width
+        img, _ = self.sim.render_labels(list(cameras), h, w, kind=kind, depth=False)
+        return {c: self._squeeze(img[:, i]) for i, c in enumerate(cameras)}
+
     def _swap_model(self, arms):
         """The base position of the camera arm is a constant of the compiled model, so moving it (env.py:394-398) means
         continuing on the other blob of the same task: identical state layout, the arm parked at (0, -2.4, -0.4) or in place.

@@ -1,5 +1,5 @@
 """The device image calls of libavsim (include/avsim.h) from Python.  ImageCalls implements compose and label, image statistics, prep, jitter,
-augment, resize, camera poses, point clouds, voxel grids and virtual views once each, against one of two array adaptors: HostArrays (numpy; BatchedSim) and DeviceArrays
+augment, resize, camera poses, label images, point clouds, voxel grids and virtual views once each, against one of two array adaptors: HostArrays (numpy; BatchedSim) and DeviceArrays
 (torch tensors on a device; DeviceImageOps, which VecEnv inherits).  The adaptors hold all that differs between the fronts:
   * numpy converts what it is given (np.ascontiguousarray of the pixels, values= to int64, lut= to float32 [-1, 3, 256]); torch takes
     contiguous tensors of the right type on the owner's device and fails an assert for anything else;
@@ -302,6 +302,38 @@ class ImageCalls:
         out = A.empty(self, (self.h.num_envs, len(ids), 16), "float32")
         check_call(self.h, self.h.L.avsim_camera_poses(self.h.h, ids.ctypes.data, len(ids), A.ptr(out)))
         return out
+
+    def label_table(self, kind="class"):
+        """(table uint8 [ngeom + 1], names) of the owner's model: segment.label_table, made once per kind."""
+        from . import segment
+        cache = self.__dict__.setdefault("_label_tables", {})
+        if kind not in cache:
+            if "model" not in cache:
+                cache["model"] = segment.read_model(self.manifest)
+            cache[kind] = segment.label_table(self.manifest, cache["model"], kind)
+        return cache[kind]
+
+    def render_labels(self, cameras, height, width, kind="class", drop=(), depth=True, out=None):
+        """(labels uint8 [N, len(cameras), height, width], depth float32 of the same shape or None): what every pixel of the named
+        cameras' depth image shows at the current state (avsim_render_labels; av_aloha_amd.segment has the tables and the specification).
+        kind: "class" (segment.FIXED_CLASSES, then the task's bodies; label_table("class")[1] names them), "body", "geom", or a table --
+        HOST uint8 [ngeom + 1], the label of every collision geom and, last, of nothing.  drop: HOST class names (of a named kind) or label
+        values; a pixel with such a label gets the far plane (30 m) as its depth, so that point_cloud, voxel_grid and virtual_views given
+        this depth leave it out; labels keeps the true label.  Where nothing is dropped, depth is render_depth's image bit for bit.
+        depth=False: no depth image (drop is then refused).  out: the label array to write.  ValueError for what the library refuses."""
+        from . import segment
+        A = self._arrays
+        A.begin(self)
+        ids = camera_ids(self.manifest, cameras)
+        N, height, width = self.h.num_envs, int(height), int(width)
+        table, names = self.label_table(kind) if isinstance(kind, str) else (np.ascontiguousarray(kind), None)
+        flags = segment.drop_flags(drop, names)
+        segment.check_labels(len(self.manifest["camera_names"]), len(self.manifest["geom_names"]), ids, height, width, table, flags, depth=bool(depth))
+        shape = (N, len(ids), height, width)
+        out = self._out("render_labels", out, shape, "uint8", "uint8 [N, cameras, height, width]")
+        dep = A.empty(self, shape, "float32") if depth else None
+        check_call(self.h, self.h.L.avsim_render_labels(self.h.h, ids.ctypes.data, len(ids), height, width, table.ctypes.data, _ffi.ptr(flags), _ffi.ptr(dep), A.ptr(out)))
+        return out, dep
 
     def point_cloud(self, cameras, height, width, bounds, npoints, max_depth=None, depth=None):
         """(xyz float32 [N, P, 3], index int32 [N, P], count int32 [N, 2]): one cloud per env in the world frame from the depth images of the

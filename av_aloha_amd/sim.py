@@ -4,7 +4,7 @@ This is the batched engine under the gym-style environments in env.py; every met
 into the C-ABI (include/avsim.h).  There is no CPU fallback.
 
 compose, compose_label, image_stats, prep_images, jitter_images, augment_images, resize_images, camera_poses,
-point_cloud, voxel_grid and virtual_views are images.ImageCalls's -- the one implementation that the torch front (images.DeviceImageOps, VecEnv)
+render_labels, point_cloud, voxel_grid and virtual_views are images.ImageCalls's -- the one implementation that the torch front (images.DeviceImageOps, VecEnv)
 runs too -- through images.HostArrays: numpy arrays in and out, inputs converted with np.ascontiguousarray, a wrong
 `out` or canvas a ValueError, image_stats in uint64 with its index checked, and no stream to bind (the handle is in
 host I/O mode and synchronous).  The JPEG methods here speak lists of bytes and stay this class's own."""

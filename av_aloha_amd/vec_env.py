@@ -25,6 +25,13 @@ per-env episodes and gymnasium's NEXT_STEP autoreset done by the library's kerne
   [N, V, VH, VW] is the winning source pixel (-1: none).  The depth, and with "colour" the u8 colour images, are rendered at the option's own
   size into its own buffers.  Refused together with "render_cam_major" / `cameras`, as voxels are; allowed next to pointcloud and voxels.
   None (the default): no call, buffer or key changes.
+* segmentation={"cameras": [...], "height": h, "width": w, "kind": "class"} adds `observation.segmentation` uint8 [N, ncam, h, w] (gym
+  format: `segmentation[cam]` uint8 [N, h, w]): what every pixel of those cameras' depth image shows (avsim_render_labels into its own
+  buffer; av_aloha_amd/segment.py has the tables), and `env.segmentation_classes`, the names of the labels.  pointcloud, voxels and views
+  accept "drop": [class names] -- their depth buffer is then filled by avsim_render_labels with those classes at the far plane, so the
+  robot (segment.ROBOT_CLASSES) leaves the cloud, the grid or the views --, and pointcloud also "labels": True, which adds
+  `info["pointcloud_label"]` uint8 [N, P]: the class of every point (255 where `pointcloud_index` is -1).  None / no "drop" (the defaults): no
+  call, buffer or key changes.
 * Every tensor returned is a preallocated buffer that the next reset / step overwrites: clone what must outlive the call.
 * NEXT_STEP: an env whose episode ended (terminated or truncated) in call t starts its next episode in call t + 1, whose action does
   not reach it; that call reports reward 0, flags 0, elapsed 0, the new `info["episode_id"]` and the new episode's first observation.
@@ -100,12 +107,13 @@ def sample_poses(task, seed, episode_ids):
 class VecEnv(DeviceImageOps):
     """num_envs envs of one task on one GPU; see the module's docstring for the semantics.  The image calls on any tensor of the env's device
     -- decode_jpeg, encode_images, compose, compose_label, image_stats, prep_images, jitter_images, augment_images, resize_images -- and
-    camera_poses / point_cloud / voxel_grid / virtual_views on demand are images.DeviceImageOps's (images.ImageCalls on tensors)."""
+    camera_poses / render_labels / point_cloud / voxel_grid / virtual_views on demand are images.DeviceImageOps's (images.ImageCalls on tensors)."""
 
     metadata = {"autoreset_mode": "NextStep", "render_modes": []}
 
     def __init__(self, task, num_arms, num_envs, max_episode_steps, device=None, cameras=(), depth_cameras=(), obs_format="lerobot",
-                 seed=0, terminate_on_success=False, f64=False, options=None, observation_height=480, observation_width=640, pointcloud=None, voxels=None, views=None):
+                 seed=0, terminate_on_success=False, f64=False, options=None, observation_height=480, observation_width=640, pointcloud=None, voxels=None, views=None,
+                 segmentation=None):
         import torch
         assert obs_format in ("lerobot", "gym"), obs_format
         assert all(c in CAMERAS for c in list(cameras) + list(depth_cameras)), "Invalid camera names"
@@ -144,6 +152,16 @@ class VecEnv(DeviceImageOps):
                   "radius": int(vv.get("radius", 1)), "bounds": np.ascontiguousarray(vv["bounds"], dtype=np.float32).reshape(-1), "colour": bool(vv.get("colour", True)),
                   "max_depth": float(pcspec.FAR_PLANE if vv.get("max_depth") is None else vv["max_depth"])}
             vvspec.check_virtual_views(len(self.manifest["camera_names"]), vv["ids"], vv["height"], vv["width"], vv["bounds"], vv["max_depth"], vv["codes"], vv["size"], vv["radius"])
+        sg = None
+        if segmentation is not None:    # likewise
+            from . import segment
+            sg = dict(segmentation)
+            cams = list(sg["cameras"])
+            assert all(c in CAMERAS for c in cams), "Invalid camera names"
+            kind = sg.get("kind", "class")
+            table, names = self.label_table(kind) if isinstance(kind, str) else (np.ascontiguousarray(kind), None)
+            sg = {"cameras": cams, "ids": camera_ids(self.manifest, cams), "height": int(sg["height"]), "width": int(sg["width"]), "table": table, "names": names}
+            segment.check_labels(len(self.manifest["camera_names"]), len(self.manifest["geom_names"]), sg["ids"], sg["height"], sg["width"], table, None, depth=False)
         flags = _ffi.AVSIM_IO_DEVICE | (_ffi.AVSIM_F64_PHYSICS if f64 else 0)
         with torch.cuda.device(self.device):
             self.h = _ffi.Handle(blob, self.num_envs, self.device.index, flags)
@@ -196,7 +214,9 @@ class VecEnv(DeviceImageOps):
             b = np.ascontiguousarray(pc["bounds"], dtype=np.float32).reshape(-1)
             md = float(pcspec.FAR_PLANE if pc.get("max_depth") is None else pc["max_depth"])
             pcspec.check_point_cloud(len(self.manifest["camera_names"]), ids, ph, pw, b, md, P)
-            self._pc = {"cameras": cams, "ids": ids, "height": ph, "width": pw, "bounds": b, "points": P, "max_depth": md,
+            self._pc = {"cameras": cams, "ids": ids, "height": ph, "width": pw, "bounds": b, "points": P, "max_depth": md, **self._drop_of(pc),
+                        "labels": torch.zeros((N, len(cams), ph, pw), dtype=torch.uint8, device=dev) if pc.get("labels") else None,
+                        "label": torch.zeros((N, P), dtype=torch.uint8, device=dev) if pc.get("labels") else None,
                         "depth": torch.zeros((N, len(cams), ph, pw), dtype=torch.float32, device=dev),
                         "xyz": torch.zeros((N, P, 3), dtype=torch.float32, device=dev), "index": torch.zeros((N, P), dtype=torch.int32, device=dev),
                         "count": torch.zeros((N, 2), dtype=torch.int32, device=dev)}
@@ -204,16 +224,20 @@ class VecEnv(DeviceImageOps):
         if vx is not None:          # a dense world-frame grid per env as an observation: its own cameras, size, depth and colour buffers
             grid = torch.zeros((N,) + vx["g"] + (8,), dtype=torch.float32, device=dev)
             nc = len(vx["cameras"])
-            self._vox = {**vx, "dims": np.array(vx["g"], dtype=np.int32), "depth": torch.zeros((N, nc, vx["height"], vx["width"]), dtype=torch.float32, device=dev),
+            self._vox = {**vx, **self._drop_of(voxels), "dims": np.array(vx["g"], dtype=np.int32), "depth": torch.zeros((N, nc, vx["height"], vx["width"]), dtype=torch.float32, device=dev),
                          "rgb": torch.zeros((N, nc, vx["height"], vx["width"], 3), dtype=torch.uint8, device=dev) if vx["colour"] else None,
                          "grid": grid, "view": grid.permute(0, 4, 1, 2, 3)}
         self._vv = None
         if vv is not None:          # RVT's orthographic images of the box per env as an observation: their own cameras, size, depth and colour buffers
             nc, vshape = len(vv["cameras"]), (N, len(vv["codes"]), int(vv["size"][0]), int(vv["size"][1]))
             out = torch.zeros(vshape + (8,), dtype=torch.float32, device=dev)
-            self._vv = {**vv, "depth": torch.zeros((N, nc, vv["height"], vv["width"]), dtype=torch.float32, device=dev),
+            self._vv = {**vv, **self._drop_of(views), "depth": torch.zeros((N, nc, vv["height"], vv["width"]), dtype=torch.float32, device=dev),
                         "rgb": torch.zeros((N, nc, vv["height"], vv["width"], 3), dtype=torch.uint8, device=dev) if vv["colour"] else None,
                         "out": out, "view": out.permute(0, 1, 4, 2, 3), "index": torch.zeros(vshape, dtype=torch.int32, device=dev)}
+        self._seg = None
+        if sg is not None:          # what every pixel shows as an observation: its own cameras, size and label buffer
+            self._seg = {**sg, "labels": torch.zeros((N, len(sg["cameras"]), sg["height"], sg["width"]), dtype=torch.uint8, device=dev)}
+            self.segmentation_classes = sg["names"]
         self._bind_stream()
         self._setup(self.seed, 0)
 
@@ -223,6 +247,24 @@ class VecEnv(DeviceImageOps):
         self.seed, self._log_capacity = int(seed), int(log_capacity)
         self.h.check(self.L.avsim_episode_setup(self.h.h, self._box.ctypes.data, self._share.ctypes.data, self.seed & 0xFFFFFFFFFFFFFFFF,
                                                 self.max_episode_steps, int(self.terminate_on_success), self._log_capacity))
+
+    def _drop_of(self, option):
+        """{"table", "drop"} of a pointcloud / voxels / views option: the class table and the flags of its "drop" names, None without any."""
+        if not option.get("drop") and not option.get("labels"):
+            return {"table": None, "drop": None}
+        from . import segment
+        table, names = self.label_table("class")
+        return {"table": table, "drop": segment.drop_flags(option.get("drop"), names)}
+
+    def _depth_of(self, o):
+        """The depth buffer of a pointcloud / voxels / views option: avsim_render_depth's image, or -- with "drop" or "labels" -- avsim_render_labels's,
+        the dropped classes at the far plane."""
+        ids, nc = o["ids"].ctypes.data, len(o["cameras"])
+        if o["table"] is None:
+            self.h.check(self.L.avsim_render_depth(self.h.h, ids, nc, o["height"], o["width"], o["depth"].data_ptr()))
+        else:
+            self.h.check(self.L.avsim_render_labels(self.h.h, ids, nc, o["height"], o["width"], o["table"].ctypes.data, _ffi.ptr(o["drop"]), o["depth"].data_ptr(),
+                                                    _ffi.ptr(o.get("labels"))))
 
     def _obs(self):
         L, h = self.L, self.h.h
@@ -246,14 +288,17 @@ class VecEnv(DeviceImageOps):
         if self._pc is not None:
             pc = self._pc
             ids, nc = pc["ids"].ctypes.data, len(pc["cameras"])
-            self.h.check(L.avsim_render_depth(h, ids, nc, pc["height"], pc["width"], pc["depth"].data_ptr()))
+            self._depth_of(pc)
             self.h.check(L.avsim_point_cloud(h, ids, nc, pc["height"], pc["width"], pc["depth"].data_ptr(), pc["bounds"].ctypes.data, pc["max_depth"], pc["points"],
                                              pc["xyz"].data_ptr(), pc["index"].data_ptr(), pc["count"].data_ptr()))
+            if pc["labels"] is not None:        # the class image gathered at the points' pixels
+                self.torch.gather(pc["labels"].view(self.num_envs, -1), 1, pc["index"].clamp(min=0).long(), out=pc["label"])
+                pc["label"].masked_fill_(pc["index"] < 0, 255)
             obs["observation.pointcloud" if self.obs_format == "lerobot" else "pointcloud"] = pc["xyz"]
         if self._vox is not None:
             vx = self._vox
             ids, nc = vx["ids"].ctypes.data, len(vx["cameras"])
-            self.h.check(L.avsim_render_depth(h, ids, nc, vx["height"], vx["width"], vx["depth"].data_ptr()))
+            self._depth_of(vx)
             if vx["rgb"] is not None:
                 self.h.check(L.avsim_render_rgb(h, ids, nc, vx["height"], vx["width"], vx["rgb"].data_ptr()))
             self.h.check(L.avsim_voxel_grid(h, ids, nc, vx["height"], vx["width"], vx["depth"].data_ptr(), _ffi.ptr(vx["rgb"]), vx["bounds"].ctypes.data, vx["max_depth"],
@@ -262,17 +307,26 @@ class VecEnv(DeviceImageOps):
         if self._vv is not None:
             vv = self._vv
             ids, nc = vv["ids"].ctypes.data, len(vv["cameras"])
-            self.h.check(L.avsim_render_depth(h, ids, nc, vv["height"], vv["width"], vv["depth"].data_ptr()))
+            self._depth_of(vv)
             if vv["rgb"] is not None:
                 self.h.check(L.avsim_render_rgb(h, ids, nc, vv["height"], vv["width"], vv["rgb"].data_ptr()))
             self.h.check(L.avsim_virtual_views(h, ids, nc, vv["height"], vv["width"], vv["depth"].data_ptr(), _ffi.ptr(vv["rgb"]), vv["bounds"].ctypes.data, vv["max_depth"],
                                                vv["codes"].ctypes.data, len(vv["codes"]), vv["size"].ctypes.data, vv["radius"], vv["out"].data_ptr(), vv["index"].data_ptr()))
             obs["observation.virtual_views" if self.obs_format == "lerobot" else "virtual_views"] = vv["view"]
+        if self._seg is not None:
+            sg = self._seg
+            self.h.check(L.avsim_render_labels(h, sg["ids"].ctypes.data, len(sg["cameras"]), sg["height"], sg["width"], sg["table"].ctypes.data, None, None, sg["labels"].data_ptr()))
+            if self.obs_format == "lerobot":
+                obs["observation.segmentation"] = sg["labels"]
+            else:
+                obs["segmentation"] = {c: sg["labels"][:, i] for i, c in enumerate(sg["cameras"])}
         return obs
 
     def _pc_info(self, info):
         if self._pc is not None:
             info["pointcloud_count"], info["pointcloud_index"] = self._pc["count"], self._pc["index"]
+            if self._pc["label"] is not None:
+                info["pointcloud_label"] = self._pc["label"]
         if self._vv is not None:
             info["virtual_views_index"] = self._vv["index"]
         return info
@@ -391,11 +445,13 @@ class VecEnv(DeviceImageOps):
 
 
 def make_vec(env_id, num_envs, max_episode_steps, device=None, cameras=None, depth_cameras=(), obs_format="lerobot", seed=0,
-             terminate_on_success=False, f64=False, options=None, observation_height=None, observation_width=None, pointcloud=None, voxels=None, views=None):
-    """A VecEnv of a registry id (env.ENVS); cameras default to the registry's, the image size to its 480 x 640.  pointcloud, voxels, views: VecEnv's."""
+             terminate_on_success=False, f64=False, options=None, observation_height=None, observation_width=None, pointcloud=None, voxels=None, views=None,
+             segmentation=None):
+    """A VecEnv of a registry id (env.ENVS); cameras default to the registry's, the image size to its 480 x 640.  pointcloud, voxels, views, segmentation: VecEnv's."""
     spec = ENVS[env_id]
     return VecEnv(_TASK_OF_CLASS[spec["env"]], spec["num_arms"], num_envs, max_episode_steps, device=device,
                   cameras=spec["cameras"] if cameras is None else cameras, depth_cameras=depth_cameras, obs_format=obs_format, seed=seed,
                   terminate_on_success=terminate_on_success, f64=f64, options=options,
                   observation_height=spec["observation_height"] if observation_height is None else observation_height,
-                  observation_width=spec["observation_width"] if observation_width is None else observation_width, pointcloud=pointcloud, voxels=voxels, views=views)
+                  observation_width=spec["observation_width"] if observation_width is None else observation_width, pointcloud=pointcloud, voxels=voxels, views=views,
+                  segmentation=segmentation)

@@ -110,7 +110,7 @@ int avsim_dims(const avsim_t* h, int32_t dims[AVSIM_NDIMS]);
  *   "order_envs"        1 (default): workgroups take the envs in the order of their cost in the previous step, most expensive
  *                       first (results do not depend on it); 0 = in index order
  *   "export_contacts"   0 skips the per-step contact export (avsim_get_contacts); "kernel_timing" 1 brackets every physics
- *                       launch AND every image kernel of avsim_render_depth / the proxy mode of avsim_render_rgb with HIP events
+ *                       launch AND every image kernel of avsim_render_depth / avsim_render_labels / the proxy mode of avsim_render_rgb with HIP events
  *                       (avsim_kernel_time, avsim_render_kernel_time; at most 1024 event pairs are kept per list, older ones are folded
  *                       into a running sum); "profile_phases" 1 enables avsim_get_phase_cycles */
 int avsim_set_option(avsim_t* h, const char* name, double value);
@@ -220,6 +220,26 @@ int avsim_camera_count(const avsim_t* h);
  * u8 image of the same call, bit for bit.  Needs the visual scene (avsim_load_visual, render_proxies 0).  Pointer conventions as
  * avsim_render_depth; in device mode nothing synchronises once a call with the same cameras has run. */
 int avsim_render_rgb_f32(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width, float* out);
+
+/* What every pixel of avsim_render_depth's image shows (k_render_depth's labels mode); av_aloha_amd/segment.py is the
+ * specification and holds the tables.  The same cast of the same collision proxies, with the winning geom kept: labels =
+ * uint8[N][ncam][height][width], table[g] of the geom g the pixel sees (g indexes the model's collision geom table, manifest "geom_names"),
+ * table[ngeom] where it sees nothing.  table NULL is the identity, table[g] = g, with 255 for nothing.  depth = float32 of the same shape:
+ * where the pixel's label is not dropped, avsim_render_depth's image of the same state, cameras and size BIT FOR BIT; where drop[label] != 0,
+ * the far plane (30 m), the value of a ray that hits nothing -- so that avsim_point_cloud, avsim_voxel_grid and avsim_virtual_views, which
+ * keep d < max_depth, leave those pixels out (the robot leaves a cloud this way).  labels always holds the true label, dropped or not.
+ * Either output may be NULL, not both.  depth and labels follow the handle's I/O mode; with AVSIM_IO_DEVICE and a width that is a multiple
+ * of 4, depth is 16-byte and labels 4-byte aligned (a row's four pixels leave in one store).  cam_ids, table (ngeom + 1 entries) and drop
+ * (256 flags) are HOST arrays in both modes, copied before the call returns.  The body poses are refreshed when they are another state's,
+ * as the render calls do; the envs go through the kernels in the chunks of option "render_chunk".  With AVSIM_IO_DEVICE nothing
+ * synchronises once a call of the same size has run.  Invisible geoms (the pin spheres) are never drawn; their table entries are unused.
+ * AVSIM_EINVAL, with nothing launched and the outputs untouched: ncam outside 1..16, height or width outside 1..4096, a camera id out of
+ * range, a null cam_ids, depth and labels both NULL, drop given with depth NULL, a misaligned device pointer (above).
+ * Debug option "render_labels_form" 1 keeps a lane's eight winners in eight registers instead of two: the same images, there so that
+ * tools/bench_segment.py can time both in one process. */
+int avsim_render_labels(avsim_t* h, const int32_t* cam_ids, int ncam, int height, int width,
+                        const uint8_t* table /* host [ngeom + 1] or NULL */, const uint8_t* drop /* host [256] or NULL */,
+                        float* depth /* [N][ncam][H][W] or NULL */, uint8_t* labels /* [N][ncam][H][W] or NULL */);
 
 /* Point clouds from depth images on the device (csrc/avsim_pointcloud.hip); av_aloha_amd/pointcloud.py is the specification.
  * avsim_camera_poses: out = float32[N][ncam][16], the world pose of camera cam_ids[c] in every env at the CURRENT state -- position pc[3],
@@ -595,7 +615,7 @@ int avsim_event_elapsed_ms(avsim_t* h, int slot_a, int slot_b, float* ms); /* sy
  * HIP events around every launch (on the launch stream, no per-launch synchronisation) when enabled via
  * avsim_set_option("kernel_timing", 1); this call synchronises on the recorded events */
 int avsim_kernel_time(avsim_t* h, int reset, double* total_ms, int64_t* launches);
-/* the same for the image kernel of avsim_render_depth / the proxy mode of avsim_render_rgb (k_render_depth alone: the pose pass
+/* the same for the image kernel of avsim_render_depth / avsim_render_labels / the proxy mode of avsim_render_rgb (k_render_depth alone: the pose pass
  * and the per-view set-up kernel in front of it are not in the figure) */
 int avsim_render_kernel_time(avsim_t* h, int reset, double* total_ms, int64_t* launches);
 
