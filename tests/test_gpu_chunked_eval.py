@@ -13,18 +13,9 @@ import pytest
 from av_aloha_amd import chunks as ck
 from av_aloha_amd.harness import chunked_policy, evaluate_vec
 from av_aloha_amd.vec_env import make_vec
+from gpu_util import torch
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
 
 PEG = "gym_guided_vision/InsertPeg-3Arms-v0"
 N, STEPS, EPISODES, C = 5, 6, 12, 4
@@ -39,7 +30,6 @@ def venv():
 
 
 def make_predictor(venv, log):
-    import torch
     k = torch.arange(C, dtype=torch.float32, device=venv.device)[None, :, None]
     a = torch.arange(venv.nj, dtype=torch.float32, device=venv.device)[None, None, :]
 
@@ -54,7 +44,6 @@ def make_predictor(venv, log):
 
 def evaluate(venv, **kw):
     """-> (the executor, the records of evaluate_vec, one dict per select_action call)"""
-    import torch
     log, calls = {}, []
     venv.reset(seed=3)
     mask = torch.zeros(N, dtype=torch.bool, device=venv.device)

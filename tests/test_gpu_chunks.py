@@ -11,27 +11,14 @@ from av_aloha_amd import chunks as ck
 from av_aloha_amd import images
 from av_aloha_amd.sim import BatchedSim
 from av_aloha_amd.vec_env import make_vec
+from avsim_test_util import same
+from gpu_util import torch as T
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
 
 PEG = "gym_guided_vision/InsertPeg-3Arms-v0"
 SHAPES = [(1, 1), (2, 1), (3, 2), (5, 21), (100, 21), (7, 14)]
 COEFFS = [0.01, 0.0, -0.5]
-
-
-def torch():
-    import torch as t
-    return t
 
 
 @pytest.fixture(scope="module")
@@ -61,19 +48,12 @@ def stats_for(A, seed=11):
 
 
 def info_of(env, ids, elapsed):
-    T = torch()
     return {"episode_id": T.from_numpy(np.ascontiguousarray(ids, dtype=np.int64)).to(env.device),
             "elapsed_steps": T.from_numpy(np.ascontiguousarray(elapsed, dtype=np.int32)).to(env.device)}
 
 
-def same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.dtype == b.dtype == np.float32 and a.shape == b.shape and not np.isnan(a).any() and not np.isnan(b).any() and np.array_equal(a, b)
-
-
 def run(env, ac, ref, x, ids, elapsed, give=None):
     """calls t = 0 .. len(x)-1 with ids[t], elapsed[t]; give[t] False: chunks=None.  Every action equal."""
-    T = torch()
     xd = T.from_numpy(x).to(env.device)
     for t in range(len(x)):
         g = give is None or give[t]
@@ -136,7 +116,7 @@ def test_queue_need_none_calls_and_starvation(envs, C, k, f):
     N, A, calls = 5, 21, 3 * k + 9
     env = envs(N)
     x = predictions(calls, N, C, A, seed=C * 8 + k)
-    xd = torch().from_numpy(x).to(env.device)
+    xd = T.from_numpy(x).to(env.device)
     for stats in (None, stats_for(A)):
         ac = ck.ActionChunks(env, C, A, n_action_steps=k, first=f, stats=stats)
         ref = ac.reference()
@@ -203,7 +183,6 @@ def test_refusals_leave_the_state_alone(envs):
 
 
 def test_calls_before_the_setup_are_refused():
-    T = torch()
     env = make_vec(PEG, 2, 10, cameras=[])
     try:
         L, h = env.L, env.h.h
@@ -234,7 +213,7 @@ def test_a_second_setup_and_reset_start_over(envs):
     run(env, ac, ref, x[:3], ids[:3], elapsed[:3])
     ac.reset()
     ref.reset()
-    a = ac.step(torch().from_numpy(x[3]).to(env.device), info_of(env, ids[3], elapsed[3])).cpu().numpy()
+    a = ac.step(T.from_numpy(x[3]).to(env.device), info_of(env, ids[3], elapsed[3])).cpu().numpy()
     assert same(a, x[3][:, 0]) and same(a, ref.step(x[3], ids[3], elapsed[3]))
     run(env, ac, ref, x[4:], ids[4:], elapsed[4:])
 
@@ -242,7 +221,6 @@ def test_a_second_setup_and_reset_start_over(envs):
 # ---- the stream ----------------------------------------------------------------------------------------------------------------------
 def test_back_to_back_calls_with_the_chunk_tensor_overwritten(envs):
     """twenty calls with no host wait in between; the one chunk tensor is overwritten as soon as each call has returned"""
-    T = torch()
     N, C, A, calls = 70, 4, 21, 20
     env = envs(N)
     ids, elapsed = fresh_schedule(N, calls)
@@ -263,7 +241,6 @@ def test_back_to_back_calls_with_the_chunk_tensor_overwritten(envs):
 
 @pytest.mark.parametrize("ensemble", [0.01, None])
 def test_need_and_step_do_not_synchronise(envs, ensemble):
-    T = torch()
     N, C, A = 70, 4, 21
     env = envs(N)
     ac = ck.ActionChunks(env, C, A, ensemble=ensemble)

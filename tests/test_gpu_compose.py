@@ -8,22 +8,13 @@ import os
 import numpy as np
 import pytest
 
-from av_aloha_amd import _ffi, compose, harness, jpeg, mjpeg
-from av_aloha_amd.sim import BatchedSim
+from av_aloha_amd import compose, harness, jpeg, mjpeg
 from av_aloha_amd.vec_env import make_vec
-from avsim_test_util import blob
+from avsim_test_util import noise
+from gpu_util import torch as T
+from gpu_util import dev, sim          # noqa: F401  (module-scoped fixtures: this module gets its own handles)
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
 
 PEG = "gym_guided_vision/InsertPeg-3Arms-v0"
 GUARD = 4096
@@ -41,41 +32,9 @@ CASES = {"17x23-5x7": ((17, 23), (5, 7)),            # taps clipped at both edge
          "64x48-30x48": ((64, 48), (30, 48))}        # the horizontal pass skipped
 
 
-def torch():
-    import torch as t
-    return t
-
-
-def noise(shape, seed):
-    return np.random.default_rng(seed).integers(0, 256, shape, dtype=np.uint8)
-
-
 def to_f32(u8_nhwc):
     """u8 [n, H, W, 3] -> float32 [n, 3, H, W] = u8 / 255, the bits of avsim_render_rgb_f32 (and (int)(v * 255 + 0.5f) gives the u8 back)."""
-    T = torch()
     return (T.from_numpy(np.ascontiguousarray(u8_nhwc)).permute(0, 3, 1, 2).float() / 255).contiguous().numpy()
-
-
-def device_handle():
-    T = torch()
-    dev = T.device("cuda", T.cuda.current_device())
-    h = _ffi.Handle(blob("insert_peg"), 2, dev.index, _ffi.AVSIM_IO_DEVICE)
-    h.check(h.L.avsim_set_stream(h.h, T.cuda.current_stream().cuda_stream))
-    return h, dev
-
-
-@pytest.fixture(scope="module")
-def sim():
-    s = BatchedSim("insert_peg", 3, 2)
-    yield s
-    s.close()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    h, d = device_handle()
-    yield h, d
-    h.close()
 
 
 def call_host(sim, src, canvas, places, clear=None):
@@ -91,7 +50,6 @@ def call_host(sim, src, canvas, places, clear=None):
 def call_device(dev, src, canvas, places, clear=None):
     """The same through the device handle: src / canvas are torch tensors on the device."""
     h, _ = dev
-    T = torch()
     sf, df = int(src.dtype == T.float32), int(canvas.dtype == T.float32)
     n, H, W = (src.shape[0], src.shape[2], src.shape[3]) if sf else src.shape[:3]
     no, CH, CW = (canvas.shape[0], canvas.shape[2], canvas.shape[3]) if df else canvas.shape[:3]
@@ -102,7 +60,6 @@ def call_device(dev, src, canvas, places, clear=None):
 
 @pytest.mark.parametrize("case", list(CASES))
 def test_compose_equals_the_reference(sim, dev, case):
-    T = torch()
     (H, W), (h, w) = CASES[case]
     src = noise((2, H, W, 3), 1)
     src[0, :, :, 0] = np.linspace(0, 255, W).astype(np.uint8)[None]            # one channel a ramp
@@ -136,7 +93,6 @@ def test_compose_equals_the_reference(sim, dev, case):
 def guarded(nbytes, offset=0):
     """A device byte buffer with GUARD bytes of FILL on either side of `nbytes` bytes that start `offset` bytes past a dword boundary
     (the allocation is aligned, GUARD a multiple of four)."""
-    T = torch()
     whole = T.full((GUARD + offset + nbytes + GUARD,), FILL, dtype=T.uint8, device="cuda")
     return whole, whole[GUARD + offset:GUARD + offset + nbytes]
 
@@ -148,7 +104,6 @@ def guards_intact(whole, nbytes, offset=0):
 
 @pytest.mark.parametrize("offset", [0, 1])             # a canvas that starts on a dword (the fill kernel's dword path) and one that does not
 def test_grid_and_two_cameras_with_guards(dev, offset):
-    T = torch()
     # six distinct source images into a 2 x 3 grid in ONE call, cleared first
     src = np.stack([noise((17, 23, 3), 10 + i) for i in range(6)])
     rows, CH, CW = compose.layout_grid(6, 5, 7, cols=3)
@@ -184,7 +139,6 @@ def test_grid_and_two_cameras_with_guards(dev, offset):
 
 
 def test_what_the_library_refuses(sim, dev):
-    T = torch()
     src = noise((2, 34, 34, 3), 3)
     base = noise((1, 20, 20, 3), 4)
     bad = {"outside the canvas": [(0, 0, 14, 0, 7, 5)],
@@ -224,7 +178,6 @@ def test_what_the_library_refuses(sim, dev):
 
 
 def test_labels_equal_the_reference(sim, dev):
-    T = torch()
     h, d = dev
     values = [0, 7, 1234567890123, -45, -(1 << 63)]
     CH, CW = 30, 150
@@ -275,7 +228,6 @@ def test_labels_equal_the_reference(sim, dev):
 
 
 def test_vec_env_compose():
-    T = torch()
     env = make_vec(PEG, num_envs=2, max_episode_steps=10, cameras=["zed_cam_left"], observation_height=48, observation_width=64)
     try:
         obs, info = env.reset(seed=3)
@@ -422,7 +374,6 @@ def test_visualize_on_the_device_equals_the_host_path(tmp_path):
 
 
 def test_evaluate_vec_grid_video(tmp_path):
-    T = torch()
     env = make_vec(PEG, num_envs=4, max_episode_steps=3, cameras=["zed_cam_left"], observation_height=48, observation_width=64)
     try:
         ids = []

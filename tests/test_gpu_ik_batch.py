@@ -12,21 +12,12 @@ import pytest
 
 import ik_reference as R
 from avsim_test_util import blob
+from gpu_util import device_handle, torch as T
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 8
 PREFIXES = (1, 2, 3, 4, 5, 15, 16, 17, 63, 64, 65, 67)
-
-
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
 
 
 class Side:
@@ -38,11 +29,8 @@ class Side:
         from av_aloha_amd import _ffi
         self.ffi, self.device_mode = _ffi, device_mode
         if device_mode:
-            import torch as T
             self.T = T
-            self.dev = T.device("cuda", T.cuda.current_device())
-            self.h = _ffi.Handle(blob("slot_insertion", num_arms), 8, self.dev.index, _ffi.AVSIM_IO_DEVICE)
-            self.h.check(self.h.L.avsim_set_stream(self.h.h, T.cuda.current_stream().cuda_stream))
+            self.h, self.dev = device_handle("slot_insertion", 8, num_arms=num_arms)
         else:
             self.h = _ffi.Handle(blob("slot_insertion", num_arms), 8)
         self.L = self.h.L

@@ -7,23 +7,14 @@ import numpy as np
 import pytest
 
 from av_aloha_amd import _ffi, imgaug
-from av_aloha_amd.sim import BatchedSim
-from avsim_test_util import blob
+from avsim_test_util import noise
+from gpu_util import Guarded, torch as T
+from gpu_util import dev, sim          # noqa: F401  (module-scoped fixtures: this module gets its own handles)
 
 pytestmark = pytest.mark.gpu
 
-
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
-
 AFFINE = 32
-SENTINEL = 0xA5A5A5A5
+SENTINEL = 0xA5A5A5A5 - (1 << 32)      # as an int32
 LARGE = (2 * 16 + 3, 2 * 64 + 5)
 SIZES = [(1, 1), (2, 5), (3, 3), (5, 67), LARGE]
 MEAN, STD = [0.485, 0.456, 0.406], [0.229, 0.224, 0.225]
@@ -31,37 +22,11 @@ FAC_A, FAC_B = [0.8, 1.2, 1.5, 0.05, 1.2], [1.2, 0.8, 0.5, -0.05, 2.0]
 SCRATCH_DEFAULT = float(128 << 20)
 
 
-def torch():
-    import torch as t
-    return t
-
-
-def noise(shape, seed):
-    return np.random.default_rng(seed).integers(0, 256, shape, dtype=np.uint8)
-
-
 def matrices(H, W):
     """float32 [10, 6]: the identity, an integer shift, a shift out of the image, 90 and 180 degrees, +-5 degrees with a translation, 45 degrees
     at scale 0.5 and 2, a sheared one."""
     m = imgaug.affine_matrix
     return np.stack([m(0), m(0, 3, -2), m(0, W + 1, 0), m(90), m(180), m(5, 2, 1), m(-5, -1, 2), m(45, 0, 0, 0.5), m(45, 1, 0, 2.0), m(10, 1, -1, 1.1, 8, -4)])
-
-
-@pytest.fixture(scope="module")
-def sim():
-    s = BatchedSim("insert_peg", 3, 2)
-    yield s
-    s.close()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    T = torch()
-    d = T.device("cuda", T.cuda.current_device())
-    h = _ffi.Handle(blob("insert_peg"), 2, d.index, _ffi.AVSIM_IO_DEVICE)
-    h.check(h.L.avsim_set_stream(h.h, T.cuda.current_stream().cuda_stream))
-    yield h, d
-    h.close()
 
 
 def boxes_for(H, W):
@@ -76,18 +41,18 @@ def boxes_for(H, W):
 
 
 def dev_augment(dev, t_img, shape, bm, fac, mat, interp, si, ms, out_hw, guard, nout=None):
-    """avsim_image_augment through the device handle into the middle of a sentinel-filled tensor -> (rc, out, the sentinels around it)."""
-    T = torch()
+    """avsim_image_augment through the device handle into the middle of a sentinel-filled tensor -> (rc, out, no word around it was
+    written, none of it was written)."""
     h, d = dev
     n, H, W = shape
     oh, ow = out_hw
     size = len(bm) * 3 * max(oh, 0) * max(ow, 0) if 0 < oh < 65536 and 0 < ow < 65536 else 64
-    whole = T.full((guard + size + 1024,), SENTINEL - (1 << 32), dtype=T.int32, device=d)
+    g = Guarded(d, size, T.int32, SENTINEL, guard, 1024)
     rc = h.L.avsim_image_augment(h.h, t_img.data_ptr(), n, H, W, bm.ctypes.data, fac.ctypes.data, _ffi.ptr(mat), interp, _ffi.ptr(si), len(bm) if nout is None else nout,
-                                 _ffi.ptr(ms), oh, ow, whole.data_ptr() + 4 * guard)
+                                 _ffi.ptr(ms), oh, ow, g.ptr())
     T.cuda.synchronize()
-    w = whole.cpu().numpy().view(np.uint32)
-    return rc, w[guard:guard + size], np.concatenate([w[:guard], w[guard + size:]])
+    out, intact, untouched = g.read()
+    return rc, out.view(np.uint32), intact, untouched
 
 
 _case = [0]
@@ -95,7 +60,6 @@ _case = [0]
 
 def both_equal_the_reference(sim, dev, u8, boxes, masks, factors, mats, interp, out_hw, src_index=None, normalise=True, what=""):
     """One call through each handle against imgaug.jitter_affine_reference."""
-    T = torch()
     bm, fac = imgaug.pack_params(boxes, masks, factors)
     mat = None if mats is None else np.ascontiguousarray(mats, dtype=np.float32).reshape(len(bm), 6)
     si = None if src_index is None else np.ascontiguousarray(src_index, dtype=np.int32)
@@ -106,10 +70,10 @@ def both_equal_the_reference(sim, dev, u8, boxes, masks, factors, mats, interp, 
     assert got.dtype == np.float32 and not np.isnan(got).any() and np.array_equal(got, want), f"host mode: {what}"
     guard = 1024 if _case[0] % 2 == 0 else 1021                                # `out` on and off a 16-byte boundary
     _case[0] += 1
-    rc, out, around = dev_augment(dev, T.from_numpy(u8).to(dev[1]), u8.shape[:3], bm, fac, mat, interp, si, imgaug.mean_std(mean, std), out_hw, guard)
+    rc, out, intact, _ = dev_augment(dev, T.from_numpy(u8).to(dev[1]), u8.shape[:3], bm, fac, mat, interp, si, imgaug.mean_std(mean, std), out_hw, guard)
     out = out.view(np.float32).reshape(want.shape)
     assert rc == 0 and not np.isnan(out).any() and np.array_equal(out, want), f"device mode: {what}"
-    assert (around == SENTINEL).all(), f"device mode: {what}: bytes outside `out` were written"
+    assert intact, f"device mode: {what}: bytes outside `out` were written"
     return got
 
 
@@ -173,7 +137,6 @@ def test_a_batch_that_mixes_masks(sim, dev, interp):
 
 def test_without_bit_5_the_call_is_image_jitter(sim, dev):
     """The same call with no bit 5 equals avsim_image_jitter's output bit for bit, with matrices given and with NULL."""
-    T = torch()
     H, W = LARGE
     u8 = noise((3, H, W, 3), 43)
     rng = np.random.default_rng(44)
@@ -190,12 +153,11 @@ def test_without_bit_5_the_call_is_image_jitter(sim, dev):
         for interp in (0, 1):
             new = sim.augment_images(u8, (bm, fac), mat, (oh, ow), interp, MEAN, STD, si)
             assert np.array_equal(new.view(np.uint32), old.view(np.uint32))
-            rc, out, around = dev_augment(dev, T.from_numpy(u8).to(dev[1]), u8.shape[:3], bm, fac, mat, interp, si, imgaug.mean_std(MEAN, STD), (oh, ow), 1024)
-            assert rc == 0 and np.array_equal(out, old.view(np.uint32).reshape(-1)) and (around == SENTINEL).all()
+            rc, out, intact, _ = dev_augment(dev, T.from_numpy(u8).to(dev[1]), u8.shape[:3], bm, fac, mat, interp, si, imgaug.mean_std(MEAN, STD), (oh, ow), 1024)
+            assert rc == 0 and np.array_equal(out, old.view(np.uint32).reshape(-1)) and intact
 
 
 def test_refusals_leave_out_untouched(sim, dev):
-    T = torch()
     H, W, oh, ow = 7, 9, 4, 5
     u8 = noise((3, H, W, 3), 21)
     t_img = T.from_numpy(u8).to(dev[1])
@@ -232,9 +194,9 @@ def test_refusals_leave_out_untouched(sim, dev):
     def device(**kw):
         a = dict(ok, **kw)
         bm, fac, mat, si, ms = arrays(a)
-        rc, out, around = dev_augment(dev, t_img, (a["nsrc"], a["h"], a["w"]), bm, fac, mat, a["interp"], si, ms, (a["out_h"], a["out_w"]), 1024, a["nout"])
-        assert (around == SENTINEL).all()
-        assert (out == SENTINEL).all() if rc else np.array_equal(out.view(np.float32).reshape(2, 3, oh, ow), reference(a)), "a refused call wrote `out`"
+        rc, out, intact, untouched = dev_augment(dev, t_img, (a["nsrc"], a["h"], a["w"]), bm, fac, mat, a["interp"], si, ms, (a["out_h"], a["out_w"]), 1024, a["nout"])
+        assert intact
+        assert untouched if rc else np.array_equal(out.view(np.float32).reshape(2, 3, oh, ow), reference(a)), "a refused call wrote `out`"
         assert rc != -1 or len(dev[0].L.avsim_last_error(dev[0].h)) > 0
         return rc
 
@@ -281,7 +243,6 @@ def test_calls_in_a_row_and_more_than_one_scratch_group(dev):
     """Six calls without a synchronisation between them, the caller's arrays overwritten as soon as a call returns (more calls than staging
     slots), each with several sharpness + affine outputs while the scratch cap holds two images: three groups or more per call, the next
     group's fill ordered behind the previous group's gather by the stream alone."""
-    T = torch()
     h, d = dev
     H, W, oh, ow, n = 33, 130, 20, 64, 9
     h.check(h.L.avsim_set_option(h.h, b"augment_scratch_bytes", float(2 * 12 * H * W + 100)))
@@ -317,7 +278,6 @@ def test_calls_in_a_row_and_more_than_one_scratch_group(dev):
 def test_the_layers_agree_with_the_reference(sim):
     """DeviceImages.augment_images (tensors, torch's stream) and BatchedSim.augment_images (numpy) on a small batch."""
     from av_aloha_amd.images import DeviceImages
-    T = torch()
     H, W, oh, ow = 20, 70, 17, 66
     u8 = noise((2, H, W, 3), 61)
     p = np.zeros(3, dtype=imgaug.PARAMS_DTYPE)

@@ -7,54 +7,19 @@ import numpy as np
 import pytest
 
 from av_aloha_amd import _ffi, imgaug
-from av_aloha_amd.sim import BatchedSim
-from avsim_test_util import blob
+from avsim_test_util import noise
+from gpu_util import Guarded, torch as T
+from gpu_util import dev, sim          # noqa: F401  (module-scoped fixtures: this module gets its own handles)
 
 pytestmark = pytest.mark.gpu
 
-
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
-
-SENTINEL = 0xA5A5A5A5
+SENTINEL = 0xA5A5A5A5 - (1 << 32)      # as an int32
 TILE_Y, TILE_X = 16, 64
 LARGE = (2 * TILE_Y + 3, 2 * TILE_X + 5)
 SIZES = [(1, 1), (2, 5), (3, 3), (5, 67), LARGE]
 MEAN, STD = [0.485, 0.456, 0.406], [0.229, 0.224, 0.225]
 # the LeRobot range ends, 0, 1, 2; hue: its range ends, 0 and +-0.5
 FACTORS = {0: [0.8, 1.2, 0, 1, 2], 1: [0.8, 1.2, 0, 1, 2], 2: [0.5, 1.5, 0, 1, 2], 3: [-0.05, 0.05, 0, -0.5, 0.5], 4: [0.8, 1.2, 0, 1, 2]}
-
-
-def torch():
-    import torch as t
-    return t
-
-
-def noise(shape, seed):
-    return np.random.default_rng(seed).integers(0, 256, shape, dtype=np.uint8)
-
-
-@pytest.fixture(scope="module")
-def sim():
-    s = BatchedSim("insert_peg", 3, 2)
-    yield s
-    s.close()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    T = torch()
-    d = T.device("cuda", T.cuda.current_device())
-    h = _ffi.Handle(blob("insert_peg"), 2, d.index, _ffi.AVSIM_IO_DEVICE)
-    h.check(h.L.avsim_set_stream(h.h, T.cuda.current_stream().cuda_stream))
-    yield h, d
-    h.close()
 
 
 def boxes_for(H, W):
@@ -71,18 +36,18 @@ def boxes_for(H, W):
 
 
 def dev_jitter(dev, t_img, shape, bm, fac, si, ms, out_hw, guard, nout=None):
-    """avsim_image_jitter through the device handle into the middle of a sentinel-filled tensor -> (rc, out, the sentinels around it)."""
-    T = torch()
+    """avsim_image_jitter through the device handle into the middle of a sentinel-filled tensor -> (rc, out, no word around it was
+    written, none of it was written)."""
     h, d = dev
     n, H, W = shape
     oh, ow = out_hw
     size = len(bm) * 3 * max(oh, 0) * max(ow, 0) if 0 < oh < 65536 and 0 < ow < 65536 else 64
-    whole = T.full((guard + size + 1024,), SENTINEL - (1 << 32), dtype=T.int32, device=d)
+    g = Guarded(d, size, T.int32, SENTINEL, guard, 1024)
     rc = h.L.avsim_image_jitter(h.h, t_img.data_ptr(), n, H, W, bm.ctypes.data, fac.ctypes.data, _ffi.ptr(si), len(bm) if nout is None else nout,
-                                _ffi.ptr(ms), oh, ow, whole.data_ptr() + 4 * guard)
+                                _ffi.ptr(ms), oh, ow, g.ptr())
     T.cuda.synchronize()
-    w = whole.cpu().numpy().view(np.uint32)
-    return rc, w[guard:guard + size], np.concatenate([w[:guard], w[guard + size:]])
+    out, intact, untouched = g.read()
+    return rc, out.view(np.uint32), intact, untouched
 
 
 _case = [0]
@@ -90,7 +55,6 @@ _case = [0]
 
 def both_equal_the_reference(sim, dev, u8, boxes, masks, factors, out_hw, src_index=None, normalise=True, what=""):
     """One call through each handle against imgaug.jitter_reference."""
-    T = torch()
     bm, fac = imgaug.pack_params(boxes, masks, factors)
     si = None if src_index is None else np.ascontiguousarray(src_index, dtype=np.int32)
     mean, std = (MEAN, STD) if normalise else (None, None)
@@ -100,10 +64,10 @@ def both_equal_the_reference(sim, dev, u8, boxes, masks, factors, out_hw, src_in
     assert got.dtype == np.float32 and not np.isnan(got).any() and np.array_equal(got, want), f"host mode: {what}"
     guard = 1024 if _case[0] % 2 == 0 else 1021                                # `out` on and off a 16-byte boundary
     _case[0] += 1
-    rc, out, around = dev_jitter(dev, T.from_numpy(u8).to(dev[1]), u8.shape[:3], bm, fac, si, imgaug.mean_std(mean, std), out_hw, guard)
+    rc, out, intact, _ = dev_jitter(dev, T.from_numpy(u8).to(dev[1]), u8.shape[:3], bm, fac, si, imgaug.mean_std(mean, std), out_hw, guard)
     out = out.view(np.float32).reshape(want.shape)
     assert rc == 0 and not np.isnan(out).any() and np.array_equal(out, want), f"device mode: {what}"
-    assert (around == SENTINEL).all(), f"device mode: {what}: bytes outside `out` were written"
+    assert intact, f"device mode: {what}: bytes outside `out` were written"
     return got
 
 
@@ -176,7 +140,6 @@ def test_a_batch_that_mixes_masks(sim, dev):
 @pytest.mark.parametrize("size", [(5, 67), LARGE, (130, 259)], ids=lambda s: f"{s[0]}x{s[1]}")
 def test_the_sums_behind_contrast(sim, dev, size):
     """S itself through avsim_image_jitter_sums, and through fc = 0, where every pixel of the output is m = float32(S / (N 2^20))."""
-    T = torch()
     H, W = size
     u8 = noise((3, H, W, 3), 51 + H)
     u8[2] = 255                                                                 # the largest sum an image of this size has
@@ -197,7 +160,6 @@ def test_the_sums_behind_contrast(sim, dev, size):
 
 
 def test_refusals_leave_out_untouched(sim, dev):
-    T = torch()
     H, W, oh, ow = 7, 9, 4, 5
     u8 = noise((3, H, W, 3), 21)
     t_img = T.from_numpy(u8).to(dev[1])
@@ -225,8 +187,8 @@ def test_refusals_leave_out_untouched(sim, dev):
     def device(**kw):
         a = dict(ok, **kw)
         bm, fac, si, ms = arrays(a)
-        rc, out, around = dev_jitter(dev, t_img, (a["nsrc"], a["h"], a["w"]), bm, fac, si, ms, (a["out_h"], a["out_w"]), 1024, a["nout"])
-        assert rc == 0 or ((out == SENTINEL).all() and (around == SENTINEL).all()), "a refused call wrote `out`"
+        rc, _, intact, untouched = dev_jitter(dev, t_img, (a["nsrc"], a["h"], a["w"]), bm, fac, si, ms, (a["out_h"], a["out_w"]), 1024, a["nout"])
+        assert rc == 0 or (untouched and intact), "a refused call wrote `out`"
         assert rc != -1 or len(dev[0].L.avsim_last_error(dev[0].h)) > 0
         return rc
 
@@ -259,7 +221,6 @@ def test_refusals_leave_out_untouched(sim, dev):
 def test_calls_in_a_row_keep_their_own_parameters(dev):
     """Six calls of the same sizes without a synchronisation between them, the caller's arrays overwritten as soon as a call returns: the
     library has copied them (more calls than it has staging slots, so slots are reused behind their events)."""
-    T = torch()
     h, d = dev
     H, W, oh, ow, n = 33, 130, 20, 64, 5
     u8 = noise((n, H, W, 3), 31)
@@ -286,7 +247,6 @@ def test_calls_in_a_row_keep_their_own_parameters(dev):
 def test_the_layers_agree_with_the_reference(sim):
     """VecEnv.jitter_images (tensors, the env's stream) and BatchedSim.jitter_images (numpy) on a small batch, a 2-env insert_peg handle each."""
     from av_aloha_amd.vec_env import make_vec
-    T = torch()
     H, W, oh, ow = 20, 70, 17, 66
     u8 = noise((2, H, W, 3), 61)
     p = np.zeros(3, dtype=imgaug.PARAMS_DTYPE)

@@ -7,31 +7,13 @@ import numpy as np
 import pytest
 
 from av_aloha_amd import _ffi, imgprep
-from av_aloha_amd.sim import BatchedSim
-from avsim_test_util import blob
+from avsim_test_util import bits, noise
+from gpu_util import Guarded, torch as T
+from gpu_util import dev, sim          # noqa: F401  (module-scoped fixtures: this module gets its own handles)
 
 pytestmark = pytest.mark.gpu
 
-
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
-
-SENTINEL = 0xA5A5A5A5
-
-
-def torch():
-    import torch as t
-    return t
-
-
-def noise(shape, seed):
-    return np.random.default_rng(seed).integers(0, 256, shape, dtype=np.uint8)
+SENTINEL = 0xA5A5A5A5 - (1 << 32)      # as an int32
 
 
 def to_f32(u8_nhwc):
@@ -39,26 +21,8 @@ def to_f32(u8_nhwc):
     return np.ascontiguousarray(np.transpose(u8_nhwc, (0, 3, 1, 2)).astype(np.float32) / np.float32(255))
 
 
-@pytest.fixture(scope="module")
-def sim():
-    s = BatchedSim("insert_peg", 3, 2)
-    yield s
-    s.close()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    T = torch()
-    d = T.device("cuda", T.cuda.current_device())
-    h = _ffi.Handle(blob("insert_peg"), 2, d.index, _ffi.AVSIM_IO_DEVICE)
-    h.check(h.L.avsim_set_stream(h.h, T.cuda.current_stream().cuda_stream))
-    yield h, d
-    h.close()
-
-
 def dev_stats(dev, arr, fmt, index=None, offset=0):
     """avsim_image_stats through the device handle; offset: the images start that many bytes into their allocation."""
-    T = torch()
     h, d = dev
     raw = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
     buf = T.zeros(len(raw) + offset + 64, dtype=T.uint8, device=d)
@@ -125,7 +89,6 @@ def test_stats_min_max(sim, dev, fmt):
 
 
 def test_stats_refusals_leave_out_untouched(sim, dev):
-    T = torch()
     u8 = noise((2, 4, 6, 3), 9)
     L = sim.h.L
     out = np.full((2, 3, 4), 0x5A5A5A5A5A5A5A5A, dtype=np.uint64)
@@ -166,27 +129,22 @@ def boxes_for(H, W, oh, ow, n):
     return np.array([(xs[i % len(xs)], ys[(i // 2) % len(ys)], (i + i // 3) % 2) for i in range(n)], dtype=np.int32)
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
 def dev_prep(dev, arr, fmt, lut, lut_index, box, src_index, out_hw, guard):
-    """avsim_image_prep through the device handle into the middle of a sentinel-filled tensor -> (out, the sentinels before and after)."""
-    T = torch()
+    """avsim_image_prep through the device handle into the middle of a sentinel-filled tensor -> (rc, out, no word before or after it was
+    written, none of it was written)."""
     h, d = dev
     n, (H, W) = arr.shape[0], (arr.shape[2:] if fmt else arr.shape[1:3])
     oh, ow = out_hw
-    size = len(box) * 3 * oh * ow
-    whole = T.full((guard + size + 1024,), SENTINEL - (1 << 32), dtype=T.int32, device=d)
+    g = Guarded(d, len(box) * 3 * oh * ow, T.int32, SENTINEL, guard, 1024)
     t_img, t_lut = T.from_numpy(np.ascontiguousarray(arr)).to(d), T.from_numpy(lut).to(d)
     li = None if lut_index is None else np.ascontiguousarray(lut_index, dtype=np.int32)
     si = None if src_index is None else np.ascontiguousarray(src_index, dtype=np.int32)
     b = np.ascontiguousarray(box, dtype=np.int32)
     rc = h.L.avsim_image_prep(h.h, t_img.data_ptr(), fmt, n, H, W, t_lut.data_ptr(), len(lut), _ffi.ptr(li), b.ctypes.data, len(b), _ffi.ptr(si), oh, ow,
-                              whole.data_ptr() + 4 * guard)
+                              g.ptr())
     T.cuda.synchronize()
-    w = whole.cpu().numpy().view(np.uint32)
-    return rc, w[guard:guard + size].reshape(len(box), 3, oh, ow), np.concatenate([w[:guard], w[guard + size:]])
+    out, intact, untouched = g.read()
+    return rc, out.view(np.uint32).reshape(len(box), 3, oh, ow), intact, untouched
 
 
 @pytest.mark.parametrize("fmt", [0, 1])
@@ -208,15 +166,15 @@ def test_prep_equals_the_reference(sim, dev, size, fmt):
             want = bits(imgprep.prep_reference(u8, lut, lut_index, box, (oh, ow), src_index))
             guard = 1024 if case % 2 == 0 else 1021                            # `out` on and off a 16-byte boundary
             case += 1
-            rc, got, around = dev_prep(dev, arr, fmt, lut, lut_index, box, src_index, (oh, ow), guard)
+            rc, got, intact, _ = dev_prep(dev, arr, fmt, lut, lut_index, box, src_index, (oh, ow), guard)
             assert rc == 0 and np.array_equal(got, want), f"device mode, {oh} x {ow}"
-            assert (around == SENTINEL).all(), f"device mode, {oh} x {ow}: bytes outside `out` were written"
+            assert intact, f"device mode, {oh} x {ow}: bytes outside `out` were written"
             assert np.array_equal(bits(sim.prep_images(arr, lut, box, (oh, ow), lut_index, src_index)), want), f"host mode, {oh} x {ow}"
     # the full-image box, NULL index arrays: output i reads image i through table 0
     box = np.array([(0, 0, 0), (0, 0, 1), (0, 0, 0)], dtype=np.int32)
     want = bits(imgprep.prep_reference(u8, lut, None, box, (H, W)))
-    rc, got, around = dev_prep(dev, arr, fmt, lut, None, box, None, (H, W), 1022)
-    assert rc == 0 and np.array_equal(got, want) and (around == SENTINEL).all()
+    rc, got, intact, _ = dev_prep(dev, arr, fmt, lut, None, box, None, (H, W), 1022)
+    assert rc == 0 and np.array_equal(got, want) and intact
     assert np.array_equal(bits(sim.prep_images(arr, lut, box, (H, W))), want)
 
 
@@ -250,9 +208,8 @@ def test_prep_refusals_leave_out_untouched(sim, dev):
         sim.prep_images(u8, lut, [(5, 1, 0)], (oh, ow))
     # the device handle: the same checks run on the host arrays before anything is launched
     for kw in (dict(box=[(5, 1, 0), (0, 0, 0)]), dict(box=[(0, 0, 2), (0, 0, 0)]), dict(lut_index=[0, 3]), dict(src_index=[3, 0])):
-        rc, got, around = dev_prep(dev, u8, 0, lut, kw.get("lut_index"), kw.get("box", ok_box), kw.get("src_index"), (oh, ow), 1024)
-        assert rc == -1 and (got == SENTINEL).all() and (around == SENTINEL).all(), kw
-    T = torch()
+        rc, _, intact, untouched = dev_prep(dev, u8, 0, lut, kw.get("lut_index"), kw.get("box", ok_box), kw.get("src_index"), (oh, ow), 1024)
+        assert rc == -1 and untouched and intact, kw
     h, d = dev
     t_img, t_lut, t_out = T.from_numpy(u8).to(d), T.from_numpy(lut).to(d), T.full((2, 3, oh, ow), 7.0, device=d)
     for fmt, oh_, ow_ in ((2, oh, ow), (0, 0, ow), (0, oh, 65536)):
@@ -265,7 +222,6 @@ def test_prep_through_both_fronts(sim):
     """BatchedSim.prep_images (numpy) and VecEnv.prep_images (torch) are one body behind two kinds of array: the same bytes from both, with
     the table and source index arrays given, and those of the specification.  An output width of 6: rows that the 16-byte store cannot take."""
     from av_aloha_amd.vec_env import make_vec
-    T = torch()
     u8, lut, out_hw = noise((2, 9, 11, 3), 41), tables(), (4, 6)
     box, lut_index, src_index = [(0, 0, 0), (5, 5, 1), (2, 3, 0)], [0, 2, 1], [1, 0, 1]
     want = bits(imgprep.prep_reference(u8, lut, lut_index, box, out_hw, src_index))
@@ -285,7 +241,6 @@ def test_prep_through_both_fronts(sim):
 def test_prep_calls_in_a_row_keep_their_own_boxes(dev):
     """Six calls without a synchronisation between them, the caller's arrays overwritten as soon as a call returns: the library has copied
     them (more calls than it has staging slots, so slots are reused behind their events)."""
-    T = torch()
     h, d = dev
     H, W, oh, ow, n = 33, 130, 20, 64, 5
     u8 = noise((n, H, W, 3), 31)

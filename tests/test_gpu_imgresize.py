@@ -8,28 +8,13 @@ import numpy as np
 import pytest
 
 from av_aloha_amd import _ffi, imgaug, imgresize
-from av_aloha_amd.sim import BatchedSim
-from avsim_test_util import blob
+from gpu_util import Guarded, torch as T
+from gpu_util import dev, sim          # noqa: F401  (module-scoped fixtures: this module gets its own handles)
 
 pytestmark = pytest.mark.gpu
 
-
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
-
-SENTINEL = 0xA5A5A5A5
+SENTINEL = 0xA5A5A5A5 - (1 << 32)      # as an int32
 MEAN, STD, FILL = [0.485, 0.456, 0.406], [0.229, 0.224, 0.225], [0.25, -0.5, 0.75]
-
-
-def torch():
-    import torch as t
-    return t
 
 
 def source(fmt, n, H, W, seed):
@@ -43,23 +28,6 @@ def shape_of(img, fmt):
     return (img.shape[0], img.shape[1], img.shape[2]) if fmt == 0 else (img.shape[0], img.shape[2], img.shape[3])
 
 
-@pytest.fixture(scope="module")
-def sim():
-    s = BatchedSim("insert_peg", 3, 2)
-    yield s
-    s.close()
-
-
-@pytest.fixture(scope="module")
-def dev():
-    T = torch()
-    d = T.device("cuda", T.cuda.current_device())
-    h = _ffi.Handle(blob("insert_peg"), 2, d.index, _ffi.AVSIM_IO_DEVICE)
-    h.check(h.L.avsim_set_stream(h.h, T.cuda.current_stream().cuda_stream))
-    yield h, d
-    h.close()
-
-
 def arrays(sb, dst, si, fill, ms):
     sb = np.ascontiguousarray(sb, dtype=np.int32).reshape(-1, 5)
     dst = np.ascontiguousarray(dst, dtype=np.int32).reshape(-1, 4)
@@ -70,18 +38,18 @@ def arrays(sb, dst, si, fill, ms):
 
 
 def dev_resize(dev, t_img, fmt, shape, sb, dst, si, aa, fill, ms, out_hw, guard, nout=None):
-    """avsim_image_resize through the device handle into the middle of a sentinel-filled tensor -> (rc, out, the sentinels around it)."""
-    T = torch()
+    """avsim_image_resize through the device handle into the middle of a sentinel-filled tensor -> (rc, out, no word around it was
+    written, none of it was written)."""
     h, d = dev
     n, H, W = shape
     oh, ow = out_hw
     size = len(sb) * 3 * oh * ow if 0 < oh < 65536 and 0 < ow < 65536 else 64
-    whole = T.full((guard + size + 1024,), SENTINEL - (1 << 32), dtype=T.int32, device=d)
+    g = Guarded(d, size, T.int32, SENTINEL, guard, 1024)
     rc = h.L.avsim_image_resize(h.h, t_img.data_ptr(), fmt, n, H, W, sb.ctypes.data, dst.ctypes.data, _ffi.ptr(si), len(sb) if nout is None else nout, aa, _ffi.ptr(fill),
-                                _ffi.ptr(ms), oh, ow, whole.data_ptr() + 4 * guard)
+                                _ffi.ptr(ms), oh, ow, g.ptr())
     T.cuda.synchronize()
-    w = whole.cpu().numpy().view(np.uint32)
-    return rc, w[guard:guard + size], np.concatenate([w[:guard], w[guard + size:]])
+    out, intact, untouched = g.read()
+    return rc, out.view(np.uint32), intact, untouched
 
 
 _case = [0]
@@ -89,7 +57,6 @@ _case = [0]
 
 def both_equal_the_reference(sim, dev, img, fmt, sb, dst, out_hw, aa, fill=None, mean=None, std=None, si=None, what="", want=None):
     """One call through each handle against imgresize.resize_reference (want: the reference, where the caller has it already)."""
-    T = torch()
     if want is None:
         want = imgresize.resize_reference(img, fmt, sb, dst, out_hw, aa, fill, mean, std, si)
     assert want.dtype == np.float32 and not np.isnan(want).any()
@@ -98,10 +65,10 @@ def both_equal_the_reference(sim, dev, img, fmt, sb, dst, out_hw, aa, fill=None,
     guard = 1024 if _case[0] % 2 == 0 else 1021                                # `out` on and off a 16-byte boundary
     _case[0] += 1
     a = arrays(sb, dst, si, fill, imgresize.mean_std(mean, std))
-    rc, out, around = dev_resize(dev, T.from_numpy(img).to(dev[1]), fmt, shape_of(img, fmt), a[0], a[1], a[2], aa, a[3], a[4], out_hw, guard)
+    rc, out, intact, _ = dev_resize(dev, T.from_numpy(img).to(dev[1]), fmt, shape_of(img, fmt), a[0], a[1], a[2], aa, a[3], a[4], out_hw, guard)
     out = out.view(np.float32).reshape(want.shape)
     assert rc == 0 and not np.isnan(out).any() and np.array_equal(out, want), f"device mode: {what}"
-    assert (around == SENTINEL).all(), f"device mode: {what}: bytes outside `out` were written"
+    assert intact, f"device mode: {what}: bytes outside `out` were written"
     return got
 
 
@@ -169,7 +136,6 @@ def test_more_outputs_than_one_grid_chunk(sim, dev):
 
 
 def test_refusals_leave_out_untouched(sim, dev):
-    T = torch()
     H, W, oh, ow = 64, 80, 16, 20
     u8 = source(0, 3, H, W, 21)
     t_img = T.from_numpy(u8).to(dev[1])
@@ -197,9 +163,9 @@ def test_refusals_leave_out_untouched(sim, dev):
     def device(**kw):
         a = dict(ok, **kw)
         sb, dst, si, fill, ms = arrays(a["src_box"], a["dst"], a["src_index"], a["fill"], a["mean_std"])
-        rc, out, around = dev_resize(dev, t_img, a["fmt"], (a["nsrc"], a["h"], a["w"]), sb, dst, si, a["aa"], fill, ms, (a["out_h"], a["out_w"]), 1024, a["nout"])
-        assert (around == SENTINEL).all()
-        assert (out == SENTINEL).all() if rc else np.array_equal(out.view(np.float32).reshape(2, 3, oh, ow), reference(a)), "a refused call wrote `out`"
+        rc, out, intact, untouched = dev_resize(dev, t_img, a["fmt"], (a["nsrc"], a["h"], a["w"]), sb, dst, si, a["aa"], fill, ms, (a["out_h"], a["out_w"]), 1024, a["nout"])
+        assert intact
+        assert untouched if rc else np.array_equal(out.view(np.float32).reshape(2, 3, oh, ow), reference(a)), "a refused call wrote `out`"
         assert rc != -1 or len(dev[0].L.avsim_last_error(dev[0].h)) > 0
         return rc
 
@@ -237,7 +203,6 @@ def test_refusals_leave_out_untouched(sim, dev):
 def test_calls_in_a_row_do_not_wait(dev):
     """Six calls of the same sizes without a synchronisation between them, the caller's arrays overwritten as soon as a call returns (more
     calls than staging slots): the library has copied them, and the stream alone orders the copies and the kernels."""
-    T = torch()
     h, d = dev
     H, W, oh, ow, n = 33, 130, 20, 64, 9
     u8 = source(0, n, H, W, 31)
@@ -269,7 +234,6 @@ def test_the_layers_agree_with_the_reference(sim):
     """DeviceImages.resize_images (tensors, torch's stream) on u8 frames and on a jitter_images result (float, not quantised), and
     BatchedSim.resize_images (numpy), with a letterbox plan."""
     from av_aloha_amd.images import DeviceImages
-    T = torch()
     H, W, oh, ow = 24, 70, 16, 32
     u8 = source(0, 2, H, W, 61)
     plan = imgresize.resize_with_pad_plan((H, W), (oh, ow))

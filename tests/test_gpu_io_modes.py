@@ -13,6 +13,7 @@ from av_aloha_amd.compiler.compile import read_blob
 from av_aloha_amd.constants import MODEL_DIR, SIM_PHYSICS_ENV_STEP_RATIO
 from av_aloha_amd.vec_env import OBJECT_BOXES, sample_poses
 from avsim_test_util import blob
+from gpu_util import device_handle, torch as T
 
 pytestmark = pytest.mark.gpu
 
@@ -20,27 +21,17 @@ TASK, N = "insert_peg", 3
 CAMS = ["zed_cam_left", "overhead_cam"]
 
 
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
-
-
 class Side:
     """One handle and the arrays it is fed: numpy (host I/O) or torch tensors on the handle's device (device I/O)."""
 
     def __init__(self, device_mode):
-        import torch as T
         self.T, self.device_mode = T, device_mode
-        self.dev = T.device("cuda", T.cuda.current_device())
-        self.h = _ffi.Handle(blob(TASK), N, self.dev.index, _ffi.AVSIM_IO_DEVICE if device_mode else 0)
-        self.L = self.h.L
         if device_mode:
-            self.h.check(self.L.avsim_set_stream(self.h.h, T.cuda.current_stream().cuda_stream))
+            self.h, self.dev = device_handle(TASK, N)
+        else:
+            self.dev = T.device("cuda", T.cuda.current_device())
+            self.h = _ffi.Handle(blob(TASK), N, self.dev.index)
+        self.L = self.h.L
 
     def arr(self, a):
         a = np.ascontiguousarray(a).copy()

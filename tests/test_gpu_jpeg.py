@@ -11,26 +11,12 @@ from av_aloha_amd import _ffi, jpeg
 from av_aloha_amd.mjpeg import read_avi
 from av_aloha_amd.sim import BatchedSim
 from av_aloha_amd.vec_env import make_vec, sample_poses
-from avsim_test_util import blob
+from gpu_util import device_handle, torch as T
+from gpu_util import sim          # noqa: F401  (a module-scoped fixture: this module gets its own handle)
 
 pytestmark = pytest.mark.gpu
 
-
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
-
 PEG = "gym_guided_vision/InsertPeg-3Arms-v0"
-
-
-def torch():
-    import torch as t
-    return t
 
 
 def images():
@@ -53,13 +39,6 @@ def encode_host(sim, imgs, quality, fmt=0, index=None, stride=None):
     idx = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
     sim.h.check(sim.h.L.avsim_jpeg_encode(sim.h.h, imgs.ctypes.data, fmt, _ffi.ptr(idx), n, H, W, quality, out.ctypes.data, stride, ln.ctypes.data))
     return [out[i, :ln[i]].tobytes() for i in range(n)], ln
-
-
-@pytest.fixture(scope="module")
-def sim():
-    s = BatchedSim("insert_peg", 3, 2)
-    yield s
-    s.close()
 
 
 def test_bound_and_argument_errors(sim):
@@ -107,7 +86,6 @@ def test_rendered_frames_equal_the_reference_in_both_formats(task):
 
 
 def test_batch_with_an_index_on_host_and_device_handles(sim):
-    T = torch()
     rng = np.random.default_rng(7)
     imgs = rng.integers(0, 256, (64, 48, 80, 3), dtype=np.uint8)
     imgs[::3] //= 4                                                  # some darker, shorter streams in between
@@ -119,9 +97,7 @@ def test_batch_with_an_index_on_host_and_device_handles(sim):
     got, ln = encode_host(sim, imgs, 90, index=index)
     assert got == [want[i] for i in index]
     # device pointers: nothing but the handle's I/O mode differs
-    dev = T.device("cuda", T.cuda.current_device())
-    h = _ffi.Handle(blob("insert_peg"), 2, dev.index, _ffi.AVSIM_IO_DEVICE)
-    h.check(h.L.avsim_set_stream(h.h, T.cuda.current_stream().cuda_stream))
+    h, dev = device_handle()
     stride = 16384
     d_img, d_idx = T.from_numpy(imgs).to(dev), T.from_numpy(index).to(dev)
     out, dl = T.zeros((64, stride), dtype=T.uint8, device=dev), T.zeros(64, dtype=T.int32, device=dev)
@@ -137,16 +113,13 @@ def test_batch_with_an_index_on_host_and_device_handles(sim):
 
 
 def test_a_stream_longer_than_the_stride_is_cut_at_the_stride():
-    T = torch()
-    dev = T.device("cuda", T.cuda.current_device())
     rng = np.random.default_rng(2)
     imgs = np.full((3, 64, 64, 3), 255, np.uint8)
     imgs[1] = rng.integers(0, 256, (64, 64, 3), dtype=np.uint8)
     want = [jpeg.encode_reference(im, 100) for im in imgs]
     stride = len(want[0]) + 101
     assert len(want[1]) > 3 * stride                                 # the noise image would run over both neighbours and the tail
-    h = _ffi.Handle(blob("insert_peg"), 2, dev.index, _ffi.AVSIM_IO_DEVICE)
-    h.check(h.L.avsim_set_stream(h.h, T.cuda.current_stream().cuda_stream))
+    h, dev = device_handle()
     buf = T.full((3 * stride + len(want[1]) + 4096,), 0xAA, dtype=T.uint8, device=dev)
     dl = T.zeros(3, dtype=T.int32, device=dev)
     h.check(h.L.avsim_jpeg_encode(h.h, T.from_numpy(imgs).to(dev).data_ptr(), 0, None, 3, 64, 64, 100, buf.data_ptr(), stride, dl.data_ptr()))
@@ -160,7 +133,6 @@ def test_a_stream_longer_than_the_stride_is_cut_at_the_stride():
 
 
 def _policy_for(env):
-    T = torch()
     base = []
 
     def policy(obs, info):
@@ -174,7 +146,6 @@ def _policy_for(env):
 
 def test_evaluate_vec_writes_the_first_episodes_videos(tmp_path):
     from av_aloha_amd.harness import evaluate_vec
-    T = torch()
     kw = dict(cameras=["zed_cam_left"], seed=3, observation_height=120, observation_width=160)
     env = make_vec(PEG, 8, 12, obs_format="lerobot", **kw)
     recs = evaluate_vec(env, _policy_for(env), 8, video_dir=str(tmp_path / "v"), video_episodes=4, video_quality=90, video_fps=25)

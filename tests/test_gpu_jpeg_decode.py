@@ -12,28 +12,14 @@ import pytest
 from av_aloha_amd import _ffi, jpeg
 from av_aloha_amd.sim import BatchedSim
 from av_aloha_amd.vec_env import make_vec, sample_poses
-from avsim_test_util import blob
+from gpu_util import device_handle, torch as T
+from gpu_util import sim          # noqa: F401  (a module-scoped fixture: this module gets its own handle)
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
 
 PEG = "gym_guided_vision/InsertPeg-3Arms-v0"
 MODES = ("replicate", "triangle")
 GUARD = 4096
-
-
-def torch():
-    import torch as t
-    return t
 
 
 def images():
@@ -79,21 +65,6 @@ def host_status(stream):
         return e.status
 
 
-def device_handle():
-    T = torch()
-    dev = T.device("cuda", T.cuda.current_device())
-    h = _ffi.Handle(blob("insert_peg"), 2, dev.index, _ffi.AVSIM_IO_DEVICE)
-    h.check(h.L.avsim_set_stream(h.h, T.cuda.current_stream().cuda_stream))
-    return h, dev
-
-
-@pytest.fixture(scope="module")
-def sim():
-    s = BatchedSim("insert_peg", 3, 2)
-    yield s
-    s.close()
-
-
 def test_argument_errors(sim):
     L = sim.h.L
     s = jpeg.encode_reference(np.zeros((16, 16, 3), np.uint8), 90)
@@ -107,7 +78,6 @@ def test_argument_errors(sim):
 
 @pytest.mark.parametrize("quality", [50, 90, 100])
 def test_synthetic_images_equal_the_reference(sim, quality):
-    T = torch()
     for name, img in images().items():
         H, W, _ = img.shape
         s = jpeg.encode_reference(img, quality)
@@ -142,7 +112,6 @@ def test_rendered_frames_equal_the_reference(task):
 
 
 def test_batch_of_mixed_qualities_with_an_index_on_host_and_device_handles(sim):
-    T = torch()
     rng = np.random.default_rng(7)
     imgs = rng.integers(0, 256, (12, 48, 80, 3), dtype=np.uint8)
     imgs[::3] //= 4                                                      # some darker, shorter streams in between
@@ -211,7 +180,6 @@ def corrupt_batch():
 def test_corrupt_streams_get_their_status_and_nothing_else_is_touched():
     """Error reporting, not fault hunting: the kernels bound every read and write themselves (csrc/avsim_jpeg.hip.h).  The C call has no
     output stride, so the gaps between image slots are made by one call per image into slots GUARD bytes apart."""
-    T = torch()
     H, W = 37, 53
     streams, lengths, want = corrupt_batch()
     good = {i: jpeg.decode_reference(streams[i]) for i in (0, 5)}
@@ -255,7 +223,6 @@ def test_corrupt_streams_get_their_status_and_nothing_else_is_touched():
 
 
 def test_vec_env_round_trip():
-    T = torch()
     kw = dict(cameras=["zed_cam_left"], seed=3, observation_height=120, observation_width=160)
     for fmt in ("lerobot", "gym"):
         env = make_vec(PEG, 4, 12, obs_format=fmt, **kw)
@@ -282,7 +249,6 @@ def test_recorded_compressed_episodes_feed_the_dataset(tmp_path):
     few frames only: it is a Python loop per coefficient."""
     from av_aloha_amd import harness
     from av_aloha_amd.dataset import CompressedDataset
-    T = torch()
     cam, H, W = "cam_right_wrist", 480, 640
     eps = harness.record_scripted("sim_insert_peg", 2, cameras=[cam], jpeg_quality=90, stream_dir=str(tmp_path), seed=11, keep_diverged=True)
     paths = [e["path"] for e in eps]

@@ -12,18 +12,10 @@ from av_aloha_amd import images, imgprep
 from av_aloha_amd import obshist as oh
 from av_aloha_amd.sim import BatchedSim
 from av_aloha_amd.vec_env import make_vec
+from avsim_test_util import same
+from gpu_util import torch as T
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
 
 PEG = "gym_guided_vision/InsertPeg-3Arms-v0"
 CAMS = ["a", "b"]
@@ -37,11 +29,6 @@ CONFIGS = [((1, 1), (1, 1), (0, 0, 0), (0, 0, 1), 0, False),
            ((35, 133), (32, 128), (0, 0, 0), (5, 3, 1), 1, False),
            ((35, 133), (32, 128), (5, 0, 1), (0, 3, 0), 0, False),
            ((35, 133), (32, 128), (2, 1, 0), (2, 1, 1), 21, True)]
-
-
-def torch():
-    import torch as t
-    return t
 
 
 @pytest.fixture(scope="module")
@@ -82,22 +69,15 @@ def observations(calls, N, D, ncam, fmt, hw, seed):
 
 
 def info_of(env, ids, elapsed):
-    T = torch()
     return {"episode_id": T.from_numpy(np.ascontiguousarray(ids, dtype=np.int64)).to(env.device),
             "elapsed_steps": T.from_numpy(np.ascontiguousarray(elapsed, dtype=np.int32)).to(env.device)}
 
 
 def obs_of(env, hist, s, imgs, t):
-    T = torch()
     obs = {f"observation.images.{c}": T.from_numpy(imgs[i][t]).to(env.device) for i, c in enumerate(hist.cameras)}
     if hist.D > 0:
         obs["observation.state"] = T.from_numpy(s[t]).to(env.device)
     return obs
-
-
-def same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.dtype == b.dtype == np.float32 and a.shape == b.shape and not np.isnan(a).any() and not np.isnan(b).any() and np.array_equal(a, b)
 
 
 def check(hist, out, ref_out, where):
@@ -177,7 +157,6 @@ def test_large_batch_fresh_per_env(envs, N):
 
 @pytest.mark.parametrize("fmt", ["gym", "lerobot"])
 def test_one_step_is_prep_images(envs, fmt):
-    T = torch()
     N, src, crop = 3, (35, 133), (32, 128)
     env = envs(N)
     st = {"observation.images.a": {"mean": np.array([0.4, 0.5, 0.6], np.float32), "std": np.array([0.2, 0.25, 0.3], np.float32)}}
@@ -194,7 +173,6 @@ def test_one_step_is_prep_images(envs, fmt):
 
 def test_an_unaligned_history_takes_the_scalar_path(envs):
     """3 h w is a multiple of four but the history starts 4 bytes off a 16-byte boundary: single floats, the same values"""
-    T = torch()
     N, K, src, crop = 3, 3, (35, 133), (32, 128)
     env = envs(N)
     hist = oh.ObsHistory(env, K, crop=crop, cameras=["a"], state_dim=0, fmt="gym", size=src, boxes={"a": (5, 3, 1)}, luts=LUTS)
@@ -225,7 +203,6 @@ def raw_setup(env, K, D, ms, ncam, fmt, H, W, lut, box, h, w):
 
 
 def test_refusals_leave_the_state_alone(envs):
-    T = torch()
     N, K, D, src, crop = 3, 2, 3, (3, 6), (2, 6)
     env = envs(N)
     lut = np.ascontiguousarray(np.stack([LUTS["a"], LUTS["b"]]), dtype=np.float32)
@@ -283,7 +260,6 @@ def test_refusals_leave_the_state_alone(envs):
 
 
 def test_calls_before_the_setup_are_refused():
-    T = torch()
     env = make_vec(PEG, 2, 10, cameras=[])
     try:
         L, h = env.L, env.h.h
@@ -324,7 +300,6 @@ def test_a_second_setup_and_reset_start_over(envs):
 # ---- the stream ----------------------------------------------------------------------------------------------------------------------
 def test_back_to_back_pushes_with_the_sources_overwritten(envs):
     """twenty calls with no host wait in between; the source tensors are overwritten as soon as each call has returned"""
-    T = torch()
     N, K, D, calls, src = 70, 3, 21, 20, (3, 6)
     env = envs(N)
     ids, elapsed = fresh_schedule(N, calls)
@@ -346,7 +321,6 @@ def test_back_to_back_pushes_with_the_sources_overwritten(envs):
 
 
 def test_push_and_reset_do_not_synchronise(envs):
-    T = torch()
     N, K, D, src = 70, 3, 21, (3, 6)
     env = envs(N)
     hist = oh.ObsHistory(env, K, cameras=["a"], state_dim=D, fmt="gym", size=src)

@@ -17,28 +17,15 @@ from av_aloha_amd import dataset, harness, imgaug, imgprep, jpeg
 from av_aloha_amd import obshist as oh
 from av_aloha_amd.harness import chunked_policy, evaluate_vec, history_preprocessor
 from av_aloha_amd.vec_env import make_vec
+from avsim_test_util import same
+from gpu_util import torch
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
 
 PEG = "gym_guided_vision/InsertPeg-3Arms-v0"
 CAM, SIZE, CROP = "zed_cam_left", (64, 80), (48, 64)
 N, STEPS, EPISODES, C, K = 5, 6, 12, 4, 2
 RESET_AT, RESET_ENVS = 16, (3, 4)          # the 17th select_action call: every env holds an id in 10 .. 14, envs 3 and 4 those past 11
-
-
-def same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.dtype == b.dtype == np.float32 and a.shape == b.shape and not np.isnan(a).any() and not np.isnan(b).any() and np.array_equal(a, b)
 
 
 @pytest.fixture(scope="module")
@@ -56,7 +43,6 @@ def eval_stats(D):
 
 def evaluate(venv, **kw):
     """-> (the history, the records of evaluate_vec, one dict per select_action call)"""
-    import torch
     st = eval_stats(venv.nj)
     mean = torch.from_numpy(st["observation.state"]["mean"]).to(venv.device)
     std = torch.from_numpy(st["observation.state"]["std"]).to(venv.device)
@@ -136,7 +122,6 @@ def test_queue_mode_skips_the_policy_not_the_history(venv):
 
 
 def test_without_observe_the_policy_reads_the_envs_observation(venv):
-    import torch
     seen = []
 
     def predict_chunk(obs, info):
@@ -251,7 +236,6 @@ def test_without_n_obs_steps_the_batches_are_what_they_were(data):
 
 def test_training_and_evaluation_stack_alike(data):
     """the nine frames of episode 1, pushed in order through ObsHistory, are the batch entries of those frames"""
-    import torch
     ds, ref, st = data
     cam, (H, W) = "cam_a", CAMS["cam_a"]
     tb = dataset.TrainingBatches(ds, batch_size=9, chunk_size=1, stats=st, crop=TCROP, crop_mode="center", n_obs_steps=KT)

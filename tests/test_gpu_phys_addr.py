@@ -17,21 +17,11 @@ import pytest
 from av_aloha_amd import _ffi
 from av_aloha_amd import workloads as W
 from av_aloha_amd.constants import SIM_PHYSICS_ENV_STEP_RATIO
-from avsim_test_util import blob
+from gpu_util import device_handle, torch as T
 from orc_env import OrcEnv
 from test_oracle_physics import model_dict
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
 
 N_RAGGED = 67                 # more than one workgroup of 8 envs, the last one part-filled, not a multiple of 64
 STEPS = 3
@@ -126,12 +116,9 @@ def test_identical_envs_unordered_and_ordered_launch():
 
 
 def test_host_io_and_device_io_handles_agree():
-    import torch as T
-    dev = T.device("cuda", T.cuda.current_device())
     poses, acts, spec, _, _ = _case(*MODELS[0])
     n, nj = N_RAGGED, 21
-    h = _ffi.Handle(blob("slot_insertion"), n, dev.index, _ffi.AVSIM_IO_DEVICE)
-    h.check(h.L.avsim_set_stream(h.h, T.cuda.current_stream().cuda_stream))
+    h, dev = device_handle("slot_insertion", n)
     d = lambda a: T.from_numpy(np.ascontiguousarray(a)).to(dev)
     obj = d(poses.astype(np.float64).reshape(n, -1))
     h.check(h.L.avsim_reset(h.h, None, _ffi.ptr(obj)))

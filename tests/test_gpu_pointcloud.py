@@ -5,23 +5,12 @@ observation and the replay of a recorded episode."""
 import numpy as np
 import pytest
 
-from av_aloha_amd import _ffi
 from av_aloha_amd import pointcloud as pc
 from av_aloha_amd.sim import BatchedSim
-from avsim_test_util import blob
+from gpu_util import Guarded, device_handle_in_state, torch as T
 from test_oracle_physics import OBJ, model_dict
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
 
 N = 3
 SENTINEL = 0x5A5A5A5A
@@ -30,11 +19,6 @@ FAR = np.float32(pc.FAR_PLANE)
 CAMS2 = ["zed_cam_left", "wrist_cam_right"]
 CAMS6 = ["zed_cam_left", "zed_cam_right", "wrist_cam_left", "wrist_cam_right", "overhead_cam", "worms_eye_cam"]
 WIDE = np.array([-50, -50, -50, 50, 50, 50], dtype=np.float32)
-
-
-def torch():
-    import torch as t
-    return t
 
 
 def spread_qpos(q):
@@ -62,29 +46,19 @@ class Dev:
     """A device-mode handle of the same model in the same state, with torch tensors for the pointers."""
 
     def __init__(self, qpos):
-        T = torch()
-        self.d = T.device("cuda", T.cuda.current_device())
-        self.h = _ffi.Handle(blob("slot_insertion"), N, self.d.index, _ffi.AVSIM_IO_DEVICE)
-        self.h.check(self.h.L.avsim_set_stream(self.h.h, T.cuda.current_stream().cuda_stream))
-        obj = T.from_numpy(np.ascontiguousarray(np.repeat(OBJ[None], N, 0))).to(self.d)
-        self.h.check(self.h.L.avsim_reset(self.h.h, None, obj.data_ptr()))
-        q = T.from_numpy(np.ascontiguousarray(qpos)).to(self.d)
-        self.h.check(self.h.L.avsim_set_qpos(self.h.h, q.data_ptr()))
-        T.cuda.synchronize()
+        self.h, self.d = device_handle_in_state("slot_insertion", N, np.repeat(OBJ[None], N, 0), qpos)
 
     def poses(self, ids):
-        T = torch()
         out = T.empty((N, len(ids), 16), dtype=T.float32, device=self.d)
         self.h.check(self.h.L.avsim_camera_poses(self.h.h, ids.ctypes.data, len(ids), out.data_ptr()))
         return out.cpu().numpy()
 
     def cloud(self, ids, H, W, depth, bounds, max_depth, P, size_p=None, null=None, ncam=None):
-        """avsim_point_cloud into the middle of sentinel-filled tensors -> (rc, xyz, index, count, the sentinels around them)."""
-        T = torch()
+        """avsim_point_cloud into the middle of sentinel-filled tensors -> (rc, xyz, index, count, no word around them was written, the raw
+        bodies in a row)."""
         sp = P if size_p is None else size_p
-        sizes = (N * sp * 3, N * sp, N * 2)
-        bufs = [T.full((GUARD + s + 1024,), SENTINEL, dtype=T.int32, device=self.d) for s in sizes]
-        ptrs = [b.data_ptr() + 4 * GUARD for b in bufs]
+        bufs = [Guarded(self.d, s, T.int32, SENTINEL, GUARD, 1024) for s in (N * sp * 3, N * sp, N * 2)]
+        ptrs = [b.ptr() for b in bufs]
         t_depth = depth if isinstance(depth, T.Tensor) else T.from_numpy(np.ascontiguousarray(depth, dtype=np.float32)).to(self.d)
         bounds = np.ascontiguousarray(bounds, dtype=np.float32)
         args = {"cam_ids": ids.ctypes.data, "depth": t_depth.data_ptr(), "bounds": bounds.ctypes.data, "xyz": ptrs[0], "index": ptrs[1], "count": ptrs[2]}
@@ -93,10 +67,8 @@ class Dev:
         rc = self.h.L.avsim_point_cloud(self.h.h, args["cam_ids"], len(ids) if ncam is None else ncam, H, W, args["depth"], args["bounds"], float(max_depth), P, args["xyz"],
                                         args["index"], args["count"])
         T.cuda.synchronize()
-        w = [b.cpu().numpy() for b in bufs]
-        around = np.concatenate([np.concatenate([x[:GUARD], x[GUARD + s:]]) for x, s in zip(w, sizes)])
-        body = [x[GUARD:GUARD + s] for x, s in zip(w, sizes)]
-        return rc, body[0].view(np.float32).reshape(N, sp, 3), body[1].reshape(N, sp), body[2].reshape(N, 2), around, np.concatenate(body)
+        body, intact, _ = zip(*(b.read() for b in bufs))
+        return rc, body[0].view(np.float32).reshape(N, sp, 3), body[1].reshape(N, sp), body[2].reshape(N, 2), all(intact), np.concatenate(body)
 
 
 @pytest.fixture(scope="module")
@@ -126,11 +98,15 @@ def both_equal_the_reference(sim, dev, cams, H, W, depth, bounds, max_depth, P, 
     same(sim.point_cloud(cams, H, W, bounds, P, max_depth=max_depth, depth=depth), want, what + ", host pointers")
     dposes = dev.poses(ids)          # (the device handle's own records: the same state, so normally the same bits)
     dwant = want if np.array_equal(dposes, poses) else pc.point_cloud_reference(dposes, depth, bounds, max_depth, P)
-    rc, xyz, index, count, around, _ = dev.cloud(ids, H, W, depth, bounds, max_depth, P)
+    rc, xyz, index, count, intact, _ = dev.cloud(ids, H, W, depth, bounds, max_depth, P)
     assert rc == 0, dev.h.L.avsim_last_error(dev.h.h)
     same((xyz, index, count), dwant, what + ", device pointers")
-    assert (around == SENTINEL).all(), what + ": a write outside the outputs"
+    assert intact, what + ": a write outside the outputs"
     return want
+
+
+def noise_rgb(seed, ncam, H, W):
+    return np.random.default_rng(seed).integers(0, 256, (N, ncam, H, W, 3), dtype=np.uint8)
 
 
 def noise_depth(seed, ncam, H, W, far_share=1 / 3):
@@ -196,7 +172,6 @@ def test_small_shapes(sim, dev):
 def test_calls_in_a_row_with_the_bounds_overwritten(sim, dev):
     """Four device-mode calls without a synchronisation between them; the caller's bounds and camera ids are overwritten as soon as a call
     returns: the call took them by value."""
-    T = torch()
     H, W, P = 24, 32, 16
     ids = ids_of(sim, CAMS2)
     poses = dev.poses(ids)
@@ -236,9 +211,9 @@ def test_refusals_leave_the_outputs_untouched(sim, dev):
     for what, kw in cases:
         a = dict(ids=ids, H=H, W=W, depth=depth, bounds=WIDE, max_depth=FAR, P=P)
         a.update({k: v for k, v in kw.items() if k in a})
-        rc, _, _, _, around, body = dev.cloud(a["ids"], a["H"], a["W"], a["depth"], a["bounds"], a["max_depth"], a["P"], size_p=P, null=kw.get("null"), ncam=kw.get("ncam"))
+        rc, _, _, _, intact, body = dev.cloud(a["ids"], a["H"], a["W"], a["depth"], a["bounds"], a["max_depth"], a["P"], size_p=P, null=kw.get("null"), ncam=kw.get("ncam"))
         assert rc == -1, f"{what}: rc {rc}"
-        assert (around == SENTINEL).all() and (body == SENTINEL).all(), f"{what}: the outputs were written"
+        assert intact and (body == SENTINEL).all(), f"{what}: the outputs were written"
         assert dev.h.L.avsim_last_error(dev.h.h)
         if "null" in kw or "ncam" in kw or kw.get("H") == 4097:
             continue
@@ -247,7 +222,6 @@ def test_refusals_leave_the_outputs_untouched(sim, dev):
                             depth=np.zeros((N, 2, max(a["H"], 0), max(a["W"], 0)), dtype=np.float32) if (a["H"], a["W"]) != (H, W) else depth)
         with pytest.raises(ValueError):
             pc.check_point_cloud(len(dev.names), a["ids"], a["H"], a["W"], a["bounds"], a["max_depth"], a["P"])
-    T = torch()
     out = T.full((N * 2 * 16 + 8,), 7.0, dtype=T.float32, device=dev.d)
     for cam, ncam in ((np.array([0, 99], dtype=np.int32), 2), (ids, 0), (ids, 17)):
         assert dev.h.L.avsim_camera_poses(dev.h.h, cam.ctypes.data, ncam, out.data_ptr()) == -1
@@ -349,7 +323,6 @@ def test_camera_poses_through_both_fronts():
     relative."""
     from av_aloha_amd.vec_env import make_vec
     from orc_env import OrcEnv
-    T = torch()
     obj = np.array([[0.15, 0.0, 0.01, 1, 0, 0, 0], [-0.15, 0.0, 0.021, 1, 0, 0, 0.0]])
     md = model_dict("insert_peg")
     sim = BatchedSim("insert_peg", 3, 2)
@@ -399,7 +372,6 @@ PCARG = {"cameras": ["zed_cam_left", "wrist_cam_left"], "height": 24, "width": 3
 
 def test_vector_env_observation():
     from av_aloha_amd.vec_env import make_vec
-    T = torch()
     plain = make_vec(SLOT, 4, 3, cameras=[], seed=2)
     keys0, info0 = set(plain.reset()[0]), set(plain.reset()[1])
     plain.close()

@@ -6,23 +6,13 @@ import os
 import numpy as np
 import pytest
 
-from av_aloha_amd import _ffi, jpeg
+from av_aloha_amd import jpeg
 from av_aloha_amd.constants import MODEL_DIR
 from av_aloha_amd.sim import BatchedSim
 from av_aloha_amd.vec_env import sample_poses
-from avsim_test_util import blob
+from gpu_util import device_handle, torch as T
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
 
 OPTIONS = {"render_shadows": 1, "render_samples": 4, "render_smooth": 1}
 CAMS = ["zed_cam_left", "zed_cam_right"]
@@ -76,17 +66,14 @@ def test_a_short_stride_reports_the_length_and_keeps_to_its_rows(sim):
 
 
 def test_device_handle_writes_the_same_streams():
-    import torch as T
     H, W = 120, 160
     poses = sample_poses("insert_peg", 1, [0, 1])
     host = BatchedSim("insert_peg", 3, 2, options=OPTIONS)
     host.reset(poses)
     want = host.render_jpeg(CAMS, H, W, 90, tile=True)
     host.close()
-    dev = T.device("cuda", T.cuda.current_device())
-    h = _ffi.Handle(blob("insert_peg"), 2, dev.index, _ffi.AVSIM_IO_DEVICE)
+    h, dev = device_handle()
     L = h.L
-    h.check(L.avsim_set_stream(h.h, T.cuda.current_stream().cuda_stream))
     for k, v in OPTIONS.items():
         h.check(L.avsim_set_option(h.h, k.encode(), float(v)))
     with open(os.path.join(MODEL_DIR, "visual_meshes.avv"), "rb") as f:

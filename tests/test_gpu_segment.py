@@ -13,21 +13,11 @@ import render_envelope as RE
 import segment_util as SU
 from av_aloha_amd import _ffi, segment
 from av_aloha_amd.sim import BatchedSim
-from avsim_test_util import blob
+from gpu_util import Guarded, device_handle_in_state, torch as T
 from orc_env import OrcEnv
 from test_oracle_physics import model_dict
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
 
 N = 3
 SENTINEL = 0x5A
@@ -35,11 +25,6 @@ GUARD = 1024            # bytes before an output: a multiple of 16, as the call 
 FAR = np.float32(RE.FAR)
 SLOT_CAMS = ["zed_cam_left", "wrist_cam_left", "overhead_cam"]
 EINVAL = -1
-
-
-def torch():
-    import torch as t
-    return t
 
 
 class World:
@@ -180,33 +165,21 @@ class Dev:
     """A device-mode f64 handle of the slot model in the world's states, outputs in the middle of sentinel-filled tensors."""
 
     def __init__(self, qpos):
-        T = torch()
-        self.d = T.device("cuda", T.cuda.current_device())
-        self.h = _ffi.Handle(blob("slot_insertion"), N, self.d.index, _ffi.AVSIM_IO_DEVICE | _ffi.AVSIM_F64_PHYSICS)
-        self.h.check(self.h.L.avsim_set_stream(self.h.h, T.cuda.current_stream().cuda_stream))
         md = model_dict()
         a0 = int(md["objects_qposadr"][0])
-        obj = T.from_numpy(np.ascontiguousarray(np.repeat(md["qpos_home"][a0:][None], N, 0))).to(self.d)
-        self.h.check(self.h.L.avsim_reset(self.h.h, None, obj.data_ptr()))
-        q = T.from_numpy(np.ascontiguousarray(qpos)).to(self.d)
-        self.h.check(self.h.L.avsim_set_qpos(self.h.h, q.data_ptr()))
-        T.cuda.synchronize()
+        self.h, self.d = device_handle_in_state("slot_insertion", N, np.repeat(md["qpos_home"][a0:][None], N, 0), qpos, _ffi.AVSIM_F64_PHYSICS)
 
     def labels(self, ids, H, W, table=None, drop=None, depth=True, labels=True, ncam=None, cam_ids=True, offset=0):
         """-> (rc, labels, depth, every byte around the two outputs is the sentinel, the outputs are all sentinels)."""
-        T = torch()
         npx = N * len(ids) * H * W
-        b_lab = T.full((GUARD + npx + 1024,), SENTINEL, dtype=T.uint8, device=self.d)
-        b_dep = T.full((GUARD + 4 * npx + 1024,), SENTINEL, dtype=T.uint8, device=self.d)
+        b_lab = Guarded(self.d, npx, T.uint8, SENTINEL, GUARD, 1024)
+        b_dep = Guarded(self.d, 4 * npx, T.uint8, SENTINEL, GUARD, 1024)
         rc = self.h.L.avsim_render_labels(self.h.h, ids.ctypes.data if cam_ids else None, len(ids) if ncam is None else ncam, H, W,
                                           None if table is None else table.ctypes.data, None if drop is None else drop.ctypes.data,
-                                          b_dep.data_ptr() + GUARD + offset if depth else None, b_lab.data_ptr() + GUARD + offset if labels else None)
+                                          b_dep.ptr(offset) if depth else None, b_lab.ptr(offset) if labels else None)
         T.cuda.synchronize()
-        wl, wd = b_lab.cpu().numpy(), b_dep.cpu().numpy()
-        around = np.concatenate([wl[:GUARD], wl[GUARD + npx:], wd[:GUARD], wd[GUARD + 4 * npx:]])
-        body_l, body_d = wl[GUARD:GUARD + npx], wd[GUARD:GUARD + 4 * npx]
-        untouched = bool((body_l == SENTINEL).all() and (body_d == SENTINEL).all())
-        return rc, body_l.reshape(N, len(ids), H, W), body_d.view(np.float32).reshape(N, len(ids), H, W), bool((around == SENTINEL).all()), untouched
+        (body_l, intact_l, same_l), (body_d, intact_d, same_d) = b_lab.read(), b_dep.read()
+        return rc, body_l.reshape(N, len(ids), H, W), body_d.view(np.float32).reshape(N, len(ids), H, W), intact_l and intact_d, same_l and same_d
 
 
 @pytest.fixture(scope="module")
@@ -246,17 +219,16 @@ def test_refusals_leave_the_outputs_untouched(slot, dev):
         a = dict(ids=ids, H=H, W=W)
         a.update(kw)
         # (the buffers are sized for the good call: a refused size launches nothing, so nothing is written)
-        T = torch()
         npx = N * 2 * 30 * 40
-        b_lab = T.full((GUARD + npx + 1024,), SENTINEL, dtype=T.uint8, device=dev.d)
-        b_dep = T.full((GUARD + 4 * npx + 1024,), SENTINEL, dtype=T.uint8, device=dev.d)
+        b_lab = Guarded(dev.d, npx, T.uint8, SENTINEL, GUARD, 1024)
+        b_dep = Guarded(dev.d, 4 * npx, T.uint8, SENTINEL, GUARD, 1024)
         off = a.get("offset", 0)
         rc = dev.h.L.avsim_render_labels(dev.h.h, a["ids"].ctypes.data if a.get("cam_ids", True) else None, a.get("ncam", len(a["ids"])), a["H"], a["W"], None,
-                                         a["drop"].ctypes.data if "drop" in a else None, b_dep.data_ptr() + GUARD + off if a.get("depth", True) else None,
-                                         b_lab.data_ptr() + GUARD + off if a.get("labels", True) else None)
+                                         a["drop"].ctypes.data if "drop" in a else None, b_dep.ptr(off) if a.get("depth", True) else None,
+                                         b_lab.ptr(off) if a.get("labels", True) else None)
         T.cuda.synchronize()
         assert rc == EINVAL, what
-        assert (b_lab == SENTINEL).all() and (b_dep == SENTINEL).all(), what
+        assert all(b_lab.read()[1:]) and all(b_dep.read()[1:]), what
         assert dev.h.L.avsim_last_error(dev.h.h), what
     # the fronts refuse the same before they allocate, as a ValueError; a good call still works afterwards
     for kw in (dict(cameras=[]), dict(cameras=[ncam_model]), dict(height=0), dict(width=4097), dict(drop=["left_arm"], depth=False), dict(kind=np.zeros(3, dtype=np.uint8)),
@@ -289,7 +261,6 @@ SEGARG = {"cameras": ["zed_cam_left", "wrist_cam_left"], "height": 33, "width": 
 
 def test_vector_env_options():
     from av_aloha_amd.vec_env import make_vec
-    T = torch()
 
     class Recorded:
         """The library with the names of the entry points that are looked up on it."""

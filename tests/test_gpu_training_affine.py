@@ -7,26 +7,14 @@ import numpy as np
 import pytest
 
 from av_aloha_amd import dataset, harness, imgaug, imgprep, jpeg
+from avsim_test_util import bits
+import gpu_util          # noqa: F401  (torch's HIP runtime comes up before libavsim's)
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
 
 CAMS = {"cam_a": (16, 24), "cam_b": (24, 32)}
 LENS = (2, 9)
 CROP = (12, 20)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 @pytest.fixture(scope="module")

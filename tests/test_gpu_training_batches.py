@@ -7,27 +7,15 @@ import pytest
 
 from av_aloha_amd import dataset, harness, imgprep, jpeg
 from av_aloha_amd.vec_env import make_vec
+from avsim_test_util import bits
+from gpu_util import torch
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
 
 PEG = "gym_guided_vision/InsertPeg-3Arms-v0"
 CAMS = {"cam_a": (16, 24), "cam_b": (24, 32)}
 LENS = (5, 7)
 CROP = (12, 20)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 @pytest.fixture(scope="module")
@@ -159,7 +147,6 @@ def test_preprocessor_feeds_a_policy_what_training_saw(fmt):
         assert np.array_equal(bits(got["observation.state"].cpu().numpy()), bits((state - st["observation.state"]["mean"]) / st["observation.state"]["std"]))
         assert set(got) == {f"observation.images.{cam}", "observation.state"}
         # VecEnv.image_stats on the same buffer, whole and through an index tensor
-        import torch
         sums = env.image_stats(env.camera_images(cam)).cpu().numpy().view(np.uint64)
         assert np.array_equal(sums, imgprep.stats_reference(src))
         index = torch.tensor([1, 1, 0], dtype=torch.int32, device=env.device)

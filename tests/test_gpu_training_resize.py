@@ -8,18 +8,9 @@ import pytest
 
 from av_aloha_amd import dataset, harness, imgaug, imgprep, imgresize, jpeg
 from av_aloha_amd.vec_env import make_vec
+import gpu_util          # noqa: F401  (torch's HIP runtime comes up before libavsim's)
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch_runtime_first():
-    """torch's HIP runtime has to come up before libavsim's in a process (vec_env.py): when pytest imports this module."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
 
 PEG = "gym_guided_vision/InsertPeg-3Arms-v0"
 CAMS = {"cam_a": (16, 24), "cam_b": (24, 32)}

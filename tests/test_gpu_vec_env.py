@@ -7,32 +7,17 @@ import pytest
 
 from av_aloha_amd.sim import BatchedSim
 from av_aloha_amd.vec_env import VecEnv, make_vec, sample_poses
+from avsim_test_util import host_observe
+from gpu_util import torch as T
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch_runtime_first():
-    """torch ships its own HIP runtime next to the one libavsim links: the vector env needs torch's to come up before libavsim's in a
-    process, so this module brings it up when pytest imports it, before any test of the session has created a handle."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
 
 TASKS = ("insert_peg", "slot_insertion", "sew_needle", "tube_transfer", "hook_package")
 PEG = "gym_guided_vision/InsertPeg-3Arms-v0"
 
 
-def torch():
-    import torch as t
-    return t
-
-
 def dev_state(env):
     """qpos, qvel, ctrl, warm, latch, reset poses of a device-mode handle, as numpy."""
-    T = torch()
     h, N, d = env.h, env.num_envs, env.device
     q, v = T.empty((N, h.nq), dtype=T.float64, device=d), T.empty((N, h.nv), dtype=T.float64, device=d)
     c, w = T.empty((N, h.nu), dtype=T.float64, device=d), T.empty((N, h.nv), dtype=T.float64, device=d)
@@ -41,12 +26,6 @@ def dev_state(env):
     h.check(h.L.avsim_get_latch(h.h, lt.data_ptr()))
     h.check(h.L.avsim_get_reset_poses(h.h, rp.data_ptr()))
     return [x.cpu().numpy() for x in (q, v, c, w, lt, rp)]
-
-
-def host_observe(sim):
-    ap = np.empty((sim.N, sim.nj))
-    sim.h.check(sim.h.L.avsim_observe(sim.h.h, ap.ctypes.data, None, None))
-    return ap
 
 
 def host_twin(task, poses, f64=False):
@@ -89,7 +68,6 @@ def test_reset_state_equals_the_host_reset(task):
 
 
 def test_next_step_autoreset():
-    T = torch()
     runs = []
     for variant in range(2):
         env = make_vec(PEG, 2, 5, cameras=[], obs_format="gym")
@@ -122,7 +100,6 @@ def test_next_step_autoreset():
 def test_staggered_partial_resets_match_host_episodes(f64):
     """Partial resets (reset_mask) between steps and NEXT_STEP autoresets: every env's per-step agent_pos, reward and success equal a
     host BatchedSim stepped through the same episode from the same poses, bit for bit."""
-    T = torch()
     task, N, steps = "slot_insertion", 3, 16
     env = VecEnv(task, 3, N, 6, cameras=(), f64=f64)
     obs, info = env.reset(seed=11)
@@ -169,7 +146,6 @@ def test_staggered_partial_resets_match_host_episodes(f64):
 
 
 def test_divergence_truncates_and_restarts_only_that_env():
-    T = torch()
     runs = []
     for poke in (False, True):
         env = make_vec("gym_guided_vision/SlotInsertion-3Arms-v0", 3, 50, cameras=[], obs_format="gym")
@@ -199,7 +175,6 @@ def test_divergence_truncates_and_restarts_only_that_env():
 
 def test_evaluate_vec_records_do_not_depend_on_the_batch():
     from av_aloha_amd.harness import evaluate_vec
-    T = torch()
 
     def policy(obs, info):
         s = obs["observation.state"]
@@ -225,7 +200,6 @@ def test_evaluate_vec_records_do_not_depend_on_the_batch():
 def test_lerobot_images_are_preprocessed_gym_images():
     from av_aloha_amd.env import make
     from av_aloha_amd.harness import preprocess_observation
-    T = torch()
     cams = ["zed_cam_left", "wrist_cam_right"]
     le = make_vec(PEG, 2, 20, cameras=cams, obs_format="lerobot", seed=4)
     gy = make_vec(PEG, 2, 20, cameras=cams, obs_format="gym", seed=4)
@@ -254,7 +228,6 @@ def test_lerobot_images_are_preprocessed_gym_images():
 
 
 def test_step_does_not_synchronise():
-    T = torch()
     env = make_vec(PEG, 4, 20, cameras=["zed_cam_left"], obs_format="lerobot", observation_height=96, observation_width=128)
     env.reset(seed=0)
     a = home_action(env)

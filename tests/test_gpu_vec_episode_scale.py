@@ -13,36 +13,16 @@ from av_aloha_amd import _ffi
 from av_aloha_amd.constants import SIM_PHYSICS_ENV_STEP_RATIO
 from av_aloha_amd.sim import BatchedSim, load_blob
 from av_aloha_amd.vec_env import OBJECT_BOXES, VecEnv, make_vec, sample_poses
+from avsim_test_util import host_observe
+from gpu_util import torch as T
 from vec_episode_model import INSERT_BEFORE, MAX_STEPS, POKE_BEFORE, EpisodeModel, check_invariants, coverage, scenario
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch_runtime_first():
-    """torch ships its own HIP runtime next to the one libavsim links: the vector env needs torch's to come up before libavsim's in a
-    process, so this module brings it up when pytest imports it, before any test of the session has created a handle."""
-    import torch as t
-    if t.cuda.is_available():
-        t.zeros(1, device="cuda")
-
-
-_torch_runtime_first()
 
 TASK, SEED = "slot_insertion", 11
 PEG = "gym_guided_vision/InsertPeg-3Arms-v0"
 SLOT_IN, STICK_IN = [0.0, 0.12, 0.0], [0.0, 0.12, 0.0005]        # test_gpu_physics.test_staged_rewards_and_success_match_the_oracle's "inserted"
 KEPT = ("elapsed", "reward", "success", "terminated", "truncated")      # what VecEnv.reset leaves of the last step for the envs it does not restart
-
-
-def torch():
-    import torch as t
-    return t
-
-
-def host_observe(sim):
-    ap = np.empty((sim.N, sim.nj))
-    sim.h.check(sim.h.L.avsim_observe(sim.h.h, ap.ctypes.data, None, None))
-    return ap
 
 
 # ---- the reference: twin + model -----------------------------------------------------------------------------------------------------
@@ -190,19 +170,19 @@ class ThroughVecEnv:
         return {"elapsed": info["elapsed_steps"], "reward": r, "success": info["is_success"], "terminated": te, "truncated": tr}
 
     def reset(self, mask, skip=()):
-        T, env = torch(), self.env
+        env = self.env
         obs, info = env.reset(options=None if mask is None else {"reset_mask": T.as_tensor(mask)})
         out = {"agent_pos": obs["agent_pos"], "id": info["episode_id"], **self._kept(info, env._reward, env._term, env._trunc)}
         return {k: v.cpu().numpy().copy() for k, v in out.items()}
 
     def step(self, a, skip=()):
-        T, env = torch(), self.env
+        env = self.env
         obs, r, te, tr, info = env.step(T.as_tensor(a, device=env.device))
         out = {"agent_pos": obs["agent_pos"], "id": info["episode_id"], **self._kept(info, r, te, tr)}
         return {k: v.cpu().numpy().copy() for k, v in out.items()}
 
     def _state(self, which):
-        T, h = torch(), self.env.h
+        h = self.env.h
         x = T.empty((self.N, h.nq if which == 0 else h.nv), dtype=T.float64, device=self.env.device)
         args = [None] * 4
         args[which] = x.data_ptr()
@@ -210,7 +190,7 @@ class ThroughVecEnv:
         return x, args
 
     def insert(self, envs):
-        T, h = torch(), self.env.h
+        h = self.env.h
         q, args = self._state(0)
         i = T.as_tensor(np.flatnonzero(envs), device=q.device)
         q[i, 23:26] = T.tensor(SLOT_IN, dtype=T.float64, device=q.device)
@@ -218,7 +198,7 @@ class ThroughVecEnv:
         h.check(h.L.avsim_set_qpos(h.h, q.data_ptr()))
 
     def poke(self, envs):
-        T, h = torch(), self.env.h
+        h = self.env.h
         v, args = self._state(1)
         v[T.as_tensor(envs, device=v.device), 30] = 1e9
         h.check(h.L.avsim_set_state(h.h, *args))
@@ -340,7 +320,6 @@ def test_evaluate_vec_records_do_not_depend_on_the_batch_across_a_chunk():
     """test_gpu_vec_env's 3 / 4 / 10 check carried over the wave and the chunk boundary: 1100 episodes on 1030 envs (ids 1024 .. 1029 start
     in the second chunk, 1030 .. 1099 in the second round) and on 10 envs give the same record for every id."""
     from av_aloha_amd.harness import evaluate_vec
-    T = torch()
 
     def policy(obs, info):
         s = obs["observation.state"]

@@ -7,7 +7,8 @@ import pytest
 
 from av_aloha_amd import pointcloud as pc
 from av_aloha_amd import virtviews as vv
-from test_gpu_pointcloud import CAMS2, FAR, N, SENTINEL, WIDE, ids_of, noise_depth, torch
+from gpu_util import Guarded, torch as T
+from test_gpu_pointcloud import CAMS2, FAR, N, SENTINEL, WIDE, ids_of, noise_depth, noise_rgb
 from test_gpu_pointcloud import dev, sim          # noqa: F401  (module-scoped fixtures: this module gets its own handles)
 
 pytestmark = pytest.mark.gpu
@@ -18,28 +19,25 @@ ALL = [0, 1, 2, 3, 4, 5]
 
 
 def views_on_device(dev, ids, H, W, depth, rgb, bounds, max_depth, views, size, radius, null=None, ncam=None, nviews=None, room=None, offset=0):
-    """avsim_virtual_views into the middle of two sentinel-filled tensors -> (rc, out [N, V, VH, VW, 8], index [N, V, VH, VW], the sentinels
-    around them, the raw bodies).  room: (V, VH, VW) the buffers are sized for, when the call's own are none."""
-    T = torch()
+    """avsim_virtual_views into the middle of two sentinel-filled tensors -> (rc, out [N, V, VH, VW, 8], index [N, V, VH, VW], no word
+    around them was written, the raw bodies).  room: (V, VH, VW) the buffers are sized for, when the call's own are none."""
     v, sz = np.ascontiguousarray(views, dtype=np.int32), np.ascontiguousarray(size, dtype=np.int32)
     V, VH, VW = (len(v), int(sz[0]), int(sz[1])) if room is None else room
     n_idx = N * V * VH * VW
-    b_out = T.full((GUARD + 8 * n_idx + 1024,), SENTINEL, dtype=T.int32, device=dev.d)
-    b_idx = T.full((GUARD + n_idx + 1024,), SENTINEL, dtype=T.int32, device=dev.d)
+    b_out = Guarded(dev.d, 8 * n_idx, T.int32, SENTINEL, GUARD, 1024)
+    b_idx = Guarded(dev.d, n_idx, T.int32, SENTINEL, GUARD, 1024)
     t_depth = T.from_numpy(np.ascontiguousarray(depth, dtype=np.float32)).to(dev.d)
     t_rgb = None if rgb is None else T.from_numpy(np.ascontiguousarray(rgb, dtype=np.uint8)).to(dev.d)
     bounds = np.ascontiguousarray(bounds, dtype=np.float32)
     args = {"cam_ids": ids.ctypes.data, "depth": t_depth.data_ptr(), "bounds": bounds.ctypes.data, "views": v.ctypes.data, "size": sz.ctypes.data,
-            "out": b_out.data_ptr() + 4 * GUARD + offset, "index": b_idx.data_ptr() + 4 * GUARD}
+            "out": b_out.ptr(offset), "index": b_idx.ptr()}
     if null:
         args[null] = None
     rc = dev.h.L.avsim_virtual_views(dev.h.h, args["cam_ids"], len(ids) if ncam is None else ncam, H, W, args["depth"], None if t_rgb is None else t_rgb.data_ptr(), args["bounds"],
                                      float(max_depth), args["views"], len(v) if nviews is None else nviews, args["size"], int(radius), args["out"], args["index"])
     T.cuda.synchronize()
-    wo, wi = b_out.cpu().numpy(), b_idx.cpu().numpy()
-    body_o, body_i = wo[GUARD:GUARD + 8 * n_idx], wi[GUARD:GUARD + n_idx]
-    around = np.concatenate([wo[:GUARD], wo[GUARD + 8 * n_idx:], wi[:GUARD], wi[GUARD + n_idx:]])
-    return rc, body_o.view(np.float32).reshape(N, V, VH, VW, 8), body_i.reshape(N, V, VH, VW), around, (body_o, body_i)
+    (body_o, intact_o, _), (body_i, intact_i, _) = b_out.read(), b_idx.read()
+    return rc, body_o.view(np.float32).reshape(N, V, VH, VW, 8), body_i.reshape(N, V, VH, VW), intact_o and intact_i, (body_o, body_i)
 
 
 def same(got, want, what):
@@ -60,16 +58,12 @@ def both_equal_the_reference(sim, dev, cams, H, W, depth, rgb, bounds, max_depth
         w = vv.virtual_views_reference(poses, depth, colour, bounds, max_depth, views, size, radius)
         same(sim.virtual_views(cams, H, W, bounds, views, size, radius=radius, max_depth=max_depth, depth=depth, rgb=colour), w, tag + ", host pointers")
         dw = w if np.array_equal(dposes, poses) else vv.virtual_views_reference(dposes, depth, colour, bounds, max_depth, views, size, radius)
-        rc, out, index, around, _ = views_on_device(dev, ids, H, W, depth, colour, bounds, max_depth, vv.view_codes(views), vv.view_size(size), radius)
+        rc, out, index, intact, _ = views_on_device(dev, ids, H, W, depth, colour, bounds, max_depth, vv.view_codes(views), vv.view_size(size), radius)
         assert rc == 0, dev.h.L.avsim_last_error(dev.h.h)
         same((out, index), dw, tag + ", device pointers")
-        assert (around == SENTINEL).all(), tag + ": a write outside out or index"
+        assert intact, tag + ": a write outside out or index"
         want = w if want is None else want
     return want
-
-
-def noise_rgb(seed, ncam, H, W):
-    return np.random.default_rng(seed).integers(0, 256, (N, ncam, H, W, 3), dtype=np.uint8)
 
 
 def base_case(sim):
@@ -143,7 +137,6 @@ def test_ties_on_the_device(sim, dev):
 def test_calls_in_a_row_with_the_host_arrays_overwritten(sim, dev):
     """Four device-mode calls without a synchronisation between them; bounds, camera ids, views and size are overwritten as soon as a call
     returns: the call took them by value."""
-    T = torch()
     H, W = 24, 32
     ids = ids_of(sim, CAMS2)
     poses = dev.poses(ids)
@@ -205,10 +198,10 @@ def test_refusals_leave_the_outputs_untouched(sim, dev):
     for what, kw in cases:
         a = dict(ids=ids, H=H, W=W, depth=depth, bounds=BOX, max_depth=FAR, views=views, size=size, radius=radius)
         a.update({k: v for k, v in kw.items() if k in a})
-        rc, _, _, around, body = views_on_device(dev, a["ids"], a["H"], a["W"], a["depth"], None, a["bounds"], a["max_depth"], a["views"], a["size"], a["radius"], null=kw.get("null"),
+        rc, _, _, intact, body = views_on_device(dev, a["ids"], a["H"], a["W"], a["depth"], None, a["bounds"], a["max_depth"], a["views"], a["size"], a["radius"], null=kw.get("null"),
                                                  ncam=kw.get("ncam"), nviews=kw.get("nviews"), room=(3, 4, 5), offset=kw.get("offset", 0))
         assert rc == -1, f"{what}: rc {rc}"
-        assert (around == SENTINEL).all() and (body[0] == SENTINEL).all() and (body[1] == SENTINEL).all(), f"{what}: an output was written"
+        assert intact and (body[0] == SENTINEL).all() and (body[1] == SENTINEL).all(), f"{what}: an output was written"
         assert dev.h.L.avsim_last_error(dev.h.h)
         if "null" in kw or "ncam" in kw or "nviews" in kw or "offset" in kw or kw.get("H") == 4097:
             continue
@@ -304,7 +297,6 @@ VVARG = {"cameras": ["zed_cam_left", "wrist_cam_left"], "height": 24, "width": 3
 
 def test_vector_env_observation():
     from av_aloha_amd.vec_env import make_vec
-    T = torch()
 
     class Recorded:
         """The library with the names of the entry points that are looked up on it."""

@@ -7,7 +7,8 @@ import pytest
 
 from av_aloha_amd import pointcloud as pc
 from av_aloha_amd import voxel
-from test_gpu_pointcloud import CAMS2, FAR, N, SENTINEL, WIDE, ids_of, noise_depth, torch
+from gpu_util import Guarded, torch as T
+from test_gpu_pointcloud import CAMS2, FAR, N, SENTINEL, WIDE, ids_of, noise_depth, noise_rgb
 from test_gpu_pointcloud import dev, sim          # noqa: F401  (module-scoped fixtures: this module gets its own handles)
 
 pytestmark = pytest.mark.gpu
@@ -17,24 +18,22 @@ BOX = np.array([-2.0, -2.0, -1.5, 2.0, 2.0, 2.5], dtype=np.float32)
 
 
 def grid_on_device(dev, ids, H, W, depth, rgb, bounds, max_depth, grid, null=None, ncam=None, size_grid=None, offset=0):
-    """avsim_voxel_grid into the middle of a sentinel-filled tensor -> (rc, out [N, gx, gy, gz, 8], the sentinels around it, the raw body)."""
-    T = torch()
+    """avsim_voxel_grid into the middle of a sentinel-filled tensor -> (rc, out [N, gx, gy, gz, 8], no word around it was written, the raw
+    body)."""
     g = np.ascontiguousarray(grid, dtype=np.int32)
     sg = g if size_grid is None else np.asarray(size_grid)
-    size = N * int(sg[0]) * int(sg[1]) * int(sg[2]) * 8
-    buf = T.full((GUARD + size + 1024,), SENTINEL, dtype=T.int32, device=dev.d)
+    buf = Guarded(dev.d, N * int(sg[0]) * int(sg[1]) * int(sg[2]) * 8, T.int32, SENTINEL, GUARD, 1024)
     t_depth = T.from_numpy(np.ascontiguousarray(depth, dtype=np.float32)).to(dev.d)
     t_rgb = None if rgb is None else T.from_numpy(np.ascontiguousarray(rgb, dtype=np.uint8)).to(dev.d)
     bounds = np.ascontiguousarray(bounds, dtype=np.float32)
-    args = {"cam_ids": ids.ctypes.data, "depth": t_depth.data_ptr(), "bounds": bounds.ctypes.data, "grid": g.ctypes.data, "out": buf.data_ptr() + 4 * GUARD + offset}
+    args = {"cam_ids": ids.ctypes.data, "depth": t_depth.data_ptr(), "bounds": bounds.ctypes.data, "grid": g.ctypes.data, "out": buf.ptr(offset)}
     if null:
         args[null] = None
     rc = dev.h.L.avsim_voxel_grid(dev.h.h, args["cam_ids"], len(ids) if ncam is None else ncam, H, W, args["depth"], None if t_rgb is None else t_rgb.data_ptr(),
                                   args["bounds"], float(max_depth), args["grid"], args["out"])
     T.cuda.synchronize()
-    w = buf.cpu().numpy()
-    body = w[GUARD:GUARD + size]
-    return rc, body.view(np.float32).reshape(N, int(sg[0]), int(sg[1]), int(sg[2]), 8), np.concatenate([w[:GUARD], w[GUARD + size:]]), body
+    body, intact, _ = buf.read()
+    return rc, body.view(np.float32).reshape(N, int(sg[0]), int(sg[1]), int(sg[2]), 8), intact, body
 
 
 def same(got, want, what):
@@ -54,16 +53,12 @@ def both_equal_the_reference(sim, dev, cams, H, W, depth, rgb, bounds, max_depth
         w = voxel.voxel_grid_reference(poses, depth, colour, bounds, max_depth, grid)
         same(sim.voxel_grid(cams, H, W, bounds, grid, max_depth=max_depth, depth=depth, rgb=colour), w, tag + ", host pointers")
         dw = w if np.array_equal(dposes, poses) else voxel.voxel_grid_reference(dposes, depth, colour, bounds, max_depth, grid)
-        rc, out, around, _ = grid_on_device(dev, ids, H, W, depth, colour, bounds, max_depth, voxel.grid_dims(grid))
+        rc, out, intact, _ = grid_on_device(dev, ids, H, W, depth, colour, bounds, max_depth, voxel.grid_dims(grid))
         assert rc == 0, dev.h.L.avsim_last_error(dev.h.h)
         same(out, dw, tag + ", device pointers")
-        assert (around == SENTINEL).all(), tag + ": a write outside out"
+        assert intact, tag + ": a write outside out"
         want = w if want is None else want
     return want
-
-
-def noise_rgb(seed, ncam, H, W):
-    return np.random.default_rng(seed).integers(0, 256, (N, ncam, H, W, 3), dtype=np.uint8)
 
 
 def base_case(sim):
@@ -146,7 +141,6 @@ def test_runs_of_length_one(sim, dev):
 def test_calls_in_a_row_with_the_host_arrays_overwritten(sim, dev):
     """Four device-mode calls without a synchronisation between them; bounds, camera ids and grid dims are overwritten as soon as a call
     returns: the call took them by value."""
-    T = torch()
     H, W = 24, 32
     ids = ids_of(sim, CAMS2)
     poses = dev.poses(ids)
@@ -200,10 +194,10 @@ def test_refusals_leave_out_untouched(sim, dev):
     for what, kw in cases:
         a = dict(ids=ids, H=H, W=W, depth=depth, bounds=BOX, max_depth=FAR, grid=grid)
         a.update({k: v for k, v in kw.items() if k in a})
-        rc, _, around, body = grid_on_device(dev, a["ids"], a["H"], a["W"], a["depth"], None, a["bounds"], a["max_depth"], a["grid"], null=kw.get("null"), ncam=kw.get("ncam"),
+        rc, _, intact, body = grid_on_device(dev, a["ids"], a["H"], a["W"], a["depth"], None, a["bounds"], a["max_depth"], a["grid"], null=kw.get("null"), ncam=kw.get("ncam"),
                                              size_grid=grid, offset=kw.get("offset", 0))
         assert rc == -1, f"{what}: rc {rc}"
-        assert (around == SENTINEL).all() and (body == SENTINEL).all(), f"{what}: out was written"
+        assert intact and (body == SENTINEL).all(), f"{what}: out was written"
         assert dev.h.L.avsim_last_error(dev.h.h)
         if "null" in kw or "ncam" in kw or "offset" in kw or kw.get("H") == 4097:
             continue
@@ -269,7 +263,6 @@ VXARG = {"cameras": ["zed_cam_left", "wrist_cam_left"], "height": 24, "width": 3
 
 def test_vector_env_observation():
     from av_aloha_amd.vec_env import make_vec
-    T = torch()
     class Recorded:
         """The library with the names of the entry points that are looked up on it."""
 
@@ -328,7 +321,6 @@ def test_on_demand_colour_in_an_env_that_renders_camera_major():
     its colour env-major all the same: the grid equals the one from an rgb put together camera by camera (with one camera the two layouts
     are one), it differs from the grid of the camera-major buffer read as env-major, and the env's own images come out as before."""
     from av_aloha_amd.vec_env import make_vec
-    T = torch()
     cams, H, W, n = ["zed_cam_left", "wrist_cam_left"], 24, 32, 3
     env = make_vec(SLOT, n, 5, cameras=cams, obs_format="gym", observation_height=H, observation_width=W, seed=4)
     try:

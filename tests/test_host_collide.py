@@ -16,19 +16,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from avsim_test_util import rand_quat
 from orc_env import OrcEnv
 from orc_ffi import ROOT, dp
 from test_oracle_physics import model_dict
-
-
-def rand_quat(rng, small):
-    if small:
-        ax = rng.normal(size=3)
-        ax /= np.linalg.norm(ax)
-        ang = rng.uniform(-0.3, 0.3)
-        return np.concatenate([[np.cos(ang / 2)], np.sin(ang / 2) * ax])
-    q = rng.normal(size=4)
-    return q / np.linalg.norm(q)
 
 
 @pytest.fixture(scope="module")

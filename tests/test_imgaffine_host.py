@@ -6,16 +6,9 @@ import pytest
 from scipy import ndimage
 
 from av_aloha_amd import imgaug
+from avsim_test_util import bits, noise
 
 A = 32                          # imgaug.AFFINE
-
-
-def noise(shape, seed):
-    return np.random.default_rng(seed).integers(0, 256, shape, dtype=np.uint8)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def coords64(H, W, M):

@@ -6,16 +6,9 @@ import numpy as np
 import pytest
 
 from av_aloha_amd import dataset, imgaug, imgprep
+from avsim_test_util import bits, noise
 
 B, C, S, Hh, SH = imgaug.BRIGHTNESS, imgaug.CONTRAST, imgaug.SATURATION, imgaug.HUE, imgaug.SHARPNESS
-
-
-def noise(shape, seed):
-    return np.random.default_rng(seed).integers(0, 256, shape, dtype=np.uint8)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def params(boxes, masks, factors):

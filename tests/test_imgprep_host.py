@@ -9,12 +9,9 @@ from fractions import Fraction
 import numpy as np
 
 from av_aloha_amd import dataset, imgprep
+from avsim_test_util import noise
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def noise(shape, seed):
-    return np.random.default_rng(seed).integers(0, 256, shape, dtype=np.uint8)
 
 
 def test_stats_reference_is_numpy_sums():

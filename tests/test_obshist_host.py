@@ -7,11 +7,7 @@ import pytest
 
 from av_aloha_amd import imgprep
 from av_aloha_amd import obshist as oh
-
-
-def same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.dtype == b.dtype == np.float32 and a.shape == b.shape and not np.isnan(a).any() and not np.isnan(b).any() and np.array_equal(a, b)
+from avsim_test_util import same
 
 
 def fresh_schedule(N, calls):
